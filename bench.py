@@ -6,13 +6,25 @@ SURVEY.md 8(d)) resident in HBM on every GPU, processed in batches of 4096 windo
 the hot path = column encode (mpileup bytes -> int32 [M,18] counts) + PileupModel forward reading the
 windows in place (-> softmax probabilities) + argmax/max post-processing.  One *step* = one sweep of the
 whole pool (256 batches = 1,048,576 sites), issued round-robin over `--streams` HIP streams (one nsnp_ctx
-each); the timed region (W warm-up steps, then exactly K steps between barrier + synchronize) is run
-`--repeat` times (default 3) and the line reports the MEDIAN pass, all values under "repeats".  After the
-timed passes and outside the clock, the outputs the last fp32 pass left behind are compared with the oracle
-("parity_sample"; the process exits non-zero when that fails).
+each); the timed region is W warm-up steps, then exactly K steps between barrier + synchronize.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what the headline needs: set up, warm up, time the K steps once, write the outputs
+(`--dump-outputs DIR`), print the line.  `--full` adds everything else the benchmark measures or checks:
+the timed region run `--repeat` times (default 3, the line reports the MEDIAN pass, all values under
+"repeats"), per-kernel HIP-event timing and the rooflines built from it, the shader clock, the outputs
+the last fp32 pass left behind compared with the oracle ("parity_sample"; the process exits non-zero when
+that fails), the bf16x3 / f16x3 second values, the other BASELINE configurations ("workloads") and the
+CPU baseline.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+`--dump-outputs DIR` (pileup workload): after the timed passes, what their last step computed, as the caller
+of the path receives it, goes to DIR as .npy files (float32 / float64, < 64 MB in all): calls.npy = the
+merged per-site calls [sites, 4] (genotype class, zygosity class, their probabilities) and the softmax
+probabilities gt_prob.npy [S, 21] / zy_prob.npy [S, 3] of a fixed, seeded sample of S = 131,072 of rank 0's
+windows (their indices: prob_sites.npy; calls_sites.npy the rows of calls.npy, all of them up to 1 M rows).
+The pool is a pure function of the seed, so the same arguments give the same inputs on every run.
 
 `--gpus N` with N > 1 and no torchrun environment: this process starts the N ranks itself (a child
 `python -m torch.distributed.run`, before anything touches the GPU), relays rank 0's JSON line and exits
@@ -23,9 +35,9 @@ inside the timed region (RCCL over xGMI).  Rank 0 prints ONE JSON line, the LAST
 "metric" key, no prose).  Everything else the run knows - per-kernel tables, notes, the full result object of every sub-workload -
 is written to bench_details.json beside this file (path on stderr).
 
-The headline `value` is the exact-fp32 path (the library default, the reference's arithmetic); the bf16x3
-mode (three bf16 terms per operand: the full fp32 significand on the bf16 matrix pipe) and the opt-in f16x3
-mode are timed afterwards on the same pool and reported under "bf16x3" / "f16x3" in the same line.
+The headline `value` is the exact-fp32 path (the library default, the reference's arithmetic); with `--full`
+the bf16x3 mode (three bf16 terms per operand: the full fp32 significand on the bf16 matrix pipe) and the
+opt-in f16x3 mode are timed afterwards on the same pool and reported under "bf16x3" / "f16x3" in the same line.
 """
 from __future__ import annotations
 
@@ -72,7 +84,8 @@ def parse_args(argv=None):
                     "(library default), 1 f16x3 split, 2 bf16x3")
     ap.add_argument("--no-second-precision", action="store_true", help="skip the labelled f16x3 pass after the fp32 headline")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="nsnp_ctx_set_option on every context (tuning)")
-    ap.add_argument("--repeat", type=int, default=3, help="timed passes of the headline arithmetic; the line reports the median pass")
+    ap.add_argument("--repeat", type=int, default=None, help="timed passes of the headline arithmetic; the line reports the median pass "
+                    "(default: 3 with --full, 1 otherwise)")
     ap.add_argument("--no-parity-sample", action="store_true", help="skip the comparison of the run's own outputs with the oracle")
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not record per-kernel HIP events")
     ap.add_argument("--timing-streams", type=int, default=4, help="record per-kernel HIP events on this many of the streams "
@@ -85,9 +98,14 @@ def parse_args(argv=None):
     ap.add_argument("--gather", default="torch", choices=["torch", "rccl-abi"], help="final merge through one torch.distributed collective "
                     "(default) or through the library's own RCCL entry nsnp_gather_results (validated at world size 1 only)")
     ap.add_argument("--share-gpu", action="store_true", help="test configuration: every rank uses GPU 0 (needs --dist-backend gloo)")
-    ap.add_argument("--workloads", default="all", help="pileup workload only: after the headline's timed region, short runs of the other BASELINE "
-                    "configurations in the same process, reported under \"workloads\" in the same line (tools/workloads.py): 'all' (default), 'none', or a "
-                    "comma-separated subset of haplotype,two_stage,deep60,hap_e2e,e2e,pd_e2e")
+    ap.add_argument("--workloads", default=None, help="pileup workload only: after the headline's timed region, short runs of the other BASELINE "
+                    "configurations in the same process, reported under \"workloads\" in the same line (tools/workloads.py): 'all' (default with "
+                    "--full), 'none' (default otherwise), or a comma-separated subset of haplotype,two_stage,deep60,hap_e2e,e2e,pd_e2e")
+    ap.add_argument("--full", action="store_true", help="pileup workload: besides the headline, everything else the benchmark measures or "
+                    "checks - median of --repeat timed passes, per-kernel timing and rooflines, shader clock, parity sample against the oracle, "
+                    "float64 error, bf16x3 / f16x3 second values, the other BASELINE configurations, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="pileup workload: write what the last timed step computed to "
+                    "DIR/<name>.npy (the merged calls, the probabilities of a fixed, seeded sample of the windows; < 64 MB)")
     ap.add_argument("--selftest-launcher", action="store_true", help="CPU/gloo dry run of the multi-rank plumbing (spawn, barrier, "
                     "max-over-ranks timing, rooted gather, one JSON line); no kernels, value is null -- tests/test_dist.py")
     return ap.parse_args(argv)
@@ -201,6 +219,39 @@ def cpu_baseline(cols, batch, weights, target_s):
     return out
 
 
+DUMP_PROB_SITES = 1 << 17           # probability rows written by --dump-outputs: 131,072 x (21 + 3) fp32 = 12.6 MB
+DUMP_CALL_ROWS = 1 << 20            # merged call rows written in full up to here (16 MB), a seeded sample of this many beyond
+
+
+def _seeded_rows(n, k, seed):
+    """row indices written for an output of n rows: all of them when n <= k, otherwise k of them drawn with a fixed seed (sorted)"""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(dirname, stage, merged, n_done):
+    """--dump-outputs DIR: what the timed path's last step computed, as its caller receives it.  calls.npy = the merged per-site calls
+    [rows, 4] float32 (genotype argmax, zygosity argmax, their max probabilities; calls_sites.npy their rows), gt_prob.npy [S, 21] /
+    zy_prob.npy [S, 3] float32 = the softmax probabilities of a fixed, seeded sample of rank 0's windows (prob_sites.npy their indices).
+    At most ~38 MB whatever the pool and world size."""
+    import numpy as np
+    torch = stage.torch
+    stage.sync()
+    os.makedirs(dirname, exist_ok=True)
+    calls = merged.cpu().numpy().astype(np.float32, copy=False)
+    crow = _seeded_rows(calls.shape[0], DUMP_CALL_ROWS, 1)
+    prow = _seeded_rows(n_done, DUMP_PROB_SITES, 2)
+    idx = torch.from_numpy(prow).to(stage.dev)
+    arrays = {"calls": calls[crow], "calls_sites": crow.astype(np.float64),
+              "gt_prob": stage.gt_all[idx].cpu().numpy(), "zy_prob": stage.zy_all[idx].cpu().numpy(), "prob_sites": prow.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    print(f"bench.py: outputs of the last timed step -> {dirname} ({', '.join(f'{k} {list(v.shape)}' for k, v in arrays.items())})",
+          file=sys.stderr, flush=True)
+
+
 def main():
     args = parse_args()
     # an application's choice, made before any OpenMP runtime loads (nanosnp_amd.host.recommend_omp_env): idle OpenMP workers spin briefly,
@@ -231,6 +282,9 @@ def main():
     if world > 1 and os.environ.get("OMP_NUM_THREADS", "1") == "1":
         os.environ["OMP_NUM_THREADS"] = str(max(1, usable_cores() // world))
     os.environ.setdefault("OMP_NUM_THREADS", str(max(1, usable_cores() // max(1, world))))
+    if args.dump_outputs and args.workload != "pileup":
+        print(f"bench.py: --dump-outputs is implemented for the pileup workload (the headline), not for --workload {args.workload}", file=sys.stderr)
+        sys.exit(2)
     if args.workload == "two-stage":
         from tools.two_stage_bench import run as run_two_stage
         sys.exit(run_two_stage(args, rank, world, local_rank))
@@ -270,8 +324,9 @@ def main():
     dev = torch.device("cuda", local_rank)
     cdev = dev if args.dist_backend == "nccl" else torch.device("cpu")       # where collective payloads live
 
+    full = args.full
     stage = PileupStage(local_rank, args.windows, batch=args.batch, streams=args.streams, coverage=args.coverage, seed=20260000 + rank,
-                        precision=args.precision, opts=args.opt, timing_streams=0 if args.no_kernel_timing else args.timing_streams,
+                        precision=args.precision, opts=args.opt, timing_streams=args.timing_streams if full and not args.no_kernel_timing else 0,
                         enc_group=args.encode_group)
     batch, n_windows, n_batches = stage.batch, stage.n_windows, stage.n_batches
     W, K = max(0, args.warmup), max(1, args.steps)
@@ -311,24 +366,27 @@ def main():
             dt = float(tmax.item())
         return dt, t_issue, merged, stage.read_timing()
 
-    passes = [timed_pass() for _ in range(max(1, args.repeat))]
+    repeat = args.repeat if args.repeat is not None else (3 if full else 1)
+    passes = [timed_pass() for _ in range(max(1, repeat))]
     order = sorted(range(len(passes)), key=lambda i: passes[i][0])
     dt, t_issue, merged, tot = passes[order[len(order) // 2]]            # the median pass is the one reported
     sites_timed = world * K * bps * batch
     repeats = [sites_timed / p[0] for p in passes]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, stage, passes[-1][2], n_done)  # the last pass: its merged calls, the probabilities it left in place
     # what the last fp32 pass left behind, for the parity sample (compared with the oracle after all timing, outside every clock)
     snap = None
-    if rank == 0 and not args.no_parity_sample and args.precision == 0:
+    if full and rank == 0 and not args.no_parity_sample and args.precision == 0:
         snap = stage.snapshot(stage.parity_ranges(n_done))
-    clock_mhz = stage.ctxs[0].shader_clock_mhz(stage.streams[0]) if rank == 0 else None
+    clock_mhz = stage.ctxs[0].shader_clock_mhz(stage.streams[0]) if (full and rank == 0) else None
 
     # the same kernels with the chip to themselves (one stream, after the timed region)
-    excl, excl_n = stage.exclusive_pass()
+    excl, excl_n = stage.exclusive_pass() if full else ({}, {})
 
     # ---- labelled second values on the same pool: bf16x3 (full fp32 operand width on the bf16 pipe) and the opt-in f16x3 ----------
     seconds = {}
     f64_err = {"fp32": stage.float64_error(snap)} if snap is not None else {}
-    if not args.no_second_precision and args.precision == 0:
+    if full and not args.no_second_precision and args.precision == 0:
         ref_gt = stage.gt_all[:n_done].clone(); ref_zy = stage.zy_all[:n_done].clone()
         torch.cuda.synchronize(dev)                     # (the copies run on torch's current stream, the forwards on the stage's)
         for prec, label, text in ((2, "bf16x3", "bf16x3 (every fp32 operand as three bf16 terms = its full 24-bit significand and exponent range, "
@@ -358,9 +416,10 @@ def main():
 
     # ---- the other BASELINE configurations, short runs in this process (every rank takes part: their merges are collectives) ----
     sub, sub_ok = {}, True
-    if args.workloads != "none":
+    workloads = args.workloads if args.workloads is not None else ("all" if full else "none")
+    if workloads != "none":
         from tools.workloads import PLAN, run_all
-        only = None if args.workloads == "all" else set(args.workloads.split(","))
+        only = None if workloads == "all" else set(workloads.split(","))
         if only is not None and not only <= {p[0] for p in PLAN}:
             print(f"bench.py: --workloads: unknown name in {sorted(only)}", file=sys.stderr)
             sys.exit(2)
@@ -406,13 +465,14 @@ def main():
                                        "oracle.pileup_forward_f64): the fp32 MFMA path's own distance from exact arithmetic is the yardstick for the split modes"}
         out["repeats"] = {"values": [round(v) for v in repeats], "reported": "median", "spread": (max(repeats) - min(repeats)) / out["value"]}
         out["timed_region_s"] = dt
-        out["shader_clock_mhz"] = {"value": clock_mhz, "how": "s_memtime / s_memrealtime in every workgroup of a ~2 ms full-chip fp32 MFMA "
-                                   "probe right after the timed passes (nsnp_ctx_shader_clock); the MFMA peaks are priced at 2400"}
+        if clock_mhz is not None:
+            out["shader_clock_mhz"] = {"value": clock_mhz, "how": "s_memtime / s_memrealtime in every workgroup of a ~2 ms full-chip fp32 MFMA "
+                                       "probe right after the timed passes (nsnp_ctx_shader_clock); the MFMA peaks are priced at 2400"}
         if snap is not None:
             out["parity_sample"] = stage.parity_check(snap)
         else:
             out["parity_sample"] = None
-        out["cpu_baseline"] = cpu_baseline(stage.cols, batch, stage.weights, args.cpu_seconds) if (not args.no_cpu_baseline and world == 1) else None
+        out["cpu_baseline"] = cpu_baseline(stage.cols, batch, stage.weights, args.cpu_seconds) if (full and not args.no_cpu_baseline and world == 1) else None
         assert merged is not None and merged.shape[0] == n_done * world
         if sub:
             out["workloads"] = sub

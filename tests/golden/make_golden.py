@@ -12,6 +12,8 @@ Groups (each runs in its own interpreter: the reference's two model packages bot
 top-level modules named model/optim/utils/options):
   encode   oracle/_ref (the reference's dna_sv_tensor programs compiled from the reference
            tree) on synthetic + adversarial mpileup text  -> encode_*.{mpileup,fa,pd}.gz
+  refbin   the same programs on the seeded contigs of test_oracle_vs_reference_binaries_*
+           (inputs rebuilt by the test from the same seeds) -> refbin_pd.npz
   pileup   PileupModel/model.py LSTMNetwork.predict with the shipped ont_pileup.chkpt
            (CPU torch)                                    -> nanosnp_amd/data/ont_pileup_weights.npz, pileup_fwd.npz
   hapfeat  HaplotypeModel/dataset_dev.get_frequency_feature -> hap_features.npz
@@ -45,17 +47,17 @@ def _stub_modules():
 
 
 # ------------------------------------------------------------------------------------------
-def run_ref_encode(workdir, contig, fasta, mpileup_bytes):
+def run_ref_encode(workdir, contig, fasta, mpileup_bytes, snp_min_af="0.12", indel_min_af="0.12", min_coverage=6):
     """DNA_CreateCanSnpTensor + DNA_CreatePredictData with the flags of
-    make_predict_data.sh:184-194,210-215; returns the .pd bytes."""
+    make_predict_data.sh:184-194,210-215 (the two thresholds apart: main.cpp:79-88); returns the .pd bytes."""
     refdir = os.path.join(ROOT, "oracle", "_ref")
     pile = os.path.join(workdir, "pile"); os.makedirs(pile, exist_ok=True)
     with open(os.path.join(pile, contig + ".mpileup"), "wb") as f:
         f.write(mpileup_bytes)
     subprocess.run([os.path.join(refdir, "DNA_CreateCanSnpTensor"), "-reference", fasta,
                     "-chr_pileup_dir", pile, "-output_dir", os.path.join(workdir, "tensor"),
-                    "-min_af", "0.12", "-snp_min_af", "0.12", "-indel_min_af", "0.12",
-                    "-min_coverage", "6", "-flanking_base", "16", "-num_threads", "1", contig],
+                    "-min_af", "0.12", "-snp_min_af", str(snp_min_af), "-indel_min_af", str(indel_min_af),
+                    "-min_coverage", str(min_coverage), "-flanking_base", "16", "-num_threads", "1", contig],
                    check=True, capture_output=True)
     subprocess.run([os.path.join(refdir, "DNA_CreatePredictData"), "-chr_tensor_dir",
                     os.path.join(workdir, "tensor"), "-reference", fasta, "-output_dir",
@@ -100,6 +102,66 @@ def cut_allele_columns(rng, n_cols, ref_seq):
                             else bytes(rng.integers(33, 127, size=ln, dtype=np.uint8)))
         cols.append(bytes(out))
     return cols
+
+
+# ---- inputs of tests/test_oracle_golden.py::test_oracle_vs_reference_binaries_*: built from seeds in the test and here alike; the
+#      compiled reference's .pd of each is stored in refbin_pd.npz (group refbin) --------------------------------------------------
+REFBIN_CUT_THRESHOLDS = (("0.12", "0.12", 6), ("0.3", "0.05", 6), ("0.05", "0.4", 3))
+
+
+def refbin_fresh_contig():
+    """a 40,000-column G1 contig with lower-case / N reference bases and position gaps -> (contig, seq, mpileup bytes)"""
+    from nanosnp_amd import host
+    M = 40000
+    cols = host.synth_columns(977, M, coverage=30)
+    rng = np.random.default_rng(5)
+    seq = np.concatenate([cols.ref, np.frombuffer(b"ACGT" * 25, np.uint8)]).copy()
+    seq[rng.random(seq.size) < 0.04] |= 0x20
+    seq[rng.random(seq.size) < 0.002] = ord("N")
+    keep = np.ones(M, bool)
+    for g in rng.integers(100, M - 100, 20):
+        keep[g:g + int(rng.integers(1, 4))] = False
+    lines = cols.mpileup_text("chrQ").split(b"\n")[:-1]
+    return "chrQ", seq, b"\n".join(l for i, l in enumerate(lines) if keep[i]) + b"\n"
+
+
+def refbin_cut_contig(seed):
+    """3,000 columns of cut_allele_columns -> (contig, seq, mpileup bytes)"""
+    rng = np.random.default_rng(seed)
+    M = 3000
+    seq = rng.choice(list(b"ACGTacgtN"), M + 100, p=[.22, .22, .22, .22, .02, .02, .02, .02, .04]).astype(np.uint8)
+    cols = cut_allele_columns(rng, M, seq)
+    return "chrC", seq, b"".join(b"chrC\t%d\tN\t%d\t%s\t%s\n" % (i + 1, 1, c, b"I") for i, c in enumerate(cols) if c)
+
+
+def refbin_cases():
+    """[(key, (contig, seq, text), (snp_min_af, indel_min_af, min_coverage))] of every stored .pd"""
+    out = [("fresh", refbin_fresh_contig(), ("0.12", "0.12", 6))]
+    for seed in (31, 32):
+        inp = refbin_cut_contig(seed)
+        out += [(f"cut{seed}_{snp}_{ind}_{mc}", inp, (snp, ind, mc)) for snp, ind, mc in REFBIN_CUT_THRESHOLDS]
+    return out
+
+
+def refbin_input_digest(contig, seq, text):
+    import hashlib
+    return hashlib.sha256(contig.encode() + b"\0" + bytes(seq) + b"\0" + text).hexdigest()
+
+
+def group_refbin():
+    """every .pd xz-compressed (a third smaller than zlib on this text) as uint8 arrays of one npz"""
+    import lzma
+    from nanosnp_amd import host
+    arrays = {}
+    for key, (contig, seq, text), (snp, ind, mc) in refbin_cases():
+        with tempfile.TemporaryDirectory() as d:
+            fa = os.path.join(d, "ref.fa")
+            host.write_fasta(fa, contig, seq)
+            pd = run_ref_encode(d, contig, fa, text, snp, ind, mc)
+        arrays[key] = np.frombuffer(lzma.compress(pd, preset=9 | lzma.PRESET_EXTREME), np.uint8)
+        arrays[key + "__input_sha256"] = np.array(refbin_input_digest(contig, seq, text))
+        print(f"refbin {key}: {text.count(10)} columns -> {pd.count(10)} sites")
+    np.savez(os.path.join(GOLD, "refbin_pd.npz"), **arrays)
 
 
 def adversarial_columns(rng, n_cols, ref_seq):
@@ -865,7 +927,7 @@ def group_cat_large():
 
 
 GROUPS = {"haparrange": group_haparrange, "twostage": group_twostage, "twostage_s2": group_twostage_s2, "next": group_next, "vcf": group_vcf, "encode": group_encode, "encode_reader": group_encode_reader, "pileup": group_pileup, "pileup_ckpts": group_pileup_ckpts, "hapfeat": group_hapfeat,
-          "hapfwd": group_hapfwd, "cat": group_cat, "hapfwd_large": group_hapfwd_large, "cat_large": group_cat_large}
+          "hapfwd": group_hapfwd, "cat": group_cat, "hapfwd_large": group_hapfwd_large, "cat_large": group_cat_large, "refbin": group_refbin}
 
 if __name__ == "__main__":
     if not os.path.isdir(REF):

@@ -85,7 +85,7 @@ SMALL_POOLS = dict(NSNP_TWO_STAGE_N2="40960", NSNP_TWO_STAGE_N5="4096", NSNP_HAP
 
 
 def test_bench_line_schema():
-    d = _run("--gpus", "1", "--steps", "4", "--warmup", "1", "--windows", "131072", "--cpu-seconds", "1.5", "--hap-batch", "2048", env=dict(os.environ, **SMALL_POOLS))
+    d = _run("--full", "--gpus", "1", "--steps", "4", "--warmup", "1", "--windows", "131072", "--cpu-seconds", "1.5", "--hap-batch", "2048", env=dict(os.environ, **SMALL_POOLS))
     # the other BASELINE configurations ride in the same line (tools/workloads.py): every one with a value, a parity sample that holds, a CPU
     # baseline, and - where a device kernel dominates - a roofline fraction
     w = d["workloads"]
@@ -251,7 +251,7 @@ def test_two_ranks_through_the_launcher_on_one_gpu(workload):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "65536",
-                          "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--no-second-precision", "--hap-batch", "2048", "--workload", workload,
+                          "--dist-backend", "gloo", "--share-gpu", "--full", "--no-cpu-baseline", "--no-second-precision", "--hap-batch", "2048", "--workload", workload,
                           "--workloads", "none"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -284,7 +284,7 @@ def test_two_ranks_pd_e2e_on_one_gpu():
 def test_bench_with_the_library_gather_entry():
     """--gather rccl-abi: the final merge through nsnp_comm_init + nsnp_gather_results (one rank here)"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--windows", "65536", "--gather", "rccl-abi",
-                          "--no-cpu-baseline", "--no-second-precision", "--workloads", "none"], capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-second-precision", "--workloads", "none"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _parse(out.stdout)
     assert d["config"]["gather"] == "rccl-abi" and d["value"] > 1e6
@@ -297,7 +297,7 @@ def test_two_ranks_with_the_other_configurations_in_the_same_line():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "65536",
-                          "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--no-second-precision", "--hap-batch", "2048",
+                          "--dist-backend", "gloo", "--share-gpu", "--full", "--no-cpu-baseline", "--no-second-precision", "--hap-batch", "2048",
                           "--workloads", "two_stage,hap_e2e,haplotype,pd_e2e"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _parse(out.stdout)
@@ -318,8 +318,52 @@ def test_direct_torchrun_keeps_the_line_last_on_the_jobs_stdout():
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "65536",
-                          "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--no-second-precision", "--workloads", "none"],
+                          "--dist-backend", "gloo", "--share-gpu", "--full", "--no-cpu-baseline", "--no-second-precision", "--workloads", "none"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _parse(out.stdout)
     assert d["n_gpus"] == 2 and d["config"]["world_size_observed"] == 2 and d["_line"]["parity_ok"] is True
+
+
+def test_plain_run_is_lean_and_dumps_what_its_last_step_computed(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one timed pass of exactly K steps and nothing measured beside the headline
+    (no sub-workloads, second precisions, per-kernel timing, parity sample, CPU baseline).  --dump-outputs DIR: the merged calls and the
+    probabilities of the last step as float32 / float64 .npy files under 64 MB, the same on a second run with the same arguments, the calls
+    the argmax / max of the probabilities, the probabilities within 1e-4 of the oracle on windows spread over the pool."""
+    import numpy as np
+    from nanosnp_amd import host
+    from nanosnp_amd.fixtures import load_pileup_weights
+    from oracle import oracle
+    n_windows = 65536
+    dumps = []
+    for k in range(2):
+        out_dir = tmp_path / f"run{k}"
+        d = _run("--gpus", "1", "--steps", "3", "--warmup", "1", "--windows", str(n_windows), "--dump-outputs", str(out_dir))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["unit"] == "sites/s" and d["higher_is_better"] is True
+        assert len(d["repeats"]["values"]) == 1 and d["config"]["sites_per_step"] == n_windows
+        assert abs(d["value"] - n_windows / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+        assert abs(d["timed_region_s"] - 3 * d["ms_per_step"] * 1e-3) < 1e-9
+        for key in ("workloads", "bf16x3", "f16x3", "shader_clock_mhz", "error_vs_float64", "kernel_exclusive_ms", "roofline_encode"):
+            assert key not in d, key
+        assert d["parity_sample"] is None and d["cpu_baseline"] is None and d["roofline"] is None
+        files = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+        assert set(files) == {"calls", "calls_sites", "gt_prob", "zy_prob", "prob_sites"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(p.stat().st_size for p in out_dir.glob("*.npy")) < 64 << 20
+        dumps.append(files)
+    a, b = dumps
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    calls, gt, zy = a["calls"], a["gt_prob"], a["zy_prob"]
+    assert calls.shape == (n_windows, 4) and np.array_equal(a["calls_sites"], np.arange(n_windows))
+    assert gt.shape == (n_windows, 21) and zy.shape == (n_windows, 3) and np.array_equal(a["prob_sites"], np.arange(n_windows))
+    assert np.array_equal(calls[:, 0], gt.argmax(1)) and np.array_equal(calls[:, 1], zy.argmax(1))
+    assert np.array_equal(calls[:, 2], gt.max(1)) and np.array_equal(calls[:, 3], zy.max(1))
+    cols = host.synth_columns(20260000, n_windows * 33, coverage=30.0, window=33)        # the pool of rank 0 (seed 20260000 + rank)
+    w = load_pileup_weights()
+    for first in (0, 4096 * 7 + 100, n_windows - 64):
+        c0, m = first * 33, 64 * 33
+        off = cols.col_off[c0:c0 + m + 1]
+        counts, _, _ = oracle.encode_columns(cols.bases[int(off[0]):int(off[-1])], off - off[0], cols.ref[c0:c0 + m])
+        ogt, ozy = oracle.pileup_forward(w, counts.reshape(64, 33, 18), nthreads=4)
+        assert np.abs(gt[first:first + 64] - ogt).max() < 1e-4 and np.abs(zy[first:first + 64] - ozy).max() < 1e-4, first

@@ -1,9 +1,8 @@
 """The CPU oracle against the golden vectors generated from the reference itself
-(tests/golden/make_golden.py), and against the reference's own compiled programs when oracle/_ref is
-present.  Integer results bit-exact; probabilities within 1e-4 (measured ~1e-6)."""
+(tests/golden/make_golden.py), including the .pd the reference's own compiled programs wrote for seeded contigs
+(refbin_pd.npz; re-run when oracle/_ref is present).  Integer results bit-exact; probabilities within 1e-4 (measured ~1e-6)."""
 import gzip
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -156,66 +155,54 @@ def test_calculate_score_matches_python_formula():
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "DNA_CreateCanSnpTensor")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BIN), reason="oracle/_ref not built (no reference tree)")
+def _make_golden():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", golden("make_golden.py"))
+    mg = importlib.util.module_from_spec(spec); spec.loader.exec_module(mg)
+    return mg
+
+
+def _reference_pd(mg, key, contig, seq, text, snp, ind, mc, tmp_path):
+    """the compiled reference's .pd of these inputs, as stored in tests/golden/refbin_pd.npz (make_golden.py refbin); where oracle/_ref
+    has been built, the reference programs run again and must still write exactly those bytes"""
+    import lzma
+    z = np.load(golden("refbin_pd.npz"))
+    assert str(z[key + "__input_sha256"]) == mg.refbin_input_digest(contig, seq, text), f"{key}: the seeded inputs differ from refbin_pd.npz's"
+    want = lzma.decompress(z[key].tobytes())
+    if os.path.exists(REF_BIN):
+        d = tmp_path / f"ref_{key}"; d.mkdir()
+        fa = str(d / "ref.fa")
+        host.write_fasta(fa, contig, seq)
+        assert mg.run_ref_encode(str(d), contig, fa, text, snp, ind, mc) == want, key
+    return want
+
+
 def test_oracle_vs_reference_binaries_on_a_fresh_contig(tmp_path):
-    """Re-pins the oracle against the compiled reference on data that is NOT in the fixtures."""
-    M = 40000
-    cols = host.synth_columns(977, M, coverage=30)
-    rng = np.random.default_rng(5)
-    seq = np.concatenate([cols.ref, np.frombuffer(b"ACGT" * 25, np.uint8)]).copy()
-    seq[rng.random(seq.size) < 0.04] |= 0x20
-    seq[rng.random(seq.size) < 0.002] = ord("N")
-    fa = str(tmp_path / "ref.fa")
-    host.write_fasta(fa, "chrQ", seq)
-    pile = tmp_path / "pile"; pile.mkdir()
-    keep = np.ones(M, bool)
-    for g in rng.integers(100, M - 100, 20):
-        keep[g:g + int(rng.integers(1, 4))] = False
-    lines = cols.mpileup_text("chrQ").split(b"\n")[:-1]
-    (pile / "chrQ.mpileup").write_bytes(b"\n".join(l for i, l in enumerate(lines) if keep[i]) + b"\n")
-    refdir = os.path.join(ROOT, "oracle", "_ref")
-    subprocess.run([os.path.join(refdir, "DNA_CreateCanSnpTensor"), "-reference", fa, "-chr_pileup_dir", str(pile),
-                    "-output_dir", str(tmp_path / "tensor"), "-min_af", "0.12", "-snp_min_af", "0.12",
-                    "-indel_min_af", "0.12", "-min_coverage", "6", "-flanking_base", "16", "-num_threads", "1", "chrQ"],
-                   check=True, capture_output=True)
-    subprocess.run([os.path.join(refdir, "DNA_CreatePredictData"), "-chr_tensor_dir", str(tmp_path / "tensor"),
-                    "-reference", fa, "-output_dir", str(tmp_path / "pd"), "-num_threads", "1", "chrQ"],
-                   check=True, capture_output=True)
-    want = (tmp_path / "pd" / "chrQ.pd").read_bytes()
-    n = oracle.mpileup_to_pd(str(pile / "chrQ.mpileup"), bytes(seq), str(tmp_path / "o.pd"))
+    """Pins the oracle against the compiled reference on data that is NOT in the encode_* fixtures: a 40,000-column contig built
+    from seeds (make_golden.refbin_fresh_contig), the reference's .pd of it from refbin_pd.npz."""
+    mg = _make_golden()
+    contig, seq, text = mg.refbin_fresh_contig()
+    want = _reference_pd(mg, "fresh", contig, seq, text, "0.12", "0.12", 6, tmp_path)
+    mp = tmp_path / f"{contig}.mpileup"
+    mp.write_bytes(text)
+    n = oracle.mpileup_to_pd(str(mp), bytes(seq), str(tmp_path / "o.pd"))
     assert n == want.count(b"\n") and n > 500
     assert (tmp_path / "o.pd").read_bytes() == want
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BIN), reason="oracle/_ref not built (no reference tree)")
 @pytest.mark.parametrize("seed", [31, 32])
 def test_oracle_vs_reference_binaries_on_cut_alleles_and_random_bytes(tmp_path, seed):
     """Fresh columns of the kind behind tests/golden/encode_cut.*: indels the end of the column cuts short beside complete alleles with
     the same visible characters (tensor_maker.cpp:101 reads `advance` characters whatever the string holds), and printable bytes drawn
-    at random under a loose grammar - the .pd of the compiled reference against the oracle's, byte for byte (alt_info included)."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("make_golden", golden("make_golden.py"))
-    mg = importlib.util.module_from_spec(spec); spec.loader.exec_module(mg)
-    rng = np.random.default_rng(seed)
-    M = 3000
-    seq = rng.choice(list(b"ACGTacgtN"), M + 100, p=[.22, .22, .22, .22, .02, .02, .02, .02, .04]).astype(np.uint8)
-    cols = mg.cut_allele_columns(rng, M, seq)
-    fa = str(tmp_path / "ref.fa")
-    host.write_fasta(fa, "chrC", seq)
-    pile = tmp_path / "pile"; pile.mkdir()
-    (pile / "chrC.mpileup").write_bytes(b"".join(b"chrC\t%d\tN\t%d\t%s\t%s\n" % (i + 1, 1, c, b"I") for i, c in enumerate(cols) if c))
-    refdir = os.path.join(ROOT, "oracle", "_ref")
-    for snp, ind, mc in (("0.12", "0.12", 6), ("0.3", "0.05", 6), ("0.05", "0.4", 3)):     # (-snp_min_af and -indel_min_af apart: main.cpp:79-88)
-        out_t, out_p = tmp_path / f"tensor{snp}{ind}", tmp_path / f"pd{snp}{ind}"
-        subprocess.run([os.path.join(refdir, "DNA_CreateCanSnpTensor"), "-reference", fa, "-chr_pileup_dir", str(pile),
-                        "-output_dir", str(out_t), "-min_af", "0.12", "-snp_min_af", snp,
-                        "-indel_min_af", ind, "-min_coverage", str(mc), "-flanking_base", "16", "-num_threads", "1", "chrC"],
-                       check=True, capture_output=True)
-        subprocess.run([os.path.join(refdir, "DNA_CreatePredictData"), "-chr_tensor_dir", str(out_t),
-                        "-reference", fa, "-output_dir", str(out_p), "-num_threads", "1", "chrC"],
-                       check=True, capture_output=True)
-        want = (out_p / "chrC.pd").read_bytes()
-        n = oracle.mpileup_to_pd(str(pile / "chrC.mpileup"), bytes(seq), str(tmp_path / "o.pd"), min_af=float(snp), indel_min_af=float(ind), min_coverage=mc)
+    at random under a loose grammar - the .pd of the compiled reference (refbin_pd.npz) against the oracle's, byte for byte (alt_info
+    included), under three threshold settings."""
+    mg = _make_golden()
+    contig, seq, text = mg.refbin_cut_contig(seed)
+    mp = tmp_path / f"{contig}.mpileup"
+    mp.write_bytes(text)
+    for snp, ind, mc in mg.REFBIN_CUT_THRESHOLDS:     # (-snp_min_af and -indel_min_af apart: main.cpp:79-88)
+        want = _reference_pd(mg, f"cut{seed}_{snp}_{ind}_{mc}", contig, seq, text, snp, ind, mc, tmp_path)
+        n = oracle.mpileup_to_pd(str(mp), bytes(seq), str(tmp_path / "o.pd"), min_af=float(snp), indel_min_af=float(ind), min_coverage=mc)
         assert n == want.count(b"\n") and n > 1000, (snp, ind)
         assert (tmp_path / "o.pd").read_bytes() == want, (snp, ind)
 

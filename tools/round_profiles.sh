@@ -53,7 +53,7 @@ line() { # name details-file bench args...
   python bench.py "$@" > gpurun_out/${R}_profiles/${R}_${name}_stdout.txt 2> gpurun_out/${R}_${name}_line.err; echo "$name rc=$?"
   cp $det gpurun_out/${R}_profiles/${R}_${name}_line.json
 }
-line default bench_details.json --steps 20 --warmup 5
+line default bench_details.json --full --steps 20 --warmup 5
 line haplotype bench_details_haplotype.json --workload haplotype --steps 20 --warmup 5
 line two_stage bench_details_two_stage.json --workload two-stage --steps 3 --warmup 1
 line deep60 bench_details_deep60.json --workload deep60 --steps 8 --warmup 2
