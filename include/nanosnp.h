@@ -111,7 +111,10 @@ int nsnp_ctx_reserve(nsnp_ctx* ctx, int64_t max_sites);
  *                                                              be allocated the call returns NSNP_ENOMEM and the previous pass size and
  *                                                              workspace stay in force)
  *   "recurrence_waves"        0 auto | 1/2/4/8                 waves per workgroup of the LDS-image recurrence kernels
- *   "l0_register_stationary"  1 (default) | 0                 f16x3 layer 0: weights in VGPRs + LDS exchange of h, or LDS images
+ *   "l0_register_stationary"  2 (default) | 1 | 0             layer 0: weights in VGPRs + LDS exchange of h (1), or LDS images (0);
+ *                                                              2 = on the fp32 path the kernel of 1 with its input block (integer
+ *                                                              counts x fp32 weights) as exact bf16 partial products, fp32 sums;
+ *                                                              in the f16x3 / bf16x3 modes 2 acts as 1
  *   "l0_site_groups"          0 auto | 1/2/4                   16-site groups per workgroup of that kernel
  *   "l1_register_stationary"  1 (default) | 2 | 0             f16x3 fused layer 1: weights in VGPRs + LDS operands as four waves x four gate
  *                                                              tiles and 16 sites per workgroup (1), as eight waves x two tiles (2), or LDS images + ring (0)
@@ -119,7 +122,9 @@ int nsnp_ctx_reserve(nsnp_ctx* ctx, int64_t max_sites);
  *   "fused_l1"                1 (default) | 0                 f16x3 layer 1: projection fused into the recurrence
  *   "fused_waves"             0 auto | 4/8/12                  waves per workgroup of the fused kernel
  *   "proj1_tiles"             1..64                            row tiles per wave of the unfused projection kernel
- *   fp32 path (pileup_precision 0): "l0_register_stationary" 1 (default) | 0, "l1_register_stationary" 1 four waves x four gate
+ *   fp32 path (pileup_precision 0): "l0_register_stationary" 2 (default: the input block of layer 0 as exact bf16 partial products,
+ *   16-site workgroups; "l0_site_groups" and "l0_input_weights_in_lds" shape the kernels of 1 only) | 1 | 0 (the fp32-MFMA
+ *   kernels, bit-identical to each other), "l1_register_stationary" 1 four waves x four gate
  *   tiles (default) | 2 eight waves x two tiles | 0 LDS-image kernels with the Xp1 round trip, "l1_site_groups" 0 | 1 | 2 | 4,
  *   "l1_stagger" 0 (default) | 1 (eight-wave kernel: waves 4-7 issue a group's next input part ahead of its cell),
  *   "head_split" 1 (default) | 0 heads with the output tiles split over eight waves, "static_priority" 0..3 (f16x3
@@ -130,7 +135,8 @@ int nsnp_ctx_reserve(nsnp_ctx* ctx, int64_t max_sites);
  *   "static_priority" and "fused_*" / "proj1_tiles" on the fp32 path.
  *   bf16x3 path (pileup_precision 2): "l0_site_groups" 0 auto | 1/2/4 and "l1_site_groups" 0 auto | 1/2/4 (16-site groups per
  *   workgroup of its layer-0 / layer-1 kernel); every combination returns the same bits.
- *   Every fp32 combination returns bit-identical probabilities. */
+ *   Every fp32 combination with the same "l0_register_stationary" class (2, or 0 / 1) returns bit-identical probabilities; the
+ *   two classes differ in the low bits of the layer-0 input block (exact partial products summed in fp32 vs an fp32 fmaf chain). */
 int nsnp_ctx_set_option(nsnp_ctx* ctx, const char* name, int64_t value);
 
 /* Optional per-kernel timing: when enabled every launch of the kernels below is bracketed by a

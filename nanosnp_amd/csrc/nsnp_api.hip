@@ -50,7 +50,7 @@ extern "C" int nsnp_ctx_create(int device, nsnp_ctx** out)
     ctx->tok_fused = 0;         // three launches, no workgroup waits for another (mpileup_tokenise.hip)
     ctx->proj1_tiles = 4;
     ctx->fused_l1 = 1;
-    ctx->l0_rs = 1;
+    ctx->l0_rs = 2;             // fp32 layer 0 with the exact bf16 input block (k_pileup_l0_rsx); the other modes treat 2 as 1
     ctx->l1_rs = 1;
     ctx->l1_stagger = 0;
     ctx->head_rs = 1;
@@ -148,7 +148,7 @@ extern "C" int nsnp_ctx_set_option(nsnp_ctx* ctx, const char* name, int64_t valu
         return NSNP_OK;
     }
     if (strcmp(name, "l0_register_stationary") == 0) {
-        if (value != 0 && value != 1) return NSNP_EINVAL;
+        if (value != 0 && value != 1 && value != 2) return NSNP_EINVAL;
         ctx->l0_rs = (int)value;
         return NSNP_OK;
     }

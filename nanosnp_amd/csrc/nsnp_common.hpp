@@ -34,6 +34,7 @@ struct PileupWeightsDev {
     float* l0_whh[2];   // [16][4][64][4]  64 KB   recurrent, K = 64
     float* l0_wih[2];   // [16][1][64][4]  16 KB   input channels 0..15
     float* l0_wlast[2]; // [16][64]         4 KB   K-step 4: channels 16,17, bias, zero (register operand)
+    void*  l0_wx[2];    // [16][3][64][8] bf16 48 KB  the input block (channels 0..17, bias at K 18, K 19..31 zero) as three bf16 planes (k_pileup_l0_rsx)
     float* l1_wih[2];   // [16][8][64][4] 128 KB   K = 128 in H0 storage order
     float* l1_bias[2];  // [16][64][4]      4 KB   b_ih + b_hh in accumulator layout, gate rows scaled like the weights
     float* l1_bias_raw[2];  // the same, unscaled (layer-1 projection kernel of the f16x3 two-kernel path)
@@ -99,7 +100,8 @@ struct nsnp_ctx {
     int hap_precision;  // HaplotypeModel forward: 0 = exact fp32 MFMA (default), 1 = f16x3 split (opt-in)
     int precision;      // PileupModel forward: 0 = exact fp32 MFMA (default), 1 = f16x3 split (opt-in), 2 = bf16x3 (three bf16 terms per operand, six bf16 MFMAs per product)
     int fused_waves;    // 0 = automatic, else 4 / 8 / 12 waves per workgroup of the fused kernel
-    int l0_rs;          // f16x3: 1 = register-stationary layer-0 kernel (default), 0 = LDS-image kernel
+    int l0_rs;          // layer 0: 2 = fp32 register-stationary kernel with the exact bf16 input block (default; fp32 mode only, 1 elsewhere),
+                        // 1 = register-stationary kernel, 0 = LDS-image kernel
     int l1_rs_groups;   // 0 = automatic, else 2 / 4 groups of 16 sites per workgroup of that kernel
     int l1_rs;          // f16x3 fused layer 1: 1 = register-stationary kernel, 0 = LDS-image / ring kernel
     int l0_rs_groups;   // 0 = automatic, else 1 / 2 / 4 groups of 16 sites per workgroup

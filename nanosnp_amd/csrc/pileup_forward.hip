@@ -19,12 +19,15 @@
 //   K4 k_pileup_head  output_proj(128->128) at t=16, tanh(dense 128->256), genotype(21) and
 //                     zygosity(3) heads, softmax; weights streamed from L2.
 //
-// All dot products are exact-fp32 MFMA (v_mfma_f32_16x16x4_f32 == a k-ordered fmaf chain);
+// All dot products are exact-fp32 MFMA (v_mfma_f32_16x16x4_f32 == a k-ordered fmaf chain), except the layer-0 input block of the
+// default layer-0 kernel K1x (integer counts x fp32 weights as exact bf16 partial products, fp32 sums: k_pileup_l0_rsx);
 // sigmoid/tanh use v_exp_f32 / v_rcp_f32 (1 ulp).  Reduced schedule: 6.29 MFLOP/site executed
 // vs 12.55 MFLOP/site in the reference schedule, results identical to fp32 rounding.
 #include "nsnp_common.hpp"
 #include "nsnp_lstm_cell.hpp"
 #include "nsnp_devclock.hpp"
+#include "nsnp_bf16.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -307,7 +310,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES >= 8 ? 4 : (WAVES == 4 ? 2 : 1))
 }
 
 // ---------------------------------------------------------------------------------------------
-// K1r / K23r: REGISTER-STATIONARY fp32 recurrence kernels (default).  K1 / K3 above give one wave 16 sites and ALL 256
+// K1r / K23r: REGISTER-STATIONARY fp32 recurrence kernels (K23r the default layer 1; K1r's layer 0 runs as K1x below by default).  K1 / K3 above give one wave 16 sites and ALL 256
 // gate rows, so a 4096-site batch is only 512 waves for 1024 SIMDs and every wave re-reads the weight images from LDS
 // each step.  Here the gate tiles are split over the waves of a workgroup instead: a wave keeps the A fragments of its
 // tiles in VGPRs for the whole kernel (v_mfma_f32_16x16x4_f32 takes ONE VGPR per operand: 84 / 96 registers), and only
@@ -562,7 +565,186 @@ __global__ __launch_bounds__(256, (WXL ? 4 : (NSG == 1 ? 3 : 2))) void k_pileup_
     NSNP_DEVCLK_STOP(0)
 }
 
-// K23r: layer 1, input projection FUSED into the recurrence (no Xp1 round trip: 70 KB/site less HBM traffic than K2 + K3).
+// K1x: layer 0 of K1r with the input block EXACT on the bf16 matrix pipe (default, "l0_register_stationary" 2).  The input block
+// multiplies fp32 weights by integer counts: a weight is exactly w0 + w1 + w2 in three bf16 terms (the fp32 packer's pre-scaled
+// values, split: nsnp_bf16.hpp), a count |c| <= 256 is exactly one bf16, any other int32 -> float cast exactly c0 + c1 + c2, and
+// every partial product w_i c_j (at most 16 significant bits) is exact in the fp32 accumulator.  So the 20 v_mfma_f32_16x16x4_f32
+// of the input block (4 tiles x (4 K-steps of channels 0-15 + 1 of channels 16, 17 and the bias column)) become 3 (9 at most)
+// v_mfma_f32_16x16x32_bf16 per tile, K = 32 covering the 18 channels and the bias column: 192 instead of 640 matrix cycles per
+// wave-step, and the bf16 MFMA leaves the vector ALU free for half of its cycles.  The bias is K1r's fp32 value (scaled b_ih + b_hh)
+// split into three bf16 terms on the constant-1 column (K position 18): exact products as well.  The recurrent block is K1r's, on
+// fp32 MFMA.  Grid, W_hh registers, cell, h exchange, barrier and the H0 layout are those of k_pileup_l0_rs32<1>.
+//
+// Split level of a step (the workgroup's one group of 16 sites): 0 = every count within +-256 (products w2 c0, w1 c0, w0 c0);
+// 1 = some c1 != 0, every c2 = 0 (6 products); 2 = some c2 != 0 (9).  Products run smallest count term first (c2, c1, c0), each
+// with w2, w1, w0, so at levels 1 and 2 w0 c2 comes before the smaller w2 c1: one B fragment is live at a time (ordering every
+// product by size keeps two live and spills).  Levels 1 and 2 need counts beyond +-256 (the depth cap of a pileup is 144).
+// The order of level l restricted to the terms of a lower level is that level's order, and planes 1 and 2 of a step always hold
+// that step's terms (zeros at level 0), so a term that is zero for a site adds an exact zero: no site's bits depend on its
+// neighbours' counts.
+// Staged x image: [buf][plane 3][quarter 4][site 16][8 bf16], K position 8 q + j = channel, 18 = the constant 1 (plane 0),
+// 19..31 zero: the B fragment of lane (n, q) is one ds_read_b128 with the site index in address bits 4-7 (conflict-free, as in
+// the bf16x3 kernels).
+constexpr int RX_PLANE = 4 * 16 * 8;          // bf16 per plane of a staged x image
+
+__global__ __launch_bounds__(256, 3) void k_pileup_l0_rsx(
+    const int32_t* __restrict__ x, const int64_t* __restrict__ center_idx, int64_t N,
+    const float* __restrict__ whh0, const float* __restrict__ whh1,
+    const __bf16* __restrict__ wx0, const __bf16* __restrict__ wx1,
+    float* __restrict__ H0)
+{
+    __shared__ __attribute__((aligned(16))) float hx[2][16][RS_XROW];
+    __shared__ __attribute__((aligned(16))) __bf16 xx[2][3][RX_PLANE];
+    __shared__ int xlvl[2][4];                                          // [buf][staging wave]: split level
+    __shared__ int64_t xofs[9 * 16];                                    // staging thread -> element offset of its input piece at t = 0
+    const int dir = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = lane & 15, q = lane >> 4;
+    NSNP_DEVCLK_START
+    const int64_t base_site = (int64_t)blockIdx.x * 16;
+
+    // ---- this wave's four gate tiles -> registers: W_hh as in K1r, the input block as three bf16 planes ----
+    f32x4 Whh[4][4];
+    b8 Wx[4][3];
+    {
+        const f32x4* __restrict__ ghh = reinterpret_cast<const f32x4*>(dir ? whh1 : whh0);     // [tile][j4 4][lane]
+        const b8* __restrict__ gx = reinterpret_cast<const b8*>(dir ? wx1 : wx0);              // [tile][plane 3][lane]
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) Whh[u][j] = ghh[((4 * wave + u) * 4 + j) * 64 + lane];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) Wx[u][p] = gx[((4 * wave + u) * 3 + p) * 64 + lane];
+        }
+    }
+
+    // ---- input windows: thread i < 144 moves the 8-byte piece i % 9 (channels 2 p, 2 p + 1) of site i / 9 per step, as in K1r ----
+    const bool xon = tid < 9 * 16;
+    const int xrow = xon ? tid / 9 : 0, piece = xon ? tid % 9 : 0;
+    if (xon) {
+        const int64_t site = base_site + xrow;
+        const int64_t sc = site < N ? site : N - 1;
+        xofs[tid] = (center_idx ? (center_idx[sc] - PCENTER) * PC : sc * (PW * PC)) + 2 * piece;
+    }
+    int2 xi = int2{0, 0};
+    // (the 64-bit source offset is read back from LDS for every load: held in registers through the step it spills)
+    auto load_x = [&](int t) { if (xon) xi = *reinterpret_cast<const int2*>(x + xofs[tid] + t * PC); };
+    auto stage_x = [&](int buf) {
+        if (!xon) return;
+        int id = tid;
+        asm volatile("" : "+v"(id));
+        const int xdst = (id % 9 >> 2) * 128 + id / 9 * 8 + 2 * (id % 9 & 3);   // K position 2 piece in the [quarter][site][8] image
+        const float f0 = (float)xi.x, f1 = (float)xi.y;                 // predict.py:49 int -> float
+        b2 p0, p1 = b2{0, 0}, p2 = b2{0, 0};
+        int lvl = 0;
+        const bool big = (unsigned)xi.x + 256u > 512u || (unsigned)xi.y + 256u > 512u;
+        if (__builtin_expect(__ballot(big) == 0ull, 1)) {
+            p0 = b2{(__bf16)f0, (__bf16)f1};                            // exact: |c| <= 256
+        } else {
+            __bf16 a0, a1, a2, c0, c1, c2;
+            split3(f0, a0, a1, a2); split3(f1, c0, c1, c2);
+            p0 = b2{a0, c0}; p1 = b2{a1, c1}; p2 = b2{a2, c2};
+            const bool nz1 = (float)a1 != 0.f || (float)c1 != 0.f, nz2 = (float)a2 != 0.f || (float)c2 != 0.f;
+            lvl = __ballot(nz2) != 0ull ? 2 : (__ballot(nz1) != 0ull ? 1 : 0);
+        }
+        *reinterpret_cast<b2*>(&xx[buf][0][xdst]) = p0;
+        *reinterpret_cast<b2*>(&xx[buf][1][xdst]) = p1;
+        *reinterpret_cast<b2*>(&xx[buf][2][xdst]) = p2;
+        if (lane == 0) xlvl[buf][wave] = lvl;
+    };
+    // K positions 18..31 are never staged: the constant 1 of the bias column in plane 0, zeros elsewhere; the level of wave 3 (no
+    // staging lanes) stays zero
+    for (int i = tid; i < 2 * 3 * RX_PLANE / 8; i += 256) reinterpret_cast<b8*>(&xx[0][0][0])[i] = b8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (tid < 8) xlvl[tid >> 2][tid & 3] = 0;
+    __syncthreads();
+    if (tid < 32) xx[tid >> 4][0][2 * 128 + (tid & 15) * 8 + 2] = (__bf16)1.0f;
+    load_x(dir ? PW - 1 : 0);
+    stage_x(0);
+    if (PW > 1) load_x(dir ? PW - 2 : 1);
+    __syncthreads();
+
+    float c[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) c[u] = 0.f;
+
+    // K1r's flush: H0 rows leave through the exchange buffer one step late, thread (row = tid / 16, chunk = tid % 16 = 4 q' + j)
+    // moving exchange position 16 j + 4 q' to H0 position 16 q' + 4 j (addresses: the workgroup's base + a 32-bit offset)
+    // (the per-thread offsets are recomputed from an opaque copy of tid in every step: hipcc hoists them out of the loop otherwise,
+    // as 64-bit addresses, and spills them)
+    float* const h0wg = H0 + (base_site * PW * 2 + dir) * 64;
+    const int nrows = (int)min((int64_t)16, N - base_site);
+    auto flush_h = [&](int buf, int t) {
+        int id = tid;
+        asm volatile("" : "+v"(id));
+        const int frow = id >> 4, fcid = id & 15;
+        if (frow < nrows)
+            *reinterpret_cast<f32x4*>(h0wg + frow * PW * 128 + t * 128 + 4 * fcid) =
+                *reinterpret_cast<const f32x4*>(&hx[buf][frow][16 * (fcid & 3) + 4 * (fcid >> 2)]);
+    };
+
+    for (int s = 0; s < PW; ++s) {
+        const int t = dir ? PW - 1 - s : s;
+        const int cur = s & 1;
+        if (s > 0) flush_h(cur ^ 1, dir ? t + 1 : t - 1);
+        // (plane 0 is read beside the level: one LDS round trip between the barrier and the first MFMA)
+        const __bf16* xr = &xx[cur][0][q * 128 + n * 8];
+        const b8 xb0 = *reinterpret_cast<const b8*>(xr);
+        const int lvl = __builtin_amdgcn_readfirstlane(max(max(xlvl[cur][0], xlvl[cur][1]), max(xlvl[cur][2], xlvl[cur][3])));
+        f32x4 hn;
+        // the whole step is instantiated per split level: a branch around the extra products alone costs the registers that keep
+        // the kernel without scratch
+        auto step = [&](auto lvl_tag) __attribute__((always_inline)) {
+            constexpr int LVL = decltype(lvl_tag)::value;
+            // recurrent B fragments one K block ahead of their MFMAs, two in flight, as in K1r
+            const float* hr = &hx[cur ^ 1][n][4 * q];
+            f32x4 hb0, hb1;
+            if (s > 0) { hb0 = *reinterpret_cast<const f32x4*>(hr); hb1 = *reinterpret_cast<const f32x4*>(hr + 16); }
+            f32x4 acc[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            // count planes smallest first, each with w2, w1, w0
+#pragma unroll
+            for (int p = LVL; p >= 0; --p) {
+                const b8 b = p ? *reinterpret_cast<const b8*>(xr + p * RX_PLANE) : xb0;
+#pragma unroll
+                for (int wp = 2; wp >= 0; --wp)
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Wx[u][wp], b, acc[u], 0, 0, 0);
+            }
+            if (s > 0) {
+#define RS_KBLOCK(J, HB)                                                                               \
+                _Pragma("unroll") for (int e = 0; e < 4; ++e)                                          \
+                    _Pragma("unroll") for (int u = 0; u < 4; ++u) acc[u] = mfma4(Whh[u][J][e], HB[e], acc[u]);
+                __builtin_amdgcn_sched_barrier(0);
+                RS_KBLOCK(0, hb0)
+                __builtin_amdgcn_sched_barrier(0);
+                hb0 = *reinterpret_cast<const f32x4*>(hr + 32);
+                RS_KBLOCK(1, hb1)
+                __builtin_amdgcn_sched_barrier(0);
+                hb1 = *reinterpret_cast<const f32x4*>(hr + 48);
+                RS_KBLOCK(2, hb0)
+                __builtin_amdgcn_sched_barrier(0);
+                RS_KBLOCK(3, hb1)
+#undef RS_KBLOCK
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) hn[u] = lstm_cell(acc[u][0], acc[u][1], acc[u][2], acc[u][3], c[u]);
+        };
+        if (__builtin_expect(lvl == 0, 1)) step(std::integral_constant<int, 0>{});
+        else if (lvl == 1)                 step(std::integral_constant<int, 1>{});
+        else                               step(std::integral_constant<int, 2>{});
+        *reinterpret_cast<f32x4*>(&hx[cur][n][16 * wave + 4 * q]) = hn;
+        if (s + 1 < PW) {
+            stage_x(cur ^ 1);                                           // x of step s+1 (its buffer was last read in step s-1)
+            if (s + 2 < PW) load_x(dir ? t - 2 : t + 2);
+        }
+        lds_barrier();
+    }
+    flush_h((PW - 1) & 1, dir ? 0 : PW - 1);
+    NSNP_DEVCLK_STOP(0)
+}
+
+// K23r: layer 1,input projection FUSED into the recurrence (no Xp1 round trip: 70 KB/site less HBM traffic than K2 + K3).
 // grid = (ceil(N / (16 NSG)), 2), block = 512: wave w owns gate tiles 2w, 2w+1 (W_ih1 K = 128 and W_hh1 K = 64: 96 VGPRs).
 // LDS: the h0_t rows of the workgroup's sites copied from H0 one step ahead (double-buffered; the 16-byte chunk (d, q, c) of
 // a row is stored at slot 16 d + 4 c + q so that the fragment reads are conflict-free) and the h1 exchange rows.
@@ -1180,13 +1362,15 @@ int nsnp_pileup_pack_weights(nsnp_ctx* ctx, const float* const* w)
     const size_t n_whh = 16 * 4 * 256, n_wih0 = 16 * 1 * 256, n_wlast = 16 * 64, n_wih1 = 16 * 8 * 256,
                  n_b1 = 16 * 256, n_proj = 8 * 8 * 256, n_pb = 8 * 256, n_dense = 16 * 8 * 256, n_db = 16 * 256,
                  n_head = 2 * 16 * 256, n_hb = 2 * 256;
-    const size_t total = 2 * (n_whh + n_wih0 + n_wlast + n_wih1 + 2 * n_b1 + n_whh) + n_proj + n_pb + n_dense + n_db + n_head + n_hb;
+    const size_t n_wx = 16 * 3 * 64 * 8 / 2;   // (bf16 planes: two per float of the arena)
+    const size_t total = 2 * (n_whh + n_wih0 + n_wlast + n_wx + n_wih1 + 2 * n_b1 + n_whh) + n_proj + n_pb + n_dense + n_db + n_head + n_hb;
     std::vector<float> host(total);
     size_t off = 0;
     auto take = [&](size_t n) { float* p = host.data() + off; off += n; return p; };
-    float* h_l0_whh[2]; float* h_l0_wih[2]; float* h_l0_wlast[2]; float* h_l1_wih[2]; float* h_l1_b[2]; float* h_l1_braw[2]; float* h_l1_whh[2];
+    float* h_l0_whh[2]; float* h_l0_wih[2]; float* h_l0_wlast[2]; float* h_l0_wx[2];
+    float* h_l1_wih[2]; float* h_l1_b[2]; float* h_l1_braw[2]; float* h_l1_whh[2];
     for (int d = 0; d < 2; ++d) {
-        h_l0_whh[d] = take(n_whh); h_l0_wih[d] = take(n_wih0); h_l0_wlast[d] = take(n_wlast);
+        h_l0_whh[d] = take(n_whh); h_l0_wih[d] = take(n_wih0); h_l0_wlast[d] = take(n_wlast); h_l0_wx[d] = take(n_wx);
         h_l1_wih[d] = take(n_wih1); h_l1_b[d] = take(n_b1); h_l1_braw[d] = take(n_b1); h_l1_whh[d] = take(n_whh);
     }
     float* h_proj = take(n_proj); float* h_pb = take(n_pb); float* h_dense = take(n_dense); float* h_db = take(n_db);
@@ -1221,6 +1405,12 @@ int nsnp_pileup_pack_weights(nsnp_ctx* ctx, const float* const* w)
                 else if (kq == 2) v = l0[2][tr] + l0[3][tr];   // b_ih + b_hh rides on a constant-1 input
                 h_l0_wlast[d][tile * 64 + lane] = v;
             }
+        // k_pileup_l0_rsx: the same scaled fp32 values of channels 0..17 and of the bias (K position 18, the constant-1 column)
+        // split into three bf16 planes, K 19..31 zero
+        pack_b3(reinterpret_cast<uint16_t*>(h_l0_wx[d]), 16, 1, [&](int row, int, int q, int j) {
+            const int k = 8 * q + j, tr = gate_row(row);
+            return k < PC ? l0[0][tr * PC + k] : (k == PC ? l0[2][tr] + l0[3][tr] : 0.f);
+        });
         m = MatRef{l1[0], 2 * PH, nullptr, nullptr};  nsnp_pack_image(h_l1_wih[d], 16, 8, f_wih1, &m);
         for (int tile = 0; tile < 16; ++tile)
             for (int lane = 0; lane < 64; ++lane)
@@ -1253,6 +1443,7 @@ int nsnp_pileup_pack_weights(nsnp_ctx* ctx, const float* const* w)
     auto dev = [&](const float* hp) { return pw.arena + (hp - host.data()); };
     for (int d = 0; d < 2; ++d) {
         pw.l0_whh[d] = dev(h_l0_whh[d]); pw.l0_wih[d] = dev(h_l0_wih[d]); pw.l0_wlast[d] = dev(h_l0_wlast[d]);
+        pw.l0_wx[d] = dev(h_l0_wx[d]);
         pw.l1_wih[d] = dev(h_l1_wih[d]); pw.l1_bias[d] = dev(h_l1_b[d]); pw.l1_bias_raw[d] = dev(h_l1_braw[d]); pw.l1_whh[d] = dev(h_l1_whh[d]);
     }
     pw.proj_w = dev(h_proj); pw.proj_b = dev(h_pb); pw.dense_w = dev(h_dense); pw.dense_b = dev(h_db);
@@ -1308,7 +1499,13 @@ int nsnp_pileup_forward_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* cen
         while (wpb > 1 && waves_total / wpb < (int64_t)ctx->n_cu / 2) wpb >>= 1;
         if (ctx->force_wpb) wpb = ctx->force_wpb;
         const dim3 g_rec((unsigned)NSNP_CDIV(n, 16 * wpb), 2);
-        if (ctx->l0_rs) {
+        if (ctx->l0_rs == 2) {
+            ScopedKernelTimer tm(ctx, NSNP_K_L0, s);
+            // 16 sites per workgroup, three workgroups per SIMD set ("l0_site_groups" and "l0_input_weights_in_lds" shape the
+            // kernels of value 1 only)
+            hipLaunchKernelGGL(k_pileup_l0_rsx, dim3((unsigned)NSNP_CDIV(n, 16), 2), dim3(256), 0, s, xc, cc, n,
+                               pw.l0_whh[0], pw.l0_whh[1], (const __bf16*)pw.l0_wx[0], (const __bf16*)pw.l0_wx[1], ctx->ws_h0);
+        } else if (ctx->l0_rs) {
             ScopedKernelTimer tm(ctx, NSNP_K_L0, s);
             // 16 sites per workgroup (three independent workgroups per SIMD set) measured best at every batch size; 32 / 64
             // sites (software-pipelined over the site groups) stay available as options

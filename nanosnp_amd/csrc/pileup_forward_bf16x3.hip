@@ -22,26 +22,16 @@
 // [site][dir][64 units] fp32.
 #include "nsnp_common.hpp"
 #include "nsnp_lstm_cell.hpp"
+#include "nsnp_bf16.hpp"
 #include <type_traits>
 
 namespace {
-
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f32x4 mfma_b(b8 a, b8 b, f32x4 c)
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
-// v = p0 + p1 + p2 exactly (see the header); hipcc emits v_cvt_pk_bf16_f32 for the casts (round to nearest even, NaN stays NaN)
-__device__ __forceinline__ void split3(float v, __bf16& p0, __bf16& p1, __bf16& p2)
-{
-    p0 = (__bf16)v;
-    const float r1 = v - (float)p0;
-    p1 = (__bf16)r1;
-    p2 = (__bf16)(r1 - (float)p1);
-}
+// split3 (v = p0 + p1 + p2 exactly, see the header): nsnp_bf16.hpp
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // the six products of one K block for NT tiles, smallest terms first; a[t][plane], b[plane]; MFMAs on one accumulator are NT issue
@@ -809,33 +799,7 @@ namespace {
 
 inline int gate_row(int row) { const int i = row >> 4, r = row & 15; return (r & 3) * PH + 4 * i + (r >> 2); }
 
-inline uint16_t bf16_rne(float v)
-{
-    uint32_t u; memcpy(&u, &v, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);     // NaN stays NaN
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-inline float bf16_f32(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float v; memcpy(&v, &u, 4); return v; }
-
-// img[tile][kb][plane][lane][j]  <-  f(row = 16 tile + (lane & 15), kb, q = lane >> 4, j)
-template <typename F>
-void pack_b3(uint16_t* img, int n_tiles, int n_kb, F f)
-{
-    for (int tile = 0; tile < n_tiles; ++tile)
-        for (int kb = 0; kb < n_kb; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const float v = f(16 * tile + (lane & 15), kb, lane >> 4, j);
-                    const uint16_t p0 = bf16_rne(v);
-                    const float r1 = v - bf16_f32(p0);
-                    const uint16_t p1 = bf16_rne(r1);
-                    const uint16_t p2 = bf16_rne(r1 - bf16_f32(p1));
-                    const size_t e = (((size_t)tile * n_kb + kb) * 3) * 64 + lane;
-                    img[e * 8 + j] = p0;
-                    img[(e + 64) * 8 + j] = p1;
-                    img[(e + 128) * 8 + j] = p2;
-                }
-}
+// bf16_rne / pack_b3: nsnp_bf16.hpp
 
 }  // namespace
 
