@@ -288,6 +288,21 @@ int nsnp_hap_arrange_reads(nsnp_ctx* ctx, const int32_t* seq, const int32_t* bq,
                            const int32_t* hap, const int32_t* n_reads, int64_t N, int R, int L, int D_out,
                            int32_t* oseq, int32_t* obq, int32_t* omq, int32_t* ohap, int32_t* depth, void* stream);
 
+/* The same with a choice of the order among reads with equal centre HP (the reference sorts with pandas' default quicksort,
+ * numpy.argsort(kind="quicksort"); the order among ties decides which reads a D_out cut keeps and the row order of every bin):
+ *   NSNP_TIE_STABLE  ties keep their input order (nsnp_hap_arrange_reads).  No numpy build is claimed: the reference's bins equal
+ *                    these up to the order inside each HP group, and at sites deeper than D_out up to which reads are kept.
+ *   NSNP_TIE_NUMPY1  NumPy 1.x's scalar introsort (aquicksort_ with its aheapsort_ fallback), exactly: the order of NumPy 1.24
+ *                    and earlier on every CPU - the reference's environment - and of later NumPy with SIMD sort dispatch disabled.
+ *                    With the rows in the order the reference first sees the reads, the planes equal its bins row for row.
+ * NumPy 1.25 and later with AVX-512 or AVX2 sort dispatch follow a CPU-dependent order that neither mode claims.
+ * Any other tie_order is NSNP_EINVAL.  Both modes accept the same shapes (NSNP_ESHAPE beyond 64 KB of LDS: 2R + D_out + 1 words). */
+#define NSNP_TIE_STABLE 0
+#define NSNP_TIE_NUMPY1 1
+int nsnp_hap_arrange_reads2(nsnp_ctx* ctx, const int32_t* seq, const int32_t* bq, const int32_t* mq,
+                            const int32_t* hap, const int32_t* n_reads, int64_t N, int R, int L, int D_out, int tie_order,
+                            int32_t* oseq, int32_t* obq, int32_t* omq, int32_t* ohap, int32_t* depth, void* stream);
+
 /* host_tensors: the 58 fp32 tensors of model_dev.LSTMNetwork.state_dict() in order
  * (pileup_encoder 26, haplotype_encoder 26, forward_layer 6), HOST pointers.
  * hidden must be a multiple of 64; F = 105 input features; 3 layers as ont_haplotype.yaml. */

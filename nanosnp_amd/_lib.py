@@ -59,6 +59,7 @@ _SIGNATURES = {
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nsnp_hap_features_i8": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nsnp_hap_arrange_reads": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "nsnp_hap_arrange_reads2": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "nsnp_hap_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int] + [C.c_int] * 5),
     "nsnp_hap_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
@@ -428,15 +429,21 @@ class Context:
               self.handle, "nsnp_hap_features")
         return out
 
-    def hap_arrange_reads(self, seq, bq, mq, hap, d_out, n_reads=None, stream=None):
+    TIE_ORDERS = {"stable": 0, "numpy1": 1}       # NSNP_TIE_STABLE, NSNP_TIE_NUMPY1
+
+    def hap_arrange_reads(self, seq, bq, mq, hap, d_out, n_reads=None, stream=None, tie_order="stable"):
+        """tie_order: "stable" (ties keep their input order) or "numpy1" (NumPy 1.x argsort(kind="quicksort"), the reference's
+        environment: with the rows in the order the reference first sees the reads, the planes equal its bins row for row)"""
         import torch
+        if tie_order not in self.TIE_ORDERS:
+            raise NanoSNPError(f"hap_arrange_reads: tie_order must be one of {sorted(self.TIE_ORDERS)}, not {tie_order!r}")
         n, r, l = seq.shape
         outs = [torch.empty((n, d_out, l), dtype=torch.int32, device=seq.device) for _ in range(4)]
         depth = torch.empty(n, dtype=torch.int32, device=seq.device)
-        check(self.lib.nsnp_hap_arrange_reads(self.handle, _dptr(seq), _dptr(bq), _dptr(mq), _dptr(hap), _dptr(n_reads),
-                                              n, r, l, int(d_out), *[_dptr(o) for o in outs], _dptr(depth),
-                                              _stream_ptr(stream)),
-              self.handle, "nsnp_hap_arrange_reads")
+        check(self.lib.nsnp_hap_arrange_reads2(self.handle, _dptr(seq), _dptr(bq), _dptr(mq), _dptr(hap), _dptr(n_reads),
+                                               n, r, l, int(d_out), self.TIE_ORDERS[tie_order], *[_dptr(o) for o in outs],
+                                               _dptr(depth), _stream_ptr(stream)),
+              self.handle, "nsnp_hap_arrange_reads2")
         return outs[0], outs[1], outs[2], outs[3], depth
 
     def hap_load_weights(self, tensors, n_features=105, hidden=256, n_layers=3, n_gt=10, n_zy=3):

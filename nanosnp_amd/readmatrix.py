@@ -6,7 +6,8 @@ feature kernel consumes.
                     positions (base code / HP tag / base quality / mapping quality; 0 = the read does not cover the column)
     group_planes    :137-207 + write_to_bins.py:15-61   per group the 11 support columns and the 33-wide window, reads kept when
                     their centre base is non-zero, ordered by the HP tag at the centre, padded with -2 / cut at D rows -- on the
-                    device through nsnp_hap_arrange_reads (the planes never visit the host again before the feature kernel)
+                    device through nsnp_hap_arrange_reads2 (the planes never visit the host again before the feature kernel);
+                    tie_order="numpy1" reproduces the reference's bins row for row
 
 The alignment file is whatever the caller's BAM library hands over: any object with pysam's ``pileup(contig, start, end,
 min_base_quality=0, min_mapping_quality=0)`` iteration (columns with ``.pos``, ``.n``, ``.pileups``; pileup reads with
@@ -123,10 +124,12 @@ def group_slices(rm, pileup_flanking_size=16):
     return out
 
 
-def group_planes(ctx, rm, max_haplotype_depth, max_pileup_depth, pileup_flanking_size=16):
+def group_planes(ctx, rm, max_haplotype_depth, max_pileup_depth, pileup_flanking_size=16, tie_order="stable"):
     """-> (candidate_positions, haplotype_positions, (seq, baseq, mapq, hap) int32 cuda [N, D_h, 11], the same [N, D_p, 33],
     depths_h, depths_p): reads filtered on the centre base, HP-sorted, padded with -2 and cut at D, exactly what
-    write_to_bins.py stores and nanosnp_amd.predict.predict_haplotype consumes (plus reference rows)."""
+    write_to_bins.py stores and nanosnp_amd.predict.predict_haplotype consumes (plus reference rows).
+    tie_order (Context.hap_arrange_reads): "numpy1" orders equal HP tags as the reference's NumPy 1.x quicksort does, so the planes
+    equal its bins row for row and a cut keeps the reads it keeps; "stable" keeps ties in read order."""
     import torch
     sl = group_slices(rm, pileup_flanking_size)
     dev = torch.device("cuda", ctx.device)
@@ -135,6 +138,6 @@ def group_planes(ctx, rm, max_haplotype_depth, max_pileup_depth, pileup_flanking
     for key, D in (("hap_cols", max_haplotype_depth), ("pile_cols", max_pileup_depth)):
         idx = torch.from_numpy(np.stack([s[key] for s in sl])).to(dev)                   # [N, L]
         mats = [f[:, idx].permute(1, 0, 2).contiguous() for f in full]                    # [N, R, L] views of the one matrix
-        outs.append(ctx.hap_arrange_reads(*mats, int(D)))
+        outs.append(ctx.hap_arrange_reads(*mats, int(D), tie_order=tie_order))
     (hs, hb, hm, hh, dh), (ps, pb, pm, ph, dp) = outs
     return ([s["candidate"] for s in sl], [s["haplotype_positions"] for s in sl], (hs, hb, hm, hh), (ps, pb, pm, ph), dh, dp)
