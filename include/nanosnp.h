@@ -217,6 +217,37 @@ int nsnp_pileup_encode_columns2(nsnp_ctx* ctx, const uint8_t* bases, const int64
                                 const uint8_t* ref, int64_t M, double snp_min_af, double indel_min_af, int min_coverage,
                                 int32_t* counts, int32_t* depth, uint8_t* flags, void* stream);
 
+/* BED bitmaps (the reference's -extended_confident_bed / -confident_bed, common/bed_intv_list.cpp): one bitmap per contig, device
+ * uint32 [(n_bits + 31) / 32]; bit i - the contig's 0-based base i, set by every interval [from, to) with from <= i < to - is bit (i & 31)
+ * of word i >> 5 (little-endian uint32: bit i & 7 of byte i >> 3).  n_bits is the contig length.  Every bit outside [0, n_bits) reads as 0
+ * (nothing is read out of bounds; the reference keeps one list over all contigs and reads the next contig's first bits there). */
+
+/* nsnp_pileup_encode_columns2 with three additions, all optional: max_del: device int32 [M] receives the column's max_del_length
+ * (main.cpp:183: the largest declared length among its counted deletions - those of declared length <= 60, one the end of the column
+ * cuts short with its declared length, tensor_maker.cpp:97-103,158 - or 0); pos: device int64 [M]; conf_bits / conf_n_bits: the
+ * confident bitmap - then NSNP_FLAG_CANDIDATE additionally needs a set bit in the 0-based range [pos - 1, pos + max_del_length + 1)
+ * (main.cpp:194; two bits without a deletion: a site whose own base lies just left of an interval still passes).  counts, depth and the
+ * other flag bits equal nsnp_pileup_encode_columns2's bit for bit; with conf_bits NULL so does NSNP_FLAG_CANDIDATE.
+ * NSNP_EINVAL: conf_bits without pos, conf_bits with conf_n_bits <= 0, conf_n_bits != 0 without conf_bits. */
+int nsnp_pileup_encode_columns3(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off,
+                                const uint8_t* ref, const int64_t* pos, int64_t M, double snp_min_af, double indel_min_af,
+                                int min_coverage, const uint32_t* conf_bits, int64_t conf_n_bits,
+                                int32_t* counts, int32_t* depth, uint8_t* flags, int32_t* max_del, void* stream);
+
+/* The extended-BED stage, in front of the encode (main.cpp:165-169: a line at position p is skipped unless bit p - 1 of the bitmap is set,
+ * before anything else sees it): pos / col_off / bases / ref as nsnp_pileup_encode_columns takes them (M columns) -> the same four arrays
+ * holding only the K kept columns, in order, bases densely repacked; none of the outputs may be its input.  Output capacities are those of
+ * the inputs (pos_out, ref_out [M], off_out [M + 1], bases_out [col_off[M]]), and entries [K, M) are filled so that the unchanged encode
+ * and selection over all M columns make nothing of them: empty columns (off_out[K..M] = the kept byte count), reference byte 'N',
+ * position -2^62 (no step to or from it is + 1) - no count has to come back to the host between the calls.  (When NO byte is kept the
+ * encode's 16-byte staging of an all-empty wave reads the 16 bytes in front of its bases: give bases_out 16 readable bytes in front, as
+ * nanosnp_amd does.)  meta: int64 [4] in any memory the device can write = { K, kept bytes, kept columns in front of column own_lo, in
+ * front of column own_hi }: the images of a streamed chunk's own range under the compaction (nsnp_pileup_select_sites_range_dev reads
+ * them there).  Three launches; scratch lives in the context (one call at a time per context). */
+int nsnp_pileup_filter_columns(nsnp_ctx* ctx, const int64_t* pos, const int64_t* col_off, const uint8_t* bases, const uint8_t* ref,
+                               int64_t M, const uint32_t* bits, int64_t n_bits, int64_t own_lo, int64_t own_hi,
+                               int64_t* pos_out, int64_t* off_out, uint8_t* bases_out, uint8_t* ref_out, int64_t* meta, void* stream);
+
 /* pos: device int64 [M], the positions in line order (fold the contig index into the high bits
  * when several contigs share a call).  A site is emitted when its 33 columns are 33 consecutive
  * positions - every step + 1, as main.cpp:174-178 resets its window at any other step: positions
@@ -232,6 +263,11 @@ int nsnp_pileup_select_sites(nsnp_ctx* ctx, const int64_t* pos, const uint8_t* f
  * read) are entries [meta[1], meta[2]) of the ascending list.  No count comes back through the host. */
 int nsnp_pileup_select_sites_range(nsnp_ctx* ctx, const int64_t* pos, const uint8_t* flags, int64_t M, int64_t own_lo, int64_t own_hi,
                                    int64_t* center_idx, int64_t cap, int64_t* meta, void* stream);
+
+/* nsnp_pileup_select_sites_range with the two bounds read from memory the device can read - own: int64 [2] = { own_lo, own_hi }, e.g. meta + 2
+ * of nsnp_pileup_filter_columns - when the launches run: a streamed chunk is filtered, encoded and selected without a host round trip. */
+int nsnp_pileup_select_sites_range_dev(nsnp_ctx* ctx, const int64_t* pos, const uint8_t* flags, int64_t M, const int64_t* own,
+                                       int64_t* center_idx, int64_t cap, int64_t* meta, void* stream);
 
 /* The per-site values PileupModel/predict.py:52-65 hands to its row loop, as one [N,13] float64 array on the device: position, argmax of
  * the genotype / zygosity heads, their maxima, the coverage channels x[:, 16, [0, 1, 2, 3, 9, 10, 11, 12]] (predict.py:63) of the centre

@@ -17,6 +17,7 @@ this package holds only the host-side mirror of the reference's interface for th
     merge                        stage-4 group selection and the final merge (select_hetesnp_homosnp.py, scripts/merge.py)
     sitefile                     flat binary containers in place of the HDF5 bins
     dist                         static site sharding over the GPUs of a node + result gather
+    bed                          BED region files -> per-contig bitmaps (DNA_CreateCanSnpTensor -extended_confident_bed / -confident_bed)
     host                         native readers / synthetic generators (libnanosnp_host.so)
 
 There is no CPU fallback: without the built extension and a gfx950 device every compute entry

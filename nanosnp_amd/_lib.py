@@ -48,6 +48,12 @@ _SIGNATURES = {
     "nsnp_pileup_encode_columns2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                               C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]),
+    "nsnp_pileup_encode_columns3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_filter_columns": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
+    "nsnp_pileup_select_sites_range_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_void_p]),
     "nsnp_pileup_select_sites": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_gather_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
@@ -319,6 +325,78 @@ class Context:
                                                    _dptr(counts), _dptr(depth), _dptr(flags), _stream_ptr(stream)),
               self.handle, "nsnp_pileup_encode_columns2")
         return counts, depth, flags
+
+    def pileup_encode_columns3(self, bases, col_off, ref, pos=None, conf_bits=None, conf_n_bits=0, min_af=0.12, min_coverage=6, stream=None,
+                               indel_min_af=None, want_max_del=True):
+        """pileup_encode_columns with the confident BED and max_del_length (nsnp_pileup_encode_columns3) -> (counts, depth, flags, max_del
+        int32 [M] or None).  conf_bits: device uint32 bitmap of the contig (bed.bed_bitmap), conf_n_bits its bits (the contig length); pos:
+        device int64 [M], needed with a bitmap."""
+        import torch
+        assert bases.is_cuda and bases.dtype == torch.uint8 and col_off.dtype == torch.int64 and ref.dtype == torch.uint8
+        m = ref.shape[0]
+        dev = ref.device
+        if conf_bits is not None:
+            if conf_bits.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not conf_bits.is_cuda or not conf_bits.is_contiguous():
+                raise NanoSNPError("conf_bits: a contiguous device tensor of 32-bit words")
+            if conf_bits.numel() * 32 < int(conf_n_bits):
+                raise NanoSNPError(f"conf_bits: {conf_bits.numel()} words hold fewer than conf_n_bits = {int(conf_n_bits)} bits")
+        if pos is not None and (pos.dtype != torch.int64 or pos.shape[0] != m or not pos.is_contiguous()):
+            raise NanoSNPError("pos: a contiguous int64 tensor of one position per column")
+        counts = torch.empty((m, 18), dtype=torch.int32, device=dev)
+        depth = torch.empty(m, dtype=torch.int32, device=dev)
+        flags = torch.empty(m, dtype=torch.uint8, device=dev)
+        max_del = torch.empty(m, dtype=torch.int32, device=dev) if want_max_del else None
+        check(self.lib.nsnp_pileup_encode_columns3(self.handle, _dptr(bases), _dptr(col_off), _dptr(ref), _dptr(pos), m,
+                                                   float(min_af), float(min_af if indel_min_af is None else indel_min_af), int(min_coverage),
+                                                   _dptr(conf_bits), int(conf_n_bits), _dptr(counts), _dptr(depth), _dptr(flags), _dptr(max_del),
+                                                   _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_encode_columns3")
+        return counts, depth, flags, max_del
+
+    FILTER_FRONT_PAD = 64     # readable bytes in front of the filtered bases (include/nanosnp.h: the encode of an all-empty wave reads 16)
+
+    def pileup_filter_columns(self, pos, col_off, bases, ref, bits, n_bits, own_lo=0, own_hi=None, meta=None, out=None, stream=None):
+        """The extended-BED stage (nsnp_pileup_filter_columns): the columns whose position p has bit p - 1 set, compacted, on the device ->
+        (pos_out [M], off_out [M + 1], bases_out, ref_out [M], meta).  Entries behind the meta[0] kept columns are filled so that encode +
+        select over all M make nothing of them.  meta: int64 [4] on the device or pinned = {K, kept bytes, kept columns in front of own_lo, of
+        own_hi}; out: the four output tensors of an earlier call to reuse (capacities >= these inputs)."""
+        import torch
+        m = int(pos.shape[0])
+        dev = pos.device
+        own_hi = m if own_hi is None else own_hi
+        nb = int(bases.numel())
+        if bits is not None and (bits.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not bits.is_cuda or not bits.is_contiguous()):
+            raise NanoSNPError("bits: a contiguous device tensor of 32-bit words")
+        if bits is not None and bits.numel() * 32 < int(n_bits):
+            raise NanoSNPError(f"bits: {bits.numel()} words hold fewer than n_bits = {int(n_bits)} bits")
+        if col_off.shape[0] != m + 1 or ref.shape[0] != m:
+            raise NanoSNPError("filter_columns: col_off [M + 1] and ref [M] must match pos [M]")
+        if out is None:
+            pad = self.FILTER_FRONT_PAD
+            out = (torch.empty(max(m, 1), dtype=torch.int64, device=dev), torch.empty(m + 1, dtype=torch.int64, device=dev),
+                   torch.empty(pad + max(nb, 1), dtype=torch.uint8, device=dev)[pad:], torch.empty(max(m, 1), dtype=torch.uint8, device=dev))
+        po, oo, bo, ro = out
+        if po.numel() < m or oo.numel() < m + 1 or bo.numel() < nb or ro.numel() < m:
+            raise NanoSNPError("filter_columns: output buffers too small")
+        meta = meta if meta is not None else torch.zeros(4, dtype=torch.int64, device=dev)
+        check(self.lib.nsnp_pileup_filter_columns(self.handle, _dptr(pos), _dptr(col_off), _dptr(bases), _dptr(ref), m, _dptr(bits), int(n_bits),
+                                                  int(own_lo), int(own_hi), _dptr(po), _dptr(oo), _dptr(bo), _dptr(ro), meta.data_ptr(),
+                                                  _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_filter_columns")
+        return po[:m], oo[:m + 1], bo[:max(nb, 1)], ro[:m], meta
+
+    def pileup_select_sites_range_dev(self, pos, flags, own, meta, stream=None):
+        """pileup_select_sites_range with the bounds {own_lo, own_hi} read from `own` (int64 [2], device or pinned: e.g. meta[2:] of
+        pileup_filter_columns) when the launches run"""
+        import torch
+        m = pos.shape[0]
+        center = torch.empty(max(m, 1), dtype=torch.int64, device=pos.device)
+        if own.dtype != torch.int64 or own.numel() < 2 or not (own.is_cuda or own.is_pinned()):
+            raise NanoSNPError("own: int64 [2] on the device or pinned")
+        check(self.lib.nsnp_pileup_select_sites_range_dev(self.handle, _dptr(pos), _dptr(flags), m, own.data_ptr(), _dptr(center), m,
+                                                          meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_select_sites_range_dev")
+        return center
 
     def pileup_select_sites(self, pos, flags, cap=None, stream=None):
         import torch

@@ -127,6 +127,7 @@ struct nsnp_ctx {
     CatWeightsDev* cw;
     void*  cat_ws; size_t cat_ws_bytes;
     int64_t* sel_tmp; size_t sel_tmp_bytes;   // select_sites scratch
+    int64_t* fil_tmp; size_t fil_tmp_bytes;   // filter_columns scratch: kept columns and bytes per tile (pileup_encode.hip)
     void* tok_ws; size_t tok_ws_bytes;        // mpileup tokeniser scratch: 20 bytes per 8 KB tile of text (mpileup_tokenise.hip)
     int tok_fused;      // mpileup tokeniser: 0 = three launches (default), 1 = one launch, chained scan (opt-in: its tiles spin on their predecessors)
     // column encode: AF threshold + smallest-passing-count table of the last min_af (pileup_encode.hip)

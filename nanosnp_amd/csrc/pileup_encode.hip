@@ -147,6 +147,47 @@ __device__ __forceinline__ void scan_column_exact(P bases, int64_t begin, int64_
     mx = rescan_maxima(bases, begin, end);
 }
 
+// main.cpp:184,194: max_del_length of a column = the largest DECLARED length among its counted deletions (tensor_maker.cpp:158: key.size() - 1,
+// also for an allele the end of the column cuts short), 0 without one.  Same scan as scan_column_exact.
+template <typename P>
+__device__ __forceinline__ int max_del_exact(P bases, int64_t begin, int64_t end)
+{
+    int md = 0;
+    for (int64_t i = begin; i < end;) {
+        const int b = bases[i];
+        if (b == '+' || b == '-') {
+            ++i;
+            long long adv = 0;
+            while (i < end && bases[i] >= '0' && bases[i] <= '9') { adv = adv > 100000000 ? adv : adv * 10 + (bases[i] - '0'); ++i; }
+            if (b == '-' && adv <= MAX_INDEL && adv > md) md = (int)adv;
+            i = adv < end - i ? i + adv : end;
+        } else if (b == '^') i += 2;
+        else ++i;
+    }
+    return md;
+}
+
+// BED bitmap: bit i of a contig (0-based base i) is bit (i & 31) of word i >> 5; n_bits bits, (n_bits + 31) / 32 words; every bit outside
+// [0, n_bits) reads as 0.  bed_any: is any bit of the half-open range [lo, hi) set (bed_intv_list.cpp:57-74)
+__device__ __forceinline__ bool bed_bit(const uint32_t* __restrict__ bits, int64_t n_bits, int64_t i)
+{
+    return i >= 0 && i < n_bits && ((bits[i >> 5] >> (i & 31)) & 1u);
+}
+__device__ __forceinline__ bool bed_any(const uint32_t* __restrict__ bits, int64_t n_bits, int64_t lo, int64_t hi)
+{
+    if (lo < 0) lo = 0;
+    if (hi > n_bits) hi = n_bits;
+    if (lo >= hi) return false;
+    const int64_t w0 = lo >> 5, w1 = (hi - 1) >> 5;
+    for (int64_t w = w0; w <= w1; ++w) {
+        uint32_t m = 0xffffffffu;
+        if (w == w0) m &= 0xffffffffu << (lo & 31);
+        if (w == w1) m &= 0xffffffffu >> (31 - ((hi - 1) & 31));
+        if (bits[w] & m) return true;
+    }
+    return false;
+}
+
 // The candidate tests compare (double)count / (double)depth with min_af (tensor_maker.cpp:195-228: float64 division).  For
 // integers count, depth < 2^31 the correctly rounded quotient is >= a double a exactly when count / depth >= the midpoint tau
 // between a and its predecessor (the quotient can never BE that midpoint: tau has an odd 54- or 55-bit mantissa, which a
@@ -231,6 +272,14 @@ constexpr int ENC_NBLK = 8;                          // 32-byte blocks of a colu
 static_assert(STAGE_BYTES >= 64 * NCH * 4, "the stage buffer doubles as the 64 x 18 output transposition buffer");
 static_assert(STAGE_BYTES <= 8192, "staged positions are kept in 13 bits");
 static_assert(4 * (ENC_WAVES * (STAGE_BYTES + (ENC_ECAP + P3_STEP) * 8 + 64 * 32) + 4096 + 2 * 512) <= 160 * 1024, "four blocks per CU (LDS)");
+// the kernel of nsnp_pileup_encode_columns3 keeps a ninth accumulator word per column (the longest counted deletion) and pays for it with
+// 32 entries of the opener list (a 60x wave then takes two segments a little more often), so that it, too, runs four blocks per CU
+constexpr int ENC_ECAP_BED = ENC_ECAP - 32;
+static_assert(4 * (ENC_WAVES * (STAGE_BYTES + (ENC_ECAP_BED + P3_STEP) * 8 + 64 * 36) + 4096 + 2 * 512) <= 160 * 1024, "four blocks per CU (LDS)");
+
+// what nsnp_pileup_encode_columns3 adds (all optional): max_del[M] receives max_del_length; with bits, NSNP_FLAG_CANDIDATE also needs a set
+// bit in [pos - 1, pos + max_del_length + 1) (main.cpp:194)
+struct EncBed { const int64_t* pos; const uint32_t* bits; int64_t n_bits; int32_t* max_del; };
 
 // inclusive prefix sum over the 64 lanes of a wave with DPP row shifts and row broadcasts (no LDS)
 __device__ __forceinline__ int wave_scan_incl(int v)
@@ -248,12 +297,16 @@ __device__ __forceinline__ int wave_scan_incl(int v)
 #ifndef NSNP_ENC_MINW
 #define NSNP_ENC_MINW 4
 #endif
-__global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
+// BED = false is k_encode_columns as it always was (nothing below depends on `bed` there); BED = true: k_encode_columns_bed
+template <bool BED>
+__device__ __forceinline__ void encode_columns_body(
     const uint8_t* __restrict__ bases, const int64_t* __restrict__ col_off, const uint8_t* __restrict__ ref,
-    int64_t M, AfThreshold af, const AfTable aft, AfThreshold afi, const AfTable afti, int min_cov, int32_t* __restrict__ counts,
+    int64_t M, const AfThreshold& af, const AfTable& aft, const AfThreshold& afi, const AfTable& afti, int min_cov, int32_t* __restrict__ counts,
     int32_t* __restrict__ depth_out,
-    uint8_t* __restrict__ flags)
+    uint8_t* __restrict__ flags, const EncBed& bed)
 {
+    constexpr int ECAP = BED ? ENC_ECAP_BED : ENC_ECAP;            // opener entries of a segment
+    constexpr int NACC = BED ? 9 : 8;
     __shared__ uint32_t af_min[128];          // 256 x uint16: smallest passing count by depth (make_af_table): the SNP threshold
     __shared__ uint32_t afi_min[128];         // the same for the indel threshold (-indel_min_af; the same table when the two are equal)
     __shared__ __attribute__((aligned(16))) uint8_t stage_b[ENC_WAVES][STAGE_BYTES];
@@ -261,14 +314,15 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
     // column ends there): { position | column << 16, end of the column }, written by the column.  The lanes that decode the openers compact the
     // counted indels to the front, in order: { q | length << 13 | minus << 19 | fwd << 20 | column << 25, the first four allele
     // bytes (zero beyond the allele's length) }
-    __shared__ uint2 ents[ENC_WAVES][ENC_ECAP + P3_STEP];
+    __shared__ uint2 ents[ENC_WAVES][ECAP + P3_STEP];
     // per column: [0..2] skipped bytes by class (the table's three counter words; bit 31 of [2]: hand the column to the exact path),
     // [3] indel reads by kind (8-bit fields),
     // [4..7] largest multiplicity of one allele by kind
     // Stored WORD-MAJOR ([word][column]): the lanes that decode openers reach the accumulators of OTHER columns through LDS atomics,
     // and with eight consecutive words per column (32 B) the word w of every column sat in one of four banks - an atomic instruction
     // over 50 distinct owner columns took 8 to 16 LDS cycles.  Now distinct columns are distinct banks (two columns 32 apart share one).
-    __shared__ uint32_t colacc[ENC_WAVES][8][64];
+    // (BED: [8] the largest declared length of a counted deletion)
+    __shared__ uint32_t colacc[ENC_WAVES][NACC][64];
     // byte -> x: A C G T, y: a c g t, z: * # (8-bit counters) | "ACGTN*" << 24, w: 1 for the construct openers + - ^
     __shared__ uint4 tab[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -325,6 +379,7 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
     Quad tot{0, 0, 0, 0};                // I, i, D, d   (kind = (sign=='-')*2 + reverse)
     Quad mx{0, 0, 0, 0};
     bool slow = false;
+    int mdel = 0;                        // (BED only)
 
     for (int first = 0; first < n_live;) {
         const int b0 = __builtin_amdgcn_readlane(rbeg, first);                    // uniform
@@ -365,7 +420,7 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
             }
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) cacc[k][lane] = 0u;
+        for (int k = 0; k < NACC; ++k) cacc[k][lane] = 0u;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
 
@@ -415,14 +470,14 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
             int n_op = 0;
 #pragma unroll
             for (int b = 0; b < ENC_NBLK; ++b) n_op += __builtin_popcount(sm[b]);
-            if (n_op > ENC_ECAP) { bad = true; n_op = 0; }
+            if (n_op > ECAP) { bad = true; n_op = 0; }
             const int incl = wave_scan_incl(n_op);
             const int excl = incl - n_op;
             const int total_ops = __builtin_amdgcn_readlane(incl, 63);
             for (int sfirst = first; total_ops > 0 && sfirst < last;) {
                 // segment = the longest run of columns from sfirst whose openers fit the entry list
                 const int sbase = __shfl(excl, sfirst);
-                const bool sfit = act && lane >= sfirst && incl - sbase <= ENC_ECAP;
+                const bool sfit = act && lane >= sfirst && incl - sbase <= ECAP;
                 const unsigned long long sfm = __ballot(sfit) >> sfirst;
                 int n_seg = (~sfm) ? __builtin_ctzll(~sfm) : 64;
                 if (n_seg > last - sfirst) n_seg = last - sfirst;
@@ -493,6 +548,7 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
                         // a flagged byte inside the bytes a construct consumes is not an opener (pass 1 cannot know): exact path; so is a
                         // counted allele the end of its column cuts short (an allele of its own in the reference: IndelIterT)
                         if (mybad || inner || (counted && adv > nskip)) atomicOr(&cacc[2][owner], 0x80000000u);   // (bit 31 of word 2)
+                        if (BED) { if (counted && b == '-') atomicMax(&cacc[NACC - 1][owner], (uint32_t)adv); }
                     }
                     // the counted indels move to the front of the list, order kept (slot c <= j: every slot of this trip has been read)
                     const unsigned long long cm = __ballot(counted);
@@ -560,6 +616,7 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
                     cnt[8] = az & 0xff; cnt[9] = (az >> 8) & 0xff;
                     tot = Quad{(int)(a0.w & 0xff), (int)((a0.w >> 8) & 0xff), (int)((a0.w >> 16) & 0xff), (int)(a0.w >> 24)};
                     mx = Quad{(int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
+                    if (BED) mdel = (int)cacc[NACC - 1][lane];
                 }
                 bad = bad || (act && (a0.z >> 31));
             }
@@ -571,6 +628,7 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
                 cnt[0] = c2.k0; cnt[1] = c2.k1; cnt[2] = c2.k2; cnt[3] = c2.k3; cnt[4] = c2.k4;
                 cnt[5] = c2.k5; cnt[6] = c2.k6; cnt[7] = c2.k7; cnt[8] = c2.k8; cnt[9] = c2.k9;
                 tot = t2; mx = m2;
+                if (BED) mdel = max_del_exact((const uint8_t*)st, (int64_t)lbeg, (int64_t)lend);
             }
         }
         __builtin_amdgcn_wave_barrier();            // the stage buffer is reused by the next sub-batch
@@ -582,6 +640,7 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
         cnt[0] = c2.k0; cnt[1] = c2.k1; cnt[2] = c2.k2; cnt[3] = c2.k3; cnt[4] = c2.k4;
         cnt[5] = c2.k5; cnt[6] = c2.k6; cnt[7] = c2.k7; cnt[8] = c2.k8; cnt[9] = c2.k9;
         tot = t2; mx = m2;
+        if (BED) mdel = max_del_exact(bases, begin64, lane == n_live - 1 ? wave_end : woff[lane + 1]);
     }
 
     // ---- assemble the 18 channels, flags (tensor_maker.cpp:127-248) ------------------------------
@@ -647,9 +706,32 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
         if (pass_af) f |= NSNP_FLAG_PASS_AF;
         if (pass_snp) f |= NSNP_FLAG_PASS_SNP;
         if (pass_indel) f |= NSNP_FLAG_PASS_INDEL;
-        if (rb < 4 && pass_af && depth >= min_cov) f |= NSNP_FLAG_CANDIDATE;
+        bool cand = rb < 4 && pass_af && depth >= min_cov;
+        if (BED) {
+            if (bed.max_del) (bed.max_del + wave_col0)[lane] = mdel;
+            if (cand && bed.bits) { const int64_t p = (bed.pos + wave_col0)[lane]; cand = bed_any(bed.bits, bed.n_bits, p - 1, p + mdel + 1); }
+        }
+        if (cand) f |= NSNP_FLAG_CANDIDATE;
         (flags + wave_col0)[lane] = f;
     }
+}
+
+__global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
+    const uint8_t* __restrict__ bases, const int64_t* __restrict__ col_off, const uint8_t* __restrict__ ref,
+    int64_t M, AfThreshold af, const AfTable aft, AfThreshold afi, const AfTable afti, int min_cov, int32_t* __restrict__ counts,
+    int32_t* __restrict__ depth_out,
+    uint8_t* __restrict__ flags)
+{
+    encode_columns_body<false>(bases, col_off, ref, M, af, aft, afi, afti, min_cov, counts, depth_out, flags, EncBed{nullptr, nullptr, 0, nullptr});
+}
+
+__global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns_bed(
+    const uint8_t* __restrict__ bases, const int64_t* __restrict__ col_off, const uint8_t* __restrict__ ref,
+    int64_t M, AfThreshold af, const AfTable aft, AfThreshold afi, const AfTable afti, int min_cov, int32_t* __restrict__ counts,
+    int32_t* __restrict__ depth_out,
+    uint8_t* __restrict__ flags, const EncBed bed)
+{
+    encode_columns_body<true>(bases, col_off, ref, M, af, aft, afi, afti, min_cov, counts, depth_out, flags, bed);
 }
 
 
@@ -759,9 +841,10 @@ __global__ void k_gather_windows(const int32_t* __restrict__ counts, const int64
 
 }  // namespace
 
-extern "C" int nsnp_pileup_encode_columns2(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off,
-                                           const uint8_t* ref, int64_t M, double snp_min_af, double indel_min_af, int min_coverage,
-                                           int32_t* counts, int32_t* depth, uint8_t* flags, void* stream)
+// bed == nullptr: k_encode_columns, the launch nsnp_pileup_encode_columns2 always made; else k_encode_columns_bed
+static int encode_columns_launch(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off,
+                                 const uint8_t* ref, int64_t M, double snp_min_af, double indel_min_af, int min_coverage,
+                                 int32_t* counts, int32_t* depth, uint8_t* flags, const EncBed* bed, void* stream)
 {
     if (!ctx || M < 0 || (M > 0 && (!bases || !col_off || !ref || !counts || !depth || !flags))) return NSNP_EINVAL;
     if (M == 0) return NSNP_OK;
@@ -787,10 +870,32 @@ extern "C" int nsnp_pileup_encode_columns2(nsnp_ctx* ctx, const uint8_t* bases, 
     }
     AfThreshold af{ctx->af_t, ctx->af_k, ctx->af_mode}, afi{ctx->af2_t, ctx->af2_k, ctx->af2_mode};
     AfTable aft, afti; memcpy(aft.w, ctx->af_table_words, sizeof(aft.w)); memcpy(afti.w, ctx->af2_table_words, sizeof(afti.w));
-    hipLaunchKernelGGL(k_encode_columns, dim3(grid), dim3(ENC_BLOCK), 0, (hipStream_t)stream,
-                       bases, col_off, ref, M, af, aft, afi, afti, min_coverage, counts, depth, flags);
+    if (bed)
+        hipLaunchKernelGGL(k_encode_columns_bed, dim3(grid), dim3(ENC_BLOCK), 0, (hipStream_t)stream,
+                           bases, col_off, ref, M, af, aft, afi, afti, min_coverage, counts, depth, flags, *bed);
+    else
+        hipLaunchKernelGGL(k_encode_columns, dim3(grid), dim3(ENC_BLOCK), 0, (hipStream_t)stream,
+                           bases, col_off, ref, M, af, aft, afi, afti, min_coverage, counts, depth, flags);
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
+}
+
+extern "C" int nsnp_pileup_encode_columns2(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off,
+                                           const uint8_t* ref, int64_t M, double snp_min_af, double indel_min_af, int min_coverage,
+                                           int32_t* counts, int32_t* depth, uint8_t* flags, void* stream)
+{
+    return encode_columns_launch(ctx, bases, col_off, ref, M, snp_min_af, indel_min_af, min_coverage, counts, depth, flags, nullptr, stream);
+}
+
+extern "C" int nsnp_pileup_encode_columns3(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off,
+                                           const uint8_t* ref, const int64_t* pos, int64_t M, double snp_min_af, double indel_min_af,
+                                           int min_coverage, const uint32_t* conf_bits, int64_t conf_n_bits,
+                                           int32_t* counts, int32_t* depth, uint8_t* flags, int32_t* max_del, void* stream)
+{
+    // a bitmap is tested at positions: it needs them; a bitmap of no bits is given as NULL (then conf_n_bits must be 0)
+    if (conf_n_bits < 0 || (conf_bits ? (conf_n_bits == 0 || (M > 0 && !pos)) : conf_n_bits != 0)) return NSNP_EINVAL;
+    const EncBed bed{pos, conf_bits, conf_n_bits, max_del};
+    return encode_columns_launch(ctx, bases, col_off, ref, M, snp_min_af, indel_min_af, min_coverage, counts, depth, flags, &bed, stream);
 }
 
 extern "C" int nsnp_pileup_encode_columns(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off,
@@ -828,12 +933,13 @@ extern "C" int nsnp_pileup_select_sites(nsnp_ctx* ctx, const int64_t* pos, const
 // ascending, so the sites a chunk OWNS (its columns without the halo it re-reads) are one run [meta[1], meta[2]) of the list.  One wave:
 // two binary searches.  meta may be pinned host memory (plain stores).
 namespace {
+// own_dev (nsnp_pileup_select_sites_range_dev): the two bounds are read from device memory - what nsnp_pileup_filter_columns wrote - instead
 __global__ void k_select_bounds(const int64_t* __restrict__ center_idx, const int64_t* __restrict__ n_sites, int64_t cap, int64_t own_lo, int64_t own_hi,
-                                int64_t* __restrict__ meta)
+                                const int64_t* __restrict__ own_dev, int64_t* __restrict__ meta)
 {
     if (threadIdx.x >= 2) return;
     const int64_t n = *n_sites < cap ? *n_sites : cap;
-    const int64_t key = threadIdx.x ? own_hi : own_lo;
+    const int64_t key = own_dev ? own_dev[threadIdx.x] : (threadIdx.x ? own_hi : own_lo);
     int64_t a = 0, b = n;                                  // first index whose centre is >= key
     while (a < b) { const int64_t m = (a + b) >> 1; if (center_idx[m] < key) a = m + 1; else b = m; }
     meta[1 + threadIdx.x] = a;
@@ -858,8 +964,8 @@ __global__ void k_call_rows(const int32_t* __restrict__ counts, const int64_t* _
 }
 }  // namespace
 
-extern "C" int nsnp_pileup_select_sites_range(nsnp_ctx* ctx, const int64_t* pos, const uint8_t* flags, int64_t M, int64_t own_lo, int64_t own_hi,
-                                              int64_t* center_idx, int64_t cap, int64_t* meta, void* stream)
+static int select_sites_range(nsnp_ctx* ctx, const int64_t* pos, const uint8_t* flags, int64_t M, int64_t own_lo, int64_t own_hi, const int64_t* own_dev,
+                              int64_t* center_idx, int64_t cap, int64_t* meta, void* stream)
 {
     if (!ctx || M < 0 || cap < 0 || !meta || (M > 0 && (!pos || !flags)) || (cap > 0 && !center_idx)) return NSNP_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -879,9 +985,22 @@ extern "C" int nsnp_pileup_select_sites_range(nsnp_ctx* ctx, const int64_t* pos,
     hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, s, ctx->sel_tmp, n_blocks, n_sites);
     hipLaunchKernelGGL(k_select_scatter, dim3((unsigned)n_blocks), dim3(SEL_BLOCK), 0, s, pos, flags, M,
                        (const int64_t*)ctx->sel_tmp, center_idx, cap);
-    hipLaunchKernelGGL(k_select_bounds, dim3(1), dim3(64), 0, s, (const int64_t*)center_idx, (const int64_t*)n_sites, cap, own_lo, own_hi, meta);
+    hipLaunchKernelGGL(k_select_bounds, dim3(1), dim3(64), 0, s, (const int64_t*)center_idx, (const int64_t*)n_sites, cap, own_lo, own_hi, own_dev, meta);
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
+}
+
+extern "C" int nsnp_pileup_select_sites_range(nsnp_ctx* ctx, const int64_t* pos, const uint8_t* flags, int64_t M, int64_t own_lo, int64_t own_hi,
+                                              int64_t* center_idx, int64_t cap, int64_t* meta, void* stream)
+{
+    return select_sites_range(ctx, pos, flags, M, own_lo, own_hi, nullptr, center_idx, cap, meta, stream);
+}
+
+extern "C" int nsnp_pileup_select_sites_range_dev(nsnp_ctx* ctx, const int64_t* pos, const uint8_t* flags, int64_t M, const int64_t* own,
+                                                  int64_t* center_idx, int64_t cap, int64_t* meta, void* stream)
+{
+    if (!own) return NSNP_EINVAL;
+    return select_sites_range(ctx, pos, flags, M, 0, 0, own, center_idx, cap, meta, stream);
 }
 
 extern "C" int nsnp_pileup_call_rows(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const int64_t* pos, const uint8_t* gt_arg,
@@ -903,6 +1022,196 @@ extern "C" int nsnp_pileup_gather_windows(nsnp_ctx* ctx, const int32_t* counts, 
     int64_t blocks = NSNP_CDIV(N * PW * PC, 256);
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(k_gather_windows, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, counts, center_idx, N, x);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+// ---- extended-BED filter: the lines main.cpp:165-169 skips leave the column arrays before the encode ------------------------------
+// A line at 1-based position p stays when bit p - 1 of the bitmap is set.  Three launches, laid out like the selection: a block owns
+// FIL_TILE consecutive columns as FIL_PER_THREAD rows of FIL_BLOCK (the lanes of a wave read consecutive positions and offsets);
+//   k_filter_count    kept columns and kept bytes of every tile
+//   k_filter_scan     their exclusive prefix sums (one block), the totals into meta
+//   k_filter_scatter  positions, reference bytes and offsets of the kept columns to their places, then the tile's kept BYTES: they are
+//                     one contiguous output range, worked off in 16-byte pieces, a piece whose bytes come from one run of kept columns
+//                     (the common case: intervals keep long runs) as one 16-byte load; the columns behind the kept ones are
+//                     filled so that the encode and the selection make nothing of them
+namespace {
+constexpr int FIL_BLOCK = 256, FIL_PER_THREAD = 8, FIL_TILE = FIL_BLOCK * FIL_PER_THREAD;
+constexpr int64_t FIL_POS_NONE = -(1ll << 62);            // position of the columns behind the kept ones: no step to or from it is + 1
+
+__device__ __forceinline__ int64_t wave_scan_incl64(int64_t v, int lane)
+{
+    for (int o = 1; o < 64; o <<= 1) { const int64_t t = __shfl_up(v, o); if (lane >= o) v += t; }
+    return v;
+}
+
+__global__ __launch_bounds__(FIL_BLOCK) void k_filter_count(const int64_t* __restrict__ pos, const int64_t* __restrict__ col_off,
+                                                             const uint32_t* __restrict__ bits, int64_t n_bits, int64_t M, int64_t n_blocks,
+                                                             int64_t* __restrict__ blk)
+{
+    __shared__ int64_t wsum[2][FIL_BLOCK / 64];
+    const int64_t base = (int64_t)blockIdx.x * FIL_TILE + threadIdx.x;
+    int64_t n = 0, nb = 0;
+#pragma unroll
+    for (int k = 0; k < FIL_PER_THREAD; ++k) {
+        const int64_t c = base + (int64_t)k * FIL_BLOCK;
+        if (c < M && bed_bit(bits, n_bits, pos[c] - 1)) { const int64_t l = col_off[c + 1] - col_off[c]; n += 1; nb += l > 0 ? l : 0; }
+    }
+    for (int o = 32; o > 0; o >>= 1) { n += __shfl_down(n, o); nb += __shfl_down(nb, o); }
+    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = n; wsum[1][threadIdx.x >> 6] = nb; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        int64_t s = 0;
+        for (int w = 0; w < FIL_BLOCK / 64; ++w) s += wsum[threadIdx.x][w];
+        blk[threadIdx.x * (n_blocks + 1) + blockIdx.x] = s;
+    }
+}
+
+// blk = { columns of tile 0 .. n_blocks - 1, K, bytes of tile 0 .. n_blocks - 1, kept bytes }: exclusive scans of both rows in place, the totals
+// behind them; meta = { K, kept bytes, image of own_lo, image of own_hi }: the images of bounds outside [1, M) here, the others by the
+// tile that holds them
+__global__ __launch_bounds__(1024) void k_filter_scan(int64_t* __restrict__ blk, int64_t n_blocks, int64_t M, int64_t own_lo, int64_t own_hi,
+                                                      int64_t* __restrict__ meta)
+{
+    __shared__ int64_t part[2][1024];
+    const int tid = threadIdx.x;
+    const int64_t per = NSNP_CDIV(n_blocks, 1024);
+    const int64_t b0 = tid * per < n_blocks ? tid * per : n_blocks, b1 = (b0 + per < n_blocks) ? b0 + per : n_blocks;
+    for (int r = 0; r < 2; ++r) {
+        const int64_t* row = blk + r * (n_blocks + 1);
+        int64_t s = 0;
+        for (int64_t b = b0; b < b1; ++b) s += row[b];
+        part[r][tid] = s;
+    }
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {     // Hillis-Steele inclusive scan of both rows
+        const int64_t v0 = tid >= o ? part[0][tid - o] : 0, v1 = tid >= o ? part[1][tid - o] : 0;
+        __syncthreads();
+        part[0][tid] += v0; part[1][tid] += v1;
+        __syncthreads();
+    }
+    for (int r = 0; r < 2; ++r) {
+        int64_t* row = blk + r * (n_blocks + 1);
+        int64_t run = tid ? part[r][tid - 1] : 0;
+        for (int64_t b = b0; b < b1; ++b) { const int64_t v = row[b]; row[b] = run; run += v; }
+        if (tid == 1023) { row[n_blocks] = part[r][1023]; meta[r] = part[r][1023]; }
+    }
+    if (tid < 2) {
+        const int64_t own = tid ? own_hi : own_lo;
+        if (own <= 0) meta[2 + tid] = 0;
+        else if (own >= M) meta[2 + tid] = part[0][1023];
+    }
+}
+
+__global__ __launch_bounds__(FIL_BLOCK) void k_filter_scatter(
+    const int64_t* __restrict__ pos, const int64_t* __restrict__ col_off, const uint8_t* __restrict__ bases, const uint8_t* __restrict__ ref,
+    const uint32_t* __restrict__ bits, int64_t n_bits, int64_t M, int64_t n_blocks, const int64_t* __restrict__ blk, int64_t own_lo, int64_t own_hi,
+    int64_t* __restrict__ pos_out, int64_t* __restrict__ off_out, uint8_t* __restrict__ bases_out, uint8_t* __restrict__ ref_out,
+    int64_t* __restrict__ meta)
+{
+    // kept column r of the tile: s_out[r] = its first output byte (s_out[kept columns of the tile] = the end of the tile's bytes),
+    // s_delta[r] = its first input byte - its first output byte (never decreasing in r: dropped bytes only add to it)
+    __shared__ int64_t s_out[FIL_TILE + 1];
+    __shared__ int64_t s_delta[FIL_TILE];
+    __shared__ int wcnt[FIL_PER_THREAD][FIL_BLOCK / 64];
+    __shared__ int64_t wbytes[FIL_PER_THREAD][FIL_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t base = (int64_t)blockIdx.x * FIL_TILE + tid;
+    const int64_t col0 = blk[blockIdx.x], K = blk[n_blocks];
+    const int64_t byte0 = blk[n_blocks + 1 + blockIdx.x], kept_bytes = blk[2 * n_blocks + 1];
+    unsigned keepm = 0; int before[FIL_PER_THREAD]; int64_t bbefore[FIL_PER_THREAD], src[FIL_PER_THREAD];
+#pragma unroll
+    for (int k = 0; k < FIL_PER_THREAD; ++k) {
+        const int64_t c = base + (int64_t)k * FIL_BLOCK;
+        bool keep = false; int64_t len = 0; src[k] = 0;
+        if (c < M) {
+            keep = bed_bit(bits, n_bits, pos[c] - 1);
+            if (keep) { src[k] = col_off[c]; len = col_off[c + 1] - src[k]; len = len > 0 ? len : 0; }
+        }
+        const unsigned long long bal = __ballot(keep);
+        before[k] = __popcll(bal & ((1ull << lane) - 1ull));
+        const int64_t incl = wave_scan_incl64(len, lane);
+        bbefore[k] = incl - len;
+        if (lane == 63) { wcnt[k][wave] = __popcll(bal); wbytes[k][wave] = incl; }
+        keepm |= (unsigned)keep << k;
+    }
+    __syncthreads();
+    int run = 0; int64_t brun = 0;                           // kept columns / bytes of the tile in front of (trip k, this wave)
+#pragma unroll
+    for (int k = 0; k < FIL_PER_THREAD; ++k) {
+#pragma unroll
+        for (int w = 0; w < FIL_BLOCK / 64; ++w) {
+            if (w == wave) {
+                const int64_t c = base + (int64_t)k * FIL_BLOCK;
+                const int r = run + before[k];
+                if ((keepm >> k) & 1u) {
+                    const int64_t o = byte0 + brun + bbefore[k];
+                    pos_out[col0 + r] = pos[c]; ref_out[col0 + r] = ref[c]; off_out[col0 + r] = o;
+                    s_out[r] = o; s_delta[r] = src[k] - o;
+                }
+                // the images of the chunk's own range under the compaction: kept columns in front of column own_lo / own_hi
+                if (c == own_lo) meta[2] = col0 + r;
+                if (c == own_hi) meta[3] = col0 + r;
+                if (c < M && c >= K) { pos_out[c] = FIL_POS_NONE; ref_out[c] = 'N'; off_out[c] = kept_bytes; }
+                if (c == M - 1) off_out[M] = kept_bytes;
+            }
+            run += wcnt[k][w]; brun += wbytes[k][w];
+        }
+    }
+    if (tid == 0) s_out[run] = byte0 + brun;                 // (run, brun: the tile's totals by now, in every thread)
+    __syncthreads();
+    const int n_kept = run;
+    const int64_t B0 = byte0, B1 = byte0 + brun;
+    if (B1 <= B0) return;
+    // 16-byte pieces of the output, aligned in memory
+    const int64_t j0 = B0 - (int64_t)((uintptr_t)(bases_out + B0) & 15);
+    for (int64_t j = j0 + 16 * (int64_t)tid; j < B1; j += 16 * FIL_BLOCK) {
+        const int64_t lo = j > B0 ? j : B0, hi = j + 16 < B1 ? j + 16 : B1;
+        int a = 0, b = n_kept - 1;                           // the last kept column that begins at or before byte lo
+        while (a < b) { const int m = (a + b + 1) >> 1; if (s_out[m] <= lo) a = m; else b = m - 1; }
+        int k = a, ke = a;
+        while (ke + 1 < n_kept && s_out[ke + 1] < hi) ++ke;  // ... at or before byte hi - 1
+        if (hi - lo == 16 && s_delta[ke] == s_delta[k]) {
+            uint4 v;
+            __builtin_memcpy(&v, bases + lo + s_delta[k], 16);
+            *reinterpret_cast<uint4*>(bases_out + lo) = v;
+        } else {
+            for (int64_t o = lo; o < hi; ++o) {
+                while (k + 1 < n_kept && s_out[k + 1] <= o) ++k;
+                bases_out[o] = bases[o + s_delta[k]];
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" int nsnp_pileup_filter_columns(nsnp_ctx* ctx, const int64_t* pos, const int64_t* col_off, const uint8_t* bases, const uint8_t* ref,
+                                          int64_t M, const uint32_t* bits, int64_t n_bits, int64_t own_lo, int64_t own_hi,
+                                          int64_t* pos_out, int64_t* off_out, uint8_t* bases_out, uint8_t* ref_out, int64_t* meta, void* stream)
+{
+    if (!ctx || M < 0 || n_bits < 0 || !meta || !off_out || (n_bits > 0 && !bits) ||
+        (M > 0 && (!pos || !col_off || !bases || !ref || !pos_out || !bases_out || !ref_out))) return NSNP_EINVAL;
+    if (pos_out == pos || off_out == col_off || bases_out == bases || ref_out == ref) return NSNP_EINVAL;       // not in place
+    hipStream_t s = (hipStream_t)stream;
+    if (M == 0) {
+        NSNP_HIP(ctx, hipMemsetAsync(meta, 0, 4 * sizeof(int64_t), s));
+        NSNP_HIP(ctx, hipMemsetAsync(off_out, 0, sizeof(int64_t), s));
+        return NSNP_OK;
+    }
+    const int64_t n_blocks = NSNP_CDIV(M, FIL_TILE);
+    const size_t need = (size_t)(2 * n_blocks + 2) * sizeof(int64_t);
+    if (ctx->fil_tmp_bytes < need) {
+        // grows only when a larger M than ever before arrives (synchronous; size it with a warm-up call)
+        NSNP_HIP(ctx, hipStreamSynchronize(s));
+        if (ctx->fil_tmp) (void)hipFree(ctx->fil_tmp);
+        ctx->fil_tmp = nullptr; ctx->fil_tmp_bytes = 0;
+        NSNP_HIP(ctx, hipMalloc((void**)&ctx->fil_tmp, need + need / 4));
+        ctx->fil_tmp_bytes = need + need / 4;
+    }
+    hipLaunchKernelGGL(k_filter_count, dim3((unsigned)n_blocks), dim3(FIL_BLOCK), 0, s, pos, col_off, bits, n_bits, M, n_blocks, ctx->fil_tmp);
+    hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(1024), 0, s, ctx->fil_tmp, n_blocks, M, own_lo, own_hi, meta);
+    hipLaunchKernelGGL(k_filter_scatter, dim3((unsigned)n_blocks), dim3(FIL_BLOCK), 0, s, pos, col_off, bases, ref, bits, n_bits, M, n_blocks,
+                       (const int64_t*)ctx->fil_tmp, own_lo, own_hi, pos_out, off_out, bases_out, ref_out, meta);
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
 }

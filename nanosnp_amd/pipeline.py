@@ -150,11 +150,69 @@ def tokenise_mode(tokenise=None):
 
 
 def stream_contig(model, text, contig, chr_seq, lo=0, hi=None, chunk_bytes=64 << 20, min_af=0.12, min_coverage=6, stats=None, on_rows=None,
-                  tokenise=None):
+                  tokenise=None, extended_bed=None, confident_bed=None, fai=None):
+    beds = _contig_beds(extended_bed, confident_bed, contig, chr_seq, fai)
     with host.gc_paused():
         if tokenise_mode(tokenise) == "device":
-            return _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows)
-        return _stream_contig(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows)
+            return _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, beds=beds)
+        return _stream_contig(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, beds=beds)
+
+
+# ---- BED region filters (nanosnp_amd/bed.py; DNA_CreateCanSnpTensor -extended_confident_bed / -confident_bed) ---------------------------
+def _contig_beds(extended_bed, confident_bed, contig, chr_seq, fai=None):
+    """the two BED arguments of a pipeline call (None, a path, or {contig: intervals}) -> None without BEDs (the pipelines then issue
+    exactly the launches they always issued), else (extended bitmap or None, confident bitmap or None) of this contig: host uint32 words"""
+    if extended_bed is None and confident_bed is None:
+        return None
+    from . import bed
+    n = int(chr_seq.size)
+    mk = lambda b: None if b is None else bed.bed_bitmap(bed.contig_intervals(b, contig, n, fai), n)
+    return mk(extended_bed), mk(confident_bed)
+
+
+def _upload_beds(model, beds, dev, copy_stream, main):
+    """the contig's bitmaps -> device int32 tensors (None where there is none), once per contig: through a pinned buffer on the copy stream,
+    allocated as the copy stream's memory, as the reference sequence travels (_stream_contig_dev: a block the compute stream has just freed
+    may still be read by work queued there); the compute stream waits for the copy"""
+    import torch
+    words = [None if b is None else np.ascontiguousarray(b).view(np.int32) for b in beds]
+    total = sum(w.size for w in words if w is not None)
+    bp = getattr(model, "_bed_pin", None)
+    if bp is None or bp.numel() < total:
+        bp = model._bed_pin = torch.empty(max(total + total // 8, 1 << 16), dtype=torch.int32, pin_memory=True)
+        model._bed_pin_free = None
+    if getattr(model, "_bed_pin_free", None) is not None:
+        model._bed_pin_free.synchronize()              # (the previous contig's bitmaps have left the pinned buffer)
+    out, o = [], 0
+    with torch.cuda.stream(copy_stream):
+        for w in words:
+            if w is None:
+                out.append(None)
+                continue
+            bp.numpy()[o:o + w.size] = w
+            d = torch.empty(max(w.size, 1), dtype=torch.int32, device=dev)[:w.size]
+            d.copy_(bp[o:o + w.size], non_blocking=True)
+            out.append(d)
+            o += w.size
+        model._bed_pin_free = torch.cuda.Event(); model._bed_pin_free.record(copy_stream)
+    for d in out:
+        if d is not None:
+            d.record_stream(main)
+    main.wait_event(model._bed_pin_free)
+    return out
+
+
+class _FilSet:
+    """the columns of one chunk behind the extended-BED filter (nsnp_pileup_filter_columns): written and read on the compute stream alone.
+    The bases lie behind a front pad (include/nanosnp.h: the encode of a chunk that keeps no byte reads the 16 bytes in front of them)."""
+    def __init__(self, cap_cols, cap_bytes, dev):
+        import torch
+        from ._lib import Context
+        self.pos = torch.empty(cap_cols, dtype=torch.int64, device=dev)
+        self.off = torch.empty(cap_cols + 1, dtype=torch.int64, device=dev)
+        self.ref = torch.empty(cap_cols, dtype=torch.uint8, device=dev)
+        self.bases = torch.empty(Context.FILTER_FRONT_PAD + cap_bytes, dtype=torch.uint8, device=dev)[Context.FILTER_FRONT_PAD:]
+        self.out = (self.pos, self.off, self.bases, self.ref)
 
 
 class _TextSet:
@@ -180,7 +238,7 @@ class _ColSet:
         self.bases = torch.empty(cap_bytes, dtype=torch.uint8, device=dev)
 
 
-def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, defer=False):
+def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, defer=False, beds=None):
     """stream_contig with the text cut into columns ON THE DEVICE (nsnp_mpileup_tokenise).  The host touches every byte of the text once - a
     multi-threaded copy of the chunk (whole lines, 16 lines of halo either side, found by a few find / rfind calls) from the page cache
     into pinned memory - and the chunks are worked off four things at a time:
@@ -195,7 +253,12 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
     path (tests/test_gpu_predict.py); text the reference's reader aborts on is refused with the same errors.
     defer=True (call_contigs): returns (rows, done, finalize) as soon as the last chunk is ISSUED - `done` is an event behind the last kernel,
     finalize() waits for it and adds the per-stage times to stats - so that the next contig's text is staged, copied and tokenised while
-    this one's last forward (1.4 ms of a 6 M-column contig's 15) still runs; the buffer sets carry their events from call to call."""
+    this one's last forward (1.4 ms of a 6 M-column contig's 15) still runs; the buffer sets carry their events from call to call.
+    beds (_contig_beds; None: nothing below changes): with an extended bitmap every chunk's columns pass nsnp_pileup_filter_columns in front
+    of the encode - the images of the chunk's own range stay on the device, the selection reads them there - and with a confident bitmap
+    the encode is nsnp_pileup_encode_columns3.  The result does not depend on the cuts for texts with ASCENDING positions: 33 kept lines
+    with consecutive positions are then 33 consecutive lines of the text, inside the 16-line halo; in a text whose positions repeat or step
+    back they may lie further apart (the whole-array calls stay exact for any position sequence)."""
     import time
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
@@ -259,6 +322,14 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
     if getattr(model, "_stream_main_id", None) != (main.device, main.stream_id):
         copy_stream.wait_stream(main)                  # (another compute stream than last time: its queued work may still read the device sets)
         model._stream_main_id = (main.device, main.stream_id)
+    ext_bits = conf_bits = fsets = fmeta = None
+    if beds is not None:
+        ext_bits, conf_bits = _upload_beds(model, beds, dev, copy_stream, main)
+        if ext_bits is not None:
+            fsets = getattr(model, "_fil_dev_sets", None)
+            if not fsets or fsets[0].pos.device != dev or fsets[0].pos.numel() < csets[0].pos.numel() or fsets[0].bases.numel() < csets[0].bases.numel():
+                fsets = model._fil_dev_sets = [_FilSet(csets[0].pos.numel(), csets[0].bases.numel(), dev) for _ in range(3)]
+            fmeta = torch.zeros((len(ranges), 4), dtype=torch.int64, device=dev)
 
     trace = st.get("trace")
 
@@ -300,18 +371,30 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
         ev[k]["a0"].record(main)
         job = None
         if own > 0:
-            d_pos = cs.pos[:M]
-            counts, depth, flags = ctx.pileup_encode_columns(cs.bases[:max(nb, 1)], cs.off[:M + 1], cs.ref[:M], min_af, min_coverage)
+            d_pos, d_off, d_bases, d_ref = cs.pos[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
+            if ext_bits is not None:
+                # the lines outside the extended BED leave the arrays; where the chunk's own range [n_lo, M - n_hi) lies among the kept
+                # columns stays on the device (fmeta[k][2:])
+                d_pos, d_off, d_bases, d_ref, _ = ctx.pileup_filter_columns(d_pos, d_off, d_bases, d_ref, ext_bits, n_seq, n_lo, M - n_hi,
+                                                                            meta=fmeta[k], out=fsets[k % len(fsets)].out, stream=main)
+            if conf_bits is not None:
+                counts, depth, flags, _ = ctx.pileup_encode_columns3(d_bases, d_off, d_ref, d_pos, conf_bits, n_seq, min_af, min_coverage,
+                                                                     want_max_del=False)
+            else:
+                counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
             # selection + the run of the chunk's own sites in the list, written into pinned memory by the last of its four launches
-            center = ctx.pileup_select_sites_range(d_pos, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
+            if ext_bits is not None:
+                center = ctx.pileup_select_sites_range_dev(d_pos, flags, fmeta[k][2:], meta_pin[k], stream=main)
+            else:
+                center = ctx.pileup_select_sites_range(d_pos, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
             sel_done = torch.cuda.Event(); sel_done.record(main)
-            job = (k, M, cs, counts, center, sel_done)
+            job = (k, M, d_pos, counts, center, sel_done)
         ev[k]["a1"].record(main)
         return job
 
     def calls_of(job):
         """the last third of a chunk: its site count is on the host by now"""
-        k, M, cs, counts, center, sel_done = job
+        k, M, d_pos, counts, center, sel_done = job
         t_w = time.perf_counter()
         sel_done.synchronize()
         st["wait_counts_s"] += time.perf_counter() - t_w
@@ -320,7 +403,7 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
         if c_hi > c_lo:
             centers = center[c_lo:c_hi]
             gt, zy, ga, za, gm, zm = ctx.pileup_forward_windows_calls(counts, centers)
-            rows_k = ctx.pileup_call_rows(counts, centers, cs.pos, ga, za, gm, zm)                  # predict.py:52-65, one launch
+            rows_k = ctx.pileup_call_rows(counts, centers, d_pos, ga, za, gm, zm)                  # predict.py:52-65, one launch
             if on_rows is not None:
                 on_rows(rows_k)
             else:
@@ -417,7 +500,7 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
     return rows
 
 
-def _stream_contig(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows):
+def _stream_contig(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, beds=None):
     """The device part of stages s1 + s2 over the lines of text[lo:hi], chunk by chunk, three things at a time:
 
         worker thread   parses chunks k + 1 and k + 2 (libnanosnp_host.so, OpenMP, straight into one of three pinned buffer sets)
@@ -486,6 +569,9 @@ def _stream_contig(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, mi
     seq_len = int(chr_seq.size)
     cov_idx = torch.tensor(list(COV_CHANNELS), dtype=torch.int64, device=dev)
     copy_stream.wait_stream(main)                      # (whatever the caller queued before us may still read the device sets)
+    # BED bitmaps (_contig_beds; None: nothing below changes): the filter and the confident test run on the device in this mode too
+    ext_bits, conf_bits = _upload_beds(model, beds, dev, copy_stream, main) if beds is not None else (None, None)
+    fmeta = torch.zeros((len(ranges), 4), dtype=torch.int64, device=dev) if ext_bits is not None else None
 
     def parse(k):
         t0 = time.perf_counter()
@@ -516,7 +602,7 @@ def _stream_contig(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, mi
 
     def calls_of(job):
         """the second half of a chunk: its site count is on the host by now"""
-        k, M, n_lo, n_hi, ds, counts, center, sel_done = job
+        k, M, n_lo, n_hi, ds, counts, center, sel_done, pos_k = job
         t_w = time.perf_counter()
         sel_done.synchronize()
         st["wait_counts_s"] += time.perf_counter() - t_w
@@ -529,7 +615,7 @@ def _stream_contig(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, mi
             # that copy waits for everything queued on the device - the forward just issued included)
             cov = counts.index_select(0, centers).index_select(1, cov_idx).to(torch.float64)      # predict.py:63
             f64 = lambda t: t.to(torch.float64)[:, None]
-            rows_k = torch.cat([f64(ds.pos[:M].index_select(0, centers)), f64(ga), f64(za), f64(gm), f64(zm), cov], dim=1)
+            rows_k = torch.cat([f64(pos_k.index_select(0, centers)), f64(ga), f64(za), f64(gm), f64(zm), cov], dim=1)
             if on_rows is not None:
                 on_rows(rows_k)
             else:
@@ -585,13 +671,24 @@ def _stream_contig(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, mi
             if own > 0:
                 d_pos = ds.pos[:M]
                 d_ref = d_seq[d_pos - 1]
-                counts, depth, flags = ctx.pileup_encode_columns(ds.bases[:max(nb, 1)], ds.off[:M + 1], d_ref, min_af, min_coverage)
-                center, n_sel = ctx.pileup_select_sites_async(d_pos, flags)
-                # halo columns belong to the neighbours: the chunk's own centres are [c_lo, c_hi) of the ascending list
-                meta = torch.stack([n_sel[0], (center < n_lo).sum(), (center < M - n_hi).sum(), n_sel[0]])
-                meta_pin[k].copy_(meta, non_blocking=True)
+                d_off, d_bases = ds.off[:M + 1], ds.bases[:max(nb, 1)]
+                if ext_bits is not None:
+                    d_pos, d_off, d_bases, d_ref, _ = ctx.pileup_filter_columns(d_pos, d_off, d_bases, d_ref, ext_bits, seq_len, n_lo, M - n_hi,
+                                                                                meta=fmeta[k], stream=main)
+                if conf_bits is not None:
+                    counts, depth, flags, _ = ctx.pileup_encode_columns3(d_bases, d_off, d_ref, d_pos, conf_bits, seq_len, min_af, min_coverage,
+                                                                         want_max_del=False)
+                else:
+                    counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
+                if ext_bits is not None:
+                    center = ctx.pileup_select_sites_range_dev(d_pos, flags, fmeta[k][2:], meta_pin[k], stream=main)
+                else:
+                    center, n_sel = ctx.pileup_select_sites_async(d_pos, flags)
+                    # halo columns belong to the neighbours: the chunk's own centres are [c_lo, c_hi) of the ascending list
+                    meta = torch.stack([n_sel[0], (center < n_lo).sum(), (center < M - n_hi).sum(), n_sel[0]])
+                    meta_pin[k].copy_(meta, non_blocking=True)
                 sel_done = torch.cuda.Event(); sel_done.record(main)
-                nxt_job = (k, M, n_lo, n_hi, ds, counts, center, sel_done)
+                nxt_job = (k, M, n_lo, n_hi, ds, counts, center, sel_done, d_pos)
             else:
                 ds.free = torch.cuda.Event(); ds.free.record(main)
             ev[k]["a1"].record(main)
@@ -679,7 +776,8 @@ def _format_rows(r, contig, chr_seq, batch_size, score_mode, as_view=False, shar
     return (text, n_rows) if shard_dev is None else (text, n_rows, n_total)
 
 
-def _call_contig_rows_beside(model, mpileup_text, contig, chr_seq, min_af, min_coverage, batch_size, score_mode, chunk_bytes, stats, tokenise=None):
+def _call_contig_rows_beside(model, mpileup_text, contig, chr_seq, min_af, min_coverage, batch_size, score_mode, chunk_bytes, stats, tokenise=None,
+                             **bed_kw):
     """call_contig for one process with the rows of finished chunks formatted on a writer thread while later chunks compute: every
     chunk's call rows travel to a pinned buffer of their own behind the chunk's forward; the writer formats the COMPLETE batches of
     `batch_size` sites that have arrived (the reference's rows depend on the batch a site falls into: predict.py:102-125) with a
@@ -726,7 +824,8 @@ def _call_contig_rows_beside(model, mpileup_text, contig, chr_seq, min_af, min_c
             events.append(ev); sizes.append(n)
             futs.append(writer.submit(work, k))
 
-        stream_contig(model, mpileup_text, contig, chr_seq, 0, None, chunk_bytes, min_af, min_coverage, stats, on_rows=on_rows, tokenise=tokenise)
+        stream_contig(model, mpileup_text, contig, chr_seq, 0, None, chunk_bytes, min_af, min_coverage, stats, on_rows=on_rows, tokenise=tokenise,
+                      **bed_kw)
         t0 = time.perf_counter()
         for f in futs:
             f.result()
@@ -743,9 +842,15 @@ def _call_contig_rows_beside(model, mpileup_text, contig, chr_seq, min_af, min_c
 
 
 def call_contig(model, mpileup_text, contig: str, chr_seq: np.ndarray, min_af=0.12, min_coverage=6,
-                batch_size=1000, score_mode=host.SCORE_FLOAT64, chunk_bytes=64 << 20, stats=None, rows_beside=None, tokenise=None):
+                batch_size=1000, score_mode=host.SCORE_FLOAT64, chunk_bytes=64 << 20, stats=None, rows_beside=None, tokenise=None,
+                extended_bed=None, confident_bed=None, fai=None):
     """One contig: returns (vcf_rows: bytes-like - a memoryview of the formatter's buffer, no copy; bytes(...) it to keep it -, n_sites, n_rows).  model: pileup_model.LSTMNetwork; mpileup_text: bytes, mmap or a
     numpy uint8 array holding the contig's samtools-mpileup text.  tokenise: "device" (default) / "host" (tokenise_mode).
+    extended_bed / confident_bed: the reference's -extended_confident_bed / -confident_bed region filters (nanosnp_amd/bed.py), each None,
+    the path of a BED file, or {contig: intervals [n, 2] of 0-based half-open (from, to)}; fai: the reference index (a {name: length} dict or
+    .fai text) a BED path is checked against - without it only this contig's lines are read and checked.  Lines outside the extended BED
+    are dropped on the device before the window rule sees them; a column is a candidate only when the confident BED holds a base of
+    [pos - 1, pos + its longest deletion + 1).  With both None the call issues exactly the launches it issued without these arguments.
 
     The text is worked off in chunks of whole lines (stream_contig: parse of chunk k + 1 on the host beside the device work of
     chunk k).  Under an initialised torch.distributed process group (one process per GPU, torchrun) the TEXT is statically sharded:
@@ -764,9 +869,11 @@ def call_contig(model, mpileup_text, contig: str, chr_seq: np.ndarray, min_af=0.
     if rows_beside is None:
         rows_beside = os.environ.get("NSNP_ROWS_BESIDE", "0") == "1"
     if rows_beside and not sharded:
-        return _call_contig_rows_beside(model, mpileup_text, contig, chr_seq, min_af, min_coverage, batch_size, score_mode, chunk_bytes, stats, tokenise)
+        return _call_contig_rows_beside(model, mpileup_text, contig, chr_seq, min_af, min_coverage, batch_size, score_mode, chunk_bytes, stats, tokenise,
+                                        extended_bed=extended_bed, confident_bed=confident_bed, fai=fai)
     cuts = line_cuts(finder, world, 0, arr.size)
-    rows = stream_contig(model, mpileup_text, contig, chr_seq, cuts[rank], cuts[rank + 1], chunk_bytes, min_af, min_coverage, stats, tokenise=tokenise)
+    rows = stream_contig(model, mpileup_text, contig, chr_seq, cuts[rank], cuts[rank + 1], chunk_bytes, min_af, min_coverage, stats, tokenise=tokenise,
+                         extended_bed=extended_bed, confident_bed=confident_bed, fai=fai)
     if sharded:
         # every rank formats ITS rows (on its own host cores, exactly as the single process would format them: _format_rows), the text
         # - about 60 B per row, half of what the calls take - travels to rank 0 in one rooted gather
@@ -800,13 +907,16 @@ def call_contig(model, mpileup_text, contig: str, chr_seq: np.ndarray, min_af=0.
     return text, n_sites, n_rows
 
 
-def call_contigs(model, items, out, min_af=0.12, min_coverage=6, batch_size=1000, score_mode=host.SCORE_FLOAT64, chunk_bytes=64 << 20, stats=None):
+def call_contigs(model, items, out, min_af=0.12, min_coverage=6, batch_size=1000, score_mode=host.SCORE_FLOAT64, chunk_bytes=64 << 20, stats=None,
+                 extended_bed=None, confident_bed=None, fai=None):
     """A run over several contigs.  items: iterable of (name, mpileup text - bytes / mmap / uint8 array -, reference sequence uint8); out:
     a binary file object the rows are appended to (None on ranks other than 0).  Returns (sites, rows).
     One process: the rows of contig c are cut, brought to the host (on a stream of their own), formatted and written on a WRITER thread
     while contig c + 1 streams - formatting + writing is 4-5 ms behind every 6 M-column contig otherwise, a fifth of its time - on a
     quarter of the host threads (the parser keeps the rest busy; the last contig's rows get them all).  Under a process group the
-    contigs run one after the other through call_contig (its collectives stay on the issuing thread)."""
+    contigs run one after the other through call_contig (its collectives stay on the issuing thread).
+    extended_bed / confident_bed / fai: as for call_contig (a BED path is read once for the run when fai is given); under a process group they
+    pass straight through to every rank's call."""
     import time
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
@@ -815,9 +925,13 @@ def call_contigs(model, items, out, min_af=0.12, min_coverage=6, batch_size=1000
     sharded = tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1
     st = stats if stats is not None else {}
     n_sites = n_rows = 0
+    if fai is not None:                                     # (a BED path: parsed once, against the whole index)
+        from . import bed as _bed
+        extended_bed, confident_bed = (b if b is None or isinstance(b, dict) else _bed.load_bed(b, fai) for b in (extended_bed, confident_bed))
     if sharded:
         for name, text, seq in items:
-            rows_text, ns, nr = call_contig(model, text, name, seq, min_af, min_coverage, batch_size, score_mode, chunk_bytes, stats)
+            rows_text, ns, nr = call_contig(model, text, name, seq, min_af, min_coverage, batch_size, score_mode, chunk_bytes, stats,
+                                            extended_bed=extended_bed, confident_bed=confident_bed, fai=fai)
             if out is not None:
                 out.write(rows_text)
             n_sites += ns; n_rows += nr
@@ -856,10 +970,12 @@ def call_contigs(model, items, out, min_af=0.12, min_coverage=6, batch_size=1000
                 done = None
                 if on_device:
                     # returns when the contig's last chunk is issued: the next contig's text is on its way while this one's tail computes
-                    rows, done, fin = _stream_contig_dev(model, text, name, seq, 0, None, chunk_bytes, min_af, min_coverage, stats, None, defer=True)
+                    rows, done, fin = _stream_contig_dev(model, text, name, seq, 0, None, chunk_bytes, min_af, min_coverage, stats, None, defer=True,
+                                                         beds=_contig_beds(extended_bed, confident_bed, name, seq, fai))
                     finals.append(fin)
                 else:
-                    rows = stream_contig(model, text, name, seq, 0, None, chunk_bytes, min_af, min_coverage, stats)
+                    rows = stream_contig(model, text, name, seq, 0, None, chunk_bytes, min_af, min_coverage, stats,
+                                         extended_bed=extended_bed, confident_bed=confident_bed, fai=fai)
                 nxt = next(it, None)
                 n_sites += int(rows.shape[0])
                 st["sites"] = st.get("sites", 0) + int(rows.shape[0])
@@ -878,7 +994,8 @@ def call_contigs(model, items, out, min_af=0.12, min_coverage=6, batch_size=1000
 
 def call_variants(model, contigs, fasta_path, fai_text, output_file, **kw):
     """contigs: iterable of (name, path to <name>.mpileup).  Writes pileup.vcf (rank 0 only under torch.distributed: see
-    call_contig); returns total rows.  The contigs are one run (call_contigs): the rows of one are written while the next streams."""
+    call_contig); returns total rows.  The contigs are one run (call_contigs): the rows of one are written while the next streams.
+    extended_bed= / confident_bed= (call_contig) are checked against fai_text."""
     import torch.distributed as tdist
     root = not (tdist.is_available() and tdist.is_initialized()) or tdist.get_rank() == 0
     maps = []
@@ -896,6 +1013,8 @@ def call_variants(model, contigs, fasta_path, fai_text, output_file, **kw):
     try:
         if root:
             f.write(host.vcf_header(fai_text).encode())
+        if kw.get("extended_bed") is not None or kw.get("confident_bed") is not None:
+            kw.setdefault("fai", fai_text)
         return call_contigs(model, items(), f, **kw)[1]
     finally:
         if f:
