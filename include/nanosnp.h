@@ -197,7 +197,8 @@ int nsnp_pileup_rows_unpack(nsnp_ctx* ctx, const double* rows, int64_t N, int64_
                             float* gt_max, float* zy_max, float* cov8, void* stream);
 
 /* predict.py:54-65: gt_arg/zy_arg = argmax, gt_max/zy_max = max probability,
- * depth = -(sum of the negative entries of x[n,16,{0,1,2,3,9,10,11,12}]).  All device. */
+ * depth = -(sum of the negative entries of x[n,16,{0,1,2,3,9,10,11,12}]).  All device.  depth may be NULL (then x may be too).
+ * N = 0 is a no-op whatever the pointers are (an empty array has no address), as in the other calls. */
 int nsnp_pileup_postprocess(nsnp_ctx* ctx, const float* gt_prob, const float* zy_prob,
                             const int32_t* x, int64_t N, uint8_t* gt_arg, uint8_t* zy_arg,
                             float* gt_max, float* zy_max, int32_t* depth, void* stream);

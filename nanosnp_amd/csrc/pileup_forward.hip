@@ -1589,7 +1589,8 @@ extern "C" int nsnp_pileup_postprocess(nsnp_ctx* ctx, const float* gt_prob, cons
                                        const int32_t* x, int64_t N, uint8_t* gt_arg, uint8_t* zy_arg,
                                        float* gt_max, float* zy_max, int32_t* depth, void* stream)
 {
-    if (!ctx || N < 0 || !gt_prob || !zy_prob || !gt_arg || !zy_arg || !gt_max || !zy_max || (depth && !x)) return NSNP_EINVAL;
+    // (N == 0 is a no-op whatever the pointers, as in every other call: an empty array has no address)
+    if (!ctx || N < 0 || (N > 0 && (!gt_prob || !zy_prob || !gt_arg || !zy_arg || !gt_max || !zy_max || (depth && !x)))) return NSNP_EINVAL;
     if (N == 0) return NSNP_OK;
     hipLaunchKernelGGL(k_pileup_post, dim3((unsigned)NSNP_CDIV(N, 256)), dim3(256), 0, (hipStream_t)stream,
                        gt_prob, zy_prob, x, N, gt_arg, zy_arg, gt_max, zy_max, depth);

@@ -51,8 +51,13 @@ class LSTMNetwork:
             raise _lib.NanoSNPError("pileup_dim and haplotype_dim must agree (one feature reduction feeds both encoders)")
         if (d["pileup_length"], d["haplotype_length"]) != (33, 11):
             raise _lib.NanoSNPError(f"unsupported window lengths {d['pileup_length']}/{d['haplotype_length']}: kernels are built for 33/11")
-        if d["hidden_size"] % 64 or d["lstm_layers"] != 3:
-            raise _lib.NanoSNPError("hidden_size must be a multiple of 64 and lstm_layers 3 (include/nanosnp.h: nsnp_hap_load_weights)")
+        if d["hidden_size"] != 256 or d["lstm_layers"] != 3:
+            raise _lib.NanoSNPError("hidden_size must be 256 and lstm_layers 3 (include/nanosnp.h: nsnp_hap_load_weights)")
+        # the ranges nsnp_hap_load_weights accepts (NSNP_ESHAPE otherwise), refused here and not at the first load / forward
+        if not 1 <= d["pileup_dim"] <= 128:
+            raise _lib.NanoSNPError(f"pileup_dim / haplotype_dim {d['pileup_dim']} outside 1..128")
+        if d["gt_num_class"] < 1 or d["zy_num_class"] < 1 or d["gt_num_class"] + d["zy_num_class"] > 16:
+            raise _lib.NanoSNPError(f"gt_num_class {d['gt_num_class']} / zy_num_class {d['zy_num_class']}: each at least 1, at most 16 together")
         self.ctx = ctx if ctx is not None else _lib.Context(device)
         self._loaded = False
 

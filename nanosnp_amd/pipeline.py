@@ -286,8 +286,11 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
     if not hsets or min(s_.buf.numel() for s_ in hsets) < cap or len(hsets) < n_hsets:
         hsets = model._text_host_sets = [_TextSet(cap) for _ in range(n_hsets)]
         model._text_dev_sets = None
+    # (model._text_dev_sets = None makes the next call build the device text AND column sets anew, as the host sets' growth above does;
+    #  tests/test_gpu_predict.py uses that to make one model grow its sets again and again)
     tsets = getattr(model, "_text_dev_sets", None)
-    if not tsets or tsets[0].buf.device != dev or min(t_.buf.numel() for t_ in tsets) < cap or len(tsets) < n_tsets:
+    fresh_sets = not tsets or tsets[0].buf.device != dev or min(t_.buf.numel() for t_ in tsets) < cap or len(tsets) < n_tsets
+    if fresh_sets:
         tsets = model._text_dev_sets = [_TextSet(cap, dev) for _ in range(n_tsets)]
         model._col_dev_sets = [_ColSet(cap, dev) for _ in range(n_sets)]
         model._copy_stream = getattr(model, "_copy_stream", None) or host.copy_stream(dev)
@@ -329,7 +332,14 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
             fsets = getattr(model, "_fil_dev_sets", None)
             if not fsets or fsets[0].pos.device != dev or fsets[0].pos.numel() < csets[0].pos.numel() or fsets[0].bases.numel() < csets[0].bases.numel():
                 fsets = model._fil_dev_sets = [_FilSet(csets[0].pos.numel(), csets[0].bases.numel(), dev) for _ in range(3)]
+                fresh_sets = True
             fmeta = torch.zeros((len(ranges), 4), dtype=torch.int64, device=dev)
+    if fresh_sets:
+        # New device sets come out of the compute stream's pool: their blocks may be ones the previous contig's tensors gave back while its
+        # last kernels (call_contigs defers them) are still queued there and still read them.  The compute stream's own later work is
+        # ordered behind those kernels; the copy stream is not, and its first write into a new text buffer would be - so it waits once
+        # for everything queued on the compute stream so far.  Nothing in the steady state: sets that are kept are not new.
+        copy_stream.wait_stream(main)
 
     trace = st.get("trace")
 

@@ -19,6 +19,7 @@ top-level modules named model/optim/utils/options):
   hapfeat  HaplotypeModel/dataset_dev.get_frequency_feature -> hap_features.npz
   hapfwd   HaplotypeModel/model_dev.LSTMNetwork.predict with seeded weights
            (trained weights are absent upstream)          -> hap_fwd_h32.npz, hap_fwd_h256.npz
+  hapfwd_dims  the same module at other feature / class counts (F = 1 .. 128, up to 16 classes) -> hap_fwd_dims.npz
 """
 from __future__ import annotations
 
@@ -462,6 +463,50 @@ def group_hapfwd():
         np.savez_compressed(os.path.join(GOLD, name + ".npz"), xp=xp, xh=xh,
                             gt=gt.numpy(), zy=zy.numpy(), seed=seed)
         print(name, ": gt argmax", gt.numpy().argmax(1), "max p %.2f .. %.2f" % (gt.numpy().max(1).min(), gt.numpy().max(1).max()))
+
+
+def group_hapfwd_dims():
+    """model_dev.LSTMNetwork.predict at the model dimensions nsnp_hap_load_weights accepts and no other fixture visits: F = 1 (one
+    feature in one chunk), 16 (a chunk without padding), 17 (a chunk of one feature and fifteen padded lanes; one class per head), 96,
+    113 (sixteen classes: the heads kernel's whole logit array), 128 (the largest); scaled seeded weights as hap_fwd_h256x, inputs
+    standard_normal * 300 as tests/test_gpu_hap.py::test_hap_forward_sensitive_inputs -> hap_fwd_dims.npz"""
+    import zlib
+    import torch
+    from tests.helpers import hap_dims_inputs, hap_weight_names, seeded_hap_weights
+    _stub_modules()
+    sys.path.insert(0, os.path.join(REF, "HaplotypeModel"))
+    from model_dev import LSTMNetwork       # noqa: E402  (reference module)
+    from utils import AttrDict              # noqa: E402
+    dims = [(1, 10, 3), (16, 10, 3), (17, 1, 1), (96, 13, 3), (113, 15, 1), (128, 10, 3)]
+    N, out, crcs = 24, {}, []
+    for i, (F, n_gt, n_zy) in enumerate(dims):
+        seed = 40 + i
+        cfg = AttrDict({"model": {"pileup_dim": F, "haplotype_dim": F, "pileup_length": 33, "haplotype_length": 11, "hidden_size": 256,
+                                  "lstm_layers": 3, "gt_num_class": n_gt, "zy_num_class": n_zy, "dropout": 0.1}})
+        m = LSTMNetwork(cfg)
+        ws = seeded_hap_weights(seed, F=F, n_gt=n_gt, n_zy=n_zy, ih_scale=0.03, head_scale=120.0)
+        missing = m.load_state_dict({k: torch.from_numpy(w) for k, w in zip(hap_weight_names(), ws)}, strict=False)
+        assert not missing.unexpected_keys and all("crit" in k for k in missing.missing_keys), missing
+        m.eval()
+        xp, xh = hap_dims_inputs(seed, N, F)
+        with torch.no_grad():
+            gt, zy = m.predict(torch.from_numpy(xp), torch.from_numpy(xh))
+        gt, zy = gt.numpy(), zy.numpy()
+        assert gt.shape == (N, n_gt) and zy.shape == (N, n_zy)
+        # outputs differ from site to site (a head of ONE class is the constant 1 whatever the input: (17, 1, 1) cannot vary)
+        if n_gt > 1:
+            assert gt.std(0).max() > 1e-3, (F, n_gt, n_zy)
+        if n_zy > 1:
+            assert zy.std(0).max() > 1e-3, (F, n_gt, n_zy)
+        # 391,776 random fp32 inputs do not compress (1.5 MB): the fixture holds their seeds and the CRC-32 of their bytes, the tests
+        # rebuild them with the same tests.helpers.hap_dims_inputs and refuse to go on when the bytes differ
+        out.update({f"gt{i}": gt, f"zy{i}": zy})
+        crcs.append((zlib.crc32(xp.tobytes()), zlib.crc32(xh.tobytes())))
+        print("hap_fwd_dims", (F, n_gt, n_zy), ": gt std %.3g, zy std %.3g" % (gt.std(0).max(), zy.std(0).max()))
+    path = os.path.join(GOLD, "hap_fwd_dims.npz")
+    np.savez_compressed(path, dims=np.array(dims, np.int32), seeds=np.arange(40, 40 + len(dims), dtype=np.int32), n_sites=N,
+                        input_crc32=np.array(crcs, np.int64), **out)
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(GOLD, "hap_fwd_h256x.npz")), os.path.getsize(path)
 
 
 def group_cat():
@@ -927,7 +972,7 @@ def group_cat_large():
 
 
 GROUPS = {"haparrange": group_haparrange, "twostage": group_twostage, "twostage_s2": group_twostage_s2, "next": group_next, "vcf": group_vcf, "encode": group_encode, "encode_reader": group_encode_reader, "pileup": group_pileup, "pileup_ckpts": group_pileup_ckpts, "hapfeat": group_hapfeat,
-          "hapfwd": group_hapfwd, "cat": group_cat, "hapfwd_large": group_hapfwd_large, "cat_large": group_cat_large, "refbin": group_refbin}
+          "hapfwd": group_hapfwd, "hapfwd_dims": group_hapfwd_dims, "cat": group_cat, "hapfwd_large": group_hapfwd_large, "cat_large": group_cat_large, "refbin": group_refbin}
 
 if __name__ == "__main__":
     if not os.path.isdir(REF):

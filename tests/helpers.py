@@ -23,6 +23,34 @@ def golden(name):
     return os.path.join(GOLDEN, name)
 
 
+def hap_dims_inputs(seed, n, F):
+    """the HaplotypeModel inputs of tests/golden/hap_fwd_dims.npz (make_golden.py hapfwd_dims) and of the dimension sweep: standard_normal *
+    300 as fp32 [n,F,33] and [n,F,11] - layer, step, direction or feature mix-ups then show as O(0.1) output differences, and every
+    magnitude stays under 2048, where the f16x3 mode keeps its 1e-4 bound (include/nanosnp.h)"""
+    rng = np.random.default_rng(400 + seed)
+    xp = (rng.standard_normal((n, F, 33)) * 300).astype(np.float32)
+    xh = (rng.standard_normal((n, F, 11)) * 300).astype(np.float32)
+    return xp, xh
+
+
+HAP_DIMS_WEIGHTS = dict(ih_scale=0.03, head_scale=120.0)          # the scaled seeded weights of hap_fwd_h256x.npz
+
+
+def hap_dims_cases():
+    """tests/golden/hap_fwd_dims.npz -> [(F, n_gt, n_zy, seed, xp, xh, gt, zy)]: model_dev.LSTMNetwork.predict at six model dimensions.  The
+    fixture holds the outputs, the seeds and the CRC-32 of the inputs' bytes (random fp32 does not compress: 1.5 MB); the inputs are
+    rebuilt here, and bytes other than those the reference module saw are an error, not a comparison against the wrong thing."""
+    import zlib
+    z = np.load(golden("hap_fwd_dims.npz"))
+    cases = []
+    for i, ((F, n_gt, n_zy), seed) in enumerate(zip(z["dims"].tolist(), z["seeds"].tolist())):
+        xp, xh = hap_dims_inputs(seed, int(z["n_sites"]), F)
+        assert [zlib.crc32(xp.tobytes()), zlib.crc32(xh.tobytes())] == z["input_crc32"][i].tolist(), \
+            "hap_fwd_dims.npz: the rebuilt inputs are not the recorded ones (another numpy random stream?)"
+        cases.append((F, n_gt, n_zy, seed, xp, xh, z[f"gt{i}"], z[f"zy{i}"]))
+    return cases
+
+
 # ---- stand-in for the pysam.AlignmentFile that create_pileup_haplotype.single_group_pileup_haplotype_feature iterates ----------
 # Only what the function touches (create_pileup_haplotype.py:39-47,90-134): .pileup() yielding columns with .pos / .n /
 # .pileups[*].alignment.{query_name, has_tag, get_tag, query_sequence, query_qualities, mapping_quality}, .is_del, .is_refskip,

@@ -233,6 +233,40 @@ def test_a_run_over_several_contigs_writes_each_contigs_rows_in_order(tmp_path, 
         assert call_contigs(m, [], f) == (0, 0)
 
 
+def test_contigs_of_growing_size_reallocate_the_device_sets_behind_queued_work(tmp_path, pileup_weights, monkeypatch):
+    """call_contigs defers every contig's last kernels, so the next contig is staged, copied and tokenised while they are still queued.  A
+    contig that needs larger device text / column sets than its predecessor re-allocates them at that moment, out of the compute stream's
+    pool - possibly the very blocks the queued kernels still read - and the copy stream, which writes chunk 0 into the new text buffer,
+    has to wait for the compute stream first (pipeline._stream_contig_dev).  Contigs of strictly growing size (2 k, 8 k, 30 k, 90 k
+    columns) as ONE chunk each and batches of 64: every contig re-allocates; three seeds on one model, its device sets dropped between
+    them so that each seed grows them again.  The output equals the concatenation of call_contig on a fresh model per contig.
+
+    A race cannot be made to fail on demand: this case passing does not prove the ordering, and it is not what the fix stands on (the
+    stream-ordering argument in the code does).  docs/rounds/r09.md records what the case did on the commit before the fix."""
+    from nanosnp_amd import host
+    from nanosnp_amd.pileup_model import LSTMNetwork
+    from nanosnp_amd.pipeline import call_contig, call_contigs
+    monkeypatch.setenv("NSNP_TOKENISE", "device")
+    m = LSTMNetwork().load_weight_list(pileup_weights)
+    for seed in range(3):
+        contigs, want, want_sites, want_rows = [], b"", 0, 0
+        for i, n in enumerate((2_000, 8_000, 30_000, 90_000)):
+            cols = host.synth_columns(20261900 + 10 * seed + i, n, coverage=30, het_rate=0.05)
+            name, text, seq = f"g{seed}_{i}", bytes(cols.mpileup_text_native(f"g{seed}_{i}")), cols.ref.copy()
+            contigs.append((name, text, seq))
+            fresh = LSTMNetwork().load_weight_list(pileup_weights)
+            t, ns, nr = call_contig(fresh, text, name, seq, batch_size=64, chunk_bytes=1 << 30)
+            want += bytes(t); want_sites += ns; want_rows += nr
+            del t
+            fresh.ctx.close()
+        assert want_rows > 1000
+        m._text_dev_sets = None                                      # (every seed starts from no device sets and grows them four times)
+        out = tmp_path / f"grow{seed}.vcf"
+        with open(out, "wb") as f:
+            assert call_contigs(m, contigs, f, batch_size=64, chunk_bytes=1 << 30) == (want_sites, want_rows)
+        assert out.read_bytes() == want, seed
+
+
 def test_streamed_pipeline_edge_inputs(pileup_weights, tok_mode):
     """call_contig on the inputs a real run meets at its edges: no text, one line, fewer columns than a window, a last line without
     its newline, CRLF line ends, a chunk size below one line (every line its own chunk), and the same contig again on the same model

@@ -94,6 +94,24 @@ def test_hap_forward_golden_with_site_dependent_outputs():
     assert np.array_equal(gt.argmax(1), z["gt"].argmax(1)) and len(set(z["gt"].argmax(1).tolist())) >= 3
 
 
+def test_hap_forward_at_other_model_dimensions_matches_the_reference_module():
+    """hap_fwd_dims.npz: model_dev.LSTMNetwork.predict at (F, n_gt, n_zy) = (1, 10, 3), (16, 10, 3), (17, 1, 1), (96, 13, 3), (113, 15, 1),
+    (128, 10, 3) - the ends of what nsnp_hap_load_weights accepts, a feature count with and without a padded last chunk of sixteen,
+    heads of one class and sixteen classes together.  Pins the oracle there: tests/test_gpu_hap_dims.py uses it as its yardstick."""
+    from tests.helpers import HAP_DIMS_WEIGHTS, hap_dims_cases
+    cases = hap_dims_cases()
+    assert [c[:3] for c in cases] == [(1, 10, 3), (16, 10, 3), (17, 1, 1), (96, 13, 3), (113, 15, 1), (128, 10, 3)]
+    for F, n_gt, n_zy, seed, xp, xh, gt_ref, zy_ref in cases:
+        ws = seeded_hap_weights(seed, F=F, n_gt=n_gt, n_zy=n_zy, **HAP_DIMS_WEIGHTS)
+        gt, zy = oracle.hap_forward(ws, xp, xh, n_gt=n_gt, n_zy=n_zy, nthreads=8)
+        assert gt.shape == gt_ref.shape == (24, n_gt) and zy.shape == zy_ref.shape == (24, n_zy)
+        d = max(np.abs(gt - gt_ref).max(), np.abs(zy - zy_ref).max())
+        print("F %d, classes %d + %d: max |oracle - reference| = %.3g" % (F, n_gt, n_zy, d))
+        assert d < PROB_ATOL, (F, n_gt, n_zy)
+        if n_gt > 1:                                    # (a head of one class is the constant 1)
+            assert gt_ref.std(0).max() > 1e-3 and np.array_equal(gt.argmax(1), gt_ref.argmax(1))
+
+
 def test_hap_features_and_forward_large_golden_incl_edge_sites():
     """hap_fwd_large.npz: 256 sites through the reference's own get_frequency_feature + ref row + LSTMNetwork.predict (all-padding
     planes, depth-1 sites, saturated features, deletion-only sites among them); the oracle runs features AND forward"""
