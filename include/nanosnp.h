@@ -12,6 +12,7 @@
  *                                + candidate test               dna_sv_tensor/src/make_candidate_snp_tensor/main.cpp:194-201
  *   nsnp_pileup_select_sites     window / pending-queue rule    dna_sv_tensor/src/make_candidate_snp_tensor/main.cpp:174-217
  *   nsnp_mpileup_tokenise        LineReader + split_line + atoll dna_sv_tensor/src/make_candidate_snp_tensor/main.cpp:162-172
+ *   nsnp_mpileup_tokenise_contigs  the same + DNA_ExtractChrPileupData dna_sv_tensor/src/extract_chr_pileup_data/main.cpp:11-80
  *   nsnp_pileup_gather_windows   33-column window emission      dna_sv_tensor/src/make_candidate_snp_tensor/main.cpp:233-244
  *   nsnp_pileup_postprocess      argmax / max / depth           PileupModel/predict.py:52-65
  *   nsnp_hap_features            get_frequency_feature + ref row HaplotypeModel/dataset_dev.py:55-87,337-349
@@ -297,6 +298,40 @@ int nsnp_pileup_call_rows(nsnp_ctx* ctx, const int32_t* counts, const int64_t* c
 int nsnp_mpileup_tokenise(nsnp_ctx* ctx, const uint8_t* text, int64_t text_len, const uint8_t* chr_seq, int64_t chr_len,
                           int64_t cap_cols, int64_t cap_bytes, int64_t* pos, int64_t* col_off, uint8_t* bases, uint8_t* ref,
                           int64_t* meta, void* stream);
+
+/* nsnp_mpileup_tokenise for a text that holds SEVERAL contigs (samtools mpileup BAM -o pileup_data: the whole genome in one file), with
+ * the contig of every line found on the device - what DNA_ExtractChrPileupData (dna_sv_tensor/src/extract_chr_pileup_data/main.cpp:11-80)
+ * does on one host thread by cutting the text into <chr>.mpileup files.  text / pos / col_off / bases: as above, bit for bit what
+ * nsnp_mpileup_tokenise gives on this text with chr_seq = NULL (always its three-launch form: the option tok_fused is ignored here).
+ * The contig table, all device arrays: names_blob + name_off (int64 [n_contigs + 1]): the wanted names laid end to end; genome (uint8
+ * [genome_len]): their sequences as stored in the FASTA, back to back; seq_off (int64 [n_contigs + 1], ascending from 0 to genome_len).
+ * A line's name is the bytes in front of its first C isspace byte (main.cpp:11-19: NOT the first tab-delimited token; a line that starts
+ * with a tab has the empty name); two names are equal when their bytes are.  A RUN starts at the first line and at every line whose name
+ * differs from the name of the line in front; a name is looked up in the table only there (the first equal entry counts).
+ *   cid  int32 [cap_cols]  the table index of the line's contig, -1 for a name the table does not hold
+ *   ref  uint8 [cap_cols]  genome[seq_off[cid] + pos - 1], 'N' for cid -1
+ *   key  int64 [cap_cols]  (cid << NSNP_TOK_KEY_SHIFT) | pos: the "position" nsnp_pileup_select_sites* and nsnp_pileup_call_rows take when
+ *                          contigs share a call; -2^62 for cid -1 (the filler of nsnp_pileup_filter_columns: no step to or from it is + 1,
+ *                          and an 'N' reference base is never a candidate)
+ *   runs int64 [cap_runs][2], in any memory the device can write: { first line, cid } of every run in line order
+ *   meta int64 [4], likewise: { lines, column-5 bytes, status, runs }
+ * LIMITS: a key must be exact in a double (nsnp_pileup_call_rows stores it in one) and a step from a contig's last position must never
+ * be + 1: n_contigs <= NSNP_TOK_MAX_CONTIGS (2^17) and genome_len < 2^NSNP_TOK_KEY_SHIFT (2^36: the table's sequences together, so
+ * every contig's length, stay below 68.7 G bases) - NSNP_EINVAL otherwise.  A name may have at most NSNP_TOK_NAME_MAX bytes: a line with
+ * a longer one sets NSNP_TOK_ENAME.  A name may straddle any tile boundary of the kernels.
+ * status: the bits above, with NSNP_TOK_EPOS = a position outside [1, length of the line's OWN contig] on a line of a known contig (lines
+ * of unknown contigs are not checked: the reference never parses them), NSNP_TOK_ERANGE also for more than cap_runs runs (meta[3] holds the
+ * count needed; the first cap_runs entries were written).  Nothing is read beyond text + text_len or written beyond the capacities.
+ * Eight launches, no workgroup waits for another; scratch lives in the context (one call at a time per context): 8 bytes per line of
+ * min(cap_cols, text_len + 1) beside the tokeniser's. */
+#define NSNP_TOK_ENAME       16
+#define NSNP_TOK_KEY_SHIFT   36
+#define NSNP_TOK_MAX_CONTIGS (1 << 17)
+#define NSNP_TOK_NAME_MAX    255
+int nsnp_mpileup_tokenise_contigs(nsnp_ctx* ctx, const uint8_t* text, int64_t text_len, const uint8_t* names_blob, const int64_t* name_off,
+                                  const uint8_t* genome, const int64_t* seq_off, int64_t n_contigs, int64_t genome_len,
+                                  int64_t cap_cols, int64_t cap_bytes, int64_t cap_runs, int64_t* pos, int64_t* col_off, uint8_t* bases,
+                                  uint8_t* ref, int32_t* cid, int64_t* key, int64_t* runs, int64_t* meta, void* stream);
 
 /* x[n][t][c] = counts[center_idx[n]-16+t][c]; x: device int32 [N,33,18]. */
 int nsnp_pileup_gather_windows(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx,

@@ -62,6 +62,7 @@ _SIGNATURES = {
                                                  C.c_void_p]),
     "nsnp_pileup_call_rows": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_mpileup_tokenise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
+    "nsnp_mpileup_tokenise_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 5 + [C.c_void_p] * 9),
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nsnp_hap_features_i8": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nsnp_hap_arrange_reads": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
@@ -94,6 +95,74 @@ def tokenise_status_check(status, what="mpileup text"):
         raise ValueError(f"{what}: position outside the reference sequence")
     if status & 8:
         raise NanoSNPError(f"{what}: tokeniser output buffers too small")
+    if status & 16:
+        raise ValueError(f"{what}: a contig name longer than {NAME_MAX} bytes")
+
+
+# nsnp_mpileup_tokenise_contigs (include/nanosnp.h): key = (contig index << KEY_SHIFT) | position, exact in a float64
+KEY_SHIFT, MAX_CONTIGS, NAME_MAX = 36, 1 << 17, 255
+KEY_FILLER = -(1 << 62)
+
+
+def check_key_limits(n_contigs, genome_len):
+    """the limits a contig table must keep so that every key is exact in a float64 and no step between two contigs is + 1"""
+    if n_contigs > MAX_CONTIGS:
+        raise NanoSNPError(f"contig table: {n_contigs} contigs, at most {MAX_CONTIGS} share a call")
+    if genome_len >= 1 << KEY_SHIFT:
+        raise NanoSNPError(f"contig table: {genome_len} bases in all, fewer than 2^{KEY_SHIFT} share a call")
+
+
+class ContigTable:
+    """The wanted contigs of a whole-genome text, resident on the device for Context.mpileup_tokenise_contigs: names_blob + name_off, genome
+    (the sequences as stored in the FASTA, back to back) + seq_off; on the host the names and lengths.  contigs: {name: uint8 sequence}
+    (in table order), or fasta= a path with names= the wanted names (host.fasta_load_contig reads each)."""
+
+    def __init__(self, contigs=None, fasta=None, names=None, device=0):
+        import numpy as np
+        import torch
+        from . import host
+        if contigs is None:
+            names = [str(n) for n in names]
+            load = lambda n: host.fasta_load_contig(fasta, n)
+        else:
+            names = [str(n) for n in contigs]
+            load = lambda n: np.ascontiguousarray(contigs[n], np.uint8).reshape(-1)
+        if len(set(names)) != len(names):
+            raise NanoSNPError("contig table: a name is listed twice")
+        check_key_limits(len(names), 0)
+        if not torch.cuda.is_available():
+            raise NanoSNPError("no GPU visible: a contig table lives on the device (nanosnp_amd has no CPU fallback)")
+        dev = torch.device("cuda", int(device))
+        self.names = names
+        # one contig on the host at a time: read, appended to the device genome, dropped (a human genome is 3.1 GB; the device array
+        # grows by doubling - copied on the device a few times, cut to size at the end - and is never held on the host as a whole)
+        self.lengths, genome, used = [], torch.empty(1 << 20, dtype=torch.uint8, device=dev), 0
+        for n in names:
+            seq = load(n)
+            m = int(seq.size)
+            if used + m > genome.numel():
+                check_key_limits(len(names), used + m)
+                grown = torch.empty(max(used + m, 2 * genome.numel()), dtype=torch.uint8, device=dev)
+                grown[:used] = genome[:used]
+                genome = grown
+            if m:
+                genome[used:used + m] = torch.from_numpy(np.array(seq, np.uint8)).to(dev)      # (a copy: the source may be read-only)
+            self.lengths.append(m); used += m
+            del seq
+        self.genome_len = used
+        check_key_limits(len(names), used)
+        self.genome = genome[:max(used, 1)] if genome.numel() <= used + used // 8 + (1 << 20) else genome[:max(used, 1)].clone()
+        del genome                                         # (what the doubling left over goes back to the pool)
+        enc = [n.encode() for n in names]
+        self.name_off_host = np.concatenate([[0], np.cumsum([len(e) for e in enc])]).astype(np.int64)
+        self.seq_off_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        up = lambda a, dt: torch.from_numpy(np.array(a, dt)).to(dev)
+        self.names_blob = up(np.frombuffer(b"".join(enc) or b"\0", np.uint8), np.uint8)
+        self.name_off = up(self.name_off_host, np.int64)
+        self.seq_off = up(self.seq_off_host, np.int64)
+
+    def __len__(self):
+        return len(self.names)
 
 _lib = None
 
@@ -454,6 +523,51 @@ class Context:
             break
         tokenise_status_check(status)
         return pos[:m], off[:m + 1], bases[:nb], (ref[:m] if ref is not None else None)
+
+    TOK_ENAME = 16
+
+    def mpileup_tokenise_contigs_into(self, text, table, pos, col_off, bases, ref, cid, key, runs, meta, stream=None):
+        """nsnp_mpileup_tokenise_contigs into the caller's buffers, asynchronously: text uint8 [T] on the device, table a ContigTable; pos
+        int64 [cap], col_off int64 [cap + 1], bases uint8 [cap_bytes], ref uint8 [cap], cid int32 [cap], key int64 [cap] on the device; runs
+        int64 [cap_runs, 2] and meta int64 [4] on the device or in pinned host memory ({lines, bytes, status, runs} once the stream has
+        passed the call)."""
+        check(self.lib.nsnp_mpileup_tokenise_contigs(self.handle, _dptr(text), int(text.numel()), _dptr(table.names_blob), _dptr(table.name_off),
+                                                     _dptr(table.genome), _dptr(table.seq_off), len(table), int(table.genome_len),
+                                                     int(min(pos.numel(), ref.numel(), cid.numel(), key.numel())), int(bases.numel()),
+                                                     int(runs.numel() // 2), _dptr(pos), _dptr(col_off), _dptr(bases), _dptr(ref), _dptr(cid),
+                                                     _dptr(key), runs.data_ptr(), meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_mpileup_tokenise_contigs")
+
+    def mpileup_tokenise_contigs(self, text, table, stream=None):
+        """mpileup text of several contigs (uint8 device tensor) -> (pos [M] int64, col_off [M + 1] int64, bases uint8, ref uint8 [M], cid int32
+        [M], key int64 [M], runs int64 [R, 2]) on the device.  Synchronous (the sizes come back from the device, read behind `stream`);
+        raises on text the reference's reader could not read."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream(text.device)
+        t = int(text.numel())
+        cap, cap_b, cap_r = t // 10 + 2, max(t, 1), 1024
+        dev = text.device
+        while True:
+            with torch.cuda.stream(s):                 # (the outputs belong to the stream that writes them)
+                pos = torch.empty(cap, dtype=torch.int64, device=dev)
+                off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+                bases = torch.empty(cap_b, dtype=torch.uint8, device=dev)
+                ref = torch.empty(cap, dtype=torch.uint8, device=dev)
+                cid = torch.empty(cap, dtype=torch.int32, device=dev)
+                key = torch.empty(cap, dtype=torch.int64, device=dev)
+                runs = torch.empty((cap_r, 2), dtype=torch.int64, device=dev)
+                meta = torch.zeros(4, dtype=torch.int64, device=dev)
+                self.mpileup_tokenise_contigs_into(text, table, pos, off, bases, ref, cid, key, runs, meta, s)
+                m, nb, status, r = meta.tolist()       # (the read is queued on `s`, behind the kernels)
+            if status & self.TOK_ERANGE and not status & (self.TOK_EFORMAT | self.TOK_BLANK | self.TOK_ENAME):
+                if (cap, cap_b, cap_r) == (max(cap, m + 1), max(cap_b, nb), max(cap_r, r)):
+                    break
+                cap, cap_b, cap_r = max(cap, m + 1), max(cap_b, nb), max(cap_r, r)
+                continue
+            break
+        tokenise_status_check(status)
+        torch.cuda.current_stream(dev).wait_stream(s)
+        return pos[:m], off[:m + 1], bases[:nb], ref[:m], cid[:m], key[:m], runs[:r]
 
     def pileup_select_sites_range(self, pos, flags, own_lo, own_hi, meta, stream=None):
         """select_sites for one chunk of a streamed text, without a host round trip: -> center_idx int64 [M] (the first meta[0] entries are the

@@ -585,6 +585,8 @@ void nsnp_tok_free(nsnp_ctx* ctx)
 {
     if (ctx->tok_ws) (void)hipFree(ctx->tok_ws);
     ctx->tok_ws = nullptr; ctx->tok_ws_bytes = 0;
+    if (ctx->ctg_ws) (void)hipFree(ctx->ctg_ws);
+    ctx->ctg_ws = nullptr; ctx->ctg_ws_bytes = 0;
 }
 
 extern "C" int nsnp_mpileup_tokenise(nsnp_ctx* ctx, const uint8_t* text, int64_t text_len, const uint8_t* chr_seq, int64_t chr_len,
@@ -625,6 +627,258 @@ extern "C" int nsnp_mpileup_tokenise(nsnp_ctx* ctx, const uint8_t* text, int64_t
     hipLaunchKernelGGL(k_tok_emit, dim3((unsigned)n_tiles), dim3(TK_BLOCK), 0, s, t, (const int64_t*)tile_nl, (const int64_t*)tile_bytes,
                        (const uint4*)chunk_masks, chr_seq, chr_len, cap_cols, cap_bytes, pos, ref, col_off, bases, ws_meta);
     hipLaunchKernelGGL(k_tok_status, dim3(1), dim3(1), 0, s, ws_meta, meta);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+// ---- the contig of every line: a whole-genome text (samtools mpileup BAM -o pileup_data, every contig in one file) ---------------------
+// Replaces DNA_ExtractChrPileupData (dna_sv_tensor/src/extract_chr_pileup_data/main.cpp:11-80), which cuts that text into one file per
+// wanted contig on one host thread: a line's name is the bytes in front of its first C isspace byte (extract_char_name), a run starts
+// where the name differs from the name of the line in front, and only there the name is looked up among the wanted ones.  Here, behind the
+// three launches of the tokeniser above (pos / col_off / bases as they are; their per-tile newline counts and newline masks reused):
+//   k_ctg_line_starts  per tile, from the newline masks of launch 1 (the text itself is not read): the byte offset every line starts at
+//   k_ctg_flag         per line: its name against the name of the line in front, byte by byte until either ends (a handful of bytes of
+//                      text per line); where they differ the name is looked up in the table; per 256 lines the run starts and the last
+//                      start's contig
+//   k_ctg_scan         one workgroup: exclusive scan of both over the blocks of 256 lines
+//   k_ctg_emit         per line: the contig of the nearest run start at or in front of it, its reference byte (one gather), its key;
+//                      the run table
+//   k_ctg_status       one thread: status and run count -> meta; re-arms the scratch words
+// No workgroup waits for another.
+namespace {
+
+constexpr int CG_BLOCK = 256;
+constexpr int CG_NONE = INT32_MIN;                 // "this line starts no run" (contig ids are >= -1)
+constexpr int CG_NAME_MAX = NSNP_TOK_NAME_MAX;
+constexpr int64_t CG_FILLER = -(1ll << 62);        // the key of a line of an unknown contig (nsnp_pileup_filter_columns' filler)
+
+struct CtgTable { const uint8_t* names; const int64_t* name_off; const uint8_t* genome; const int64_t* seq_off; int64_t n, genome_len; };
+
+__device__ __forceinline__ bool cg_space(int c) { return c == ' ' || (c >= '\t' && c <= '\r'); }      // isspace of the C locale
+
+__global__ __launch_bounds__(TK_BLOCK) void k_ctg_line_starts(TokText t, const int64_t* __restrict__ tile_nl, const uint4* __restrict__ chunk_masks,
+                                                               int64_t n_tiles, int64_t cap_lines, int64_t* __restrict__ ls,
+                                                               int64_t* __restrict__ ws_meta)
+{
+    __shared__ int sh[TK_BLOCK / 64][2];
+    const int tid = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.x * TK_TILE + tid * TK_CHUNK;
+    const uint32_t nlm = chunk_masks[(int64_t)blockIdx.x * TK_BLOCK + tid].x;
+    const BlockScan s = tk_block_scan(__popc(nlm), 0, sh);
+    int64_t line = tile_nl[blockIdx.x] + s.v_excl;             // newlines in front of this chunk = the index of the line its first newline ends
+    for (uint32_t m = nlm; m; m &= m - 1) {
+        const int64_t p = p0 + __ffs(m) - 1;
+        ++line;                                                // the line behind this newline - when the text goes on
+        if (p + 1 < t.hi && line < cap_lines) ls[line] = p + 1 - t.lo;
+    }
+    if (blockIdx.x == 0 && tid == 0 && cap_lines > 0) ls[0] = 0;
+    if (blockIdx.x == n_tiles - 1 && tid == 0) ws_meta[4] = tile_nl[blockIdx.x] + s.v_total;          // lines of the text, for the per-line launches
+}
+
+__global__ __launch_bounds__(CG_BLOCK) void k_ctg_flag(const uint8_t* __restrict__ text, int64_t text_len, CtgTable tb, const int64_t* __restrict__ ls,
+                                                        int64_t cap_lines, int32_t* __restrict__ cid, int64_t* __restrict__ blk_cnt,
+                                                        int* __restrict__ blk_last, int64_t* __restrict__ ws_meta)
+{
+    __shared__ int sh_cnt[CG_BLOCK / 64], sh_last[CG_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t n_lines = ws_meta[4] < cap_lines ? ws_meta[4] : cap_lines;
+    const int64_t b0 = (int64_t)blockIdx.x * CG_BLOCK;
+    if (b0 >= n_lines) return;
+    const int64_t L = b0 + tid;
+    int mine = CG_NONE;
+    uint32_t err = 0;
+    if (L < n_lines) {
+        const int64_t s = ls[L];
+        bool start = L == 0;
+        if (!start) {
+            const int64_t sp = ls[L - 1];
+            for (int i = 0;; ++i) {
+                if (i > CG_NAME_MAX) { err |= NSNP_TOK_ENAME; break; }
+                const int a = s + i < text_len ? (int)text[s + i] : '\n';
+                const int b = sp + i < text_len ? (int)text[sp + i] : '\n';
+                const bool ea = cg_space(a), eb = cg_space(b);
+                if (ea || eb) { start = !(ea && eb); break; }
+                if (a != b) { start = true; break; }
+            }
+        }
+        if (start && !err) {
+            int len = 0;
+            while (len <= CG_NAME_MAX && s + len < text_len && !cg_space(text[s + len])) ++len;
+            mine = -1;
+            if (len > CG_NAME_MAX) err |= NSNP_TOK_ENAME;
+            else {
+                for (int64_t k = 0; k < tb.n; ++k) {
+                    const int64_t o = tb.name_off[k];
+                    if (tb.name_off[k + 1] - o != len) continue;
+                    int j = 0;
+                    while (j < len && tb.names[o + j] == text[s + j]) ++j;
+                    if (j == len) { mine = (int)k; break; }
+                }
+            }
+        }
+        cid[L] = mine;
+    }
+    if (err) atomicOr(reinterpret_cast<unsigned long long*>(ws_meta + 3), (unsigned long long)err);
+    const unsigned long long bm = __ballot(mine != CG_NONE);
+    const int last = __shfl(mine, bm ? 63 - __builtin_clzll(bm) : 0);
+    if (lane == 0) { sh_cnt[wave] = __popcll(bm); sh_last[wave] = bm ? last : CG_NONE; }
+    __syncthreads();
+    if (tid == 0) {
+        int cnt = 0, l = CG_NONE;
+        for (int k = 0; k < CG_BLOCK / 64; ++k) { cnt += sh_cnt[k]; if (sh_last[k] != CG_NONE) l = sh_last[k]; }
+        blk_cnt[blockIdx.x] = cnt; blk_last[blockIdx.x] = l;
+    }
+}
+
+// one workgroup: run starts / the last start's contig in front of every block of 256 lines (in place); the run count -> ws_meta[5]
+__global__ __launch_bounds__(1024) void k_ctg_scan(int64_t* __restrict__ blk_cnt, int* __restrict__ blk_last, int64_t cap_lines,
+                                                    int64_t* __restrict__ ws_meta)
+{
+    __shared__ long long sh_v[16];
+    __shared__ int sh_l[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t n_lines = ws_meta[4] < cap_lines ? ws_meta[4] : cap_lines;
+    const int64_t nb = NSNP_CDIV(n_lines, (int64_t)CG_BLOCK);
+    long long carry_n = 0;
+    int carry_l = CG_NONE;
+    for (int64_t base = 0; base < nb; base += 1024) {
+        const int64_t i = base + tid;
+        long long vi = i < nb ? blk_cnt[i] : 0;
+        int li = i < nb ? blk_last[i] : CG_NONE;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long pv = __shfl_up(vi, o); const int pl = __shfl_up(li, o);
+            if (lane >= o) { vi += pv; if (li == CG_NONE) li = pl; }
+        }
+        if (lane == 63) { sh_v[wave] = vi; sh_l[wave] = li; }
+        __syncthreads();
+        long long vb = 0, vt = 0; int lb = CG_NONE, lt = CG_NONE;
+        for (int k = 0; k < 16; ++k) {
+            if (k == wave) { vb = vt; lb = lt; }
+            vt += sh_v[k]; if (sh_l[k] != CG_NONE) lt = sh_l[k];
+        }
+        long long ve = __shfl_up(vi, 1); int le = __shfl_up(li, 1);
+        if (lane == 0) { ve = 0; le = CG_NONE; }
+        if (i < nb) {
+            blk_cnt[i] = carry_n + vb + ve;
+            blk_last[i] = le != CG_NONE ? le : (lb != CG_NONE ? lb : carry_l);
+        }
+        carry_n += vt;
+        if (lt != CG_NONE) carry_l = lt;
+        __syncthreads();
+    }
+    if (tid == 0) ws_meta[5] = carry_n;
+}
+
+__global__ __launch_bounds__(CG_BLOCK) void k_ctg_emit(CtgTable tb, const int64_t* __restrict__ pos, const int64_t* __restrict__ blk_cnt,
+                                                        const int* __restrict__ blk_last, int64_t cap_lines, int64_t cap_runs,
+                                                        int32_t* __restrict__ cid, uint8_t* __restrict__ ref, int64_t* __restrict__ key,
+                                                        int64_t* __restrict__ runs, int64_t* __restrict__ ws_meta)
+{
+    __shared__ int sh_cnt[CG_BLOCK / 64], sh_last[CG_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t n_lines = ws_meta[4] < cap_lines ? ws_meta[4] : cap_lines;
+    const int64_t b0 = (int64_t)blockIdx.x * CG_BLOCK;
+    if (b0 >= n_lines) return;
+    const int64_t L = b0 + tid;
+    const int mine = L < n_lines ? cid[L] : CG_NONE;
+    const bool flag = mine != CG_NONE;
+    const unsigned long long bm = __ballot(flag);
+    const unsigned long long upto = bm & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));       // run starts of this wave at or in front of this lane
+    const int near = __shfl(mine, upto ? 63 - __builtin_clzll(upto) : lane);
+    const int wlast = __shfl(mine, bm ? 63 - __builtin_clzll(bm) : 0);
+    if (lane == 0) { sh_cnt[wave] = __popcll(bm); sh_last[wave] = bm ? wlast : CG_NONE; }
+    __syncthreads();
+    int64_t before = blk_cnt[blockIdx.x];
+    int c = blk_last[blockIdx.x];
+    for (int k = 0; k < wave; ++k) { before += sh_cnt[k]; if (sh_last[k] != CG_NONE) c = sh_last[k]; }
+    if (upto) c = near;
+    if (c == CG_NONE) c = -1;                                  // (only behind a refused name: the status says so)
+    if (L >= n_lines) return;
+    if (flag) {
+        const int64_t r = before + __popcll(upto) - 1;
+        if (r < cap_runs) { runs[2 * r] = L; runs[2 * r + 1] = c; }
+    }
+    cid[L] = c;
+    uint8_t rb = 'N';
+    int64_t kv = CG_FILLER;
+    if (c >= 0) {
+        const int64_t p = pos[L], o = tb.seq_off[c], len = tb.seq_off[c + 1] - o;
+        if (p >= 1 && p <= len && o >= 0 && o + p <= tb.genome_len) { rb = tb.genome[o + p - 1]; kv = ((int64_t)c << NSNP_TOK_KEY_SHIFT) | p; }
+        else atomicOr(reinterpret_cast<unsigned long long*>(ws_meta + 3), (unsigned long long)TOK_EPOS);
+    }
+    ref[L] = rb; key[L] = kv;
+}
+
+__global__ void k_ctg_status(int64_t* __restrict__ ws_meta, int64_t cap_runs, int64_t* __restrict__ meta)
+{
+    int64_t status = meta[2] | ws_meta[3];
+    if (ws_meta[5] > cap_runs) status |= TOK_ERANGE;
+    meta[2] = status; meta[3] = ws_meta[5];
+    ws_meta[2] = 0; ws_meta[3] = 0; ws_meta[4] = 0; ws_meta[5] = 0;
+}
+
+}  // namespace
+
+static int ctg_reserve(nsnp_ctx* ctx, size_t need, hipStream_t s)
+{
+    if (ctx->ctg_ws_bytes >= need) return NSNP_OK;
+    NSNP_HIP(ctx, hipStreamSynchronize(s));
+    if (ctx->ctg_ws) (void)hipFree(ctx->ctg_ws);
+    ctx->ctg_ws = nullptr; ctx->ctg_ws_bytes = 0;
+    const size_t want = need + need / 4;
+    NSNP_HIP(ctx, hipMalloc(&ctx->ctg_ws, want));
+    ctx->ctg_ws_bytes = want;
+    return NSNP_OK;
+}
+
+extern "C" int nsnp_mpileup_tokenise_contigs(nsnp_ctx* ctx, const uint8_t* text, int64_t text_len, const uint8_t* names_blob, const int64_t* name_off,
+                                             const uint8_t* genome, const int64_t* seq_off, int64_t n_contigs, int64_t genome_len,
+                                             int64_t cap_cols, int64_t cap_bytes, int64_t cap_runs, int64_t* pos, int64_t* col_off, uint8_t* bases,
+                                             uint8_t* ref, int32_t* cid, int64_t* key, int64_t* runs, int64_t* meta, void* stream)
+{
+    if (!ctx || text_len < 0 || cap_cols < 0 || cap_bytes < 0 || cap_runs < 0 || !meta || !col_off || (text_len > 0 && !text) ||
+        (cap_cols > 0 && (!pos || !ref || !cid || !key)) || (cap_bytes > 0 && !bases) || (cap_runs > 0 && !runs) ||
+        n_contigs < 0 || genome_len < 0 || (n_contigs > 0 && (!name_off || !seq_off)) || (genome_len > 0 && !genome))
+        return NSNP_EINVAL;
+    if (n_contigs > NSNP_TOK_MAX_CONTIGS || genome_len >= (1ll << NSNP_TOK_KEY_SHIFT)) return NSNP_EINVAL;     // a key would not be exact
+    hipStream_t s = (hipStream_t)stream;
+    if (text_len == 0) {
+        NSNP_HIP(ctx, hipMemsetAsync(meta, 0, 4 * sizeof(int64_t), s));
+        NSNP_HIP(ctx, hipMemsetAsync(col_off, 0, sizeof(int64_t), s));
+        return NSNP_OK;
+    }
+    const int mis = (int)((uintptr_t)text & 15);
+    TokText t;
+    t.base = text - mis; t.lo = mis; t.hi = mis + text_len;
+    const int64_t n_tiles = NSNP_CDIV(t.hi + 1, (int64_t)TK_TILE);
+    int rc = tok_reserve(ctx, n_tiles, s);
+    if (rc != NSNP_OK) return rc;
+    const int64_t cap_lines = cap_cols < text_len + 1 ? cap_cols : text_len + 1;
+    const int64_t n_blk = cap_lines > 0 ? NSNP_CDIV(cap_lines, (int64_t)CG_BLOCK) : 1;
+    rc = ctg_reserve(ctx, (size_t)cap_lines * 8 + (size_t)n_blk * 12 + 64, s);
+    if (rc != NSNP_OK) return rc;
+    uint8_t* ws = (uint8_t*)ctx->tok_ws;
+    int64_t* ws_meta = (int64_t*)ws;                               // [2] status of launch 1, [3] of the per-line launches, [4] lines, [5] runs
+    int64_t* tile_nl = (int64_t*)(ws + 64);
+    int64_t* tile_bytes = tile_nl + n_tiles;
+    uint4* chunk_masks = (uint4*)(tile_bytes + n_tiles);
+    int64_t* ls = (int64_t*)ctx->ctg_ws;
+    int64_t* blk_cnt = ls + cap_lines;
+    int* blk_last = (int*)(blk_cnt + n_blk);
+    const CtgTable tb{names_blob, name_off, genome, seq_off, n_contigs, genome_len};
+    hipLaunchKernelGGL(k_tok_count, dim3((unsigned)n_tiles), dim3(TK_BLOCK), 0, s, t, tile_nl, tile_bytes, chunk_masks, ws_meta);
+    hipLaunchKernelGGL(k_tok_scan, dim3(1), dim3(1024), 0, s, tile_nl, tile_bytes, n_tiles, (const int64_t*)ws_meta, cap_cols, cap_bytes, col_off, meta);
+    hipLaunchKernelGGL(k_tok_emit, dim3((unsigned)n_tiles), dim3(TK_BLOCK), 0, s, t, (const int64_t*)tile_nl, (const int64_t*)tile_bytes,
+                       (const uint4*)chunk_masks, (const uint8_t*)nullptr, (int64_t)0, cap_cols, cap_bytes, pos, (uint8_t*)nullptr, col_off, bases, ws_meta);
+    hipLaunchKernelGGL(k_ctg_line_starts, dim3((unsigned)n_tiles), dim3(TK_BLOCK), 0, s, t, (const int64_t*)tile_nl, (const uint4*)chunk_masks, n_tiles,
+                       cap_lines, ls, ws_meta);
+    hipLaunchKernelGGL(k_ctg_flag, dim3((unsigned)n_blk), dim3(CG_BLOCK), 0, s, text, text_len, tb, (const int64_t*)ls, cap_lines, cid, blk_cnt, blk_last,
+                       ws_meta);
+    hipLaunchKernelGGL(k_ctg_scan, dim3(1), dim3(1024), 0, s, blk_cnt, blk_last, cap_lines, ws_meta);
+    hipLaunchKernelGGL(k_ctg_emit, dim3((unsigned)n_blk), dim3(CG_BLOCK), 0, s, tb, (const int64_t*)pos, (const int64_t*)blk_cnt, (const int*)blk_last,
+                       cap_lines, cap_runs, cid, ref, key, runs, ws_meta);
+    hipLaunchKernelGGL(k_ctg_status, dim3(1), dim3(1), 0, s, ws_meta, cap_runs, meta);
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
 }

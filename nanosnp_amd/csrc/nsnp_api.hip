@@ -3,7 +3,7 @@
 
 #include <new>
 
-extern "C" int nsnp_version(void) { return 100; }
+extern "C" int nsnp_version(void) { return 101; }
 
 extern "C" const char* nsnp_strerror(int code)
 {

@@ -1304,3 +1304,420 @@ def _predict_pileup_bins(model, testing_paths, fai_text, output_file, batch_size
 
 
 predict_pileup_bins.__doc__ = _predict_pileup_bins.__doc__
+
+
+# ---- a whole-genome mpileup text -> pileup.vcf (DNA_ExtractChrPileupData + everything behind it) ----------------------------------------
+class _KeySet:
+    """what nsnp_mpileup_tokenise_contigs adds to a _ColSet: the contig index and the key of every line of one chunk"""
+    def __init__(self, cap_cols, dev):
+        import torch
+        self.cid = torch.empty(cap_cols, dtype=torch.int32, device=dev)
+        self.key = torch.empty(cap_cols, dtype=torch.int64, device=dev)
+
+
+def fai_names(fai_text):
+    """the contig names of a .fai (its text, or its path as host.vcf_header takes it), in its order"""
+    if isinstance(fai_text, os.PathLike) or (isinstance(fai_text, str) and "\n" not in fai_text and "\t" not in fai_text and os.path.isfile(fai_text)):
+        with open(fai_text) as f:
+            fai_text = f.read()
+    return [line.split()[0] for line in fai_text.split("\n") if line.strip()]
+
+
+def cut_rows_by_contig(keys):
+    """keys: int64 [n], the key column of call rows in text order ((contig index << _lib.KEY_SHIFT) | position) -> [(contig index, lo, hi)]:
+    the rows of every contig, in the order the contigs appear.  NanoSNPError when a contig's rows come in two pieces."""
+    from ._lib import KEY_SHIFT, NanoSNPError
+    k = np.asarray(keys, np.int64)
+    if not k.size:
+        return []
+    cid = k >> KEY_SHIFT
+    edges = np.flatnonzero(cid[1:] != cid[:-1]) + 1
+    lo = np.concatenate([[0], edges]); hi = np.concatenate([edges, [k.size]])
+    out = [(int(cid[a]), int(a), int(b)) for a, b in zip(lo, hi)]
+    if len({c for c, _, _ in out}) != len(out):
+        raise NanoSNPError("call rows: the rows of one contig come in two separate pieces")
+    return out
+
+
+def complete_rows(key):
+    """key: column 0 of call rows in text order (a float64 / int64 torch tensor, every contig's rows in one piece) -> how many leading
+    rows belong to contigs that are complete when more of the text may follow: all but the trailing rows of the LAST row's contig.  The
+    table index says nothing about the order of the text (contigs= may be sorted otherwise than the text is), so the rule looks at
+    nothing but where the last row's contig begins."""
+    from ._lib import KEY_SHIFT
+    n = int(key.shape[0])
+    if n == 0:
+        return 0
+    base = (int(key[-1].item()) >> KEY_SHIFT) << KEY_SHIFT
+    mine = (key >= base) & (key < base + (1 << KEY_SHIFT))         # (both bounds are exact in a float64)
+    return n - int(mine.sum().item())
+
+
+class ContigRuns:
+    """The run tables of a streamed text's chunks ({first line, contig index} per run: nsnp_mpileup_tokenise_contigs), put together on the
+    host: which wanted contigs the text holds, in its order - and the refusal of a wanted contig that comes in two separate runs (the
+    reference's splitter would open its file a second time with "w" and keep only the last run)."""
+    def __init__(self, names):
+        self.names = list(names)
+        self.order = []
+        self._seen = set()
+
+    def feed(self, runs, n_lines, own_lo, own_hi):
+        """runs: int64 [r, 2] of one chunk of n_lines lines of which [own_lo, own_hi) are its own (the others: halo, re-read from its
+        neighbours) -> the wanted contigs that START among the own lines, in order"""
+        from ._lib import NanoSNPError
+        runs = np.asarray(runs, np.int64).reshape(-1, 2)
+        started = []
+        for i in range(len(runs)):
+            first, cid = int(runs[i, 0]), int(runs[i, 1])
+            end = int(runs[i + 1, 0]) if i + 1 < len(runs) else int(n_lines)
+            if cid < 0 or end <= own_lo or first >= own_hi or first < own_lo:
+                continue                                   # (a run that began in front of the own lines was counted by the chunk that owns its first line)
+            if cid in self._seen:
+                raise NanoSNPError(f"{self.names[cid]}: the text holds this contig in two separate runs (the reference's splitter would keep "
+                                   "only the last one)")
+            self._seen.add(cid); self.order.append(cid); started.append(cid)
+        return started
+
+
+def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stats, on_rows, cap_runs=None):
+    """_stream_contig_dev for a text of several contigs: the same four stations - staging thread, copy stream, tokeniser, encode + select,
+    forward + rows, counts read one chunk late through pinned memory - with nsnp_mpileup_tokenise_contigs in the tokeniser's place and its
+    `key` where the per-contig path hands a position to the window rule and the call rows.  The run table of every chunk arrives in pinned
+    memory with its counts.  on_rows(rows_k, started): the call rows of a chunk ([n, 13] float64 on the device, column 0 = key) or None, and
+    the wanted contigs that start among the chunk's own lines; called in chunk order as soon as the chunk's last kernels are issued."""
+    import time
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    ctx = model.ctx
+    dev = torch.device("cuda", ctx.device)
+    finder, arr = _as_bytes_like(text)
+    lo, hi = 0, arr.size
+    st = stats if stats is not None else {}
+    for k in ("parse_s", "h2d_s", "gpu_s", "tok_s", "text_bytes", "columns", "chunks", "setup_s", "wait_parse_s", "issue_s", "wait_counts_s", "drain_s"):
+        st.setdefault(k, 0.0)
+    st["tokenise"] = "device"
+    t_enter = time.perf_counter()
+    tracker = ContigRuns(table.names)
+    if hi <= lo:
+        return tracker
+    cuts = ramp_cuts(finder, lo, hi, int(chunk_bytes))
+    ranges = [halo_range(finder, cuts[k], cuts[k + 1]) for k in range(len(cuts) - 1) if cuts[k + 1] > cuts[k]]
+    cap = max(b - a for a, b, _, _ in ranges) + 64
+    # the buffer sets of _stream_contig_dev, kept on the model and shared with it (one call at a time per model), by its rules
+    hsets = getattr(model, "_text_host_sets", None)
+    n_hsets, n_tsets, n_sets = min(4, len(ranges)), min(3, len(ranges)), min(3, len(ranges))
+    if not hsets or min(s_.buf.numel() for s_ in hsets) < cap or len(hsets) < n_hsets:
+        hsets = model._text_host_sets = [_TextSet(cap) for _ in range(n_hsets)]
+        model._text_dev_sets = None
+    tsets = getattr(model, "_text_dev_sets", None)
+    fresh_sets = not tsets or tsets[0].buf.device != dev or min(t_.buf.numel() for t_ in tsets) < cap or len(tsets) < n_tsets
+    if fresh_sets:
+        tsets = model._text_dev_sets = [_TextSet(cap, dev) for _ in range(n_tsets)]
+        model._col_dev_sets = [_ColSet(cap, dev) for _ in range(n_sets)]
+        model._copy_stream = getattr(model, "_copy_stream", None) or host.copy_stream(dev)
+    csets, copy_stream = model._col_dev_sets, model._copy_stream
+    ksets = getattr(model, "_key_dev_sets", None)
+    if not ksets or len(ksets) < len(csets) or ksets[0].key.device != dev or min(k_.key.numel() for k_ in ksets) < max(c_.pos.numel() for c_ in csets):
+        ksets = model._key_dev_sets = [_KeySet(c_.pos.numel(), dev) for c_ in csets]
+    # the run table of a chunk: one entry per KB of text, at least 4096 - a run is at least one line, and a chunk whose runs average fewer
+    # than ten lines is refused with a status that says so (16 bytes per entry in pinned memory: 1 MB per slot at 64 MB chunks)
+    cap_runs = int(cap_runs or max(4096, cap // 1024))
+    n_ring = 4                                             # a chunk's counts and run table are read one chunk late: four slots are never in use at once
+    if getattr(model, "_run_pin", None) is None or model._run_pin.shape[1] < cap_runs:
+        model._run_pin = torch.zeros((n_ring, cap_runs, 2), dtype=torch.int64, pin_memory=True)
+        model._ctok_meta_pin = torch.zeros((n_ring, 4), dtype=torch.int64, pin_memory=True)
+    if len(getattr(model, "_meta_pin", ())) < len(ranges):
+        model._meta_pin = torch.zeros((len(ranges), 4), dtype=torch.int64, pin_memory=True)
+    meta_pin, tok_pin, run_pin = model._meta_pin, model._ctok_meta_pin, model._run_pin
+    main = torch.cuda.current_stream(dev)
+    if getattr(model, "_stream_main_id", None) != (main.device, main.stream_id):
+        copy_stream.wait_stream(main)
+        model._stream_main_id = (main.device, main.stream_id)
+    if fresh_sets:
+        copy_stream.wait_stream(main)                      # (new device sets may be blocks that work queued on the compute stream still reads)
+
+    def stage(k):
+        t0 = time.perf_counter()
+        a, b, _, _ = ranges[k]
+        host.stage_values(hsets[k % len(hsets)].np, b - a, src=arr, src_off=a, src_dtype=np.uint8)
+        return time.perf_counter() - t0
+
+    st["setup_s"] += time.perf_counter() - t_enter
+    tev = lambda: torch.cuda.Event(enable_timing=True)
+    ev = [dict(h0=tev(), h1=tev(), t0=tev(), t1=tev(), a0=tev(), a1=tev(), b0=tev(), b1=tev()) for _ in ranges]
+
+    def encode_of(tk):
+        k, n_lo, n_hi, cs, ks, tok_done = tk
+        t_w = time.perf_counter()
+        tok_done.synchronize()
+        st["wait_counts_s"] += time.perf_counter() - t_w
+        M, nb, status, n_runs = tok_pin[k % n_ring].tolist()
+        if status & ctx.TOK_EFORMAT:
+            raise host.HostError("malformed input (a line with fewer than five tab-separated fields)")
+        if status & ctx.TOK_BLANK:
+            raise host.HostError("mpileup text holds empty line(s): malformed input (every line must be one pileup column)")
+        if status & ctx.TOK_ENAME:
+            raise host.HostError("mpileup text holds a contig name longer than 255 bytes")
+        if status & ctx.TOK_EPOS:
+            raise ValueError("position outside the reference sequence of the line's contig")
+        if status & ctx.TOK_ERANGE:
+            if n_runs > cap_runs:
+                raise host.HostError(f"a chunk of the text holds {n_runs} contig runs, more than the {cap_runs} budgeted (one per KB of text): "
+                                     "use a smaller chunk_bytes")
+            raise host.HostError(f"a chunk of the text holds {M} lines / {nb} column-5 bytes, more than its column set of {cs.pos.numel()} lines / "
+                                 f"{cs.bases.numel()} bytes (lines shorter than 10 bytes: malformed input)")
+        if status:
+            raise host.HostError(f"tokeniser status {status}")
+        started = tracker.feed(run_pin[k % n_ring, :n_runs].numpy(), M, n_lo, M - n_hi)
+        own = M - n_lo - n_hi
+        st["columns"] += own
+        ev[k]["a0"].record(main)
+        job = (k, started, None)
+        if own > 0:
+            d_key, d_off, d_bases, d_ref = ks.key[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
+            counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
+            center = ctx.pileup_select_sites_range(d_key, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
+            sel_done = torch.cuda.Event(); sel_done.record(main)
+            job = (k, started, (d_key, counts, center, sel_done))
+        ev[k]["a1"].record(main)
+        return job
+
+    def calls_of(job):
+        k, started, work = job
+        rows_k = None
+        ev[k]["b0"].record(main)
+        if work is not None:
+            d_key, counts, center, sel_done = work
+            t_w = time.perf_counter()
+            sel_done.synchronize()
+            st["wait_counts_s"] += time.perf_counter() - t_w
+            _, c_lo, c_hi, _ = meta_pin[k].tolist()
+            if c_hi > c_lo:
+                centers = center[c_lo:c_hi]
+                gt, zy, ga, za, gm, zm = ctx.pileup_forward_windows_calls(counts, centers)
+                rows_k = ctx.pileup_call_rows(counts, centers, d_key, ga, za, gm, zm)
+        ev[k]["b1"].record(main)
+        on_rows(rows_k, started)
+
+    pending, job = deque(), None
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        futs = [pool.submit(stage, j) for j in range(min(3, len(ranges)))]
+
+        def send(j):
+            t_w = time.perf_counter()
+            t_stage = futs[j].result()
+            st["wait_parse_s"] += time.perf_counter() - t_w
+            a_, b_, _, _ = ranges[j]
+            n_ = b_ - a_
+            hs, ts = hsets[j % len(hsets)], tsets[j % len(tsets)]
+            st["parse_s"] += t_stage; st["text_bytes"] += n_; st["chunks"] += 1
+            if ts.free is not None:
+                copy_stream.wait_event(ts.free)
+            with torch.cuda.stream(copy_stream):
+                ev[j]["h0"].record(copy_stream)
+                ts.buf[:n_].copy_(hs.buf[:n_], non_blocking=True)
+                ev[j]["h1"].record(copy_stream)
+            hs.h2d_done = ev[j]["h1"]
+            if j + 3 < len(ranges):
+                nxt = hsets[(j + 3) % len(hsets)]
+                if nxt.h2d_done is not None:
+                    nxt.h2d_done.synchronize()
+                futs.append(pool.submit(stage, j + 3))
+
+        try:
+            send(0)
+            for k, (a, b, n_lo, n_hi) in enumerate(ranges):
+                t_i = time.perf_counter()
+                if k + 1 < len(ranges):
+                    send(k + 1)
+                ts, cs, ks = tsets[k % len(tsets)], csets[k % len(csets)], ksets[k % len(csets)]
+                n = b - a
+                main.wait_event(ev[k]["h1"])
+                ev[k]["t0"].record(main)
+                ctx.mpileup_tokenise_contigs_into(ts.buf[:n], table, cs.pos, cs.off, cs.bases, cs.ref, ks.cid, ks.key, run_pin[k % n_ring],
+                                                  tok_pin[k % n_ring], stream=main)
+                ev[k]["t1"].record(main)
+                ts.free = ev[k]["t1"]
+                tok_done = torch.cuda.Event(); tok_done.record(main)
+                pending.append((k, n_lo, n_hi, cs, ks, tok_done))
+                nxt_job = encode_of(pending.popleft()) if len(pending) > 1 else None
+                if job is not None:
+                    calls_of(job)
+                job = nxt_job
+                st["issue_s"] += time.perf_counter() - t_i
+            t_i = time.perf_counter()
+            while pending or job is not None:
+                nxt_job = encode_of(pending.popleft()) if pending else None
+                if job is not None:
+                    calls_of(job)
+                job = nxt_job
+            st["issue_s"] += time.perf_counter() - t_i
+        finally:
+            # whatever ends the loop, nothing queued may outlive the call: the pinned and device sets stay on the model for the next one
+            t_d = time.perf_counter()
+            for f_ in futs:
+                f_.cancel()
+            main.synchronize()
+            copy_stream.synchronize()
+            st["drain_s"] += time.perf_counter() - t_d
+    for e in ev:
+        st["h2d_s"] += e["h0"].elapsed_time(e["h1"]) * 1e-3
+        tk = e["t0"].elapsed_time(e["t1"]) * 1e-3
+        st["tok_s"] += tk; st["gpu_s"] += tk
+        for x0, x1 in (("a0", "a1"), ("b0", "b1")):
+            st["gpu_s"] += e[x0].elapsed_time(e[x1]) * 1e-3
+    return tracker
+
+
+def _format_key_rows(rows, table, batch_size, score_mode, ctx, nthreads=None):
+    """call rows whose column 0 is a key, of any number of WHOLE contigs in text order -> [(VCF text, rows written)] per contig: the rows
+    come to the host as typed columns (pileup_rows_unpack writes them into pinned memory), are cut by contig from the key's high bits
+    (cut_rows_by_contig) and formatted with the reference's batches restarting at every contig, as its loop restarts them with every
+    .bin file"""
+    import torch
+    from ._lib import KEY_SHIFT
+    n = int(rows.shape[0])
+    hb = getattr(ctx, "_rows_host", None)
+    if hb is None or hb[0].numel() < n:
+        cap = max(n + n // 4, 65536)
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=True)
+        hb = ctx._rows_host = (mk(cap, torch.int64), mk(cap, torch.uint8), mk(cap, torch.uint8), mk(cap, torch.float32), mk(cap, torch.float32),
+                               mk((cap, 8), torch.float32))
+    s_ = torch.cuda.current_stream(rows.device)
+    ctx.pileup_rows_unpack(rows.contiguous(), hb, stream=s_)
+    # the reference base of every site: one gather from the resident genome
+    key = rows[:, 0].to(torch.int64)
+    refb = table.genome[table.seq_off[key >> KEY_SHIFT] + (key & ((1 << KEY_SHIFT) - 1)) - 1].cpu()
+    s_.synchronize()
+    keys, ga, za, gm, zm = (t[:n].numpy() for t in hb[:5])
+    cov = hb[5][:n].numpy()
+    site_ref = refb.numpy() & 0xDF                                           # make_predict_data/main.cpp:91 upper-cases
+    out = []
+    for cid, a, b in cut_rows_by_contig(keys):
+        pos = keys[a:b] & ((1 << KEY_SHIFT) - 1)
+        out.append(host.vcf_format_batches(host.ContigTable([table.names[cid]]), np.zeros(b - a, np.int32), pos, site_ref[a:b], ga[a:b], za[a:b],
+                                           gm[a:b], zm[a:b], cov[a:b], batch_size=batch_size, score_mode=score_mode, nthreads=nthreads))
+    return out
+
+
+def call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, contigs=None, batch_size=1000, score_mode=host.SCORE_FLOAT64,
+                 chunk_bytes=64 << 20, min_af=0.12, min_coverage=6, stats=None, extended_bed=None, confident_bed=None):
+    """call_variants from the file the reference's stage 1 starts from: ONE mpileup text holding every contig (samtools mpileup BAM -o
+    pileup_data, make_predict_data.sh:117,151), not cut into <chr>.mpileup files by DNA_ExtractChrPileupData first.  mpileup_path_or_bytes:
+    a path, or bytes / mmap / uint8 array; contigs: the wanted names (the reference's ALL_CHR_LIST; None: every name of fai_text, as -g);
+    writes pileup.vcf, returns the rows written.
+    The text is ONE stream (_stream_text_dev): staged chunks of whole lines with the 16-line halo cross PCIe once, the device finds the contig
+    of every line (nsnp_mpileup_tokenise_contigs: the host never scans the text for names) and hands encode, window rule and call rows
+    a key = (contig index << 36) | position, so that no window crosses a contig; lines of names outside `contigs` become filler the
+    window rule makes nothing of.  The rows of finished contigs are cut by contig on the host from the key's high bits and formatted - the
+    batches restart with every contig - and written, in the order the contigs appear in the text, on a writer thread while the text
+    streams on.  For a text whose wanted contigs each form one run the file equals, byte for byte, call_variants over the files the
+    splitter would have written, at every chunk_bytes and whatever the order of `contigs` (the table) is against the order of the text.  The wanted contigs' sequences are resident on the device (3.1 GB for a human genome).
+    Departures from the splitter: a wanted contig in two separate runs raises NanoSNPError (the splitter would reopen its file with "w" and
+    keep only the last run); an empty line is refused as the tokeniser refuses it (the splitter skips it).  NotImplementedError: under a
+    process group of more than one rank, with NSNP_TOKENISE=host, with extended_bed= / confident_bed=."""
+    import time
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    import torch.distributed as tdist
+    from . import _lib
+    if extended_bed is not None or confident_bed is not None:
+        raise NotImplementedError("call_mpileup: BED region filters over several contigs (use call_variants on per-contig files)")
+    if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+        raise NotImplementedError("call_mpileup: sharding a whole-genome text over ranks")
+    if tokenise_mode() != "device":
+        raise NotImplementedError("call_mpileup: the contigs are found by the device tokeniser (NSNP_TOKENISE=host is not supported)")
+    if not torch.cuda.is_available():
+        raise _lib.NanoSNPError("no GPU visible: nanosnp_amd has no CPU fallback")
+    names = list(contigs) if contigs is not None else fai_names(fai_text)
+    table = _lib.ContigTable(fasta=fasta_path, names=names, device=model.ctx.device)
+    st = stats if stats is not None else {}
+    dev = torch.device("cuda", model.ctx.device)
+    side = getattr(model, "_rows_stream", None)
+    if side is None:
+        side = model._rows_stream = torch.cuda.Stream(dev)
+        model._rows_ctx = _lib.Context(model.ctx.device)     # the writer thread's own context (call_contigs)
+    wctx = model._rows_ctx
+    few = max(1, host.lib().nsnp_host_threads() // 4)
+    g = text = None
+    if isinstance(mpileup_path_or_bytes, (str, os.PathLike)):
+        g = open(mpileup_path_or_bytes, "rb")
+        size = os.fstat(g.fileno()).st_size
+        text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if size else None
+    f = None
+    n_rows = 0
+    try:
+        f = open(output_file, "wb")
+        f.write(host.vcf_header(fai_text).encode())
+        src = (text if text is not None else b"") if g is not None else mpileup_path_or_bytes
+        acc, futs, carry = [], deque(), []
+
+        def finish(pieces, done, last):
+            """writer thread (one worker: the hand-overs run in the order they were made): formats and writes the rows of the contigs that
+            are complete - every one but the contig of the last row, whose rows may go on in later chunks and wait in `carry` for the
+            next hand-over - or everything when the text is over.  Returns the rows written."""
+            done.synchronize()
+            t0 = time.perf_counter()
+            pieces = carry + pieces
+            del carry[:]
+            if not pieces:
+                return 0
+            with torch.cuda.stream(side):
+                rows = torch.cat(pieces) if len(pieces) > 1 else pieces[0]
+                if not last:
+                    keep = complete_rows(rows[:, 0])
+                    if keep < rows.shape[0]:
+                        carry.append(rows[keep:])
+                    rows = rows[:keep]
+                parts = _format_key_rows(rows, table, batch_size, score_mode, wctx, nthreads=0 if last else few) if rows.shape[0] else []
+            nr = 0
+            for t_, r_ in parts:
+                f.write(t_); nr += r_
+            st["vcf_s"] = st.get("vcf_s", 0.0) + time.perf_counter() - t0
+            return nr
+
+        with host.gc_paused(), ThreadPoolExecutor(max_workers=1) as writer:
+            main = torch.cuda.current_stream(dev)
+
+            def flush(last):
+                """hands the rows issued so far to the writer; the issuing thread waits only when two hand-overs are still unfinished (the
+                rows they hold stay allocated on the device until they are written)"""
+                nonlocal acc, n_rows
+                while len(futs) > 1:
+                    n_rows += futs.popleft().result()
+                if acc or last:
+                    done = torch.cuda.Event(); done.record(main)
+                    futs.append(writer.submit(finish, acc, done, last))
+                    acc = []
+
+            def on_rows(rows_k, started):
+                if started and acc:
+                    flush(False)                             # a wanted contig begins in this chunk: the ones in front of it are complete
+                if rows_k is not None:
+                    st["sites"] = st.get("sites", 0) + int(rows_k.shape[0])
+                    acc.append(rows_k)
+
+            try:
+                _stream_text_dev(model, src, table, chunk_bytes, min_af, min_coverage, st, on_rows)
+                flush(True)
+                while futs:
+                    n_rows += futs.popleft().result()
+            except BaseException:
+                for fu in futs:                              # (what the writer has begun it finishes: the executor waits for it)
+                    fu.cancel()
+                raise
+        st["vcf_rows"] = st.get("vcf_rows", 0) + n_rows
+        return n_rows
+    finally:
+        if f:
+            f.close()
+        if text is not None:
+            try:
+                text.close()
+            except BufferError:                  # (an exception on its way up still holds views of the mapping)
+                pass
+        if g is not None:
+            g.close()
