@@ -505,23 +505,29 @@ class Context:
 
     def mpileup_tokenise(self, text, chr_seq=None, stream=None):
         """mpileup text (uint8 device tensor) -> (pos [M] int64, col_off [M + 1] int64, bases uint8, ref uint8 [M] or None) on the device.
-        Synchronous (the sizes come back from the device); raises on text the reference's reader could not read."""
+        Synchronous (the sizes come back from the device, read behind `stream`); raises on text the reference's reader could not read."""
         import torch
+        dev = text.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
         t = int(text.numel())
         cap, cap_b = t // 10 + 2, max(t, 1)
         while True:
-            pos = torch.empty(cap, dtype=torch.int64, device=text.device)
-            off = torch.empty(cap + 1, dtype=torch.int64, device=text.device)
-            bases = torch.empty(cap_b, dtype=torch.uint8, device=text.device)
-            ref = torch.empty(cap, dtype=torch.uint8, device=text.device) if chr_seq is not None else None
-            meta = torch.zeros(4, dtype=torch.int64, device=text.device)
-            self.mpileup_tokenise_into(text, chr_seq, pos, off, bases, ref, meta, stream)
-            m, nb, status, _ = meta.tolist()
+            with torch.cuda.stream(s):                 # (the outputs belong to the stream that writes them)
+                pos = torch.empty(cap, dtype=torch.int64, device=dev)
+                off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+                bases = torch.empty(cap_b, dtype=torch.uint8, device=dev)
+                ref = torch.empty(cap, dtype=torch.uint8, device=dev) if chr_seq is not None else None
+                meta = torch.zeros(4, dtype=torch.int64, device=dev)
+                self.mpileup_tokenise_into(text, chr_seq, pos, off, bases, ref, meta, s)
+                m, nb, status, _ = meta.tolist()       # (the read is queued on `s`, behind the kernels)
             if status & self.TOK_ERANGE and not status & (self.TOK_EFORMAT | self.TOK_BLANK):
+                if (cap, cap_b) == (max(cap, m + 1), max(cap_b, nb)):
+                    break
                 cap, cap_b = max(cap, m + 1), max(cap_b, nb)
                 continue
             break
         tokenise_status_check(status)
+        torch.cuda.current_stream(dev).wait_stream(s)
         return pos[:m], off[:m + 1], bases[:nb], (ref[:m] if ref is not None else None)
 
     TOK_ENAME = 16

@@ -124,6 +124,32 @@ def test_rows_handed_to_the_writer_are_whole_contigs_in_any_table_order():
     assert complete_rows(torch.zeros(0, dtype=torch.float64)) == 0
 
 
+def test_keys_of_the_highest_contig_indices_and_positions_on_the_host():
+    """cut_rows_by_contig and complete_rows on the key column as float64 (what the call rows carry) and as int64 (what rows_unpack hands
+    back): contig indices 0, 2^17 - 1 and 2^16 in that order - the table order is not the text order -, positions 1 and 2^36 - 1"""
+    import torch
+    from nanosnp_amd._lib import NanoSNPError
+    from nanosnp_amd.pipeline import complete_rows, cut_rows_by_contig
+    top_c, top_p = (1 << 17) - 1, (1 << KEY_SHIFT) - 1
+    order = (0, top_c, 1 << 16)
+    keys = np.array([(c << KEY_SHIFT) | p for c in order for p in (1, 77, top_p)], np.int64)
+    assert keys.max() == (1 << 53) - 1 and np.array_equal(keys.astype(np.float64).astype(np.int64), keys)     # the test's own premise
+    want = [(c, 3 * i, 3 * i + 3) for i, c in enumerate(order)]
+    for col in (keys, keys.astype(np.float64)):
+        assert cut_rows_by_contig(col) == want
+        t = torch.from_numpy(col)
+        assert complete_rows(t) == 6
+        for cut in range(1, 10):                           # rows issued so far -> whole contigs handed over
+            assert complete_rows(t[:cut]) == 3 * ((cut - 1) // 3)
+            assert cut_rows_by_contig(col[:cut]) == [(c, a, min(b, cut)) for c, a, b in want if a < cut]
+        # a contig's last position and the next contig's first differ by one in the contig index alone: they are cut apart
+        assert cut_rows_by_contig(col[2:4]) == [(0, 0, 1), (top_c, 1, 2)] and complete_rows(t[2:4]) == 1
+    two = np.array([(top_c << KEY_SHIFT) | top_p, ((1 << 16) << KEY_SHIFT) | 1, (top_c << KEY_SHIFT) | 1], np.int64)
+    for col in (two, two.astype(np.float64)):
+        with pytest.raises(NanoSNPError, match="two separate pieces"):
+            cut_rows_by_contig(col)
+
+
 def test_fai_names():
     from nanosnp_amd.pipeline import fai_names
     assert fai_names("chr1\t100\t6\t60\t61\nchr2\t50\t120\t60\t61\n") == ["chr1", "chr2"]

@@ -137,3 +137,51 @@ def test_errors_and_what_they_leave_behind(genome):
         call_mpileup(genome["model"], str(beyond), *args, extended_bed=str(d / "x.bed"))
     # the model still works after the errors
     assert call_mpileup(genome["model"], t["ctg2"] + t["ctg4"], *args, batch_size=64) > 100
+
+
+# ---- one chunk of more than 16,384 lines -----------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def long_genome(tmp_path_factory, genome):
+    """three wanted contigs of 9,000 columns each (2.8 MB of text - the names are long ones, about 100 bytes per line -, 27,600 lines with
+    the 600 of an unlisted contig between the second and the third): in one chunk the contig tokeniser's scan over blocks of 256 lines leaves its first wave (64 blocks = 16,384 lines).
+    -> the text, the per-contig files, FASTA and index, and what call_variants writes for the files (computed once)"""
+    from nanosnp_amd import host
+    from nanosnp_amd.pipeline import call_variants
+    d = tmp_path_factory.mktemp("long_genome")
+    texts, fasta, fai = {}, b"", ""
+    for i in range(3):
+        name = f"long{i}_KI270706v1_random"
+        cols = host.synth_columns(20261400 + i, 9000, coverage=30, het_rate=0.05)
+        texts[name] = bytes(cols.mpileup_text_native(name))
+        seq = cols.ref.copy()
+        (d / f"{name}.mpileup").write_bytes(texts[name])
+        fasta += b">" + name.encode() + b"\n" + b"\n".join(bytes(seq[a:a + 60]) for a in range(0, seq.size, 60)) + b"\n"
+        fai += f"{name}\t{seq.size}\t0\t60\t61\n"
+    (d / "ref.fa").write_bytes(fasta)
+    extra = bytes(host.synth_columns(20261499, 600, coverage=30, het_rate=0.05).mpileup_text_native("longX_KI270706v1_unlisted"))
+    names = list(texts)
+    whole = texts[names[0]] + texts[names[1]] + extra + texts[names[2]]
+    (d / "pileup_data").write_bytes(whole)
+    rows = call_variants(genome["model"], [(n, str(d / f"{n}.mpileup")) for n in names], str(d / "ref.fa"), fai, str(d / "want.vcf"), batch_size=1000)
+    assert rows > 300                                      # (an empty comparison cannot pass)
+    return dict(dir=d, texts=texts, whole=whole, names=names, fasta=str(d / "ref.fa"), fai=fai, want=(rows, (d / "want.vcf").read_bytes()))
+
+
+@pytest.mark.parametrize("chunk_bytes", [None, 1_000_000], ids=["default_chunk", "1MB"])
+def test_a_chunk_of_more_than_16384_lines(genome, long_genome, chunk_bytes):
+    """at the default chunk size the whole text is ONE chunk of 27,600 lines; at 1,000,000 bytes the cuts fall inside contigs, the third
+    chunk beginning beyond line 16,384 of the text: the same bytes as call_variants over the per-contig files either way"""
+    from nanosnp_amd.pipeline import call_mpileup, ramp_cuts
+    g = long_genome
+    whole = g["whole"]
+    assert whole.count(b"\n") == 27_600 > 256 * 64 and 2_600_000 < len(whole) < 64 << 20
+    cuts = ramp_cuts(whole, 0, len(whole), 1_000_000)
+    bounds = set(np.cumsum([0] + [len(g["texts"][n]) for n in g["names"][:2]] + [len(whole) - sum(map(len, g["texts"].values()))]).tolist())
+    assert len(cuts) == 4 and not bounds & set(cuts[1:-1])             # two cuts, both inside a contig ...
+    assert whole[:cuts[2]].count(b"\n") > 256 * 64 and cuts[2] > max(bounds)          # ... the second beyond line 16,384, in the third contig
+    out = g["dir"] / f"got_{chunk_bytes}.vcf"
+    st = {}
+    kw = {} if chunk_bytes is None else dict(chunk_bytes=chunk_bytes)
+    rows = call_mpileup(genome["model"], str(g["dir"] / "pileup_data"), g["fasta"], g["fai"], str(out), contigs=g["names"], batch_size=1000, stats=st, **kw)
+    assert (rows, out.read_bytes()) == g["want"]
+    assert st["vcf_rows"] == rows and (st["chunks"] == 1 if chunk_bytes is None else st["chunks"] == 3)

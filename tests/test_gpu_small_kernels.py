@@ -166,6 +166,37 @@ def test_gather_forward_windows_and_call_rows_at_the_edges(gpu_ctx, pileup_weigh
     assert rows.shape == (n, 13) and np.array_equal(rows.cpu().numpy(), want)
 
 
+def test_keys_of_high_contig_indices_survive_call_rows_and_rows_unpack(gpu_ctx):
+    """the "position" of a call over several contigs is the key (contig index << 36) | position (include/nanosnp.h,
+    nsnp_mpileup_tokenise_contigs): nsnp_pileup_call_rows stores it in column 0 of its float64 rows, nsnp_pileup_rows_unpack hands it back
+    as int64 - exactly, for the lowest and the highest contig index (2^17 - 1) and position (2^36 - 1) the limits allow"""
+    import torch
+    keys = np.array([(c << 36) | p for c in (0, 1, (1 << 17) - 1) for p in (1, (1 << 36) - 1)], np.int64)
+    assert keys.max() == (1 << 53) - 1 and len(set(keys.tolist())) == 6
+    rng = np.random.default_rng(36)
+    m, n = 40, 6
+    counts = rng.integers(-30, 40, (m, 18)).astype(np.int32)
+    cen = np.array([21, 16, 19, 17, 20, 18], np.int64)                 # unsorted: row i holds the key of column cen[i]
+    pos = rng.integers(1, 1 << 40, m).astype(np.int64)
+    pos[16:22] = keys
+    ga = rng.integers(0, 21, n).astype(np.uint8); za = rng.integers(0, 3, n).astype(np.uint8)
+    gm = rng.random(n).astype(np.float32); zm = rng.random(n).astype(np.float32)
+    rows = gpu_ctx.pileup_call_rows(_cuda(counts), _cuda(cen), _cuda(pos), _cuda(ga), _cuda(za), _cuda(gm), _cuda(zm))
+    torch.cuda.synchronize()
+    want = keys[cen - 16]
+    col0 = rows.cpu().numpy()[:, 0]
+    assert col0.dtype == np.float64 and [int(v) for v in col0] == want.tolist()
+    for pinned in (False, True):
+        kw = dict(pin_memory=True) if pinned else dict(device="cuda")
+        outs = (torch.full((n + 2,), -7, dtype=torch.int64, **kw), torch.zeros(n, dtype=torch.uint8, **kw), torch.zeros(n, dtype=torch.uint8, **kw),
+                torch.zeros(n, dtype=torch.float32, **kw), torch.zeros(n, dtype=torch.float32, **kw), torch.zeros((n, 8), dtype=torch.float32, **kw))
+        gpu_ctx.pileup_rows_unpack(rows, outs)
+        torch.cuda.synchronize()
+        got = outs[0].cpu().numpy()
+        assert got.dtype == np.int64 and np.array_equal(got[:n], want) and (got[n:] == -7).all()
+        assert np.array_equal(got[:n] >> 36, want >> 36) and np.array_equal(outs[1].cpu().numpy(), ga) and np.array_equal(outs[3].cpu().numpy(), gm)
+
+
 # ---- nsnp_cat_groups ---------------------------------------------------------------------------------------------------------------
 def _tag_planes(rng, n, d, L):
     """(read, baseq, mapq) int32 [n,d,L] of one tag.  Rows from a random count of real reads on are -2 padding in all three planes (a tag

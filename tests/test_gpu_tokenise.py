@@ -167,3 +167,28 @@ def test_random_bytes_equal_the_oracle_reader(ctx):
     for rnd in range(6):
         text = _random_mpileup_text(rng, 4000)
         _check(ctx, text, shift=int(rng.integers(0, 40)))
+
+
+def test_a_side_stream_orders_the_size_read_behind_the_kernels(gpu_ctx):
+    """stream= another stream than the current one, kept busy by queued element-wise work on 256 MB: the sizes (meta) are read behind the
+    tokeniser's kernels, not in front of them (a stale meta reads 0 lines and the call would hand back empty arrays without an error), the
+    outputs belong to that stream, and the current stream waits for it before they are handed back.  A text of three tiles"""
+    import torch
+    lines = [b"c\t%d\tN\t3\tA+1Ga^]t$\tIII" % (100 + i) for i in range(900)]
+    text = np.frombuffer(b"\n".join(lines) + b"\n", np.uint8)
+    assert text.size > 2 * 8192
+    seq = np.frombuffer(b"ACGT", np.uint8)[np.random.default_rng(2).integers(0, 4, 1200)]
+    opos, ooff, obases = oracle.mpileup_tokenise(text)
+    d, d_seq = _dev(text), _dev(seq)
+    side = torch.cuda.Stream()
+    big = torch.ones(64 << 20, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        for _ in range(16):
+            big.add_(1.0)
+    pos, off, bases, ref = gpu_ctx.mpileup_tokenise(d, d_seq, stream=side)
+    assert pos.numel() == 900 == opos.size
+    assert np.array_equal(pos.cpu().numpy(), opos) and np.array_equal(off.cpu().numpy(), ooff) and np.array_equal(bases.cpu().numpy(), obases)
+    assert np.array_equal(ref.cpu().numpy(), seq[opos - 1])
+    torch.cuda.synchronize()
+    assert float(big[0]) == 17.0
