@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import mmap
 import os
+from collections import deque, namedtuple
 
 import numpy as np
 
@@ -170,36 +171,45 @@ def _contig_beds(extended_bed, confident_bed, contig, chr_seq, fai=None):
     return mk(extended_bed), mk(confident_bed)
 
 
-def _upload_beds(model, beds, dev, copy_stream, main):
-    """the contig's bitmaps -> device int32 tensors (None where there is none), once per contig: through a pinned buffer on the copy stream,
-    allocated as the copy stream's memory, as the reference sequence travels (_stream_contig_dev: a block the compute stream has just freed
-    may still be read by work queued there); the compute stream waits for the copy"""
+def _upload_pinned(model, attr, arrays, dtype, floor, dev, copy_stream, main):
+    """What a contig brings along once - its reference sequence (attr "_seq_pin", uint8), its BED bitmaps ("_bed_pin", int32 words) - as
+    device tensors.  arrays: numpy arrays of the type the torch `dtype` names, None where there is none; -> one tensor (or None) per array,
+    each marked record_stream(main), for the compute stream is where it is read and given back.
+    The values travel through a pinned buffer on the COPY stream: a copy from pageable memory on the compute stream would wait for
+    everything queued there - the previous contig's last forward - and stall this thread for as long.  The compute stream waits for the copy.
+    The pinned buffer is kept on the model as `attr`; one that is too small is replaced by one an eighth larger than needed, at least
+    `floor` elements."""
     import torch
-    words = [None if b is None else np.ascontiguousarray(b).view(np.int32) for b in beds]
-    total = sum(w.size for w in words if w is not None)
-    bp = getattr(model, "_bed_pin", None)
-    if bp is None or bp.numel() < total:
-        bp = model._bed_pin = torch.empty(max(total + total // 8, 1 << 16), dtype=torch.int32, pin_memory=True)
-        model._bed_pin_free = None
-    if getattr(model, "_bed_pin_free", None) is not None:
-        model._bed_pin_free.synchronize()              # (the previous contig's bitmaps have left the pinned buffer)
+    total = sum(a.size for a in arrays if a is not None)
+    pin, free = getattr(model, attr, None), getattr(model, attr + "_free", None)
+    if pin is None or pin.numel() < total:
+        pin, free = torch.empty(max(total + total // 8, floor), dtype=dtype, pin_memory=True), None
+        setattr(model, attr, pin)
+    if free is not None:
+        free.synchronize()                             # (the previous contig's values have left the pinned buffer)
     out, o = [], 0
-    with torch.cuda.stream(copy_stream):
-        for w in words:
-            if w is None:
+    with torch.cuda.stream(copy_stream):               # (allocated as the copy stream's memory: a block the compute stream has just freed may
+        for a in arrays:                               # still be read by work queued there)
+            if a is None:
                 out.append(None)
                 continue
-            bp.numpy()[o:o + w.size] = w
-            d = torch.empty(max(w.size, 1), dtype=torch.int32, device=dev)[:w.size]
-            d.copy_(bp[o:o + w.size], non_blocking=True)
-            out.append(d)
-            o += w.size
-        model._bed_pin_free = torch.cuda.Event(); model._bed_pin_free.record(copy_stream)
-    for d in out:
-        if d is not None:
+            pin.numpy()[o:o + a.size] = a
+            d = torch.empty(max(a.size, 1), dtype=dtype, device=dev)[:a.size]
+            d.copy_(pin[o:o + a.size], non_blocking=True)
             d.record_stream(main)
-    main.wait_event(model._bed_pin_free)
+            out.append(d)
+            o += a.size
+        free = torch.cuda.Event(); free.record(copy_stream)
+    setattr(model, attr + "_free", free)
+    main.wait_event(free)
     return out
+
+
+def _upload_beds(model, beds, dev, copy_stream, main):
+    """the contig's bitmaps -> device int32 tensors (None where there is none), once per contig, as the reference sequence travels"""
+    import torch
+    return _upload_pinned(model, "_bed_pin", [None if b is None else np.ascontiguousarray(b).view(np.int32) for b in beds], torch.int32, 1 << 16,
+                          dev, copy_stream, main)
 
 
 class _FilSet:
@@ -238,43 +248,35 @@ class _ColSet:
         self.bases = torch.empty(cap_bytes, dtype=torch.uint8, device=dev)
 
 
-def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, defer=False, beds=None):
-    """stream_contig with the text cut into columns ON THE DEVICE (nsnp_mpileup_tokenise).  The host touches every byte of the text once - a
-    multi-threaded copy of the chunk (whole lines, 16 lines of halo either side, found by a few find / rfind calls) from the page cache
-    into pinned memory - and the chunks are worked off four things at a time:
+_STREAM_STATS = ("parse_s", "h2d_s", "gpu_s", "tok_s", "text_bytes", "columns", "chunks", "setup_s", "wait_parse_s", "issue_s", "wait_counts_s", "drain_s")
 
-        worker thread   copies chunks k + 2 and k + 3 into two of four pinned text buffers (libnanosnp_host.so: nsnp_stage_values)
-        copy stream     sends the text of chunk k + 1 (three device text buffers: a copy waits for the tokeniser three chunks back)
-        compute stream  tokenise chunk k -> positions, reference bytes, column-5 strings (three column sets on the device)
-                        encode + select chunk k - 1 (its line count came back through pinned memory while chunk k was being issued)
-                        PileupModel forward + argmax / max of chunk k - 2 (its site count likewise)
 
-    so this thread never waits for work it has just issued, and the device never waits for this thread.  Same rows as the host-parsed
-    path (tests/test_gpu_predict.py); text the reference's reader aborts on is refused with the same errors.
-    defer=True (call_contigs): returns (rows, done, finalize) as soon as the last chunk is ISSUED - `done` is an event behind the last kernel,
-    finalize() waits for it and adds the per-stage times to stats - so that the next contig's text is staged, copied and tokenised while
-    this one's last forward (1.4 ms of a 6 M-column contig's 15) still runs; the buffer sets carry their events from call to call.
-    beds (_contig_beds; None: nothing below changes): with an extended bitmap every chunk's columns pass nsnp_pileup_filter_columns in front
-    of the encode - the images of the chunk's own range stay on the device, the selection reads them there - and with a confident bitmap
-    the encode is nsnp_pileup_encode_columns3.  The result does not depend on the cuts for texts with ASCENDING positions: 33 kept lines
-    with consecutive positions are then 33 consecutive lines of the text, inside the 16-line halo; in a text whose positions repeat or step
-    back they may lie further apart (the whole-array calls stay exact for any position sequence)."""
-    import time
-    from collections import deque
-    from concurrent.futures import ThreadPoolExecutor
-    import torch
-    ctx = model.ctx
-    dev = torch.device("cuda", ctx.device)
-    finder, arr = _as_bytes_like(text)
-    hi = arr.size if hi is None else hi
+def _stream_stats(stats):
+    """the stats dict of a device-tokenised run, with every key the chunk loop adds to"""
     st = stats if stats is not None else {}
-    for k in ("parse_s", "h2d_s", "gpu_s", "tok_s", "text_bytes", "columns", "chunks", "setup_s", "wait_parse_s", "issue_s", "wait_counts_s", "drain_s"):
+    for k in _STREAM_STATS:
         st.setdefault(k, 0.0)
     st["tokenise"] = "device"
-    t_enter = time.perf_counter()
-    if hi <= lo:
-        empty = torch.zeros((0, 13), dtype=torch.float64, device=dev)
-        return (empty, None, lambda: None) if defer else empty
+    return st
+
+
+def _count_slots(model, attr, n):
+    """at least n pinned rows of four int64, kept on the model as `attr`: where the last launch of a chunk's stage leaves its counts"""
+    import torch
+    if len(getattr(model, attr, ())) < n:
+        setattr(model, attr, torch.zeros((n, 4), dtype=torch.int64, pin_memory=True))
+    return getattr(model, attr)
+
+
+_ChunkSets = namedtuple("_ChunkSets", "ranges cap hsets tsets csets copy_stream main fresh")
+
+
+def _text_chunk_sets(model, finder, lo, hi, chunk_bytes, dev):
+    """The chunk plan of text[lo:hi] - ranges: (from, to, halo lines in front, halo lines behind) per chunk of whole lines; cap: the bytes a
+    buffer must hold for the longest of them - and the buffer sets its chunks travel through, kept on the model (one call at a time per
+    model) and built anew when a chunk no longer fits: pinned text sets, device text sets, column sets, and the copy stream, which has
+    waited for the compute stream where it must.  -> _ChunkSets; fresh: the device sets are new."""
+    import torch
     cuts = ramp_cuts(finder, lo, hi, int(chunk_bytes))
     ranges = [halo_range(finder, cuts[k], cuts[k + 1]) for k in range(len(cuts) - 1) if cuts[k + 1] > cuts[k]]
     cap = max(b - a for a, b, _, _ in ranges) + 64
@@ -289,59 +291,54 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
     # (model._text_dev_sets = None makes the next call build the device text AND column sets anew, as the host sets' growth above does;
     #  tests/test_gpu_predict.py uses that to make one model grow its sets again and again)
     tsets = getattr(model, "_text_dev_sets", None)
-    fresh_sets = not tsets or tsets[0].buf.device != dev or min(t_.buf.numel() for t_ in tsets) < cap or len(tsets) < n_tsets
-    if fresh_sets:
+    fresh = not tsets or tsets[0].buf.device != dev or min(t_.buf.numel() for t_ in tsets) < cap or len(tsets) < n_tsets
+    if fresh:
         tsets = model._text_dev_sets = [_TextSet(cap, dev) for _ in range(n_tsets)]
         model._col_dev_sets = [_ColSet(cap, dev) for _ in range(n_sets)]
         model._copy_stream = getattr(model, "_copy_stream", None) or host.copy_stream(dev)
-    csets, copy_stream = model._col_dev_sets, model._copy_stream
-    if len(getattr(model, "_meta_pin", ())) < len(ranges):
-        model._meta_pin = torch.zeros((len(ranges), 4), dtype=torch.int64, pin_memory=True)
-    if len(getattr(model, "_tok_meta_pin", ())) < len(ranges):
-        model._tok_meta_pin = torch.zeros((len(ranges), 4), dtype=torch.int64, pin_memory=True)
-    meta_pin, tok_pin = model._meta_pin, model._tok_meta_pin
+    copy_stream = model._copy_stream
     main = torch.cuda.current_stream(dev)
     # (the sets keep their events from the previous call: a pinned buffer is rewritten only behind the copy that read it, a device text buffer
     # behind the tokeniser that read it - whichever call issued those; the column sets are written and read on the compute stream alone)
-    # the reference sequence: through a pinned buffer on the copy stream (a copy from pageable memory on the compute stream would wait for
-    # everything queued there - the previous contig's last forward - and stall this thread for as long)
-    n_seq = int(chr_seq.size)
-    sp = getattr(model, "_seq_pin", None)
-    if sp is None or sp.numel() < n_seq:
-        sp = model._seq_pin = torch.empty(max(n_seq + n_seq // 8, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        model._seq_pin_free = None
-    if getattr(model, "_seq_pin_free", None) is not None:
-        model._seq_pin_free.synchronize()              # (the previous contig's sequence has left the pinned buffer)
-    sp.numpy()[:n_seq] = np.ascontiguousarray(chr_seq)
-    with torch.cuda.stream(copy_stream):               # (allocated as the copy stream's memory: a block the compute stream has just freed may
-        d_seq = torch.empty(max(n_seq, 1), dtype=torch.uint8, device=dev)[:n_seq]      # still be read by work queued there)
-        d_seq.copy_(sp[:n_seq], non_blocking=True)
-        model._seq_pin_free = torch.cuda.Event(); model._seq_pin_free.record(copy_stream)
-    d_seq.record_stream(main)
-    main.wait_event(model._seq_pin_free)
-    cov_idx = getattr(model, "_cov_idx", None)
-    if cov_idx is None or cov_idx.device != dev:
-        cov_idx = model._cov_idx = torch.tensor(list(COV_CHANNELS), dtype=torch.int64, device=dev)
     if getattr(model, "_stream_main_id", None) != (main.device, main.stream_id):
         copy_stream.wait_stream(main)                  # (another compute stream than last time: its queued work may still read the device sets)
         model._stream_main_id = (main.device, main.stream_id)
-    ext_bits = conf_bits = fsets = fmeta = None
-    if beds is not None:
-        ext_bits, conf_bits = _upload_beds(model, beds, dev, copy_stream, main)
-        if ext_bits is not None:
-            fsets = getattr(model, "_fil_dev_sets", None)
-            if not fsets or fsets[0].pos.device != dev or fsets[0].pos.numel() < csets[0].pos.numel() or fsets[0].bases.numel() < csets[0].bases.numel():
-                fsets = model._fil_dev_sets = [_FilSet(csets[0].pos.numel(), csets[0].bases.numel(), dev) for _ in range(3)]
-                fresh_sets = True
-            fmeta = torch.zeros((len(ranges), 4), dtype=torch.int64, device=dev)
-    if fresh_sets:
+    if fresh:
         # New device sets come out of the compute stream's pool: their blocks may be ones the previous contig's tensors gave back while its
         # last kernels (call_contigs defers them) are still queued there and still read them.  The compute stream's own later work is
         # ordered behind those kernels; the copy stream is not, and its first write into a new text buffer would be - so it waits once
         # for everything queued on the compute stream so far.  Nothing in the steady state: sets that are kept are not new.
         copy_stream.wait_stream(main)
+    return _ChunkSets(ranges, cap, hsets, tsets, model._col_dev_sets, copy_stream, main, fresh)
 
+
+def _run_text_chunks(sets, arr, st, tokenise, encode, calls):
+    """The chunks of sets.ranges (_text_chunk_sets) of the text `arr` (numpy uint8), worked off four things at a time:
+
+        worker thread   copies chunks k + 2 and k + 3 into two of four pinned text buffers (libnanosnp_host.so: nsnp_stage_values)
+        copy stream     sends the text of chunk k + 1 (three device text buffers: a copy waits for the tokeniser three chunks back)
+        compute stream  tokenise(k, text of chunk k on the device, column set)  the caller's tokeniser, its counts into the caller's pinned slot
+                        encode(k, column set, n_lo, n_hi) of chunk k - 1: its line count came back through pinned memory while chunk k was being
+                            issued; the caller reads it, refuses what it must, issues encode + select -> a job, or None without columns of its own
+                        calls(k, job) of chunk k - 2, its site count likewise: forward + call rows; called for every chunk, in order
+
+    so this thread never waits for work it has just issued, and the device never waits for this thread.  An exception - a caller's refusal
+    of the text among them - leaves nothing queued behind it.  Returns, as soon as the last chunk is ISSUED, finalize(done): it waits for `done`
+    (an event of the compute stream behind the last thing the caller issued) and the copy stream and adds the per-stage times to st; the
+    buffer sets carry their events from call to call, so the next call may start before.  st["trace"], a list: gets (what, chunk, t0, t1)."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    ranges, hsets, tsets, csets, copy_stream, main = sets.ranges, sets.hsets, sets.tsets, sets.csets, sets.copy_stream, sets.main
     trace = st.get("trace")
+    t_enter = time.perf_counter()
+    ev0 = torch.cuda.Event(enable_timing=True)
+    if trace is not None:
+        torch.cuda.synchronize(main.device); ev0.record(main); torch.cuda.synchronize(main.device)
+    t_ev0 = time.perf_counter()
+    st["setup_s"] += t_ev0 - t_enter                   # (the trace's two waits for the device belong to the setup, as they always did)
+    tev = lambda: torch.cuda.Event(enable_timing=True)
+    ev = [dict(h0=tev(), h1=tev(), t0=tev(), t1=tev(), a0=tev(), a1=tev(), b0=tev(), b1=tev()) for _ in ranges]
 
     def stage(k):
         t0 = time.perf_counter()
@@ -352,75 +349,31 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
             trace.append(("stage", k, t0, t1))
         return t1 - t0
 
-    rows_all = []
-    ev0 = torch.cuda.Event(enable_timing=True)
-    if trace is not None:
-        torch.cuda.synchronize(dev); ev0.record(main); torch.cuda.synchronize(dev)
-    t_ev0 = time.perf_counter()
-    st["setup_s"] += time.perf_counter() - t_enter
-    tev = lambda: torch.cuda.Event(enable_timing=True)
-    ev = [dict(h0=tev(), h1=tev(), t0=tev(), t1=tev(), a0=tev(), a1=tev(), b0=tev(), b1=tev()) for _ in ranges]
+    def wait_counts(event):
+        t_w = time.perf_counter()
+        event.synchronize()
+        st["wait_counts_s"] += time.perf_counter() - t_w
 
-    def encode_of(tk):
+    def second(k, cs, n_lo, n_hi, tok_done):
         """the second third of a chunk: its line count is on the host by now"""
-        k, n_lo, n_hi, cs, tok_done = tk
-        t_w = time.perf_counter()
-        tok_done.synchronize()
-        st["wait_counts_s"] += time.perf_counter() - t_w
-        M, nb, status, _ = tok_pin[k].tolist()
-        if status & ctx.TOK_EFORMAT:
-            raise host.HostError(f"{contig}: malformed input (a line with fewer than five tab-separated fields)")
-        if status & ctx.TOK_BLANK:
-            raise host.HostError(f"{contig}: mpileup text holds empty line(s): malformed input (every line must be one pileup column)")
-        if status & ctx.TOK_EPOS:
-            raise ValueError(f"{contig}: position outside the reference sequence")
-        if status:
-            raise host.HostError(f"{contig}: tokeniser status {status}")
-        own = M - n_lo - n_hi
-        st["columns"] += own
+        wait_counts(tok_done)
         ev[k]["a0"].record(main)
-        job = None
-        if own > 0:
-            d_pos, d_off, d_bases, d_ref = cs.pos[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
-            if ext_bits is not None:
-                # the lines outside the extended BED leave the arrays; where the chunk's own range [n_lo, M - n_hi) lies among the kept
-                # columns stays on the device (fmeta[k][2:])
-                d_pos, d_off, d_bases, d_ref, _ = ctx.pileup_filter_columns(d_pos, d_off, d_bases, d_ref, ext_bits, n_seq, n_lo, M - n_hi,
-                                                                            meta=fmeta[k], out=fsets[k % len(fsets)].out, stream=main)
-            if conf_bits is not None:
-                counts, depth, flags, _ = ctx.pileup_encode_columns3(d_bases, d_off, d_ref, d_pos, conf_bits, n_seq, min_af, min_coverage,
-                                                                     want_max_del=False)
-            else:
-                counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
-            # selection + the run of the chunk's own sites in the list, written into pinned memory by the last of its four launches
-            if ext_bits is not None:
-                center = ctx.pileup_select_sites_range_dev(d_pos, flags, fmeta[k][2:], meta_pin[k], stream=main)
-            else:
-                center = ctx.pileup_select_sites_range(d_pos, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
-            sel_done = torch.cuda.Event(); sel_done.record(main)
-            job = (k, M, d_pos, counts, center, sel_done)
+        job = encode(k, cs, n_lo, n_hi)
         ev[k]["a1"].record(main)
-        return job
+        sel_done = None
+        if job is not None:
+            sel_done = torch.cuda.Event(); sel_done.record(main)
+        return k, job, sel_done
 
-    def calls_of(job):
+    def last(k, job, sel_done):
         """the last third of a chunk: its site count is on the host by now"""
-        k, M, d_pos, counts, center, sel_done = job
-        t_w = time.perf_counter()
-        sel_done.synchronize()
-        st["wait_counts_s"] += time.perf_counter() - t_w
-        _, c_lo, c_hi, _ = meta_pin[k].tolist()
+        if sel_done is not None:
+            wait_counts(sel_done)
         ev[k]["b0"].record(main)
-        if c_hi > c_lo:
-            centers = center[c_lo:c_hi]
-            gt, zy, ga, za, gm, zm = ctx.pileup_forward_windows_calls(counts, centers)
-            rows_k = ctx.pileup_call_rows(counts, centers, d_pos, ga, za, gm, zm)                  # predict.py:52-65, one launch
-            if on_rows is not None:
-                on_rows(rows_k)
-            else:
-                rows_all.append(rows_k)
+        calls(k, job)
         ev[k]["b1"].record(main)
 
-    pending, job = deque(), None
+    pending, third = deque(), None
     with ThreadPoolExecutor(max_workers=1) as pool:
         futs = [pool.submit(stage, j) for j in range(min(3, len(ranges)))]
 
@@ -449,40 +402,47 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
                     nxt.h2d_done.synchronize()          # the copy engine is done with the buffer the staging thread is about to overwrite (chunk j - 1)
                 futs.append(pool.submit(stage, j + 3))
 
-        send(0)
-        for k, (a, b, n_lo, n_hi) in enumerate(ranges):
+        try:
+            send(0)
+            for k, (a, b, n_lo, n_hi) in enumerate(ranges):
+                t_i = time.perf_counter()
+                if k + 1 < len(ranges):
+                    send(k + 1)                         # one chunk ahead of the tokeniser
+                ts, cs = tsets[k % len(tsets)], csets[k % len(csets)]
+                # ---- first third of chunk k on the compute stream: the tokeniser; lines / bytes / status land in pinned memory ----
+                main.wait_event(ev[k]["h1"])
+                ev[k]["t0"].record(main)
+                tokenise(k, ts.buf[:b - a], cs)
+                ev[k]["t1"].record(main)
+                ts.free = ev[k]["t1"]
+                tok_done = torch.cuda.Event(); tok_done.record(main)
+                pending.append((k, cs, n_lo, n_hi, tok_done))
+                # ---- second third of chunk k - 1, last third of chunk k - 2 ----
+                nxt_third = second(*pending.popleft()) if len(pending) > 1 else None
+                if third is not None:
+                    last(*third)
+                third = nxt_third
+                st["issue_s"] += time.perf_counter() - t_i
+                if trace is not None:
+                    trace.append(("main: issue", k, t_i, time.perf_counter()))
             t_i = time.perf_counter()
-            if k + 1 < len(ranges):
-                send(k + 1)                             # one chunk ahead of the tokeniser
-            ts, cs = tsets[k % len(tsets)], csets[k % len(csets)]
-            n = b - a
-            # ---- first third of chunk k on the compute stream: the tokeniser; lines / bytes / status land in pinned memory ----
-            main.wait_event(ev[k]["h1"])
-            ev[k]["t0"].record(main)
-            ctx.mpileup_tokenise_into(ts.buf[:n], d_seq, cs.pos, cs.off, cs.bases, cs.ref, tok_pin[k], stream=main)
-            ev[k]["t1"].record(main)
-            ts.free = ev[k]["t1"]
-            tok_done = torch.cuda.Event(); tok_done.record(main)
-            pending.append((k, n_lo, n_hi, cs, tok_done))
-            # ---- second third of chunk k - 1, last third of chunk k - 2 ----
-            nxt_job = encode_of(pending.popleft()) if len(pending) > 1 else None
-            if job is not None:
-                calls_of(job)
-            job = nxt_job
+            while pending or third is not None:
+                nxt_third = second(*pending.popleft()) if pending else None
+                if third is not None:
+                    last(*third)
+                third = nxt_third
             st["issue_s"] += time.perf_counter() - t_i
-            if trace is not None:
-                trace.append(("main: issue", k, t_i, time.perf_counter()))
-        t_i = time.perf_counter()
-        while pending or job is not None:
-            nxt_job = encode_of(pending.popleft()) if pending else None
-            if job is not None:
-                calls_of(job)
-            job = nxt_job
-        st["issue_s"] += time.perf_counter() - t_i
-    rows = None if on_rows is not None else (torch.cat(rows_all) if rows_all else torch.zeros((0, 13), dtype=torch.float64, device=dev))
-    done = torch.cuda.Event(); done.record(main)
+        except BaseException:
+            # whatever ends the loop early, nothing queued may outlive the call: the pinned and device sets stay on the model for the next one
+            t_d = time.perf_counter()
+            for f_ in futs:
+                f_.cancel()
+            main.synchronize()
+            copy_stream.synchronize()
+            st["drain_s"] += time.perf_counter() - t_d
+            raise
 
-    def finalize():
+    def finalize(done):
         t_d = time.perf_counter()
         done.synchronize()
         copy_stream.synchronize()
@@ -490,23 +450,118 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
         if trace is not None:
             for k, e in enumerate(ev):
                 for what, x0, x1 in (("h2d", "h0", "h1"), ("tokenise", "t0", "t1"), ("encode+select", "a0", "a1"), ("forward+rows", "b0", "b1")):
-                    try:
-                        trace.append((what, k, t_ev0 + ev0.elapsed_time(e[x0]) * 1e-3, t_ev0 + ev0.elapsed_time(e[x1]) * 1e-3))
-                    except (RuntimeError, ValueError):
-                        pass
+                    trace.append((what, k, t_ev0 + ev0.elapsed_time(e[x0]) * 1e-3, t_ev0 + ev0.elapsed_time(e[x1]) * 1e-3))
         for e in ev:
             st["h2d_s"] += e["h0"].elapsed_time(e["h1"]) * 1e-3
             tk = e["t0"].elapsed_time(e["t1"]) * 1e-3
             st["tok_s"] += tk; st["gpu_s"] += tk
-            for x0, x1 in (("a0", "a1"), ("b0", "b1")):
-                try:
-                    st["gpu_s"] += e[x0].elapsed_time(e[x1]) * 1e-3
-                except (RuntimeError, ValueError):
-                    pass                               # (a chunk without columns of its own never recorded its last third)
+            st["gpu_s"] += (e["a0"].elapsed_time(e["a1"]) + e["b0"].elapsed_time(e["b1"])) * 1e-3
 
+    return finalize
+
+
+def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, defer=False, beds=None):
+    """stream_contig with the text cut into columns ON THE DEVICE (nsnp_mpileup_tokenise).  The host touches every byte of the text once - a
+    multi-threaded copy of the chunk (whole lines, 16 lines of halo either side, found by a few find / rfind calls) from the page cache
+    into pinned memory - and the chunks are worked off four things at a time by _run_text_chunks, over the buffer sets of _text_chunk_sets;
+    this function brings what belongs to ONE contig: its reference sequence and BED bitmaps on the device, the filter sets, the pinned
+    count slots of its chunks and the three stage bodies.  Same rows as the host-parsed path (tests/test_gpu_predict.py); text the
+    reference's reader aborts on is refused with the same errors.
+    defer=True (call_contigs): returns (rows, done, finalize) as soon as the last chunk is ISSUED - `done` is an event behind the last kernel,
+    finalize() waits for it and adds the per-stage times to stats - so that the next contig's text is staged, copied and tokenised while
+    this one's last forward (1.4 ms of a 6 M-column contig's 15) still runs; the buffer sets carry their events from call to call.
+    beds (_contig_beds; None: nothing below changes): with an extended bitmap every chunk's columns pass nsnp_pileup_filter_columns in front
+    of the encode - the images of the chunk's own range stay on the device, the selection reads them there - and with a confident bitmap
+    the encode is nsnp_pileup_encode_columns3.  The result does not depend on the cuts for texts with ASCENDING positions: 33 kept lines
+    with consecutive positions are then 33 consecutive lines of the text, inside the 16-line halo; in a text whose positions repeat or step
+    back they may lie further apart (the whole-array calls stay exact for any position sequence)."""
+    import time
+    import torch
+    ctx = model.ctx
+    dev = torch.device("cuda", ctx.device)
+    finder, arr = _as_bytes_like(text)
+    hi = arr.size if hi is None else hi
+    st = _stream_stats(stats)
+    t_enter = time.perf_counter()
+    if hi <= lo:
+        empty = torch.zeros((0, 13), dtype=torch.float64, device=dev)
+        return (empty, None, lambda: None) if defer else empty
+    sets = _text_chunk_sets(model, finder, lo, hi, chunk_bytes, dev)
+    ranges, csets, copy_stream, main = sets.ranges, sets.csets, sets.copy_stream, sets.main
+    meta_pin, tok_pin = _count_slots(model, "_meta_pin", len(ranges)), _count_slots(model, "_tok_meta_pin", len(ranges))
+    n_seq = int(chr_seq.size)
+    d_seq, = _upload_pinned(model, "_seq_pin", [chr_seq], torch.uint8, 1 << 20, dev, copy_stream, main)
+    cov_idx = getattr(model, "_cov_idx", None)
+    if cov_idx is None or cov_idx.device != dev:
+        cov_idx = model._cov_idx = torch.tensor(list(COV_CHANNELS), dtype=torch.int64, device=dev)
+    ext_bits = conf_bits = fsets = fmeta = None
+    if beds is not None:
+        ext_bits, conf_bits = _upload_beds(model, beds, dev, copy_stream, main)
+        if ext_bits is not None:
+            fsets = getattr(model, "_fil_dev_sets", None)
+            if not fsets or fsets[0].pos.device != dev or fsets[0].pos.numel() < csets[0].pos.numel() or fsets[0].bases.numel() < csets[0].bases.numel():
+                fsets = model._fil_dev_sets = [_FilSet(csets[0].pos.numel(), csets[0].bases.numel(), dev) for _ in range(3)]
+                if not sets.fresh:
+                    copy_stream.wait_stream(main)      # (new filter sets are new device sets: _text_chunk_sets says why the copy stream waits)
+            fmeta = torch.zeros((len(ranges), 4), dtype=torch.int64, device=dev)
+    rows_all = []
+
+    def tokenise(k, text_k, cs):
+        ctx.mpileup_tokenise_into(text_k, d_seq, cs.pos, cs.off, cs.bases, cs.ref, tok_pin[k], stream=main)
+
+    def encode(k, cs, n_lo, n_hi):
+        M, nb, status, _ = tok_pin[k].tolist()
+        if status & ctx.TOK_EFORMAT:
+            raise host.HostError(f"{contig}: malformed input (a line with fewer than five tab-separated fields)")
+        if status & ctx.TOK_BLANK:
+            raise host.HostError(f"{contig}: mpileup text holds empty line(s): malformed input (every line must be one pileup column)")
+        if status & ctx.TOK_EPOS:
+            raise ValueError(f"{contig}: position outside the reference sequence")
+        if status:
+            raise host.HostError(f"{contig}: tokeniser status {status}")
+        own = M - n_lo - n_hi
+        st["columns"] += own
+        if own <= 0:
+            return None
+        d_pos, d_off, d_bases, d_ref = cs.pos[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
+        if ext_bits is not None:
+            # the lines outside the extended BED leave the arrays; where the chunk's own range [n_lo, M - n_hi) lies among the kept
+            # columns stays on the device (fmeta[k][2:])
+            d_pos, d_off, d_bases, d_ref, _ = ctx.pileup_filter_columns(d_pos, d_off, d_bases, d_ref, ext_bits, n_seq, n_lo, M - n_hi,
+                                                                        meta=fmeta[k], out=fsets[k % len(fsets)].out, stream=main)
+        if conf_bits is not None:
+            counts, depth, flags, _ = ctx.pileup_encode_columns3(d_bases, d_off, d_ref, d_pos, conf_bits, n_seq, min_af, min_coverage,
+                                                                 want_max_del=False)
+        else:
+            counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
+        # selection + the run of the chunk's own sites in the list, written into pinned memory by the last of its four launches
+        if ext_bits is not None:
+            center = ctx.pileup_select_sites_range_dev(d_pos, flags, fmeta[k][2:], meta_pin[k], stream=main)
+        else:
+            center = ctx.pileup_select_sites_range(d_pos, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
+        return d_pos, counts, center
+
+    def calls(k, job):
+        if job is None:
+            return
+        d_pos, counts, center = job
+        _, c_lo, c_hi, _ = meta_pin[k].tolist()
+        if c_hi > c_lo:
+            centers = center[c_lo:c_hi]
+            gt, zy, ga, za, gm, zm = ctx.pileup_forward_windows_calls(counts, centers)
+            rows_k = ctx.pileup_call_rows(counts, centers, d_pos, ga, za, gm, zm)                  # predict.py:52-65, one launch
+            if on_rows is not None:
+                on_rows(rows_k)
+            else:
+                rows_all.append(rows_k)
+
+    st["setup_s"] += time.perf_counter() - t_enter
+    finalize = _run_text_chunks(sets, arr, st, tokenise, encode, calls)
+    rows = None if on_rows is not None else (torch.cat(rows_all) if rows_all else torch.zeros((0, 13), dtype=torch.float64, device=dev))
+    done = torch.cuda.Event(); done.record(main)
     if defer:
-        return rows, done, finalize
-    finalize()
+        return rows, done, lambda: finalize(done)
+    finalize(done)
     return rows
 
 
@@ -1381,78 +1436,43 @@ class ContigRuns:
 
 
 def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stats, on_rows, cap_runs=None):
-    """_stream_contig_dev for a text of several contigs: the same four stations - staging thread, copy stream, tokeniser, encode + select,
-    forward + rows, counts read one chunk late through pinned memory - with nsnp_mpileup_tokenise_contigs in the tokeniser's place and its
+    """_stream_contig_dev for a text of several contigs: the same chunk loop over the same buffer sets (_run_text_chunks, _text_chunk_sets)
+    with nsnp_mpileup_tokenise_contigs in the tokeniser's place and its
     `key` where the per-contig path hands a position to the window rule and the call rows.  The run table of every chunk arrives in pinned
     memory with its counts.  on_rows(rows_k, started): the call rows of a chunk ([n, 13] float64 on the device, column 0 = key) or None, and
     the wanted contigs that start among the chunk's own lines; called in chunk order as soon as the chunk's last kernels are issued."""
     import time
-    from collections import deque
-    from concurrent.futures import ThreadPoolExecutor
     import torch
     ctx = model.ctx
     dev = torch.device("cuda", ctx.device)
     finder, arr = _as_bytes_like(text)
-    lo, hi = 0, arr.size
-    st = stats if stats is not None else {}
-    for k in ("parse_s", "h2d_s", "gpu_s", "tok_s", "text_bytes", "columns", "chunks", "setup_s", "wait_parse_s", "issue_s", "wait_counts_s", "drain_s"):
-        st.setdefault(k, 0.0)
-    st["tokenise"] = "device"
+    st = _stream_stats(stats)
     t_enter = time.perf_counter()
     tracker = ContigRuns(table.names)
-    if hi <= lo:
+    if not arr.size:
         return tracker
-    cuts = ramp_cuts(finder, lo, hi, int(chunk_bytes))
-    ranges = [halo_range(finder, cuts[k], cuts[k + 1]) for k in range(len(cuts) - 1) if cuts[k + 1] > cuts[k]]
-    cap = max(b - a for a, b, _, _ in ranges) + 64
-    # the buffer sets of _stream_contig_dev, kept on the model and shared with it (one call at a time per model), by its rules
-    hsets = getattr(model, "_text_host_sets", None)
-    n_hsets, n_tsets, n_sets = min(4, len(ranges)), min(3, len(ranges)), min(3, len(ranges))
-    if not hsets or min(s_.buf.numel() for s_ in hsets) < cap or len(hsets) < n_hsets:
-        hsets = model._text_host_sets = [_TextSet(cap) for _ in range(n_hsets)]
-        model._text_dev_sets = None
-    tsets = getattr(model, "_text_dev_sets", None)
-    fresh_sets = not tsets or tsets[0].buf.device != dev or min(t_.buf.numel() for t_ in tsets) < cap or len(tsets) < n_tsets
-    if fresh_sets:
-        tsets = model._text_dev_sets = [_TextSet(cap, dev) for _ in range(n_tsets)]
-        model._col_dev_sets = [_ColSet(cap, dev) for _ in range(n_sets)]
-        model._copy_stream = getattr(model, "_copy_stream", None) or host.copy_stream(dev)
-    csets, copy_stream = model._col_dev_sets, model._copy_stream
+    # the buffer sets of _stream_contig_dev, kept on the model and shared with it (one call at a time per model)
+    sets = _text_chunk_sets(model, finder, 0, arr.size, chunk_bytes, dev)
+    ranges, csets, main = sets.ranges, sets.csets, sets.main
     ksets = getattr(model, "_key_dev_sets", None)
     if not ksets or len(ksets) < len(csets) or ksets[0].key.device != dev or min(k_.key.numel() for k_ in ksets) < max(c_.pos.numel() for c_ in csets):
         ksets = model._key_dev_sets = [_KeySet(c_.pos.numel(), dev) for c_ in csets]
     # the run table of a chunk: one entry per KB of text, at least 4096 - a run is at least one line, and a chunk whose runs average fewer
     # than ten lines is refused with a status that says so (16 bytes per entry in pinned memory: 1 MB per slot at 64 MB chunks)
-    cap_runs = int(cap_runs or max(4096, cap // 1024))
+    cap_runs = int(cap_runs or max(4096, sets.cap // 1024))
     n_ring = 4                                             # a chunk's counts and run table are read one chunk late: four slots are never in use at once
     if getattr(model, "_run_pin", None) is None or model._run_pin.shape[1] < cap_runs:
         model._run_pin = torch.zeros((n_ring, cap_runs, 2), dtype=torch.int64, pin_memory=True)
         model._ctok_meta_pin = torch.zeros((n_ring, 4), dtype=torch.int64, pin_memory=True)
-    if len(getattr(model, "_meta_pin", ())) < len(ranges):
-        model._meta_pin = torch.zeros((len(ranges), 4), dtype=torch.int64, pin_memory=True)
-    meta_pin, tok_pin, run_pin = model._meta_pin, model._ctok_meta_pin, model._run_pin
-    main = torch.cuda.current_stream(dev)
-    if getattr(model, "_stream_main_id", None) != (main.device, main.stream_id):
-        copy_stream.wait_stream(main)
-        model._stream_main_id = (main.device, main.stream_id)
-    if fresh_sets:
-        copy_stream.wait_stream(main)                      # (new device sets may be blocks that work queued on the compute stream still reads)
+    meta_pin, tok_pin, run_pin = _count_slots(model, "_meta_pin", len(ranges)), model._ctok_meta_pin, model._run_pin
+    started = {}                                           # chunk -> the wanted contigs that start among its own lines
 
-    def stage(k):
-        t0 = time.perf_counter()
-        a, b, _, _ = ranges[k]
-        host.stage_values(hsets[k % len(hsets)].np, b - a, src=arr, src_off=a, src_dtype=np.uint8)
-        return time.perf_counter() - t0
+    def tokenise(k, text_k, cs):
+        ks = ksets[k % len(csets)]
+        ctx.mpileup_tokenise_contigs_into(text_k, table, cs.pos, cs.off, cs.bases, cs.ref, ks.cid, ks.key, run_pin[k % n_ring],
+                                          tok_pin[k % n_ring], stream=main)
 
-    st["setup_s"] += time.perf_counter() - t_enter
-    tev = lambda: torch.cuda.Event(enable_timing=True)
-    ev = [dict(h0=tev(), h1=tev(), t0=tev(), t1=tev(), a0=tev(), a1=tev(), b0=tev(), b1=tev()) for _ in ranges]
-
-    def encode_of(tk):
-        k, n_lo, n_hi, cs, ks, tok_done = tk
-        t_w = time.perf_counter()
-        tok_done.synchronize()
-        st["wait_counts_s"] += time.perf_counter() - t_w
+    def encode(k, cs, n_lo, n_hi):
         M, nb, status, n_runs = tok_pin[k % n_ring].tolist()
         if status & ctx.TOK_EFORMAT:
             raise host.HostError("malformed input (a line with fewer than five tab-separated fields)")
@@ -1470,104 +1490,31 @@ def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stat
                                  f"{cs.bases.numel()} bytes (lines shorter than 10 bytes: malformed input)")
         if status:
             raise host.HostError(f"tokeniser status {status}")
-        started = tracker.feed(run_pin[k % n_ring, :n_runs].numpy(), M, n_lo, M - n_hi)
+        started[k] = tracker.feed(run_pin[k % n_ring, :n_runs].numpy(), M, n_lo, M - n_hi)
         own = M - n_lo - n_hi
         st["columns"] += own
-        ev[k]["a0"].record(main)
-        job = (k, started, None)
-        if own > 0:
-            d_key, d_off, d_bases, d_ref = ks.key[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
-            counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
-            center = ctx.pileup_select_sites_range(d_key, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
-            sel_done = torch.cuda.Event(); sel_done.record(main)
-            job = (k, started, (d_key, counts, center, sel_done))
-        ev[k]["a1"].record(main)
-        return job
+        if own <= 0:
+            return None
+        d_key, d_off, d_bases, d_ref = ksets[k % len(csets)].key[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
+        counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
+        center = ctx.pileup_select_sites_range(d_key, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
+        return d_key, counts, center
 
-    def calls_of(job):
-        k, started, work = job
+    def calls(k, job):
         rows_k = None
-        ev[k]["b0"].record(main)
-        if work is not None:
-            d_key, counts, center, sel_done = work
-            t_w = time.perf_counter()
-            sel_done.synchronize()
-            st["wait_counts_s"] += time.perf_counter() - t_w
+        if job is not None:
+            d_key, counts, center = job
             _, c_lo, c_hi, _ = meta_pin[k].tolist()
             if c_hi > c_lo:
                 centers = center[c_lo:c_hi]
                 gt, zy, ga, za, gm, zm = ctx.pileup_forward_windows_calls(counts, centers)
                 rows_k = ctx.pileup_call_rows(counts, centers, d_key, ga, za, gm, zm)
-        ev[k]["b1"].record(main)
-        on_rows(rows_k, started)
+        on_rows(rows_k, started.pop(k))
 
-    pending, job = deque(), None
-    with ThreadPoolExecutor(max_workers=1) as pool:
-        futs = [pool.submit(stage, j) for j in range(min(3, len(ranges)))]
-
-        def send(j):
-            t_w = time.perf_counter()
-            t_stage = futs[j].result()
-            st["wait_parse_s"] += time.perf_counter() - t_w
-            a_, b_, _, _ = ranges[j]
-            n_ = b_ - a_
-            hs, ts = hsets[j % len(hsets)], tsets[j % len(tsets)]
-            st["parse_s"] += t_stage; st["text_bytes"] += n_; st["chunks"] += 1
-            if ts.free is not None:
-                copy_stream.wait_event(ts.free)
-            with torch.cuda.stream(copy_stream):
-                ev[j]["h0"].record(copy_stream)
-                ts.buf[:n_].copy_(hs.buf[:n_], non_blocking=True)
-                ev[j]["h1"].record(copy_stream)
-            hs.h2d_done = ev[j]["h1"]
-            if j + 3 < len(ranges):
-                nxt = hsets[(j + 3) % len(hsets)]
-                if nxt.h2d_done is not None:
-                    nxt.h2d_done.synchronize()
-                futs.append(pool.submit(stage, j + 3))
-
-        try:
-            send(0)
-            for k, (a, b, n_lo, n_hi) in enumerate(ranges):
-                t_i = time.perf_counter()
-                if k + 1 < len(ranges):
-                    send(k + 1)
-                ts, cs, ks = tsets[k % len(tsets)], csets[k % len(csets)], ksets[k % len(csets)]
-                n = b - a
-                main.wait_event(ev[k]["h1"])
-                ev[k]["t0"].record(main)
-                ctx.mpileup_tokenise_contigs_into(ts.buf[:n], table, cs.pos, cs.off, cs.bases, cs.ref, ks.cid, ks.key, run_pin[k % n_ring],
-                                                  tok_pin[k % n_ring], stream=main)
-                ev[k]["t1"].record(main)
-                ts.free = ev[k]["t1"]
-                tok_done = torch.cuda.Event(); tok_done.record(main)
-                pending.append((k, n_lo, n_hi, cs, ks, tok_done))
-                nxt_job = encode_of(pending.popleft()) if len(pending) > 1 else None
-                if job is not None:
-                    calls_of(job)
-                job = nxt_job
-                st["issue_s"] += time.perf_counter() - t_i
-            t_i = time.perf_counter()
-            while pending or job is not None:
-                nxt_job = encode_of(pending.popleft()) if pending else None
-                if job is not None:
-                    calls_of(job)
-                job = nxt_job
-            st["issue_s"] += time.perf_counter() - t_i
-        finally:
-            # whatever ends the loop, nothing queued may outlive the call: the pinned and device sets stay on the model for the next one
-            t_d = time.perf_counter()
-            for f_ in futs:
-                f_.cancel()
-            main.synchronize()
-            copy_stream.synchronize()
-            st["drain_s"] += time.perf_counter() - t_d
-    for e in ev:
-        st["h2d_s"] += e["h0"].elapsed_time(e["h1"]) * 1e-3
-        tk = e["t0"].elapsed_time(e["t1"]) * 1e-3
-        st["tok_s"] += tk; st["gpu_s"] += tk
-        for x0, x1 in (("a0", "a1"), ("b0", "b1")):
-            st["gpu_s"] += e[x0].elapsed_time(e[x1]) * 1e-3
+    st["setup_s"] += time.perf_counter() - t_enter
+    finalize = _run_text_chunks(sets, arr, st, tokenise, encode, calls)
+    done = torch.cuda.Event(); done.record(main)
+    finalize(done)
     return tracker
 
 

@@ -267,6 +267,48 @@ def test_contigs_of_growing_size_reallocate_the_device_sets_behind_queued_work(t
         assert out.read_bytes() == want, seed
 
 
+def test_a_refused_contig_in_a_deferred_run_leaves_the_model_usable(tmp_path, pileup_weights, monkeypatch):
+    """call_contigs over [good A, bad, good B] of 3,000 columns each at chunk_bytes=100_000 (2-3 chunks per contig): `bad` is A's text with
+    one empty line in its second chunk, so the refusal comes while A's last kernels are still deferred and while chunks of `bad` are staged,
+    copied and tokenised ahead of the one that is refused.  The call raises the tokeniser's refusal; the buffer sets and events the model
+    keeps from the broken run do not disturb the next one: the same model then writes, for [A, B], the bytes a fresh model writes."""
+    from nanosnp_amd import host
+    from nanosnp_amd.pileup_model import LSTMNetwork
+    from nanosnp_amd.pipeline import call_contigs, ramp_cuts
+    monkeypatch.setenv("NSNP_TOKENISE", "device")
+    cb = 100_000
+    contigs = []
+    for i, name in enumerate(("dA", "dB")):
+        cols = host.synth_columns(20262100 + i, 3000, coverage=30, het_rate=0.05)
+        contigs.append((name, bytes(cols.mpileup_text_native(name)), cols.ref.copy()))
+    n_chunks = [len(ramp_cuts(t, 0, len(t), cb)) - 1 for _, t, _ in contigs]
+    assert all(2 <= n <= 3 for n in n_chunks), n_chunks
+    (_, text_a, seq_a), _ = contigs
+    cuts = ramp_cuts(text_a, 0, len(text_a), cb)
+    at = text_a.find(b"\n", (cuts[1] + cuts[2]) // 2) + 1            # a line boundary in the middle of the second chunk
+    bad = ("dBad", text_a[:at] + b"\n" + text_a[at:], seq_a)
+    bad_cuts = ramp_cuts(bad[1], 0, len(bad[1]), cb)
+    assert bad_cuts[1] < at < bad_cuts[2]
+
+    def run(model, items, path):
+        st = {}
+        with open(path, "wb") as f:
+            n = call_contigs(model, items, f, batch_size=64, chunk_bytes=cb, stats=st)
+        return n, path.read_bytes(), st
+
+    (want_sites, want_rows), want, st = run(LSTMNetwork().load_weight_list(pileup_weights), contigs, tmp_path / "fresh.vcf")
+    assert want_rows > 100 and st["chunks"] == sum(n_chunks)
+    m = LSTMNetwork().load_weight_list(pileup_weights)
+    st_bad = {}
+    with open(tmp_path / "bad.vcf", "wb") as f:
+        with pytest.raises(host.HostError, match="empty line"):
+            call_contigs(m, [contigs[0], bad, contigs[1]], f, batch_size=64, chunk_bytes=cb, stats=st_bad)
+    # (all of A; of `bad` at least the chunk in front of the refused one and that one)
+    assert n_chunks[0] + 2 <= st_bad["chunks"] <= n_chunks[0] + len(bad_cuts) - 1
+    got_n, got, st = run(m, contigs, tmp_path / "after.vcf")
+    assert got_n == (want_sites, want_rows) and got == want and st["chunks"] == sum(n_chunks)
+
+
 def test_streamed_pipeline_edge_inputs(pileup_weights, tok_mode):
     """call_contig on the inputs a real run meets at its edges: no text, one line, fewer columns than a window, a last line without
     its newline, CRLF line ends, a chunk size below one line (every line its own chunk), and the same contig again on the same model
