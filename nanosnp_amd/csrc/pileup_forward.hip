@@ -586,6 +586,7 @@ __global__ __launch_bounds__(256, (WXL ? 4 : (NSG == 1 ? 3 : 2))) void k_pileup_
 // 19..31 zero: the B fragment of lane (n, q) is one ds_read_b128 with the site index in address bits 4-7 (conflict-free, as in
 // the bf16x3 kernels).
 constexpr int RX_PLANE = 4 * 16 * 8;          // bf16 per plane of a staged x image
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsx(
     const int32_t* __restrict__ x, const int64_t* __restrict__ center_idx, int64_t N,
@@ -595,13 +596,14 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsx(
 {
     __shared__ __attribute__((aligned(16))) float hx[2][16][RS_XROW];
     __shared__ __attribute__((aligned(16))) __bf16 xx[2][3][RX_PLANE];
-    __shared__ int xlvl[2][4];                                          // [buf][staging wave]: split level
-    __shared__ int64_t xofs[9 * 16];                                    // staging thread -> element offset of its input piece at t = 0
+    __shared__ __attribute__((aligned(16))) int xlvl[2][4];             // [buf][staging wave]: split level
+    __shared__ int64_t xofs[9 * 16];                                    // center_idx only: staging thread -> element offset of its piece at t = 0
     const int dir = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, q = lane >> 4;
     NSNP_DEVCLK_START
     const int64_t base_site = (int64_t)blockIdx.x * 16;
+    const int nrows = (int)min((int64_t)16, N - base_site);
 
     // ---- this wave's four gate tiles -> registers: W_hh as in K1r, the input block as three bf16 planes ----
     f32x4 Whh[4][4];
@@ -618,39 +620,49 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsx(
         }
     }
 
-    // ---- input windows: thread i < 144 moves the 8-byte piece i % 9 (channels 2 p, 2 p + 1) of site i / 9 per step, as in K1r ----
+    // ---- input windows: the 18 counts of (site, t) are nine 8-byte pieces (channels 2 p, 2 p + 1).  Wave 0 moves pieces 0..3 of the
+    // 16 sites per step (site = lane >> 2, piece = lane & 3), wave 1 pieces 4..7, lanes 0..15 of wave 2 piece 8, wave 3 none: in the
+    // [quarter][site][8] image a lane of waves 0, 1 then owns the bf16 pair 2 lane of quarter `wave`, and everything a staging
+    // thread needs per step is one LDS offset and one source offset, both fixed before the loop ----
     const bool xon = tid < 9 * 16;
-    const int xrow = xon ? tid / 9 : 0, piece = xon ? tid % 9 : 0;
-    if (xon) {
-        const int64_t site = base_site + xrow;
-        const int64_t sc = site < N ? site : N - 1;
-        xofs[tid] = (center_idx ? (center_idx[sc] - PCENTER) * PC : sc * (PW * PC)) + 2 * piece;
-    }
+    const int xrow = min(wave < 2 ? lane >> 2 : n, nrows - 1);          // (rows past N restage the last site: never stored)
+    const int piece = wave < 2 ? 4 * wave + (lane & 3) : 8;
+    const int xdst = wave < 2 ? 128 * wave + 2 * lane : 256 + 8 * n;    // K position 2 piece of the staged row
+    // contiguous windows: the workgroup's base in scalar registers + a 32-bit byte offset per thread; center_idx: 64-bit offsets, kept
+    // in LDS and read back for every load
+    const int32_t* const xwg = x + base_site * (PW * PC);
+    unsigned xoff = (unsigned)(xrow * (PW * PC) + 2 * piece) * 4u;
+    if (center_idx && xon) xofs[tid] = (center_idx[base_site + xrow] - PCENTER) * PC + 2 * piece;
     int2 xi = int2{0, 0};
-    // (the 64-bit source offset is read back from LDS for every load: held in registers through the step it spills)
-    auto load_x = [&](int t) { if (xon) xi = *reinterpret_cast<const int2*>(x + xofs[tid] + t * PC); };
+    auto load_x = [&](int t) {
+        if (!xon) return;
+        if (center_idx) xi = *reinterpret_cast<const int2*>(x + xofs[tid] + t * PC);
+        else {
+            asm volatile("" : "+v"(xoff));
+            xi = *reinterpret_cast<const int2*>(reinterpret_cast<const char*>(xwg + t * PC) + xoff);
+        }
+    };
+    // counts beyond +-256 (no pileup has them): two or three bf16 terms per count and the workgroup's level, out of the step's line
+    auto stage_x_split = [&](b2* d, int* lv) {
+        __bf16 a0, a1, a2, c0, c1, c2;
+        split3((float)xi.x, a0, a1, a2); split3((float)xi.y, c0, c1, c2);
+        d[0] = b2{a0, c0}; d[RX_PLANE / 2] = b2{a1, c1}; d[RX_PLANE] = b2{a2, c2};
+        const bool nz1 = (float)a1 != 0.f || (float)c1 != 0.f, nz2 = (float)a2 != 0.f || (float)c2 != 0.f;
+        const int lvl = __ballot(nz2) != 0ull ? 2 : (__ballot(nz1) != 0ull ? 1 : 0);
+        if (lane == 0) *lv = lvl;
+    };
     auto stage_x = [&](int buf) {
         if (!xon) return;
-        int id = tid;
-        asm volatile("" : "+v"(id));
-        const int xdst = (id % 9 >> 2) * 128 + id / 9 * 8 + 2 * (id % 9 & 3);   // K position 2 piece in the [quarter][site][8] image
-        const float f0 = (float)xi.x, f1 = (float)xi.y;                 // predict.py:49 int -> float
-        b2 p0, p1 = b2{0, 0}, p2 = b2{0, 0};
-        int lvl = 0;
+        b2* const d = reinterpret_cast<b2*>(&xx[buf][0][xdst]);
         const bool big = (unsigned)xi.x + 256u > 512u || (unsigned)xi.y + 256u > 512u;
         if (__builtin_expect(__ballot(big) == 0ull, 1)) {
-            p0 = b2{(__bf16)f0, (__bf16)f1};                            // exact: |c| <= 256
+            d[0] = __builtin_convertvector(f32x2{(float)xi.x, (float)xi.y}, b2);       // predict.py:49 int -> float; exact: |c| <= 256
+            d[RX_PLANE / 2] = b2{0, 0};                                  // planes 1 and 2 always hold this step's terms
+            d[RX_PLANE] = b2{0, 0};
+            if (lane == 0) xlvl[buf][wave] = 0;
         } else {
-            __bf16 a0, a1, a2, c0, c1, c2;
-            split3(f0, a0, a1, a2); split3(f1, c0, c1, c2);
-            p0 = b2{a0, c0}; p1 = b2{a1, c1}; p2 = b2{a2, c2};
-            const bool nz1 = (float)a1 != 0.f || (float)c1 != 0.f, nz2 = (float)a2 != 0.f || (float)c2 != 0.f;
-            lvl = __ballot(nz2) != 0ull ? 2 : (__ballot(nz1) != 0ull ? 1 : 0);
+            stage_x_split(d, &xlvl[buf][wave]);
         }
-        *reinterpret_cast<b2*>(&xx[buf][0][xdst]) = p0;
-        *reinterpret_cast<b2*>(&xx[buf][1][xdst]) = p1;
-        *reinterpret_cast<b2*>(&xx[buf][2][xdst]) = p2;
-        if (lane == 0) xlvl[buf][wave] = lvl;
     };
     // K positions 18..31 are never staged: the constant 1 of the bias column in plane 0, zeros elsewhere; the level of wave 3 (no
     // staging lanes) stays zero
@@ -668,18 +680,21 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsx(
     for (int u = 0; u < 4; ++u) c[u] = 0.f;
 
     // K1r's flush: H0 rows leave through the exchange buffer one step late, thread (row = tid / 16, chunk = tid % 16 = 4 q' + j)
-    // moving exchange position 16 j + 4 q' to H0 position 16 q' + 4 j (addresses: the workgroup's base + a 32-bit offset)
-    // (the per-thread offsets are recomputed from an opaque copy of tid in every step: hipcc hoists them out of the loop otherwise,
-    // as 64-bit addresses, and spills them)
+    // moving exchange position 16 j + 4 q' to H0 position 16 q' + 4 j, 16 lanes to one 256-byte row.  The LDS address and the
+    // 32-bit byte offset behind the workgroup's base are fixed here; a step adds its buffer and t * 128 to the scalar base.  (The
+    // offset is made opaque in every step: hipcc otherwise folds base + offset into a 64-bit address per thread and spills it.
+    // Storing the cell's own f32x4 straight to H0, 16 bytes per lane as k_pileup_l0_b3 does, needs no read-back and measured 3.5 %
+    // slower per launch: four times the store requests, a quarter of a line each - docs/rounds/r13.md)
     float* const h0wg = H0 + (base_site * PW * 2 + dir) * 64;
-    const int nrows = (int)min((int64_t)16, N - base_site);
+    const int frow = tid >> 4, fcid = tid & 15;
+    unsigned foff = (unsigned)(frow * (PW * 128) + 4 * fcid) * 4u;
+    const float* const fl = &hx[0][frow][16 * (fcid & 3) + 4 * (fcid >> 2)];
+    const bool fon = frow < nrows;
     auto flush_h = [&](int buf, int t) {
-        int id = tid;
-        asm volatile("" : "+v"(id));
-        const int frow = id >> 4, fcid = id & 15;
-        if (frow < nrows)
-            *reinterpret_cast<f32x4*>(h0wg + frow * PW * 128 + t * 128 + 4 * fcid) =
-                *reinterpret_cast<const f32x4*>(&hx[buf][frow][16 * (fcid & 3) + 4 * (fcid >> 2)]);
+        asm volatile("" : "+v"(foff));
+        if (fon)
+            *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(h0wg + t * 128) + foff) =
+                *reinterpret_cast<const f32x4*>(fl + buf * (16 * RS_XROW));
     };
 
     for (int s = 0; s < PW; ++s) {
@@ -689,7 +704,8 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsx(
         // (plane 0 is read beside the level: one LDS round trip between the barrier and the first MFMA)
         const __bf16* xr = &xx[cur][0][q * 128 + n * 8];
         const b8 xb0 = *reinterpret_cast<const b8*>(xr);
-        const int lvl = __builtin_amdgcn_readfirstlane(max(max(xlvl[cur][0], xlvl[cur][1]), max(xlvl[cur][2], xlvl[cur][3])));
+        const i32x4 lv = *reinterpret_cast<const i32x4*>(xlvl[cur]);
+        const int lvl = __builtin_amdgcn_readfirstlane(max(max(lv[0], lv[1]), max(lv[2], lv[3])));
         f32x4 hn;
         // the whole step is instantiated per split level: a branch around the extra products alone costs the registers that keep
         // the kernel without scratch
