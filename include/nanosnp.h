@@ -337,6 +337,57 @@ int nsnp_mpileup_tokenise_contigs(nsnp_ctx* ctx, const uint8_t* text, int64_t te
 int nsnp_pileup_gather_windows(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx,
                                int64_t N, int32_t* x, void* stream);
 
+/* The first two arrays of a stage-1 window file (<chr>.pd.bin; make_predict_data/main.cpp:76-127 + make_bin_predict_data.py:48-100) for
+ * the N selected sites center_idx[0..N) of a chunk of M encoded columns (counts int32 [M,18], pos int64 [M], both on the device):
+ *   position_matrix [N,33,18]  int16 (elem 2) or int32 (elem 4): position_matrix[n][t][c] = counts[center_idx[n] - 16 + t][c]
+ *   position        [N,83]     uint8: name ':' decimal(pos[centre]) ':' then toupper(chr_seq[p - 1]) for p in [pos - 16, pos + 16] (C locale:
+ *                              only a-z change), zeros up to NSNP_POSITION_WIDTH bytes
+ * Both outputs and meta (int64 [4]) may lie in any memory the device can write (device or pinned host); position_matrix must be aligned to
+ * 16 bytes, position to 4.  chr_seq: device uint8 [chr_len] as stored in the FASTA; name: HOST bytes, name_len of them.
+ * meta = { N, overflow, status, 0 } when the stream has passed the call: overflow != 0 when elem is 2 and a value lies outside int16 (the
+ * stored value is then unspecified: call again with elem 4); status != 0 when a centre lay outside [16, M - 17], a position outside
+ * [0, 10^11) or a window outside the contig - the selection never hands such a site over; the kernels clamp instead of following it.
+ * NSNP_EINVAL: an empty name, a NUL in it, name_len + 1 + 11 + 1 + 33 > NSNP_POSITION_WIDTH (11 digits: the longest position below
+ * 2^36), elem not 2 or 4, N > 0 with M < 33.  Three launches, no scratch memory. */
+#define NSNP_POSITION_WIDTH 83   /* make_bin_predict_data.py:94  StringAtom(itemsize = no_of_positions + 50) */
+int nsnp_pileup_window_records(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const int64_t* pos, int64_t M, int64_t N,
+                               const uint8_t* chr_seq, int64_t chr_len, const uint8_t* name, int name_len, int elem,
+                               void* position_matrix, uint8_t* position, int64_t* meta, void* stream);
+
+/* nsnp_pileup_window_records with the name of every site taken from ITS text: DNA_CreateCanSnpTensor prints column 0 of the line that
+ * emits a site (make_candidate_snp_tensor/main.cpp:248: the line at centre + 16), not its contig argument.  line_idx: device int32 [M] and
+ * names: device uint8 [..][NSNP_NAME_ENTRY] as nsnp_mpileup_line_names leaves them for the same lines (line_idx NULL: the entry above).
+ * A name that leaves no room for 11 digits (longer than 37 bytes) sets meta[2]. */
+#define NSNP_NAME_ENTRY 44       /* 40 name bytes (zero-padded), then the token's length as int32 */
+int nsnp_pileup_window_records2(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const int64_t* pos, int64_t M, int64_t N,
+                                const uint8_t* chr_seq, int64_t chr_len, const uint8_t* name, int name_len, int elem,
+                                const int32_t* line_idx, const uint8_t* names,
+                                void* position_matrix, uint8_t* position, int64_t* meta, void* stream);
+
+/* Column 0 of every line of a chunk of mpileup text (device uint8 [text_len], whole lines, in the tokeniser's line order; a text the
+ * tokeniser refuses gives nothing usable here either): line_idx[line] = -1 where the first tab-delimited token (split_line: leading tabs
+ * skipped) equals `name` (HOST bytes), else the index of the entry of `names` the token was copied to (entry order means nothing).
+ * meta int64 [4] (device or pinned) = { lines whose token differs, NSNP_TOK_ERANGE when they outnumber cap_names - call again with a
+ * larger table -, 0, 0 }.  Four launches, no workgroup waits for another; scratch in the context: 8 bytes per 4 KB of text. */
+int nsnp_mpileup_line_names(nsnp_ctx* ctx, const uint8_t* text, int64_t text_len, const uint8_t* name, int name_len, int64_t cap_lines,
+                            int32_t* line_idx, uint8_t* names, int64_t cap_names, int64_t* meta, void* stream);
+
+/* The third field of a .pd line - "<depth>-" + the column's alternative alleles as `key ' ' count ' '` in key order, right-trimmed
+ * (tensor_maker.cpp:83-169, main.cpp:220-251, make_predict_data/main.cpp:88; every quirk of it: oracle/pileup_encode_oracle.c) - for the
+ * same N sites, from the chunk's columns as nsnp_mpileup_tokenise leaves them (bases uint8 [n_bytes], col_off int64 [M + 1], ref uint8 [M],
+ * pos int64 [M]) and the encode's depth int32 [M]; chr_seq as above.  Keys: 'I' + base + upper(allele) per distinct insertion (an allele the
+ * column's end cuts short is a key of its own), 'D' + the reference bytes chr_seq[pos, pos + d) per declared deletion length d <= 60,
+ * 'X' + base per mismatching base.  The first key holding a NUL - a deletion reaching past chr_len, a cut insertion - is written up to
+ * that NUL, without a count, and ends the text.  Exact for any column: nothing is bounded by a list or a staged length.
+ *   blob    uint8 [cap]     the texts laid end to end          (any memory the device can write)
+ *   offsets int64 [N + 1]   text n is blob[offsets[n], offsets[n + 1])   (likewise)
+ *   meta    int64 [4]       { bytes needed, status, 0, 0 }: status NSNP_TOK_ERANGE when needed > cap - the blob is then left untouched, the
+ *                           offsets are still right
+ * Four launches, no workgroup waits for another; scratch (8 bytes per site + cap) lives in the context: one call at a time per context. */
+int nsnp_pileup_alt_info(nsnp_ctx* ctx, const uint8_t* bases, int64_t n_bytes, const int64_t* col_off, const uint8_t* ref, const int64_t* pos,
+                         const int32_t* depth, int64_t M, const int64_t* center_idx, int64_t N, const uint8_t* chr_seq, int64_t chr_len,
+                         uint8_t* blob, int64_t cap, int64_t* offsets, int64_t* meta, void* stream);
+
 /* ---- HaplotypeModel ------------------------------------------------------------------- */
 /* seq/bq/mq/hap: device int32 [N,D,L] planes as write_to_bins.py:44-61 stores them (padding
  * rows are -2); ref_row: device int32 [N,L].  out: device fp32 [N,105,L] -- float64 math as

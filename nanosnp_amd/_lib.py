@@ -61,6 +61,12 @@ _SIGNATURES = {
     "nsnp_pileup_select_sites_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                  C.c_void_p]),
     "nsnp_pileup_call_rows": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_window_records": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "nsnp_pileup_window_records2": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "nsnp_mpileup_line_names": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p]),
+    "nsnp_pileup_alt_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_mpileup_tokenise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
     "nsnp_mpileup_tokenise_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 5 + [C.c_void_p] * 9),
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -597,6 +603,98 @@ class Context:
                                              _dptr(zy_max), n, _dptr(rows), _stream_ptr(stream)),
               self.handle, "nsnp_pileup_call_rows")
         return rows
+
+    POSITION_WIDTH = 83       # NSNP_POSITION_WIDTH = sitefile.POSITION_WIDTH
+
+    NAME_ENTRY = 44           # NSNP_NAME_ENTRY
+
+    def mpileup_line_names(self, text, name, cap_lines, cap_names=64, line_idx=None, names=None, meta=None, stream=None):
+        """Column 0 of every line of a device text against `name` (nsnp_mpileup_line_names) -> (line_idx int32 [cap_lines]: -1 where the
+        line's first token is `name`, else its entry in names; names uint8 [cap_names, 44]; meta int64 [4] = {lines that differ, status})"""
+        import torch
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        dev = text.device
+        if line_idx is None:
+            line_idx = torch.empty(max(int(cap_lines), 1), dtype=torch.int32, device=dev)
+        if names is None:
+            names = torch.empty((max(int(cap_names), 1), self.NAME_ENTRY), dtype=torch.uint8, device=dev)
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        assert text.dtype == torch.uint8 and text.is_cuda and line_idx.dtype == torch.int32 and line_idx.is_cuda and names.is_cuda
+        check(self.lib.nsnp_mpileup_line_names(self.handle, _dptr(text), int(text.numel()), name, len(name), int(line_idx.numel()), _dptr(line_idx),
+                                               _dptr(names), int(names.shape[0]), meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_mpileup_line_names")
+        return line_idx, names, meta
+
+    def pileup_window_records(self, counts, center_idx, pos, chr_seq, name, elem=2, position_matrix=None, position=None, meta=None, stream=None,
+                              line_names=None):
+        """The first two arrays of a .pd.bin for the sites center_idx [N] of a chunk (nsnp_pileup_window_records) -> (position_matrix
+        [N,33,18] int16 / int32 for elem 2 / 4, position uint8 [N,83], meta int64 [4] = {N, int16 overflow, status, 0}).  counts int32 [M,18],
+        pos int64 [M], chr_seq uint8: device tensors; name: the contig name (str or bytes).  The three outputs may be given: device or
+        pinned tensors with room for N sites (the first N rows are written); meta is valid once the stream has passed the call."""
+        import torch
+        n, m = int(center_idx.shape[0]), int(counts.shape[0])
+        dev = counts.device
+        assert counts.dtype == torch.int32 and center_idx.dtype == torch.int64 and pos.dtype == torch.int64 and chr_seq.dtype == torch.uint8
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        dt = {2: torch.int16, 4: torch.int32}.get(elem)
+        if dt is None:
+            raise NanoSNPError("elem: 2 (int16) or 4 (int32)")
+        if position_matrix is None:
+            position_matrix = torch.empty((max(n, 1), 33, 18), dtype=dt, device=dev)
+        if position is None:
+            position = torch.empty((max(n, 1), self.POSITION_WIDTH), dtype=torch.uint8, device=dev)
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        for t, what in ((position_matrix, "position_matrix"), (position, "position"), (meta, "meta")):
+            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
+                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
+        if position_matrix.dtype != dt or position_matrix.numel() < n * 594 or position.dtype != torch.uint8 or position.numel() < n * self.POSITION_WIDTH:
+            raise NanoSNPError("window_records: output buffers too small or of the wrong type")
+        line_idx, names = line_names if line_names is not None else (None, None)      # (mpileup_line_names of the same lines: per-site names)
+        if line_idx is not None and (line_idx.dtype != torch.int32 or line_idx.numel() < m or not line_idx.is_cuda or not names.is_cuda):
+            raise NanoSNPError("line_names: device int32 [M] and the name table of mpileup_line_names")
+        check(self.lib.nsnp_pileup_window_records2(self.handle, _dptr(counts), _dptr(center_idx), _dptr(pos), m, n, _dptr(chr_seq), int(chr_seq.numel()),
+                                                   name, len(name), int(elem), _dptr(line_idx), _dptr(names), position_matrix.data_ptr(),
+                                                   position.data_ptr(), meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_window_records2")
+        return position_matrix.view(-1)[:n * 594].view(n, 33, 18), position.view(-1)[:n * self.POSITION_WIDTH].view(n, self.POSITION_WIDTH), meta
+
+    def pileup_alt_info(self, bases, col_off, ref, pos, depth, center_idx, chr_seq, cap=None, blob=None, offsets=None, meta=None, stream=None):
+        """The alt_info texts of the sites center_idx [N] (nsnp_pileup_alt_info) -> (blob uint8 [cap], offsets int64 [N + 1], meta int64 [4] =
+        {bytes needed, status, 0, 0}); text n is blob[offsets[n]:offsets[n + 1]].  status has TOK_ERANGE when needed > cap (the blob is then
+        untouched).  blob / offsets / meta may be given (device or pinned); without a cap the call waits and runs again when the first
+        guess was too small."""
+        import torch
+        n, m = int(center_idx.shape[0]), int(ref.shape[0])
+        dev = ref.device
+        assert bases.dtype == torch.uint8 and col_off.dtype == torch.int64 and ref.dtype == torch.uint8 and pos.dtype == torch.int64
+        assert depth.dtype == torch.int32 and center_idx.dtype == torch.int64 and chr_seq.dtype == torch.uint8
+        if col_off.shape[0] != m + 1 or pos.shape[0] != m or depth.shape[0] != m:
+            raise NanoSNPError("alt_info: col_off [M + 1], pos [M] and depth [M] must match ref [M]")
+        retry = cap is None and blob is None
+        cap = int(blob.numel() if blob is not None else (64 * n + 4096 if cap is None else cap))
+        if blob is None:
+            blob = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        for t, what in ((blob, "blob"), (offsets, "offsets"), (meta, "meta")):
+            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
+                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
+        if blob.numel() < cap or offsets.numel() < n + 1:
+            raise NanoSNPError("alt_info: output buffers too small")
+        check(self.lib.nsnp_pileup_alt_info(self.handle, _dptr(bases), int(bases.numel()), _dptr(col_off), _dptr(ref), _dptr(pos), _dptr(depth), m,
+                                            _dptr(center_idx), n, _dptr(chr_seq), int(chr_seq.numel()), blob.data_ptr(), cap, offsets.data_ptr(),
+                                            meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_alt_info")
+        if retry:
+            (stream or torch.cuda.current_stream(dev)).synchronize()
+            need = int(meta[0])
+            if need > cap:
+                return self.pileup_alt_info(bases, col_off, ref, pos, depth, center_idx, chr_seq, cap=need, offsets=offsets, meta=meta, stream=stream)
+        return blob, offsets[:n + 1], meta
 
     def pileup_gather_windows(self, counts, center_idx, stream=None):
         import torch

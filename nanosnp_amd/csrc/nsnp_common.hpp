@@ -128,7 +128,8 @@ struct nsnp_ctx {
     void*  cat_ws; size_t cat_ws_bytes;
     int64_t* sel_tmp; size_t sel_tmp_bytes;   // select_sites scratch
     int64_t* fil_tmp; size_t fil_tmp_bytes;   // filter_columns scratch: kept columns and bytes per tile (pileup_encode.hip)
-    void* tok_ws; size_t tok_ws_bytes;        // mpileup tokeniser scratch: 20 bytes per 8 KB tile of text (mpileup_tokenise.hip)
+    void* rec_tmp; size_t rec_tmp_bytes;      // nsnp_pileup_alt_info scratch: scanned sizes + the staging blob (pileup_records.hip)
+    void* tok_ws; size_t tok_ws_bytes;        // mpileup tokeniser scratch: 4,112 bytes per 8 KB tile of text (mpileup_tokenise.hip)
     void* ctg_ws; size_t ctg_ws_bytes;        // nsnp_mpileup_tokenise_contigs scratch: 8 bytes per line + 16 per 256 lines (mpileup_tokenise.hip)
     int tok_fused;      // mpileup tokeniser: 0 = three launches (default), 1 = one launch, chained scan (opt-in: its tiles spin on their predecessors)
     // column encode: AF threshold + smallest-passing-count table of the last min_af (pileup_encode.hip)

@@ -269,6 +269,15 @@ def _count_slots(model, attr, n):
 
 
 _ChunkSets = namedtuple("_ChunkSets", "ranges cap hsets tsets csets copy_stream main fresh")
+# what the record kernels of a chunk read beside its counts and centres (device tensors; seq: the contig's sequence)
+_ChunkColumns = namedtuple("_ChunkColumns", "bases off ref pos depth seq names")
+
+
+class _NamesOverflow(Exception):
+    """more lines of a chunk carry another token than the contig's name in column 0 than the name table holds (contig_to_bin runs again)"""
+    def __init__(self, need):
+        super().__init__(need)
+        self.need = int(need)
 
 
 def _text_chunk_sets(model, finder, lo, hi, chunk_bytes, dev):
@@ -460,7 +469,8 @@ def _run_text_chunks(sets, arr, st, tokenise, encode, calls):
     return finalize
 
 
-def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, defer=False, beds=None):
+def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af, min_coverage, stats, on_rows, defer=False, beds=None,
+                       indel_min_af=None, records=None, name_cap=1024):
     """stream_contig with the text cut into columns ON THE DEVICE (nsnp_mpileup_tokenise).  The host touches every byte of the text once - a
     multi-threaded copy of the chunk (whole lines, 16 lines of halo either side, found by a few find / rfind calls) from the page cache
     into pinned memory - and the chunks are worked off four things at a time by _run_text_chunks, over the buffer sets of _text_chunk_sets;
@@ -474,7 +484,9 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
     of the encode - the images of the chunk's own range stay on the device, the selection reads them there - and with a confident bitmap
     the encode is nsnp_pileup_encode_columns3.  The result does not depend on the cuts for texts with ASCENDING positions: 33 kept lines
     with consecutive positions are then 33 consecutive lines of the text, inside the 16-line halo; in a text whose positions repeat or step
-    back they may lie further apart (the whole-array calls stay exact for any position sequence)."""
+    back they may lie further apart (the whole-array calls stay exact for any position sequence).
+    records (contig_to_bin; None: nothing below changes): the third station issues no forward - records(chunk's arrays) is called for every
+    chunk that owns sites and issues what it wants of them instead; no rows come back.  indel_min_af (None: min_af) goes to the encode."""
     import time
     import torch
     ctx = model.ctx
@@ -506,8 +518,15 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
             fmeta = torch.zeros((len(ranges), 4), dtype=torch.int64, device=dev)
     rows_all = []
 
+    # records: column 0 of every line against the contig's name, while the chunk's text is still on the device (the reference prints the
+    # emitting line's token into the position string: nsnp_mpileup_line_names)
+    names_pin = _count_slots(model, "_names_meta_pin", len(ranges)) if records is not None else None
+    names_of = {}
+
     def tokenise(k, text_k, cs):
         ctx.mpileup_tokenise_into(text_k, d_seq, cs.pos, cs.off, cs.bases, cs.ref, tok_pin[k], stream=main)
+        if records is not None:
+            names_of[k] = ctx.mpileup_line_names(text_k, contig, int(text_k.numel()) // 10 + 2, name_cap, meta=names_pin[k], stream=main)[:2]
 
     def encode(k, cs, n_lo, n_hi):
         M, nb, status, _ = tok_pin[k].tolist()
@@ -521,6 +540,16 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
             raise host.HostError(f"{contig}: tokeniser status {status}")
         own = M - n_lo - n_hi
         st["columns"] += own
+        names = None
+        if records is not None:
+            names = names_of.pop(k)
+            n_other, n_status, _, _ = names_pin[k].tolist()
+            if n_status:
+                raise _NamesOverflow(n_other)
+            if n_other == 0:
+                names = None                                 # (every line names the contig: the records carry the one name)
+            elif ext_bits is not None:
+                raise NotImplementedError(f"{contig}: lines with another name in column 0 under an extended BED (the filter does not carry them along)")
         if own <= 0:
             return None
         d_pos, d_off, d_bases, d_ref = cs.pos[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
@@ -531,18 +560,25 @@ def _stream_contig_dev(model, text, contig, chr_seq, lo, hi, chunk_bytes, min_af
                                                                         meta=fmeta[k], out=fsets[k % len(fsets)].out, stream=main)
         if conf_bits is not None:
             counts, depth, flags, _ = ctx.pileup_encode_columns3(d_bases, d_off, d_ref, d_pos, conf_bits, n_seq, min_af, min_coverage,
-                                                                 want_max_del=False)
+                                                                 want_max_del=False, indel_min_af=indel_min_af)
         else:
-            counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
+            counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage, indel_min_af=indel_min_af)
         # selection + the run of the chunk's own sites in the list, written into pinned memory by the last of its four launches
         if ext_bits is not None:
             center = ctx.pileup_select_sites_range_dev(d_pos, flags, fmeta[k][2:], meta_pin[k], stream=main)
         else:
             center = ctx.pileup_select_sites_range(d_pos, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
+        if records is not None:
+            return d_pos, counts, center, _ChunkColumns(d_bases, d_off, d_ref, d_pos, depth, d_seq, names)
         return d_pos, counts, center
 
     def calls(k, job):
         if job is None:
+            return
+        if records is not None:
+            _, c_lo, c_hi, _ = meta_pin[k].tolist()
+            if c_hi > c_lo:
+                records(k, job[1], job[2][c_lo:c_hi], job[3], main)
             return
         d_pos, counts, center = job
         _, c_lo, c_hi, _ = meta_pin[k].tolist()
@@ -1668,3 +1704,217 @@ def call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file
                 pass
         if g is not None:
             g.close()
+
+
+# ---- <chr>.mpileup text -> <chr>.pd.bin: stage s1 alone (make_predict_data.sh:167-234) ------------------------------------------------
+class _RecSlot:
+    """pinned result buffers of one chunk's records in flight: written by the record kernels, read by the writer thread"""
+    def __init__(self, rows, blob_bytes):
+        import torch
+        from ._lib import Context
+        self.rows = int(rows)
+        self.matrix = torch.empty(self.rows * 594 * 4, dtype=torch.uint8, pin_memory=True)          # (room for int32: a restart keeps the slot)
+        self.position = torch.empty((self.rows, Context.POSITION_WIDTH), dtype=torch.uint8, pin_memory=True)
+        self.blob = torch.empty(int(blob_bytes), dtype=torch.uint8, pin_memory=True)
+        self.offsets = torch.empty(self.rows + 1, dtype=torch.int64, pin_memory=True)
+        self.meta = torch.zeros((2, 4), dtype=torch.int64, pin_memory=True)                         # window_records' and alt_info's
+        self.busy = None                                                                           # the writer thread's future over this slot
+
+    def matrix_as(self, elem):
+        import torch
+        return self.matrix.view(torch.int16 if elem == 2 else torch.int32)[:self.rows * 594]
+
+
+def _bins_refusals():
+    """what the stage-1 entries do not do, said before anything is touched"""
+    import torch
+    import torch.distributed as tdist
+    from ._lib import NanoSNPError
+    if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+        raise NotImplementedError("contig_to_bin / make_pileup_bins under a process group of more than one rank (window files are not sharded)")
+    if tokenise_mode() == "host":
+        raise NotImplementedError("contig_to_bin / make_pileup_bins with NSNP_TOKENISE=host (the records are built from the device tokeniser's columns)")
+    if not torch.cuda.is_available():
+        raise NanoSNPError("no GPU visible: nanosnp_amd has no CPU fallback")
+
+
+def contig_to_bin(model, mpileup_text, contig, chr_seq, path, *, alt_info=True, matrix_dtype="int16", min_af=0.12, indel_min_af=None,
+                  min_coverage=6, chunk_bytes=64 << 20, stats=None, extended_bed=None, confident_bed=None, fai=None):
+    """Stage s1 alone: one contig's samtools-mpileup text -> its <chr>.pd.bin (sitefile: position_matrix, position, alt_info,
+    alt_info_offsets), the file DNA_CreateCanSnpTensor -> DNA_CreatePredictData -> make_bin_predict_data.py leave behind
+    (make_predict_data.sh:167-234), byte for byte what sitefile.pd_to_bin makes of the reference's .pd.  Returns the number of sites.
+
+    model: only the holder of the context and the buffer sets - pileup_model.LSTMNetwork() without weights will do.  The text runs through
+    the chunk loop of call_contig (tokenise k, BED filter + encode + select k - 1); where that loop runs the forward, this one issues
+    nsnp_pileup_window_records and nsnp_pileup_alt_info for the chunk's own sites into one of three pinned slots, and a writer thread
+    appends the slot to a sitefile.PileupBinWriter when its event has passed.  A slot with too few rows is replaced before the launch
+    (the site count is on the host by then); a chunk whose alt_info text outgrows its slot, or a count outside int16, starts the contig
+    over with larger slots / as int32 - nothing is ever cut.  min_af / indel_min_af / min_coverage, extended_bed / confident_bed / fai: as
+    for call_contig; text the reference's reader aborts on raises the same errors.  On any error neither `path` nor `path + ".tmp"` is
+    left by this call (a file that was at `path` before stays as it was).
+    matrix_dtype: as for sitefile.write_pileup_bin; alt_info=False leaves the two alt_info arrays out.
+    The name in a position string is column 0 of the line that emits the site (the line at centre + 16), as the reference prints it:
+    `contig` in any text samtools or the splitter wrote; a line with another token there has that token (nsnp_mpileup_line_names).  Not
+    together with an extended BED (NotImplementedError when such a line is met), and a token longer than 37 bytes is refused.
+    NOT done here: one whole-genome text (call_mpileup-style keys), sharding over a process group, a .pd TEXT writer, the reference's
+    .tensor / .alt_info side files."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from . import sitefile
+    _bins_refusals()
+    name = contig.encode() if isinstance(contig, str) else bytes(contig)
+    if not name or b"\0" in name or len(name) + 1 + 11 + 1 + 33 > sitefile.POSITION_WIDTH:
+        raise ValueError(f"{contig!r}: a contig name of 1 to {sitefile.POSITION_WIDTH - 46} bytes without NUL is needed for the "
+                         f"{sitefile.POSITION_WIDTH}-byte position field")
+    if matrix_dtype not in ("int16", "int32"):
+        raise sitefile.SiteFileError("matrix_dtype: 'int16' or 'int32'")
+    ctx = model.ctx
+    beds = _contig_beds(extended_bed, confident_bed, contig, chr_seq, fai)
+    st = _stream_stats(stats)
+    state = dict(elem=2 if matrix_dtype == "int16" else 4, blob_min=0)
+    writer = sitefile.PileupBinWriter(path, matrix_dtype, alt_info)
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        try:
+            while True:
+                again = _contig_records_pass(model, ctx, mpileup_text, name, contig, chr_seq, chunk_bytes, min_af, indel_min_af, min_coverage, st, beds,
+                                             alt_info, state, writer, pool)
+                if not again:
+                    break
+                st["restarts"] = st.get("restarts", 0) + 1
+                writer.restart("int16" if state["elem"] == 2 else "int32")
+            n = writer.close()
+        except BaseException:
+            writer.abort()
+            raise
+    st["sites"] = st.get("sites", 0) + n
+    return n
+
+
+def _contig_records_pass(model, ctx, text, name, contig, chr_seq, chunk_bytes, min_af, indel_min_af, min_coverage, st, beds, alt_info, state, writer, pool):
+    """one pass of contig_to_bin over the text -> True when it has to be run again (state says how: elem 4, or blob_min bytes per slot)"""
+    import torch
+    from ._lib import NanoSNPError
+    elem = state["elem"]
+    text_len = int(_as_bytes_like(text)[1].size)
+    slots = getattr(model, "_rec_slots", None)
+    if slots is None:
+        slots = model._rec_slots = [None, None, None]
+    flag = dict(overflow=False, alt_need=0, status=0)
+    turn, spans = [0], []
+
+    def write_piece(slot, n, done):
+        done.synchronize()
+        m = slot.meta.numpy()
+        if m[0, 1]:
+            flag["overflow"] = True
+        if m[0, 2]:
+            flag["status"] = int(m[0, 2])
+        if alt_info and (m[1, 1] & ctx.TOK_ERANGE):
+            flag["alt_need"] = max(flag["alt_need"], int(m[1, 0]))
+        if flag["overflow"] or flag["alt_need"] or flag["status"]:
+            return                                           # (the pass is run again, or refused: nothing more is appended)
+        x = slot.matrix.numpy().view(np.int16 if elem == 2 else np.int32)[:n * 594].reshape(n, 33, 18)
+        if alt_info:
+            writer.append(x, slot.position.numpy()[:n], slot.blob.numpy()[:int(m[1, 0])], slot.offsets.numpy()[:n + 1])
+        else:
+            writer.append(x, slot.position.numpy()[:n])
+        st["record_bytes"] = st.get("record_bytes", 0) + n * (594 * elem + 83) + (int(m[1, 0]) + 8 * n if alt_info else 0)
+
+    def records(k, counts, centers, cols, main):
+        if flag["overflow"] or flag["alt_need"] or flag["status"]:
+            return                                           # (this pass is lost: the rest of it only has to end)
+        n = int(centers.shape[0])
+        i = turn[0] % 3
+        turn[0] += 1
+        slot = slots[i]
+        if slot is not None and slot.busy is not None:
+            slot.busy.result()                               # the writer is done with the slot's previous chunk (three chunks back)
+            slot.busy = None
+        want_blob = max(64 * n + (1 << 16), state["blob_min"])
+        if slot is None or slot.rows < n or slot.blob.numel() < want_blob:
+            # (a 30x chunk selects 3-4 % of its columns and budgets one column per 24 bytes: 1 / 64 of them is about as many rows as it fills)
+            rows = max(n + n // 4, _cols_for(min(int(chunk_bytes), text_len)) // 64, 1024 if slot is None else slot.rows)
+            slot = slots[i] = _RecSlot(rows, max(64 * rows + (1 << 16), state["blob_min"]))
+        timed = st.get("time_records")                       # (stats["time_records"] = True: HIP-event time of the record kernels -> stats["window_records_s"], ["alt_info_s"])
+        if timed:
+            t0, t1, t2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            t0.record(main)
+        ctx.pileup_window_records(counts, centers, cols.pos, cols.seq, name, elem, position_matrix=slot.matrix_as(elem), position=slot.position,
+                                  meta=slot.meta[0], stream=main, line_names=cols.names)
+        if timed:
+            t1.record(main)
+        if alt_info:
+            ctx.pileup_alt_info(cols.bases, cols.off, cols.ref, cols.pos, cols.depth, centers, cols.seq, blob=slot.blob, offsets=slot.offsets,
+                                meta=slot.meta[1], stream=main)
+        if timed:
+            t2.record(main)
+            spans.append((t0, t1, t2))
+        done = torch.cuda.Event(); done.record(main)
+        slot.busy = pool.submit(write_piece, slot, n, done)
+
+    def drain(swallow):
+        for slot in slots:
+            if slot is not None and slot.busy is not None:
+                busy, slot.busy = slot.busy, None
+                try:
+                    busy.result()
+                except BaseException:
+                    if not swallow:
+                        raise
+
+    try:
+        with host.gc_paused():
+            _stream_contig_dev(model, text, contig, chr_seq, 0, None, chunk_bytes, min_af, min_coverage, st, None, beds=beds,
+                               indel_min_af=indel_min_af, records=records, name_cap=state.get("name_cap", 1024))
+        drain(False)
+        for t0, t1, t2 in spans:
+            st["window_records_s"] = st.get("window_records_s", 0.0) + t0.elapsed_time(t1) * 1e-3
+            st["alt_info_s"] = st.get("alt_info_s", 0.0) + t1.elapsed_time(t2) * 1e-3
+            st["record_chunks"] = st.get("record_chunks", 0) + 1
+    except _NamesOverflow as e:
+        drain(True)
+        state["name_cap"] = 2 * e.need + 64
+        return True
+    except BaseException:
+        drain(True)                                          # (the streams have been waited for: the writer's pieces end at once)
+        raise
+    if flag["status"]:
+        raise NanoSNPError(f"{contig}: a selected site outside the columns or the contig (record status {flag['status']})")
+    if flag["overflow"]:
+        if elem == 4:
+            raise NanoSNPError(f"{contig}: int16 overflow reported for int32 records")
+        state["elem"] = 4
+        return True
+    if flag["alt_need"]:
+        state["blob_min"] = 2 * flag["alt_need"]
+        return True
+    return False
+
+
+def make_pileup_bins(model, contigs, fasta_path, fai_text, out_dir, **kw):
+    """The s1 drop-in beside call_variants.  contigs: iterable of (name, path to <name>.mpileup), as call_variants takes them; writes
+    <out_dir>/<name>.pd.bin per contig (contig_to_bin: its keyword arguments pass through; extended_bed= / confident_bed= are checked
+    against fai_text) -> {name: sites}.  The files are what predict_pileup_bins reads."""
+    _bins_refusals()
+    if kw.get("extended_bed") is not None or kw.get("confident_bed") is not None:
+        kw.setdefault("fai", fai_text)
+        if not all(b is None or isinstance(b, dict) for b in (kw.get("extended_bed"), kw.get("confident_bed"))):
+            from . import bed as _bed                          # (a BED path: parsed once, against the whole index)
+            kw["extended_bed"], kw["confident_bed"] = (b if b is None or isinstance(b, dict) else _bed.load_bed(b, kw["fai"])
+                                                       for b in (kw.get("extended_bed"), kw.get("confident_bed")))
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    for name, path in contigs:
+        seq = host.fasta_load_contig(fasta_path, name)
+        with open(path, "rb") as g:
+            size = os.fstat(g.fileno()).st_size
+            text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if size else b""
+            try:
+                out[name] = contig_to_bin(model, text, name, seq, os.path.join(out_dir, f"{name}.pd.bin"), **kw)
+            finally:
+                if size:
+                    try:
+                        text.close()
+                    except BufferError:                      # (an exception on its way up still holds views of the mapping)
+                        pass
+    return out

@@ -159,6 +159,148 @@ def write_pileup_bin(path, position_matrix, position, alt_info=None, matrix_dtyp
     write_arrays(path, arrays)
 
 
+class PileupBinWriter:
+    """A <chr>.pd.bin written piece by piece, for a producer that does not know the site count in advance (pipeline.contig_to_bin appends
+    every chunk's sites as they come back from the device).  close() leaves a file byte-identical to write_pileup_bin of the same rows in
+    one call: same arrays in the same order, same dtypes, 64-byte alignment and header.
+
+    position_matrix is the first array, so its offset follows from the NUMBER of arrays alone: its rows stream into their final place and
+    are never held whole in memory.  The small arrays (83 bytes of position string and the alt_info text per site) are held back and
+    written behind the matrix at close(), the header last.  Everything goes to path + ".tmp", renamed into place by close(); abort()
+    leaves neither file.  matrix_dtype "int16" takes rows of any integer type whose values fit (SiteFileError otherwise: restart("int32")
+    starts the file over, and the producer appends its rows again)."""
+
+    def __init__(self, path, matrix_dtype="int16", alt_info=True):
+        if matrix_dtype not in ("int16", "int32"):
+            raise SiteFileError("matrix_dtype: 'int16' or 'int32'")
+        self.path, self.tmp = path, path + ".tmp"
+        self.alt_info = bool(alt_info)
+        self._f = None
+        self._start(matrix_dtype)
+
+    def _start(self, matrix_dtype):
+        import os
+        self.matrix_dtype = np.dtype(matrix_dtype)
+        self.n = 0
+        self._positions, self._blobs, self._lens = [], [], []
+        n_arrays = 4 if self.alt_info else 2
+        self._x_off = (len(MAGIC) + 8 + _REC.size * n_arrays + 63) & ~63
+        if self._f is None:
+            self._f = open(self.tmp, "wb")
+        self._f.seek(0)
+        self._f.truncate(0)
+        self._f.seek(self._x_off)
+
+    def restart(self, matrix_dtype="int32"):
+        """drops everything appended so far and starts the file over with another matrix type"""
+        if matrix_dtype not in ("int16", "int32"):
+            raise SiteFileError("matrix_dtype: 'int16' or 'int32'")
+        if self._f is None:
+            raise SiteFileError("restart() of a writer that was closed or aborted")
+        self._start(matrix_dtype)
+
+    def append(self, position_matrix_rows, position_rows, alt_blob=None, alt_offsets=None):
+        """position_matrix_rows: integer [n,33,18]; position_rows: uint8 [n, POSITION_WIDTH] (zero-padded) or n strings; alt_blob uint8 +
+        alt_offsets int64 [n + 1]: text i of this piece is alt_blob[alt_offsets[i]:alt_offsets[i + 1]] (any base offset)."""
+        if self._f is None:
+            raise SiteFileError("append() to a writer that was closed or aborted")
+        x = np.asarray(position_matrix_rows)
+        n = x.shape[0]
+        if x.dtype.kind not in "iu" or x.shape[1:] != (33, 18):
+            raise SiteFileError("position_matrix rows must be integers [n,33,18]")
+        if isinstance(position_rows, np.ndarray) and position_rows.dtype == np.uint8:
+            pos = position_rows
+            if pos.shape != (n, POSITION_WIDTH):
+                raise SiteFileError(f"position rows must be uint8 [n,{POSITION_WIDTH}] with one row per site")
+        else:
+            if len(position_rows) != n:
+                raise SiteFileError("one position string per row")
+            pos = np.zeros((n, POSITION_WIDTH), np.uint8)
+            for i, p in enumerate(position_rows):
+                b = p.encode() if isinstance(p, str) else bytes(p)
+                if len(b) > POSITION_WIDTH:
+                    raise SiteFileError(f"position string longer than {POSITION_WIDTH} bytes: {b[:40]!r}...")
+                pos[i, :len(b)] = np.frombuffer(b, np.uint8)
+        if self.alt_info:
+            if alt_blob is None or alt_offsets is None:
+                raise SiteFileError("this writer holds alt_info: every piece needs alt_blob and alt_offsets")
+            offs = np.asarray(alt_offsets, np.int64)
+            if offs.shape != (n + 1,) or (n and (np.diff(offs) < 0).any()) or (n and int(offs[-1]) > len(alt_blob)) or int(offs[0]) < 0:
+                raise SiteFileError("alt_offsets must be n + 1 ascending offsets into alt_blob")
+        if n == 0:
+            return
+        if x.dtype != self.matrix_dtype:
+            if self.matrix_dtype == np.int16 and (x.dtype.itemsize > 2 or x.dtype == np.uint16) and (int(x.min()) < -32768 or int(x.max()) > 32767):
+                raise SiteFileError("a count outside int16: restart('int32') and append the rows again")
+            x = x.astype(self.matrix_dtype)
+        self._f.write(memoryview(np.ascontiguousarray(x)).cast("B"))
+        self._positions.append(np.array(pos, np.uint8, copy=True))
+        if self.alt_info:
+            self._blobs.append(np.array(np.asarray(alt_blob, np.uint8)[int(offs[0]):int(offs[-1])], copy=True))
+            self._lens.append(np.diff(offs))
+        self.n += n
+
+    def close(self):
+        """writes the held-back arrays and the header, renames the file into place -> the number of sites"""
+        import os
+        if self._f is None:
+            raise SiteFileError("close() of a writer that was closed or aborted")
+        f, n = self._f, self.n
+        small = [("position", np.concatenate(self._positions) if self._positions else np.zeros((0, POSITION_WIDTH), np.uint8))]
+        if self.alt_info:
+            offs = np.zeros(n + 1, np.int64)
+            if self._lens:
+                np.cumsum(np.concatenate(self._lens), out=offs[1:])
+            small.append(("alt_info", np.concatenate(self._blobs) if self._blobs else np.empty(0, np.uint8)))
+            small.append(("alt_info_offsets", offs))
+        recs = [_REC.pack(b"position_matrix", self.matrix_dtype.str.encode(), 3, 0, n, 33, 18, 0, self._x_off, n * 594 * self.matrix_dtype.itemsize)]
+        try:
+            off = self._x_off + n * 594 * self.matrix_dtype.itemsize
+            if f.tell() != off:
+                raise SiteFileError("internal: matrix bytes written do not match the site count")
+            for name, a in small:
+                o = (off + 63) & ~63
+                f.write(b"\0" * (o - off))
+                f.write(a.tobytes())
+                recs.append(_REC.pack(name.encode(), a.dtype.str.encode(), a.ndim, 0, *(list(a.shape) + [0] * (4 - a.ndim)), o, a.nbytes))
+                off = o + a.nbytes
+            f.truncate(off)                                # (empty arrays at the end still count their padding, as write_arrays writes it)
+            f.seek(0)
+            f.write(MAGIC + struct.pack("<II", len(recs), 0))
+            for r in recs:
+                f.write(r)
+            f.close()
+            self._f = None
+            os.replace(self.tmp, self.path)
+        except BaseException:
+            self.abort()
+            raise
+        return n
+
+    def abort(self):
+        """drops the file being written: path + '.tmp' is removed and path was never created (idempotent)"""
+        import os
+        if self._f is not None:
+            try:
+                self._f.close()
+            finally:
+                self._f = None
+        try:
+            os.remove(self.tmp)
+        except FileNotFoundError:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, et, ev, tb):
+        if et is not None:
+            self.abort()
+        elif self._f is not None:
+            self.close()
+        return False
+
+
 def read_pileup_bin(path, mmap=True):
     """-> (contig_names list[str], positions int64[N], reference_bases uint8[N], position_matrix int32[N,33,18]):
     what ``PileupModel/dataset.py:118-139`` extracts (``reference_bases = ord(seq[16])``)."""

@@ -1,0 +1,499 @@
+"""Stage s1 alone on the device (pipeline.contig_to_bin / make_pileup_bins, nsnp_pileup_window_records, nsnp_pileup_alt_info): the
+<chr>.pd.bin written from mpileup text against the .pd files the reference's compiled programs wrote (tests/golden), the two kernels
+alone against numpy and the oracle, the round trip through predict_pileup_bins against call_variants, and what errors leave behind.
+Every comparison is exact."""
+import gzip
+import importlib.util
+import lzma
+import os
+
+import numpy as np
+import pytest
+
+from nanosnp_amd import _lib, host, sitefile
+from tests.helpers import golden
+
+pytestmark = pytest.mark.gpu
+
+TAGS = ["g1", "adv", "end", "cut", "pos", "rdr"]
+
+
+def _model():
+    from nanosnp_amd.pileup_model import LSTMNetwork
+    return LSTMNetwork()                                     # no weights: the stage-1 path needs only the context and the buffer sets
+
+
+@pytest.fixture(scope="module")
+def model():
+    return _model()
+
+
+def _fixture(tag):
+    text = gzip.open(golden(f"encode_{tag}.mpileup.gz")).read()
+    fa = gzip.open(golden(f"encode_{tag}.fa.gz")).read()
+    pd = gzip.open(golden(f"encode_{tag}.pd.gz")).read()
+    seq = np.frombuffer(b"".join(fa.split(b"\n")[1:]), np.uint8)
+    contig = pd.split(b"\n")[0].split(b"\t")[1].split(b":")[0].decode()          # the .pd's own position field names the contig
+    return text, seq, pd, contig
+
+
+def _n_chunks(text, chunk_bytes):
+    from nanosnp_amd.pipeline import ramp_cuts
+    return len(ramp_cuts(text, 0, len(text), chunk_bytes)) - 1
+
+
+# ---- 1. the reference's fixtures, whole file ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("chunks", ["one", "many"])
+@pytest.mark.parametrize("tag", TAGS)
+def test_reference_fixture_whole_file(tmp_path, model, tag, chunks):
+    """The whole file against sitefile.pd_to_bin of the .pd the reference's compiled programs wrote.  `rdr` carries `some_other_name` in
+    column 0 of 96 of its 5,000 lines, and 12 of its 526 sites are emitted by such a line: DNA_CreateCanSnpTensor prints column 0 of the
+    LINE THAT EMITS a site (make_candidate_snp_tensor/main.cpp:248, the line at centre + 16), not its contig argument."""
+    from nanosnp_amd.pipeline import contig_to_bin
+    text, seq, pd, contig = _fixture(tag)
+    want = tmp_path / "want.pd.bin"
+    n_want = sitefile.pd_to_bin(pd, want)
+    assert n_want == pd.count(b"\n") and n_want > (50 if tag in ("g1", "adv", "end") else 0)
+    chunk_bytes = 64 << 20 if chunks == "one" else max(4096, len(text) // 9)
+    assert _n_chunks(text, chunk_bytes) == 1 if chunks == "one" else _n_chunks(text, chunk_bytes) >= 4
+    got = tmp_path / "got.pd.bin"
+    st = {}
+    assert contig_to_bin(model, text, contig, seq, str(got), chunk_bytes=chunk_bytes, stats=st) == n_want
+    assert not os.path.exists(str(got) + ".tmp") and st["sites"] == n_want and st.get("restarts", 0) == 0
+    assert st["chunks"] == _n_chunks(text, chunk_bytes)
+    a, b = sitefile.read_arrays(got), sitefile.read_arrays(want)
+    assert list(a) == list(b)
+    for k in ("position_matrix", "alt_info", "alt_info_offsets"):
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+    rows = np.flatnonzero((np.asarray(a["position"]) != np.asarray(b["position"])).any(1))
+    print(f"{tag}/{chunks}: {n_want} sites, {rows.size} position rows differ" + (f", first {rows[0]}: {bytes(a['position'][rows[0]])[:24]!r} against "
+                                                                              f"{bytes(b['position'][rows[0]])[:24]!r}" if rows.size else ""))
+    assert got.read_bytes() == want.read_bytes()
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_reference_fixture_without_alt_info(tmp_path, model, tag):
+    from nanosnp_amd.pipeline import contig_to_bin
+    text, seq, pd, contig = _fixture(tag)
+    x, names, pos, refb = host.pd_parse(pd)
+    position = [l.split(b"\t")[1].strip() for l in pd.split(b"\n") if l.strip()]
+    sitefile.write_pileup_bin(tmp_path / "want.bin", x, position, alt_info=None)
+    assert contig_to_bin(model, text, contig, seq, str(tmp_path / "got.bin"), alt_info=False) == x.shape[0]
+    assert (tmp_path / "got.bin").read_bytes() == (tmp_path / "want.bin").read_bytes()
+    assert list(sitefile.read_arrays(tmp_path / "got.bin")) == ["position_matrix", "position"]
+    # the reference's Int32Atom on request
+    sitefile.write_pileup_bin(tmp_path / "want32.bin", x, position, alt_info=None, matrix_dtype="int32")
+    assert contig_to_bin(model, text, contig, seq, str(tmp_path / "got32.bin"), alt_info=False, matrix_dtype="int32") == x.shape[0]
+    assert (tmp_path / "got32.bin").read_bytes() == (tmp_path / "want32.bin").read_bytes()
+
+
+def test_names_come_from_the_text_not_from_the_argument(tmp_path, model):
+    """the rdr text under a contig name none of its lines carries: every site's name is still column 0 of its emitting line, so the file
+    is the reference's; 5,000 lines outnumber the name table of a chunk (1,024 entries), so the contig is run once more"""
+    from nanosnp_amd.pipeline import contig_to_bin
+    text, seq, pd, contig = _fixture("rdr")
+    n = sitefile.pd_to_bin(pd, tmp_path / "want.bin")
+    st = {}
+    assert contig_to_bin(model, text, "another", seq, str(tmp_path / "got.bin"), stats=st) == n
+    assert (tmp_path / "got.bin").read_bytes() == (tmp_path / "want.bin").read_bytes() and st["restarts"] == 1
+    # a token too long for the 83-byte field is refused, and so is another name under an extended BED
+    long_text = text.replace(b"some_other_name", b"some_other_name_" + b"x" * 30)
+    with pytest.raises(_lib.NanoSNPError):
+        contig_to_bin(model, long_text, contig, seq, str(tmp_path / "no.bin"))
+    with pytest.raises(NotImplementedError):
+        contig_to_bin(model, text, contig, seq, str(tmp_path / "no.bin"), extended_bed={contig: np.array([[0, seq.size]])})
+    assert not os.path.exists(tmp_path / "no.bin") and not os.path.exists(str(tmp_path / "no.bin") + ".tmp")
+
+
+def test_line_names_against_python(gpu_ctx):
+    """nsnp_mpileup_line_names: the first tab-delimited token of every line (leading tabs skipped) against the name - over many tiles,
+    names that are a prefix of / prefixed by the name, a last line without newline, a table that is too small"""
+    import torch
+    rng = np.random.default_rng(5)
+    tokens = [b"chrR", b"chrR", b"chrR", b"chr", b"chrRx", b"some_other_name", b"c" * 45, b"X"]
+    lines = []
+    for i in range(3000):
+        t = tokens[0] if rng.random() < 0.8 else tokens[int(rng.integers(0, len(tokens)))]
+        lead = b"\t" * int(rng.integers(0, 3)) if rng.random() < 0.1 else b""
+        lines.append(lead + t + b"\t%d\tN\t3\t%s\tIII" % (i + 1, bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), int(rng.integers(1, 200))))) + (b"\r" if i % 9 == 0 else b""))
+    for text in (b"\n".join(lines), b"\n".join(lines) + b"\n", b"\n".join(lines[:1]), b"\t\tchr\t1\tN\t1\tA\tI\n" * 3):
+        toks = [l.lstrip(b"\t").split(b"\t")[0] for l in text.split(b"\n") if l]
+        d = torch.from_numpy(np.frombuffer(text, np.uint8).copy()).cuda()
+        idx, names, meta = gpu_ctx.mpileup_line_names(d, "chrR", len(toks) + 5, 4096)
+        torch.cuda.synchronize()
+        idx, names = idx.cpu().numpy()[:len(toks)], names.cpu().numpy()
+        differ = [i for i, t in enumerate(toks) if t != b"chrR"]
+        assert meta.tolist() == [len(differ), 0, 0, 0]
+        assert np.array_equal(np.flatnonzero(idx >= 0), np.array(differ, np.int64))
+        assert sorted(idx[differ].tolist()) == list(range(len(differ)))                  # every entry handed out once
+        for i in differ:
+            e = names[idx[i]]
+            assert int(e[40:44].view(np.int32)[0]) == len(toks[i]) and bytes(e[:40]).rstrip(b"\0") == toks[i][:40]
+    idx, names, meta = gpu_ctx.mpileup_line_names(d, "chrR", 8, 2)
+    torch.cuda.synchronize()
+    assert meta.tolist() == [3, gpu_ctx.TOK_ERANGE, 0, 0]
+
+
+# ---- 2. thresholds apart and cut alleles: the seeded contigs behind refbin_pd.npz ---------------------------------------------------
+def _make_golden():
+    spec = importlib.util.spec_from_file_location("make_golden", golden("make_golden.py"))
+    mg = importlib.util.module_from_spec(spec); spec.loader.exec_module(mg)
+    return mg
+
+
+def _refbin(mg, key, contig, seq, text):
+    z = np.load(golden("refbin_pd.npz"))
+    assert str(z[key + "__input_sha256"]) == mg.refbin_input_digest(contig, seq, text), f"{key}: the seeded inputs differ from refbin_pd.npz's"
+    return lzma.decompress(z[key].tobytes())
+
+
+def test_seeded_fresh_contig(tmp_path, model):
+    from nanosnp_amd.pipeline import contig_to_bin
+    mg = _make_golden()
+    contig, seq, text = mg.refbin_fresh_contig()
+    pd = _refbin(mg, "fresh", contig, seq, text)
+    n = sitefile.pd_to_bin(pd, tmp_path / "want.bin")
+    assert n > 500
+    for chunk_bytes in (64 << 20, max(4096, len(text) // 7)):
+        assert contig_to_bin(model, bytes(text), contig, np.frombuffer(bytes(seq), np.uint8), str(tmp_path / "got.bin"), chunk_bytes=chunk_bytes) == n
+        assert (tmp_path / "got.bin").read_bytes() == (tmp_path / "want.bin").read_bytes()
+
+
+@pytest.mark.parametrize("seed", [31, 32])
+def test_seeded_cut_alleles_under_three_threshold_sets(tmp_path, model, seed):
+    from nanosnp_amd.pipeline import contig_to_bin
+    mg = _make_golden()
+    contig, seq, text = mg.refbin_cut_contig(seed)
+    seq_a = np.frombuffer(bytes(seq), np.uint8)
+    for snp, ind, mc in mg.REFBIN_CUT_THRESHOLDS:
+        pd = _refbin(mg, f"cut{seed}_{snp}_{ind}_{mc}", contig, seq, text)
+        n = sitefile.pd_to_bin(pd, tmp_path / "want.bin")
+        assert n > 1000
+        got = contig_to_bin(model, bytes(text), contig, seq_a, str(tmp_path / "got.bin"), min_af=float(snp), indel_min_af=float(ind), min_coverage=mc,
+                            chunk_bytes=max(4096, len(text) // 5))
+        assert got == n, (snp, ind, mc)
+        assert (tmp_path / "got.bin").read_bytes() == (tmp_path / "want.bin").read_bytes(), (snp, ind, mc)
+
+
+# ---- 3. nsnp_pileup_window_records alone against numpy ------------------------------------------------------------------------------
+def _np_records(counts, centers, pos, seq, name, elem):
+    n, m = centers.size, counts.shape[0]
+    c = np.clip(centers, 16, m - 17)
+    x = counts[c[:, None] + np.arange(-16, 17)[None, :]] if n else np.empty((0, 33, 18), np.int32)
+    out = np.zeros((n, 83), np.uint8)
+    up = seq.copy()
+    low = (up >= ord("a")) & (up <= ord("z"))
+    up[low] -= 32
+    for i in range(n):
+        p = int(pos[c[i]])
+        q = min(max(p, 0), 10 ** 11 - 1)
+        idx = np.clip(np.arange(q - 17, q + 16), 0, seq.size - 1)
+        s = name + b":" + str(q).encode() + b":" + up[idx].tobytes()
+        out[i, :len(s)] = np.frombuffer(s, np.uint8)
+    return x.astype(np.int16 if elem == 2 else np.int32), out
+
+
+@pytest.fixture(scope="module")
+def rec_inputs():
+    rng = np.random.default_rng(14)
+    m = 5000
+    counts = rng.integers(-144, 145, (m, 18)).astype(np.int32)
+    counts[100, 3], counts[200, 17] = -32768, 32767                      # the ends of int16: no overflow
+    seq = rng.choice(np.frombuffer(b"acgtnNACGTRYKM[`{@zZ09", np.uint8), 60_000).astype(np.uint8)     # (only a-z change under toupper)
+    pos = np.sort(rng.choice(np.arange(17, seq.size - 16), m, replace=False)).astype(np.int64)
+    return counts, pos, seq
+
+
+@pytest.mark.parametrize("where", ["device", "pinned"])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 4097])
+def test_window_records_against_numpy(gpu_ctx, rec_inputs, n, where):
+    import torch
+    counts, pos, seq = rec_inputs
+    m = counts.shape[0]
+    rng = np.random.default_rng(n)
+    centers = np.sort(rng.integers(16, m - 16, n)).astype(np.int64)
+    if n >= 2:
+        centers[0], centers[-1] = 16, m - 17                            # the first and the last column a window can be centred on
+    if n == 63:
+        centers = np.concatenate([np.arange(90, 121), np.arange(185, 217)]).astype(np.int64)      # (rows 100 and 200, the int16 extremes, are in these windows)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    dc, dcen, dpos, dseq = d(counts), d(centers), d(pos), d(seq)
+    for elem, name in ((2, b"c"), (4, b"c" * 37), (2, b"chr7_KI270803v1_alt")):
+        kw = {}
+        if where == "pinned":
+            kw = dict(position_matrix=torch.zeros(max(n, 1) * 594 + 8, dtype=torch.int16 if elem == 2 else torch.int32, pin_memory=True),
+                      position=torch.zeros((n + 1, 83), dtype=torch.uint8, pin_memory=True), meta=torch.full((4,), -1, dtype=torch.int64, pin_memory=True))
+            kw["position_matrix"][n * 594:] = 77
+            kw["position"][n:] = 77
+        x, s, meta = gpu_ctx.pileup_window_records(dc, dcen, dpos, dseq, name, elem, **kw)
+        torch.cuda.synchronize()
+        wx, ws = _np_records(counts, centers, pos, seq, name, elem)
+        assert meta.tolist() == [n, 0, 0, 0], (elem, name)
+        assert np.array_equal(x.cpu().numpy().reshape(-1), wx.reshape(-1)) and np.array_equal(s.cpu().numpy(), ws), (elem, name)
+        if where == "pinned":                                            # nothing behind the n sites is touched
+            assert (kw["position_matrix"][n * 594:] == 77).all() and (kw["position"][n:] == 77).all()
+
+
+def test_window_records_overflow_positions_and_names(gpu_ctx, rec_inputs):
+    import torch
+    counts, pos, seq = rec_inputs
+    m = counts.shape[0]
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    centers = np.array([16, 700, 701, 1500, m - 17], np.int64)
+    for bad in (-32769, 32768):
+        c2 = counts.copy()
+        c2[1500 + 16, 17] = bad                                          # the last value of a window
+        x, s, meta = gpu_ctx.pileup_window_records(d(c2), d(centers), d(pos), d(seq), "c", 2)
+        torch.cuda.synchronize()
+        assert meta[0].item() == 5 and meta[1].item() != 0 and meta[2].item() == 0
+        x, s, meta = gpu_ctx.pileup_window_records(d(c2), d(centers), d(pos), d(seq), "c", 4)
+        torch.cuda.synchronize()
+        assert meta.tolist() == [5, 0, 0, 0] and np.array_equal(x.cpu().numpy(), _np_records(c2, centers, pos, seq, b"c", 4)[0])
+        c2[1500 + 16, 17] = 0
+        c2[1500 + 17, 0] = bad                                           # the first value behind it: not this site's
+        assert gpu_ctx.pileup_window_records(d(c2), d(centers), d(pos), d(seq), "c", 2)[2].tolist() == [5, 0, 0, 0]
+    # positions of 1, 2, 10 and 11 digits: the digits are exact; their windows lie outside this contig, which the status word says
+    # while the reference bytes are read at the nearest index inside it
+    p2 = pos.copy()
+    p2[centers] = [7, 42, 9_876_543_210, 98_765_432_101, 10 ** 11 - 1]
+    x, s, meta = gpu_ctx.pileup_window_records(d(counts), d(centers), d(p2), d(seq), "ctg", 2)
+    torch.cuda.synchronize()
+    wx, ws = _np_records(counts, centers, p2, seq, b"ctg", 2)
+    assert meta[0].item() == 5 and meta[1].item() == 0 and meta[2].item() != 0
+    assert np.array_equal(s.cpu().numpy(), ws) and np.array_equal(x.cpu().numpy(), wx)
+    assert [bytes(r).split(b":")[1] for r in s.cpu().numpy()] == [b"7", b"42", b"9876543210", b"98765432101", b"99999999999"]
+    # a centre outside [16, M - 17] is not followed
+    x, s, meta = gpu_ctx.pileup_window_records(d(counts), d(np.array([3, m - 1, 1 << 40, -5], np.int64)), d(pos), d(seq), "c", 2)
+    torch.cuda.synchronize()
+    assert meta[0].item() == 4 and meta[2].item() != 0
+    # names: 37 bytes is the longest (37 + 1 + 11 + 1 + 33 = 83)
+    for name in (b"", b"c" * 38, b"a\0b"):
+        with pytest.raises(_lib.NanoSNPError):
+            gpu_ctx.pileup_window_records(d(counts), d(centers), d(pos), d(seq), name, 2)
+    with pytest.raises(_lib.NanoSNPError):
+        gpu_ctx.pileup_window_records(d(counts), d(centers), d(pos), d(seq), "c", 3)
+
+
+# ---- 4. nsnp_pileup_alt_info alone against the oracle -------------------------------------------------------------------------------
+def _alt_text():
+    """-> (contig, seq, mpileup text, {kind: 1-based position}): consecutive positions 1..L, the special columns far enough apart and from
+    the ends to be the centre of 33 consecutive positions, 6,000 columns of random printable bytes behind them"""
+    rng = np.random.default_rng(41)
+    specials = {}
+    cols = []
+    seq = rng.choice(np.frombuffer(b"ACGT", np.uint8), 40 + 40 * 12 + 6000 + 17).astype(np.uint8)
+    seq[rng.random(seq.size) < 0.1] |= 0x20                              # lower-case reference bases among them
+
+    def other(r, k=0):
+        return [b for b in b"CGTA" if b != (r & 0xDF)][k:k + 1]
+
+    def plain(p):
+        r = bytes([seq[p - 1] & 0xDF])
+        return r * 8 + r.lower() * 4
+
+    def special(kind, make):
+        p = 40 + 40 * len(specials)
+        specials[kind] = p
+        return p, make(bytes([seq[p - 1] & 0xDF]), bytes(other(seq[p - 1])), p)
+
+    let = b"ACGTNRYK"                                                    # (distinct after upper-casing too: 500 keys)
+    distinct = [bytes(let[(k // 8 ** j) % 8] for j in range(3)) for k in range(500)]
+    makers = [
+        ("500 distinct insertions", lambda r, o, p: o * 10 + b"".join(b"+3" + a for a in distinct)),
+        ("same allele in both cases", lambda r, o, p: r * 10 + b"+2ac" * 3 + b"+2AC" * 4 + b"+2Ac" + b"-2gt" * 2 + b"-2GT"),
+        ("+0 and -0", lambda r, o, p: o * 7 + b"+0" + r * 3 + b"-0" + b"+" + b"-"),
+        ("cut insertion beside the complete one", lambda r, o, p: o * 9 + b"+2AC+2AC+2ac+3AC"),
+        ("deletions of 60 and 61", lambda r, o, p: r * 10 + (b"-60" + b"N" * 60) * 2 + (b"-61" + b"N" * 61) * 3),
+        ("longer than 5000 bytes", lambda r, o, p: o * 10 + b"+3ACG" * 1200 + r * 20),
+        ("counts of 1 to 4 digits", lambda r, o, p: o * 10 + b"+1A" + b"+1C" * 12 + b"+1G" * 123 + b"+2TT" * 1234),
+        ("indel only", lambda r, o, p: r * 6 + r.lower() * 4 + b"+2GT" * 5),
+        ("mismatches of three bases in both cases", lambda r, o, p: bytes(other(r[0], 0) * 3 + other(r[0], 1) * 2 + other(r[0], 2)) + bytes(other(r[0], 0)).lower() * 4 + r * 2),
+    ]
+    by_pos = {}
+    for kind, make in makers:
+        p, c = special(kind, make)
+        by_pos[p] = c
+    n_front = 40 + 40 * 12
+    L = seq.size
+    # the last column a window can be centred on: its deletions reach past the end of the contig
+    p_end = L - 16
+    specials["deletion past the end"] = p_end
+    r = bytes([seq[p_end - 1] & 0xDF]); o = bytes(other(seq[p_end - 1]))
+    by_pos[p_end] = o * 10 + b"-3ACG" * 2 + b"-20" + b"A" * 20 + b"-40" + b"C" * 40 + b"+2GG" * 3
+    rnd = iter(bytes(rng.integers(33, 127, int(rng.integers(1, 300)), dtype=np.uint8)) for _ in range(6000))
+    lines = []
+    for p in range(1, L + 1):
+        c = by_pos.get(p) or (plain(p) if p <= n_front or p > n_front + 6000 else next(rnd))
+        lines.append(b"ctgA\t%d\tN\t%d\t%s\t%s\n" % (p, len(c), c, b"I"))
+    return "ctgA", seq, b"".join(lines), specials
+
+
+@pytest.fixture(scope="module")
+def alt_case(tmp_path_factory):
+    """the text, its columns and the oracle's .pd (computed once, shared, never changed)"""
+    from oracle import oracle
+    contig, seq, text, specials = _alt_text()
+    d = tmp_path_factory.mktemp("alt")
+    (d / "a.mpileup").write_bytes(text)
+    n = oracle.mpileup_to_pd(str(d / "a.mpileup"), seq.tobytes(), str(d / "a.pd"))
+    pd = (d / "a.pd").read_bytes()
+    want = {}
+    for line in pd.split(b"\n"):
+        if line:
+            _, position, alt = line.split(b"\t", 2)
+            want[int(position.split(b":")[1])] = alt
+    assert len(want) == n
+    pos, off, bases = host.mpileup_parse(text)
+    ref = seq[pos - 1]
+    _, depth, _ = oracle.encode_columns(bases, off, ref)
+    return dict(contig=contig, seq=seq, text=text, specials=specials, want=want, pos=pos, off=off, bases=bases, ref=ref, depth=depth, pd=pd)
+
+
+def _alt_on_device(ctx, a, centers, **kw):
+    import torch
+    d = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    out = ctx.pileup_alt_info(d(a["bases"]), d(a["off"]), d(a["ref"]), d(a["pos"]), d(a["depth"]), d(centers), d(a["seq"]), **kw)
+    torch.cuda.synchronize()
+    return out
+
+
+def test_alt_info_against_the_oracle(gpu_ctx, alt_case):
+    a = alt_case
+    want, sp = a["want"], a["specials"]
+    # the oracle selected every special column and a good many random ones: the text cannot pass empty
+    for kind, p in sp.items():
+        assert p in want, kind
+    assert sum(1 for p in want if 520 < p <= 6520) > 300
+    assert want[sp["500 distinct insertions"]].count(b" ") == 2 * 500 - 1 + 2
+    assert want[sp["same allele in both cases"]].endswith(b"AC 8") and want[sp["same allele in both cases"]].count(b"I") == 1
+    assert want[sp["deletion past the end"]].count(b"D") >= 2 and b"I" not in want[sp["deletion past the end"]] and b"X" not in want[sp["deletion past the end"]]
+    assert not want[sp["deletion past the end"]].endswith(tuple(b"%d" % k for k in range(10)))      # ends inside a key: no count behind it
+    assert want[sp["indel only"]].split(b"-", 1)[1].startswith(b"I") and b"X" not in want[sp["indel only"]]
+    assert len(a["off"]) and int(np.diff(a["off"]).max()) > 5000
+    for cnt in (b" 1 ", b" 12 ", b" 123 ", b" 1234"):
+        assert cnt in want[sp["counts of 1 to 4 digits"]] + b" "
+    sites = np.array(sorted(want), np.int64)
+    centers = sites - 1                                                  # positions 1..L, one line each: column index = position - 1
+    assert np.array_equal(a["pos"][centers], sites)
+    blob, offsets, meta = _alt_on_device(gpu_ctx, a, centers)
+    blob, offsets = blob.cpu().numpy(), offsets.cpu().numpy()
+    total = sum(len(want[int(p)]) for p in sites)
+    assert meta.tolist() == [total, 0, 0, 0] and offsets[0] == 0 and offsets[-1] == total
+    for i, p in enumerate(sites):                                        # every selected site, none skipped
+        got = blob[offsets[i]:offsets[i + 1]].tobytes()
+        assert got == want[int(p)], (int(p), got[:80], want[int(p)][:80])
+    # pinned outputs, and a subset in another order (a site's text does not depend on its neighbours)
+    import torch
+    sub = centers[::-3].copy()
+    pb, po, pm = (torch.zeros(total, dtype=torch.uint8, pin_memory=True), torch.zeros(sub.size + 1, dtype=torch.int64, pin_memory=True),
+                  torch.zeros(4, dtype=torch.int64, pin_memory=True))
+    _alt_on_device(gpu_ctx, a, sub, blob=pb, offsets=po, meta=pm)
+    for i, c in enumerate(sub):
+        assert pb.numpy()[int(po[i]):int(po[i + 1])].tobytes() == want[int(c) + 1]
+    assert pm.tolist()[1] == 0
+    # no sites
+    blob0, off0, meta0 = _alt_on_device(gpu_ctx, a, centers[:0])
+    assert off0.tolist() == [0] and meta0.tolist() == [0, 0, 0, 0]
+
+
+def test_alt_info_blob_one_byte_too_small(gpu_ctx, alt_case):
+    import torch
+    a = alt_case
+    sites = np.array(sorted(a["want"]), np.int64)
+    total = sum(len(a["want"][int(p)]) for p in sites)
+    blob = torch.full((total + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+    _, offsets, meta = _alt_on_device(gpu_ctx, a, sites - 1, cap=total - 1, blob=blob[:total - 1])
+    assert meta.tolist() == [total, gpu_ctx.TOK_ERANGE, 0, 0]
+    assert (blob.cpu().numpy()[total - 1:] == 0xEE).all()                # nothing written beyond cap
+    assert offsets.cpu().numpy()[-1] == total
+    _, _, meta = _alt_on_device(gpu_ctx, a, sites - 1, blob=blob[:total])
+    assert meta.tolist() == [total, 0, 0, 0] and (blob.cpu().numpy()[total:] == 0xEE).all()
+    assert blob.cpu().numpy()[:total].tobytes() == b"".join(a["want"][int(p)] for p in sites)
+
+
+def test_alt_case_through_the_pipeline(tmp_path, alt_case):
+    """the same text through contig_to_bin: alt_info of a column longer than a small chunk's slot budget, 500 keys, the cut text"""
+    from nanosnp_amd.pipeline import contig_to_bin
+    a = alt_case
+    n = sitefile.pd_to_bin(a["pd"], tmp_path / "want.bin")
+    assert contig_to_bin(_model(), a["text"], a["contig"], a["seq"], str(tmp_path / "got.bin"), chunk_bytes=1 << 16) == n
+    assert (tmp_path / "got.bin").read_bytes() == (tmp_path / "want.bin").read_bytes()
+
+
+def test_alt_text_outgrowing_its_slot_starts_the_contig_over(tmp_path):
+    """200 neighbouring sites of 120 distinct insertions each: a chunk's alt_info (about 1 KB a site) does not fit the slot budgeted for
+    it (64 bytes a site + 64 KB); the contig is run again with larger slots and nothing is cut"""
+    from oracle import oracle
+    from nanosnp_amd.pipeline import contig_to_bin
+    rng = np.random.default_rng(43)
+    seq = rng.choice(np.frombuffer(b"ACGT", np.uint8), 300).astype(np.uint8)
+    let = b"ACGTNRYK"
+    ins = b"".join(b"+3" + bytes(let[(k // 8 ** j) % 8] for j in range(3)) for k in range(120))
+    lines = []
+    for p in range(1, 301):
+        c = bytes([seq[p - 1]]) * 10 + (ins if 50 <= p < 250 else b"")
+        lines.append(b"big\t%d\tN\t10\t%s\tI\n" % (p, c))
+    text = b"".join(lines)
+    (tmp_path / "b.mpileup").write_bytes(text)
+    n = oracle.mpileup_to_pd(str(tmp_path / "b.mpileup"), seq.tobytes(), str(tmp_path / "b.pd"))
+    assert n == 200 and sitefile.pd_to_bin((tmp_path / "b.pd").read_bytes(), tmp_path / "want.bin") == n
+    st = {}
+    assert contig_to_bin(_model(), text, "big", seq, str(tmp_path / "got.bin"), stats=st) == n
+    assert st["restarts"] == 1
+    assert (tmp_path / "got.bin").read_bytes() == (tmp_path / "want.bin").read_bytes()
+
+
+# ---- 5. round trip: make_pileup_bins -> predict_pileup_bins == call_variants -------------------------------------------------------
+@pytest.mark.parametrize("beds", [False, True])
+def test_round_trip_equals_call_variants(tmp_path, pileup_weights, beds):
+    from nanosnp_amd.pileup_model import LSTMNetwork
+    from nanosnp_amd.pipeline import call_variants, make_pileup_bins, predict_pileup_bins
+    contigs, fasta, fai = [], b"", ""
+    for i, n in enumerate((4000, 2500)):
+        name = f"rt{i}"
+        cols = host.synth_columns(20261400 + i, n, coverage=30, het_rate=0.05)
+        (tmp_path / f"{name}.mpileup").write_bytes(bytes(cols.mpileup_text_native(name)))
+        seq = cols.ref.copy()
+        fasta += b">" + name.encode() + b"\n" + b"\n".join(bytes(seq[a:a + 60]) for a in range(0, seq.size, 60)) + b"\n"
+        fai += f"{name}\t{seq.size}\t0\t60\t61\n"
+        contigs.append((name, str(tmp_path / f"{name}.mpileup")))
+    (tmp_path / "ref.fa").write_bytes(fasta)
+    kw = {}
+    if beds:
+        kw = dict(extended_bed={"rt0": np.array([[100, 3000], [3300, 3900]]), "rt1": np.array([[0, 2500]])},
+                  confident_bed={"rt0": np.array([[200, 1500], [1800, 2600]]), "rt1": np.array([[50, 1200], [1300, 2400]])})
+    sites = make_pileup_bins(_model(), contigs, str(tmp_path / "ref.fa"), fai, str(tmp_path / "bins"), chunk_bytes=100_000, **kw)       # no weights loaded
+    assert list(sites) == ["rt0", "rt1"] and min(sites.values()) > 20
+    files = [str(tmp_path / "bins" / f"{name}.pd.bin") for name, _ in contigs]
+    assert all(os.path.exists(f) for f in files) and sorted(os.listdir(tmp_path / "bins")) == ["rt0.pd.bin", "rt1.pd.bin"]
+    m = LSTMNetwork().load_weight_list(pileup_weights)
+    for bs in (1000, 64):
+        want = tmp_path / f"want{bs}.vcf"
+        rows = call_variants(m, contigs, str(tmp_path / "ref.fa"), fai, str(want), batch_size=bs, chunk_bytes=100_000, **kw)
+        got = tmp_path / f"got{bs}.vcf"
+        assert predict_pileup_bins(m, files, fai, str(got), batch_size=bs) == rows and rows > 20
+        assert got.read_bytes() == want.read_bytes(), bs
+
+
+# ---- 6. errors and what they leave behind ------------------------------------------------------------------------------------------
+def test_errors_leave_no_file_and_a_working_model(tmp_path, model):
+    from nanosnp_amd.pipeline import contig_to_bin
+    cols = host.synth_columns(20261450, 1500, coverage=30, het_rate=0.05)
+    text, seq = bytes(cols.mpileup_text_native("e0")), cols.ref.copy()
+    p = tmp_path / "e0.pd.bin"
+    lines = text.split(b"\n")
+    malformed = b"\n".join(lines[:700] + [b"e0\t701\tN"] + lines[701:])
+    beyond = b"\n".join(lines[:-2] + [lines[-2].replace(b"\t1500\t", b"\t1501\t", 1), b""])
+    assert b"\t1501\t" in beyond
+    for bad_text, name, exc in ((malformed, "e0", host.HostError), (beyond, "e0", ValueError), (text, "e" * 38, ValueError)):
+        for chunk_bytes in (64 << 20, 1 << 15):
+            with pytest.raises(exc):
+                contig_to_bin(model, bad_text, name, seq, str(p), chunk_bytes=chunk_bytes)
+            assert not p.exists() and not os.path.exists(str(p) + ".tmp")
+    n = contig_to_bin(model, text, "e0", seq, str(p), chunk_bytes=1 << 15)
+    assert n > 20 and sitefile.read_arrays(p)["position_matrix"].shape == (n, 33, 18)
+    assert bytes(sitefile.read_arrays(p)["position"][0]).startswith(b"e0:")
+    # an empty text is an empty file, not an error
+    assert contig_to_bin(model, b"", "e0", seq, str(tmp_path / "none.pd.bin")) == 0
+    sitefile.write_pileup_bin(tmp_path / "none_want.bin", np.empty((0, 33, 18), np.int32), [], [])
+    assert (tmp_path / "none.pd.bin").read_bytes() == (tmp_path / "none_want.bin").read_bytes()
