@@ -319,3 +319,20 @@ def test_select_sites_range_and_call_rows_equal_the_elementwise_forms(gpu_ctx):
     want = torch.cat([f64(pos.index_select(0, centers)), f64(ga), f64(za), f64(gm), f64(zm), cov], dim=1)
     assert rows.dtype == torch.float64 and torch.equal(rows, want)
     assert gpu_ctx.pileup_call_rows(c, centers[:0], pos, ga[:0], za[:0], gm[:0], zm[:0]).shape == (0, 13)
+
+
+def test_a_column_of_33000_reads_leaves_int16_exactly(gpu_ctx):
+    """the deep column of tests/records_cases.deep_text alone and among its neighbours: counts of -33,010 and 33,000 (the stage-1 records
+    of such a column are int32: tests/test_gpu_pileup_bins.py)"""
+    from oracle import oracle
+    from tests import records_cases as rc
+    contig, seq, text = rc.deep_text()
+    pos, off, bases = host.mpileup_parse(text)
+    ref = seq[pos - 1]
+    oc, od, of = oracle.encode_columns(bases, off, ref)
+    assert oc.min() == -(rc.DEEP_READS + 10) and oc.max() == rc.DEEP_READS
+    for lo, hi in ((0, pos.size), (299, 300)):
+        b, o, r = bases[off[lo]:off[hi]], off[lo:hi + 1] - off[lo], ref[lo:hi]
+        c, d, f = _enc(gpu_ctx, b, o, r)
+        assert np.array_equal(c.cpu().numpy(), oc[lo:hi]), (lo, hi)
+        assert np.array_equal(d.cpu().numpy(), od[lo:hi]) and np.array_equal(f.cpu().numpy(), of[lo:hi])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from nanosnp_amd import _lib, host, sitefile
+from tests import records_cases as rc
 from tests.helpers import golden
 
 pytestmark = pytest.mark.gpu
@@ -176,23 +177,6 @@ def test_seeded_cut_alleles_under_three_threshold_sets(tmp_path, model, seed):
 
 
 # ---- 3. nsnp_pileup_window_records alone against numpy ------------------------------------------------------------------------------
-def _np_records(counts, centers, pos, seq, name, elem):
-    n, m = centers.size, counts.shape[0]
-    c = np.clip(centers, 16, m - 17)
-    x = counts[c[:, None] + np.arange(-16, 17)[None, :]] if n else np.empty((0, 33, 18), np.int32)
-    out = np.zeros((n, 83), np.uint8)
-    up = seq.copy()
-    low = (up >= ord("a")) & (up <= ord("z"))
-    up[low] -= 32
-    for i in range(n):
-        p = int(pos[c[i]])
-        q = min(max(p, 0), 10 ** 11 - 1)
-        idx = np.clip(np.arange(q - 17, q + 16), 0, seq.size - 1)
-        s = name + b":" + str(q).encode() + b":" + up[idx].tobytes()
-        out[i, :len(s)] = np.frombuffer(s, np.uint8)
-    return x.astype(np.int16 if elem == 2 else np.int32), out
-
-
 @pytest.fixture(scope="module")
 def rec_inputs():
     rng = np.random.default_rng(14)
@@ -227,7 +211,7 @@ def test_window_records_against_numpy(gpu_ctx, rec_inputs, n, where):
             kw["position"][n:] = 77
         x, s, meta = gpu_ctx.pileup_window_records(dc, dcen, dpos, dseq, name, elem, **kw)
         torch.cuda.synchronize()
-        wx, ws = _np_records(counts, centers, pos, seq, name, elem)
+        wx, ws, _ = rc.np_records(counts, centers, pos, seq, name, elem)
         assert meta.tolist() == [n, 0, 0, 0], (elem, name)
         assert np.array_equal(x.cpu().numpy().reshape(-1), wx.reshape(-1)) and np.array_equal(s.cpu().numpy(), ws), (elem, name)
         if where == "pinned":                                            # nothing behind the n sites is touched
@@ -248,7 +232,7 @@ def test_window_records_overflow_positions_and_names(gpu_ctx, rec_inputs):
         assert meta[0].item() == 5 and meta[1].item() != 0 and meta[2].item() == 0
         x, s, meta = gpu_ctx.pileup_window_records(d(c2), d(centers), d(pos), d(seq), "c", 4)
         torch.cuda.synchronize()
-        assert meta.tolist() == [5, 0, 0, 0] and np.array_equal(x.cpu().numpy(), _np_records(c2, centers, pos, seq, b"c", 4)[0])
+        assert meta.tolist() == [5, 0, 0, 0] and np.array_equal(x.cpu().numpy(), rc.np_records(c2, centers, pos, seq, b"c", 4)[0])
         c2[1500 + 16, 17] = 0
         c2[1500 + 17, 0] = bad                                           # the first value behind it: not this site's
         assert gpu_ctx.pileup_window_records(d(c2), d(centers), d(pos), d(seq), "c", 2)[2].tolist() == [5, 0, 0, 0]
@@ -258,7 +242,7 @@ def test_window_records_overflow_positions_and_names(gpu_ctx, rec_inputs):
     p2[centers] = [7, 42, 9_876_543_210, 98_765_432_101, 10 ** 11 - 1]
     x, s, meta = gpu_ctx.pileup_window_records(d(counts), d(centers), d(p2), d(seq), "ctg", 2)
     torch.cuda.synchronize()
-    wx, ws = _np_records(counts, centers, p2, seq, b"ctg", 2)
+    wx, ws, _ = rc.np_records(counts, centers, p2, seq, b"ctg", 2)
     assert meta[0].item() == 5 and meta[1].item() == 0 and meta[2].item() != 0
     assert np.array_equal(s.cpu().numpy(), ws) and np.array_equal(x.cpu().numpy(), wx)
     assert [bytes(r).split(b":")[1] for r in s.cpu().numpy()] == [b"7", b"42", b"9876543210", b"98765432101", b"99999999999"]
@@ -275,78 +259,10 @@ def test_window_records_overflow_positions_and_names(gpu_ctx, rec_inputs):
 
 
 # ---- 4. nsnp_pileup_alt_info alone against the oracle -------------------------------------------------------------------------------
-def _alt_text():
-    """-> (contig, seq, mpileup text, {kind: 1-based position}): consecutive positions 1..L, the special columns far enough apart and from
-    the ends to be the centre of 33 consecutive positions, 6,000 columns of random printable bytes behind them"""
-    rng = np.random.default_rng(41)
-    specials = {}
-    cols = []
-    seq = rng.choice(np.frombuffer(b"ACGT", np.uint8), 40 + 40 * 12 + 6000 + 17).astype(np.uint8)
-    seq[rng.random(seq.size) < 0.1] |= 0x20                              # lower-case reference bases among them
-
-    def other(r, k=0):
-        return [b for b in b"CGTA" if b != (r & 0xDF)][k:k + 1]
-
-    def plain(p):
-        r = bytes([seq[p - 1] & 0xDF])
-        return r * 8 + r.lower() * 4
-
-    def special(kind, make):
-        p = 40 + 40 * len(specials)
-        specials[kind] = p
-        return p, make(bytes([seq[p - 1] & 0xDF]), bytes(other(seq[p - 1])), p)
-
-    let = b"ACGTNRYK"                                                    # (distinct after upper-casing too: 500 keys)
-    distinct = [bytes(let[(k // 8 ** j) % 8] for j in range(3)) for k in range(500)]
-    makers = [
-        ("500 distinct insertions", lambda r, o, p: o * 10 + b"".join(b"+3" + a for a in distinct)),
-        ("same allele in both cases", lambda r, o, p: r * 10 + b"+2ac" * 3 + b"+2AC" * 4 + b"+2Ac" + b"-2gt" * 2 + b"-2GT"),
-        ("+0 and -0", lambda r, o, p: o * 7 + b"+0" + r * 3 + b"-0" + b"+" + b"-"),
-        ("cut insertion beside the complete one", lambda r, o, p: o * 9 + b"+2AC+2AC+2ac+3AC"),
-        ("deletions of 60 and 61", lambda r, o, p: r * 10 + (b"-60" + b"N" * 60) * 2 + (b"-61" + b"N" * 61) * 3),
-        ("longer than 5000 bytes", lambda r, o, p: o * 10 + b"+3ACG" * 1200 + r * 20),
-        ("counts of 1 to 4 digits", lambda r, o, p: o * 10 + b"+1A" + b"+1C" * 12 + b"+1G" * 123 + b"+2TT" * 1234),
-        ("indel only", lambda r, o, p: r * 6 + r.lower() * 4 + b"+2GT" * 5),
-        ("mismatches of three bases in both cases", lambda r, o, p: bytes(other(r[0], 0) * 3 + other(r[0], 1) * 2 + other(r[0], 2)) + bytes(other(r[0], 0)).lower() * 4 + r * 2),
-    ]
-    by_pos = {}
-    for kind, make in makers:
-        p, c = special(kind, make)
-        by_pos[p] = c
-    n_front = 40 + 40 * 12
-    L = seq.size
-    # the last column a window can be centred on: its deletions reach past the end of the contig
-    p_end = L - 16
-    specials["deletion past the end"] = p_end
-    r = bytes([seq[p_end - 1] & 0xDF]); o = bytes(other(seq[p_end - 1]))
-    by_pos[p_end] = o * 10 + b"-3ACG" * 2 + b"-20" + b"A" * 20 + b"-40" + b"C" * 40 + b"+2GG" * 3
-    rnd = iter(bytes(rng.integers(33, 127, int(rng.integers(1, 300)), dtype=np.uint8)) for _ in range(6000))
-    lines = []
-    for p in range(1, L + 1):
-        c = by_pos.get(p) or (plain(p) if p <= n_front or p > n_front + 6000 else next(rnd))
-        lines.append(b"ctgA\t%d\tN\t%d\t%s\t%s\n" % (p, len(c), c, b"I"))
-    return "ctgA", seq, b"".join(lines), specials
-
-
 @pytest.fixture(scope="module")
 def alt_case(tmp_path_factory):
     """the text, its columns and the oracle's .pd (computed once, shared, never changed)"""
-    from oracle import oracle
-    contig, seq, text, specials = _alt_text()
-    d = tmp_path_factory.mktemp("alt")
-    (d / "a.mpileup").write_bytes(text)
-    n = oracle.mpileup_to_pd(str(d / "a.mpileup"), seq.tobytes(), str(d / "a.pd"))
-    pd = (d / "a.pd").read_bytes()
-    want = {}
-    for line in pd.split(b"\n"):
-        if line:
-            _, position, alt = line.split(b"\t", 2)
-            want[int(position.split(b":")[1])] = alt
-    assert len(want) == n
-    pos, off, bases = host.mpileup_parse(text)
-    ref = seq[pos - 1]
-    _, depth, _ = oracle.encode_columns(bases, off, ref)
-    return dict(contig=contig, seq=seq, text=text, specials=specials, want=want, pos=pos, off=off, bases=bases, ref=ref, depth=depth, pd=pd)
+    return rc.alt_case_data(tmp_path_factory.mktemp("alt"))
 
 
 def _alt_on_device(ctx, a, centers, **kw):
@@ -497,3 +413,297 @@ def test_errors_leave_no_file_and_a_working_model(tmp_path, model):
     assert contig_to_bin(model, b"", "e0", seq, str(tmp_path / "none.pd.bin")) == 0
     sitefile.write_pileup_bin(tmp_path / "none_want.bin", np.empty((0, 33, 18), np.int32), [], [])
     assert (tmp_path / "none.pd.bin").read_bytes() == (tmp_path / "none_want.bin").read_bytes()
+
+
+# ---- 7. nsnp_mpileup_line_names above 1,024 tiles: the serial part of k_names_scan (tests/records_cases.py builds the texts) ------------
+def _line_names(ctx, text, name, cap_lines, cap_names, marker=-7):
+    """-> (line_idx [cap_lines + 8] with the marker behind cap_lines, names [cap_names + 2, 44] with 0xEE behind cap_names, meta)"""
+    import torch
+    d = torch.from_numpy(np.frombuffer(text, np.uint8).copy()).cuda()
+    line_idx = torch.full((cap_lines + 8,), marker, dtype=torch.int32, device="cuda")
+    names = torch.full((cap_names + 2, 44), 0xEE, dtype=torch.uint8, device="cuda")
+    _, _, meta = ctx.mpileup_line_names(d, name, cap_lines, line_idx=line_idx[:cap_lines], names=names[:cap_names])
+    torch.cuda.synchronize()
+    return line_idx.cpu().numpy(), names.cpu().numpy(), meta.tolist()
+
+
+def _assert_line_names(idx, names, toks, differ, n_lines):
+    """every line of the first n_lines, none sampled: which carry an entry, every entry handed out once, all 44 bytes of every entry"""
+    differ = np.array([i for i in differ if i < n_lines], np.int64)
+    assert np.array_equal(np.flatnonzero(idx[:n_lines] >= 0), differ) and (idx[:n_lines][idx[:n_lines] < 0] == -1).all()
+    assert np.array_equal(np.sort(idx[differ]), np.arange(differ.size))
+    want = np.stack([rc.name_entry(toks[i]) for i in differ])
+    rows = np.flatnonzero((names[idx[differ]] != want).any(1))
+    assert rows.size == 0, (rows[:5], differ[rows[:5]])
+
+
+@pytest.mark.parametrize("newline", [True, False])
+@pytest.mark.parametrize("rest", [1, 4095, 4096])
+@pytest.mark.parametrize("tiles", [1025, 2049])
+def test_line_names_above_1024_tiles(gpu_ctx, tiles, rest, newline):
+    """k_names_scan with 2 and 3 tiles per thread: another token on the first and last line start of the first and last tile of scan
+    threads, in tile 0 and the last tiles, tokens and leading tabs over a tile edge, tiles without a newline, text lengths one beside a
+    multiple of 4,096, a last line with and without its newline (test_line_names_texts_hold_what_they_are_built_for asserts all that)"""
+    text, name = rc.names_text(tiles, rest, newline)
+    assert rc.n_tiles(len(text)) == tiles and rc.scan_per(tiles) == {1025: 2, 2049: 3}[tiles] and text.endswith(b"\n") == newline
+    toks, differ = rc.line_names_rule(text, name)
+    assert len(differ) > 500 and differ[0] == 0 and differ[-1] == len(toks) - 1
+    idx, names, meta = _line_names(gpu_ctx, text, name, len(toks), len(differ))
+    assert meta == [len(differ), 0, 0, 0]
+    _assert_line_names(idx, names, toks, differ, len(toks))
+    assert (idx[len(toks):] == -7).all() and (names[len(differ):] == 0xEE).all()
+
+
+def test_line_names_capacities_above_1024_tiles(gpu_ctx):
+    text, name = rc.names_text(1025, 4095, True)
+    toks, differ = rc.line_names_rule(text, name)
+    n, k = len(toks), len(differ)
+    assert rc.n_tiles(len(text)) == 1025 and k > 500
+    # the table one entry short: the count is the true one, one line has no entry, nothing is written behind the table
+    idx, names, meta = _line_names(gpu_ctx, text, name, n, k - 1)
+    assert meta == [k, gpu_ctx.TOK_ERANGE, 0, 0]
+    assert (names[k - 1:] == 0xEE).all() and (idx[n:] == -7).all()
+    assert np.array_equal(np.flatnonzero(idx[:n] >= 0), np.array(differ))
+    got = idx[differ]
+    assert int((got == rc.NO_ROOM).sum()) == 1 and np.array_equal(np.sort(got[got != rc.NO_ROOM]), np.arange(k - 1))
+    for i in np.array(differ)[got != rc.NO_ROOM]:
+        assert np.array_equal(names[idx[i]], rc.name_entry(toks[i])), i
+    # fewer line entries than lines: the first cap_lines are right, the marker behind them is intact
+    for cap_lines in (n - 1, n // 2 + 3, 1):
+        k_in = sum(1 for i in differ if i < cap_lines)
+        idx, names, meta = _line_names(gpu_ctx, text, name, cap_lines, k)
+        assert (idx[cap_lines:] == -7).all(), cap_lines
+        _assert_line_names(idx, names, toks, differ, cap_lines)
+        assert meta == [k_in, 0, 0, 0], cap_lines                         # entries are handed out to recorded lines only
+
+
+# ---- 8. nsnp_pileup_window_records with per-site names, alone against numpy -----------------------------------------------------------
+@pytest.mark.parametrize("where", ["device", "pinned"])
+@pytest.mark.parametrize("n", [1, 2, 5, 64, 4097])
+def test_window_records_with_per_site_names(gpu_ctx, rec_inputs, n, where):
+    """line_idx and the name table built in numpy: consecutive centres alternate between the contig's name and entries of 1, 2, 36 and 37
+    bytes, so the name changes inside a 4-byte word of the 83-byte rows"""
+    import torch
+    counts, pos, seq = rec_inputs
+    m = counts.shape[0]
+    centers, line_idx, names = rc.site_names_case(n, m, seed=n)
+    assert np.array_equal(centers, np.arange(16, 16 + n)) and (n < 2 or (line_idx[centers + 16] >= 0).any())
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    dc, dcen, dpos, dseq, dli, dnm = d(counts), d(centers), d(pos), d(seq), d(line_idx), d(names)
+    for elem, name in ((2, b"ctgN"), (4, b"q" * 37)):
+        wx, ws, refused = rc.np_records(counts, centers, pos, seq, name, elem, line_idx, names)
+        assert not refused
+        kw = {}
+        if where == "pinned":
+            kw = dict(position_matrix=torch.zeros(n * 594 + 8, dtype=torch.int16 if elem == 2 else torch.int32, pin_memory=True),
+                      position=torch.zeros((n + 1, 83), dtype=torch.uint8, pin_memory=True), meta=torch.full((4,), -1, dtype=torch.int64, pin_memory=True))
+            kw["position_matrix"][n * 594:] = 77
+            kw["position"][n:] = 77
+        x, s, meta = gpu_ctx.pileup_window_records(dc, dcen, dpos, dseq, name, elem, line_names=(dli, dnm), **kw)
+        torch.cuda.synchronize()
+        assert meta.tolist() == [n, 0, 0, 0], (elem, name)
+        s = s.cpu().numpy()
+        rows = np.flatnonzero((s != ws).any(1))
+        assert rows.size == 0, (elem, rows[:5], bytes(s[rows[0]]), bytes(ws[rows[0]]))
+        assert np.array_equal(x.cpu().numpy().reshape(-1), wx.reshape(-1))
+        if where == "pinned":
+            assert (kw["position_matrix"][n * 594:] == 77).all() and (kw["position"][n:] == 77).all()
+
+
+def test_window_records_refused_name_entries(gpu_ctx, rec_inputs):
+    """an entry whose length is 0, 38, 45 or negative, and a line the table had no room for: meta[2] says so, the row carries the clamped
+    name / the contig's name, and the rows beside it are what they are without it"""
+    import torch
+    counts, pos, seq = rec_inputs
+    m = counts.shape[0]
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    centers = np.arange(2000, 2009, dtype=np.int64)
+    names = np.zeros((3, 44), np.uint8)
+    names[:, :40] = np.frombuffer(b"abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMN", np.uint8)
+    names[0, 40:44] = np.frombuffer(np.int32(5).tobytes(), np.uint8)
+    names[2, 40:44] = np.frombuffer(np.int32(36).tobytes(), np.uint8)
+    base_idx = np.full(m, -1, np.int32)
+    base_idx[centers[[1, 3, 7]] + 16] = 0                               # sites 1, 3, 7: a valid 5-byte name; site 5: a 36-byte one
+    base_idx[centers[5] + 16] = 2
+    run = lambda li, nm: gpu_ctx.pileup_window_records(d(counts), d(centers), d(pos), d(seq), b"ctg", 2, line_names=(d(li), d(nm)))
+    x0, s0, meta0 = run(base_idx, names)
+    torch.cuda.synchronize()
+    want0 = rc.np_records(counts, centers, pos, seq, b"ctg", 2, base_idx, names)
+    assert meta0.tolist() == [9, 0, 0, 0] and not want0[2] and np.array_equal(s0.cpu().numpy(), want0[1])
+    for bad in (0, 38, 45, -3, "no room"):
+        li, nm = base_idx.copy(), names.copy()
+        if bad == "no room":
+            li[centers[4] + 16] = rc.NO_ROOM
+        else:
+            li[centers[4] + 16] = 1
+            nm[1, 40:44] = np.frombuffer(np.int32(bad).tobytes(), np.uint8)
+        x, s, meta = run(li, nm)
+        torch.cuda.synchronize()
+        wx, ws, refused = rc.np_records(counts, centers, pos, seq, b"ctg", 2, li, nm)
+        s = s.cpu().numpy()
+        assert refused and meta[0].item() == 9 and meta[1].item() == 0 and meta[2].item() != 0, bad
+        assert np.array_equal(s, ws) and np.array_equal(x.cpu().numpy(), wx), bad
+        rest = [0, 1, 2, 3, 5, 6, 7, 8]
+        assert np.array_equal(s[rest], s0.cpu().numpy()[rest]), bad
+        lead = {0: b"a:", 38: b"abcdefghijklmnopqrstuvwxyzABCDEFGHIJK:", 45: b"abcdefghijklmnopqrstuvwxyzABCDEFGHIJK:", -3: b"a:", "no room": b"ctg:"}[bad]
+        assert bytes(s[4]).startswith(lead + str(int(pos[centers[4]])).encode() + b":"), bad
+
+
+# ---- 9. nsnp_pileup_alt_info: the scan's serial part and a total above one sweep of k_alt_copy ----------------------------------------
+def _alt_expected(a, centers):
+    texts = [a["want"][int(c) + 1] for c in centers]
+    off = np.zeros(len(texts) + 1, np.int64)
+    np.cumsum([len(t) for t in texts], out=off[1:])
+    return b"".join(texts), off
+
+
+@pytest.mark.parametrize("n", rc.ALT_SCAN_N)
+def test_alt_info_scan_edges(gpu_ctx, alt_case, n):
+    """k_alt_scan with 1, 2 and 3 sites per thread: sites in a seeded order, with repeats; offsets, meta and every text"""
+    centers = rc.alt_scan_centers(alt_case["want"], n)
+    assert centers.size == n and rc.scan_per(n) == {1: 1, 1023: 1, 1024: 1, 1025: 2, 2048: 2, 2049: 3}[n]
+    blob_want, off_want = _alt_expected(alt_case, centers)
+    blob, offsets, meta = _alt_on_device(gpu_ctx, alt_case, centers)
+    assert meta.tolist() == [len(blob_want), 0, 0, 0]
+    assert np.array_equal(offsets.cpu().numpy(), off_want)
+    assert blob.cpu().numpy()[:len(blob_want)].tobytes() == blob_want
+
+
+@pytest.fixture(scope="module")
+def alt_sweep(alt_case):
+    centers, total = rc.alt_sweep_centers(alt_case["want"], alt_case["specials"])
+    blob_want, off_want = _alt_expected(alt_case, centers)
+    return centers, total, blob_want, off_want
+
+
+@pytest.mark.parametrize("where", ["device", "pinned", "unaligned"])
+def test_alt_info_beyond_one_copy_sweep(gpu_ctx, alt_case, alt_sweep, where):
+    """a total above the 4,194,304 bytes k_alt_copy's grid moves in one sweep, no multiple of 16, with cap == total: into a device blob, a
+    pinned blob and a device blob that starts one byte into its allocation (the byte path); nothing is written behind the total"""
+    import torch
+    centers, total, blob_want, off_want = alt_sweep
+    assert total == len(blob_want) and total > rc.COPY_SWEEP + 16 and total % 16 != 0
+    lead = 1 if where == "unaligned" else 0
+    buf = torch.full((lead + total + 64,), 0xEE, dtype=torch.uint8, **(dict(pin_memory=True) if where == "pinned" else dict(device="cuda")))
+    blob = buf[lead:lead + total]
+    assert blob.data_ptr() % 16 == lead
+    _, offsets, meta = _alt_on_device(gpu_ctx, alt_case, centers, blob=blob)
+    assert meta.tolist() == [total, 0, 0, 0] and np.array_equal(offsets.cpu().numpy(), off_want)
+    got = buf.cpu().numpy()
+    assert (got[:lead] == 0xEE).all() and (got[lead + total:] == 0xEE).all()
+    diff = np.flatnonzero(got[lead:lead + total] != np.frombuffer(blob_want, np.uint8))
+    assert diff.size == 0, (diff[:5], diff.size)
+
+
+def test_alt_info_one_byte_short_beyond_one_copy_sweep(gpu_ctx, alt_case, alt_sweep):
+    import torch
+    centers, total, blob_want, off_want = alt_sweep
+    assert total > rc.COPY_SWEEP + 16
+    buf = torch.full((total + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+    _, offsets, meta = _alt_on_device(gpu_ctx, alt_case, centers, blob=buf[:total - 1])
+    assert meta.tolist() == [total, gpu_ctx.TOK_ERANGE, 0, 0] and offsets.cpu().numpy()[-1] == total
+    assert (buf.cpu().numpy() == 0xEE).all()                              # the blob is untouched
+
+
+# ---- 10. contig_to_bin at the production shape and through every restart ---------------------------------------------------------------
+def _bin_against_the_oracle(tmp_path, model, text, contig, seq, **kw):
+    """the whole file against sitefile.pd_to_bin of oracle.mpileup_to_pd's .pd -> (stats, the .pd)"""
+    from nanosnp_amd.pipeline import contig_to_bin
+    pd, n = rc.oracle_pd(tmp_path, text, seq)
+    assert sitefile.pd_to_bin(pd, tmp_path / "want.bin") == n
+    st = {}
+    got = tmp_path / "got.bin"
+    assert contig_to_bin(model, text, contig, seq, str(got), stats=st, **kw) == n
+    a, b = sitefile.read_arrays(got), sitefile.read_arrays(tmp_path / "want.bin")
+    assert list(a) == list(b)
+    for k in b:
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+    assert got.read_bytes() == (tmp_path / "want.bin").read_bytes()
+    return st, pd
+
+
+@pytest.mark.parametrize("n_other", [600, 1500])
+def test_a_chunk_above_4_mib(tmp_path, model, n_other):
+    """one chunk of more than 1,440 tiles (k_names_scan with two tiles per thread, in place): a site's name comes from a line in another tile;
+    1,500 other lines outnumber the table of 1,024 and the contig runs once more"""
+    text0, seq = rc.synth_text(20261500, 70_000, "ctgE")
+    text, which = rc.rename_lines(text0, n_other, 61)
+    chunks, sizes = rc.chunk_lines(text, 64 << 20)
+    assert len(chunks) == 1 and sizes[0] > 4_194_304 and (which.size > 1024) == (n_other == 1500)
+    st, pd = _bin_against_the_oracle(tmp_path, model, text, "ctgE", seq)
+    assert sum(nm != b"ctgE" for nm, _, _ in rc.pd_fields(pd)) > (20 if n_other == 1500 else 5)
+    assert st.get("restarts", 0) == (1 if n_other == 1500 else 0) and st["chunks"] == 1 + st.get("restarts", 0)
+
+
+def test_three_chunks_and_more_two_of_them_above_4_mib(tmp_path, model):
+    text0, seq = rc.synth_text(20261501, rc.GROWN_COLS, "ctgF")
+    text, which = rc.rename_lines(text0, rc.GROWN_OTHER, 62)
+    chunks, sizes = rc.chunk_lines(text, rc.GROWN_CHUNK)
+    assert len(chunks) >= 3 and sum(s > 4_194_304 for s in sizes) >= 2
+    per_chunk = [int(((which >= lo) & (which < hi)).sum()) for _, _, lo, hi in chunks]
+    assert max(per_chunk) > 1024                                         # the last chunk's table overflows: one restart
+    st, pd = _bin_against_the_oracle(tmp_path, model, text, "ctgF", seq, chunk_bytes=rc.GROWN_CHUNK)
+    assert st.get("restarts", 0) == 1
+
+
+@pytest.mark.parametrize("matrix_dtype", ["int16", "int32"])
+def test_a_count_outside_int16_restarts_the_contig_as_int32(tmp_path, model, matrix_dtype):
+    """33,000 mismatching reads in one column: the device's int16 records report the overflow, the contig is run again with elem 4 and
+    the file is the int32 one pd_to_bin writes; asked for int32 at once, the same bytes without a restart"""
+    contig, seq, text = rc.deep_text()
+    assert _n_chunks(text, rc.DEEP_CHUNK) >= 2
+    st, pd = _bin_against_the_oracle(tmp_path, model, text, contig, seq, chunk_bytes=rc.DEEP_CHUNK, matrix_dtype=matrix_dtype)
+    x = sitefile.read_arrays(tmp_path / "got.bin")["position_matrix"]
+    assert x.dtype == np.int32 and x.shape[0] == 1 and x.min() == -(rc.DEEP_READS + 10) and x.max() == rc.DEEP_READS
+    assert st.get("restarts", 0) == (1 if matrix_dtype == "int16" else 0)
+
+
+def test_three_restart_causes_in_one_call_and_nothing_left_behind(tmp_path):
+    """more than 1,024 other names, a count outside int16 and alt_info that outgrows a first slot, in one text: one cause is handled per
+    pass, so the contig runs four times; a plain fixture on the same model afterwards is exact and runs once"""
+    contig, seq, text, renamed = rc.three_causes_text()
+    assert len(renamed) > 1024 and _n_chunks(text, 64 << 20) == 1
+    m = _model()
+    (tmp_path / "a").mkdir(); (tmp_path / "b").mkdir()
+    st, pd = _bin_against_the_oracle(tmp_path / "a", m, text, contig, seq)
+    assert [p for _, p, _ in rc.pd_fields(pd)] == list(range(50, 250)) + [1000]
+    assert st["restarts"] == 3
+    assert sitefile.read_arrays(tmp_path / "a" / "got.bin")["position_matrix"].dtype == np.int32
+    from nanosnp_amd.pipeline import contig_to_bin
+    text, seq, pd, contig = _fixture("g1")
+    n = sitefile.pd_to_bin(pd, tmp_path / "b" / "want.bin")
+    st = {}
+    assert contig_to_bin(m, text, contig, seq, str(tmp_path / "b" / "got.bin"), stats=st) == n
+    assert st.get("restarts", 0) == 0 and (tmp_path / "b" / "got.bin").read_bytes() == (tmp_path / "b" / "want.bin").read_bytes()
+    assert sitefile.read_arrays(tmp_path / "b" / "got.bin")["position_matrix"].dtype == np.int16
+
+
+def test_a_slot_of_an_earlier_call_is_replaced(tmp_path, alt_case):
+    """slots live on the model: a small contig leaves slots of 1,024 rows, the alt_case text as one chunk then selects 4,827 sites"""
+    from nanosnp_amd.pipeline import contig_to_bin
+    m = _model()
+    text, seq, pd, contig = _fixture("g1")
+    n = sitefile.pd_to_bin(pd, tmp_path / "want.bin")
+    assert contig_to_bin(m, text, contig, seq, str(tmp_path / "got.bin")) == n and n < rc.FIRST_ROWS
+    assert (tmp_path / "got.bin").read_bytes() == (tmp_path / "want.bin").read_bytes()
+    assert m._rec_slots[0].rows == rc.FIRST_ROWS
+    a = alt_case
+    n = sitefile.pd_to_bin(a["pd"], tmp_path / "want2.bin")
+    assert n == 4827 and _n_chunks(a["text"], 64 << 20) == 1
+    st = {}
+    assert contig_to_bin(m, a["text"], a["contig"], a["seq"], str(tmp_path / "got2.bin"), stats=st) == n
+    assert (tmp_path / "got2.bin").read_bytes() == (tmp_path / "want2.bin").read_bytes()
+    assert st.get("restarts", 0) == 0 and m._rec_slots[0].rows >= n
+
+
+def test_a_busy_slot_is_replaced_within_one_call(tmp_path):
+    """three chunks of a few sites each fill the three slots (1,024 rows); the fourth chunk selects more than that and takes the first
+    slot's turn while the writer may still hold it"""
+    contig, seq, text = rc.slot_growth_text()
+    pd, n = rc.oracle_pd(tmp_path, text, seq, "pre")
+    per_chunk = rc.sites_per_chunk(pd, text, rc.SLOT_CHUNK)
+    assert len(per_chunk) == 4 and all(1 <= k < rc.FIRST_ROWS for k in per_chunk[:3]) and per_chunk[3] > rc.FIRST_ROWS
+    m = _model()
+    st, _ = _bin_against_the_oracle(tmp_path, m, text, contig, seq, chunk_bytes=rc.SLOT_CHUNK)
+    assert st.get("restarts", 0) == 0 and st["chunks"] == 4
+    assert [s.rows for s in m._rec_slots[1:]] == [rc.FIRST_ROWS] * 2 and m._rec_slots[0].rows >= per_chunk[3]

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from nanosnp_amd import _lib, pipeline, sitefile
+from tests import records_cases as rc
 
 
 def _rows(n, seed, wide=False):
@@ -171,3 +172,172 @@ def test_refusals_of_process_groups_and_the_host_tokeniser(tmp_path, monkeypatch
         with pytest.raises(NotImplementedError, match="process group"):
             f()
     assert not p.exists() and not os.path.exists(str(p) + ".tmp") and not (tmp_path / "out").exists()
+
+
+# ---- the builders of tests/records_cases.py: what each text must hold for its GPU test to mean anything (oracle only, no GPU) ---------
+
+
+def _newline_free_tiles(text):
+    a = np.frombuffer(text, np.uint8)
+    pad = np.zeros(rc.n_tiles(a.size) * rc.NM_TILE, np.uint8)
+    pad[:a.size] = a
+    return np.flatnonzero((pad.reshape(-1, rc.NM_TILE) == 10).sum(1) == 0).tolist()
+
+
+@pytest.mark.parametrize("newline", [True, False])
+@pytest.mark.parametrize("rest", [1, 4095, 4096])
+@pytest.mark.parametrize("tiles", [1025, 2049])
+def test_line_names_texts_hold_what_they_are_built_for(tiles, rest, newline):
+    text, name = rc.names_text(tiles, rest, newline)
+    per = rc.scan_per(tiles)
+    T = rc.NM_TILE
+    assert len(text) == (tiles - 1) * T + rest and rc.n_tiles(len(text)) == tiles and per == {1025: 2, 2049: 3}[tiles]
+    assert (tiles - 1) // per < 1023                                     # scan threads behind the last owner own nothing
+    assert text.endswith(b"\n") == newline
+    lines = rc.text_lines(text)
+    toks, differ = rc.line_names_rule(text, name)
+    assert len(lines) > 80_000 and min(len(l) for l in lines) >= 29 and sorted(len(l) for l in lines)[-3] <= 70
+    assert 500 < len(differ) < 1300 and {len(toks[i]) for i in differ} == {1, 3, 4, 5, 15, 37, 40, 45}
+    # tiles without a newline: inside the two long lines (the first tiles thread 300 owns, the last tile thread 41 owns and the next)
+    empty = _newline_free_tiles(text)
+    assert empty[:4] == [per * 41 + per - 1, per * 41 + per, per * 300, per * 300 + 1]
+    assert empty[4:] == ([tiles - 1] if rest == 1 and not newline else [])
+    starts = np.concatenate([[0], np.cumsum([len(l) + 1 for l in lines])[:-1]])
+    tile_of = starts // T
+    is_other = np.zeros(len(lines), bool)
+    is_other[differ] = True
+    marked = rc.names_marked_tiles(tiles)
+    assert {0, tiles - 1, tiles - 2, per, 2 * per - 1, ((tiles - 1) // per) * per}.issubset(marked)
+    held = 0
+    for t in marked:                                                     # first and last line start of every marked tile that holds one
+        here = np.flatnonzero(tile_of == t)
+        if here.size:
+            held += 1
+            assert is_other[here[0]] and is_other[here[-1]], t
+    assert held >= len(marked) - 3 and is_other[0] and is_other[-1]
+    # the anchored lines: where they start, and that token / tabs reach over the tile edge
+    by_start = {int(s): i for i, s in enumerate(starts)}
+    for off, kind in rc.names_anchors(tiles).items():
+        i = by_start[off]
+        if kind == "long":
+            assert len(lines[i]) == rc.LN_LONG - 1 and not is_other[i] and is_other[i - 1] and is_other[i + 1]
+            continue
+        assert is_other[i] == kind.endswith("_other"), (off, kind)
+        edge = -(-off // T) * T
+        if kind.startswith("tok"):
+            assert off < edge < off + len(toks[i]) and not lines[i].startswith(b"\t")
+        elif kind.startswith("tabs"):
+            assert lines[i].startswith(b"\t\t\t\t") and off < edge < off + 4 and (off + 4) // T == off // T + 1
+        else:
+            assert off % T == 0
+
+
+def test_site_names_case_alternates_the_contig_name_with_every_length():
+    for n in (1, 2, 5, 64, 4097):
+        centers, line_idx, names = rc.site_names_case(n, 5000)
+        assert np.array_equal(np.diff(centers), np.ones(n - 1, np.int64)) and centers[0] == 16
+        e = line_idx[centers + 16]
+        lens = np.where(e < 0, 0, names[np.maximum(e, 0), 40:44].copy().view(np.int32)[:, 0])
+        assert set(names[:, 40:44].copy().view(np.int32)[:, 0].tolist()) == {1, 2, 36, 37}
+        if n >= 64:
+            pairs = set(zip(lens[:-1].tolist(), lens[1:].tolist()))
+            for l in (1, 2, 36, 37):
+                assert (0, l) in pairs and (l, 0) in pairs                # beside the contig's name, on either side
+            assert {(37, 1), (1, 36), (36, 2), (2, 37), (37, 2), (2, 1)}.issubset(pairs)    # and two entries of different lengths side by side
+        # a row of 83 bytes: three of every four sites start inside a 4-byte word
+        assert n < 4 or sum((83 * j) % 4 != 0 for j in range(n)) * 4 >= 3 * (n - n % 4)
+
+
+@pytest.fixture(scope="module")
+def alt_data(tmp_path_factory):
+    return rc.alt_case_data(tmp_path_factory.mktemp("alt_host"))
+
+
+def test_alt_info_cases_reach_the_scan_and_the_second_copy_sweep(alt_data):
+    want, sp = alt_data["want"], alt_data["specials"]
+    assert len(want) == 4827 and sum(len(v) for v in want.values()) == 131_811 < rc.COPY_SWEEP
+    assert [rc.scan_per(n) for n in rc.ALT_SCAN_N] == [1, 1, 1, 2, 2, 3]
+    for n in rc.ALT_SCAN_N:
+        c = rc.alt_scan_centers(want, n)
+        assert c.size == n and all(int(p) + 1 in want for p in c)
+        assert n < 1024 or np.unique(c).size < n                         # repeats
+    centers, total = rc.alt_sweep_centers(want, sp)
+    assert total == sum(len(want[int(c) + 1]) for c in centers)
+    assert total > rc.COPY_SWEEP + 16 and total % 16 != 0 and total < 2 * rc.COPY_SWEEP
+    big = sp["500 distinct insertions"]
+    assert int((centers + 1 == big).sum()) == 1100 and len(want[big]) > 3800
+    assert all(int(centers[i]) + 1 == big and len(want[int(centers[i + 1]) + 1]) < 40 for i in range(0, 2200, 2))
+    assert (centers.size, total) == (2200, 4_436_141)
+
+
+@pytest.mark.parametrize("n_other", [600, 1500])
+def test_big_chunk_text_is_one_chunk_above_4_mib(tmp_path, n_other):
+    text0, seq = rc.synth_text(20261500, 70_000, "ctgE")
+    text, which = rc.rename_lines(text0, n_other, 61)
+    chunks, sizes = rc.chunk_lines(text, 64 << 20)
+    assert len(chunks) == 1 and sizes[0] == len(text) > 4_194_304 and rc.n_tiles(len(text)) > 1024 and rc.scan_per(rc.n_tiles(len(text))) == 2
+    toks, differ = rc.line_names_rule(text, b"ctgE")
+    assert differ == which.tolist() and (len(differ) > 1024) == (n_other == 1500)
+    assert all(1 <= len(toks[i]) <= 37 for i in differ)
+    pd, n = rc.oracle_pd(tmp_path, text, seq)
+    fields = rc.pd_fields(pd)
+    renamed = [(nm, p) for nm, p, _ in fields if nm != b"ctgE"]
+    assert n > 3000 and len(renamed) > (20 if n_other == 1500 else 5)
+    # a site's name is column 0 of the line at centre + 16 - in another tile than the site's own line for some of them
+    starts = np.concatenate([[0], np.flatnonzero(np.frombuffer(text, np.uint8) == 10) + 1])
+    assert all(toks[p - 1 + 16] == nm for nm, p in renamed)
+    assert sum(starts[p - 1] // 4096 != starts[p - 1 + 16] // 4096 for _, p in renamed) >= 1
+    assert (len(text), rc.n_tiles(len(text)), n, len(renamed)) == {600: (5_905_709, 1442, 3693, 25), 1500: (5_918_489, 1445, 3693, 89)}[n_other]
+
+
+def test_grown_text_has_three_chunks_two_of_them_above_4_mib(tmp_path):
+    text0, seq = rc.synth_text(20261501, rc.GROWN_COLS, "ctgF")
+    text, which = rc.rename_lines(text0, rc.GROWN_OTHER, 62)
+    chunks, sizes = rc.chunk_lines(text, rc.GROWN_CHUNK)
+    assert len(chunks) >= 3 and sum(s > 4_194_304 for s in sizes) >= 2
+    per_chunk = [int(((which >= lo) & (which < hi)).sum()) for _, _, lo, hi in chunks]
+    assert max(per_chunk) > 1024 and min(per_chunk) > 0                  # one chunk's table of 1,024 overflows
+    assert len(text) == 15_709_390 and sizes == [1_250_042, 1_875_038, 2_812_500, 4_218_771, 5_553_039] and per_chunk == [270, 382, 536, 778, 1035]
+
+
+def test_deep_column_leaves_int16_in_the_oracle(tmp_path):
+    from nanosnp_amd import host
+    from oracle import oracle
+    contig, seq, text = rc.deep_text()
+    chunks, sizes = rc.chunk_lines(text, rc.DEEP_CHUNK)
+    assert len(chunks) >= 2
+    pos, off, bases = host.mpileup_parse(text)
+    counts, depth, flags = oracle.encode_columns(bases, off, seq[pos - 1])
+    assert counts.min() == -(rc.DEEP_READS + 10) and counts.max() == rc.DEEP_READS and int(depth.max()) == rc.DEEP_READS + 10
+    assert np.flatnonzero((counts < -32768).any(1) | (counts > 32767).any(1)).tolist() == [299]
+    pd, n = rc.oracle_pd(tmp_path, text, seq)
+    assert n == 1 and rc.pd_fields(pd)[0][1] == 300
+    sitefile.pd_to_bin(pd, tmp_path / "w.bin")
+    assert sitefile.read_arrays(tmp_path / "w.bin")["position_matrix"].dtype == np.int32
+
+
+def test_three_causes_text_holds_all_three(tmp_path):
+    contig, seq, text, renamed = rc.three_causes_text()
+    chunks, sizes = rc.chunk_lines(text, 64 << 20)
+    assert len(chunks) == 1
+    toks, differ = rc.line_names_rule(text, contig.encode())
+    assert differ == renamed and len(differ) > 1024
+    pd, n = rc.oracle_pd(tmp_path, text, seq)
+    fields = rc.pd_fields(pd)
+    assert [p for _, p, _ in fields] == list(range(50, 250)) + [1000]
+    assert sum(len(a) for _, _, a in fields) > 64 * rc.FIRST_ROWS + (1 << 16)        # more than a first slot's blob
+    assert sum(nm != contig.encode() for nm, _, _ in fields) > 100
+    sitefile.pd_to_bin(pd, tmp_path / "w.bin")
+    assert sitefile.read_arrays(tmp_path / "w.bin")["position_matrix"].dtype == np.int32
+
+
+def test_slot_growth_text_selects_few_sites_three_times_then_many(tmp_path):
+    contig, seq, text = rc.slot_growth_text()
+    pd, n = rc.oracle_pd(tmp_path, text, seq)
+    per_chunk = rc.sites_per_chunk(pd, text, rc.SLOT_CHUNK)
+    assert len(per_chunk) == 4 and sum(per_chunk) == n
+    assert all(1 <= k < rc.FIRST_ROWS for k in per_chunk[:3]) and per_chunk[3] > rc.FIRST_ROWS + rc.FIRST_ROWS // 4
+    from nanosnp_amd.pipeline import _cols_for
+    assert _cols_for(rc.SLOT_CHUNK) // 64 < rc.FIRST_ROWS                # a first slot has 1,024 rows at this chunk size
+    assert sum(len(a) for _, _, a in rc.pd_fields(pd)) < 64 * per_chunk[3]              # no blob restart: the rows alone outgrow the slot
+    assert per_chunk == [4, 5, 176, 2737]
