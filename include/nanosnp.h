@@ -388,6 +388,46 @@ int nsnp_pileup_alt_info(nsnp_ctx* ctx, const uint8_t* bases, int64_t n_bytes, c
                          const int32_t* depth, int64_t M, const int64_t* center_idx, int64_t N, const uint8_t* chr_seq, int64_t chr_len,
                          uint8_t* blob, int64_t cap, int64_t* offsets, int64_t* meta, void* stream);
 
+/* The three stage-1 record entries for a chunk that holds SEVERAL contigs (one whole-genome text: make_predict_data.sh:117-234 without the
+ * DNA_ExtractChrPileupData pass, extract_chr_pileup_data/main.cpp:11-80).  They take the chunk's `key` (int64 [M], (cid << NSNP_TOK_KEY_SHIFT)
+ * | pos as nsnp_mpileup_tokenise_contigs leaves it) where the entries above take `pos`, and the resident contig table of that call (names_blob
+ * + name_off, genome + seq_off, n_contigs: device arrays; genome holds at least one readable byte) where they take chr_seq / chr_len / name.
+ *
+ * nsnp_pileup_window_records_keys = nsnp_pileup_window_records2 (make_predict_data/main.cpp:76-127; the name of make_candidate_snp_tensor/
+ * main.cpp:248): per site cid = key[centre] >> NSNP_TOK_KEY_SHIFT, p = key[centre] & (2^NSNP_TOK_KEY_SHIFT - 1); the 33 reference bases are
+ * genome[seq_off[cid] + ...], bounded by the contig's OWN length seq_off[cid + 1] - seq_off[cid]; the name is the table's name cid unless
+ * line_idx[centre + 16] names an entry of `names` (nsnp_mpileup_line_names_contigs of the same lines; line_idx NULL: always the table's).
+ * cap_names: the entries `names` holds - an index at or above it is treated like the "no room" entry 0x7fffffff: not followed, meta[2] set.
+ *   site_key int64 [N]  key[centre] of every site (any memory the device can write, aligned to 8 bytes): the host cuts a chunk's records by
+ *                       contig from it
+ * meta = { N, overflow, status, 0 } as above; status != 0 also for a centre whose key is the filler or whose cid lies outside [0, n_contigs),
+ * a window outside the site's own contig, a name longer than 37 bytes: all of them clamped, never followed.  The window matrix is the
+ * kernel of the entries above.  Three launches, no scratch memory. */
+int nsnp_pileup_window_records_keys(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const int64_t* key, int64_t M, int64_t N,
+                                    const uint8_t* names_blob, const int64_t* name_off, const uint8_t* genome, const int64_t* seq_off,
+                                    int64_t n_contigs, int elem, const int32_t* line_idx, const uint8_t* names, int64_t cap_names,
+                                    void* position_matrix, uint8_t* position, int64_t* site_key, int64_t* meta, void* stream);
+
+/* nsnp_mpileup_line_names against the table instead of one name: cid int32 [lines] as nsnp_mpileup_tokenise_contigs wrote it for the same
+ * text (same line order).  line_idx[line] = -1 where the line's first tab-delimited token (split_line: leading tabs skipped) equals the
+ * table name of cid[line], and where cid[line] < 0 (such a line never emits a site); else the index of the entry the token was copied to.
+ * The CONTIG of a line follows the splitter's rule (the bytes in front of the first C isspace byte, extract_chr_pileup_data/main.cpp:11-19),
+ * the name the window program prints is the tab token (make_candidate_snp_tensor/main.cpp:248): for a line "chr1 x<TAB>..." they differ, and
+ * this entry keeps the position string exact ("chr1 x").  meta and the overflow rule: as nsnp_mpileup_line_names.  Four launches, no
+ * workgroup waits for another; scratch in the context: 8 bytes per 4 KB of text. */
+int nsnp_mpileup_line_names_contigs(nsnp_ctx* ctx, const uint8_t* text, int64_t text_len, const int32_t* cid, const uint8_t* names_blob,
+                                    const int64_t* name_off, int64_t n_contigs, int64_t cap_lines, int32_t* line_idx, uint8_t* names,
+                                    int64_t cap_names, int64_t* meta, void* stream);
+
+/* nsnp_pileup_alt_info (tensor_maker.cpp:83-169, main.cpp:220-251) with key for pos and the table's genome for chr_seq: the 'D' keys read
+ * genome[seq_off[cid] + p + q] only while p + q lies below the OWN contig's length and meet NUL beyond it - in a back-to-back genome the next
+ * contig's bases lie right there.  A site whose key is the filler or whose cid lies outside [0, n_contigs) is a contig of length 0, and sets
+ * NSNP_TOK_EPOS in the status.  blob / offsets / meta = { bytes needed, status, 0, 0 }, NSNP_TOK_ERANGE, the untouched blob, the four launches
+ * and the scratch: as nsnp_pileup_alt_info. */
+int nsnp_pileup_alt_info_keys(nsnp_ctx* ctx, const uint8_t* bases, int64_t n_bytes, const int64_t* col_off, const uint8_t* ref, const int64_t* key,
+                              const int32_t* depth, int64_t M, const int64_t* center_idx, int64_t N, const uint8_t* genome,
+                              const int64_t* seq_off, int64_t n_contigs, uint8_t* blob, int64_t cap, int64_t* offsets, int64_t* meta, void* stream);
+
 /* ---- HaplotypeModel ------------------------------------------------------------------- */
 /* seq/bq/mq/hap: device int32 [N,D,L] planes as write_to_bins.py:44-61 stores them (padding
  * rows are -2); ref_row: device int32 [N,L].  out: device fp32 [N,105,L] -- float64 math as

@@ -67,6 +67,12 @@ _SIGNATURES = {
                                           C.c_void_p]),
     "nsnp_pileup_alt_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_window_records_keys": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_int64] + [C.c_void_p] * 5),
+    "nsnp_mpileup_line_names_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_int64, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_alt_info_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_mpileup_tokenise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
     "nsnp_mpileup_tokenise_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 5 + [C.c_void_p] * 9),
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -694,6 +700,106 @@ class Context:
             need = int(meta[0])
             if need > cap:
                 return self.pileup_alt_info(bases, col_off, ref, pos, depth, center_idx, chr_seq, cap=need, offsets=offsets, meta=meta, stream=stream)
+        return blob, offsets[:n + 1], meta
+
+    def mpileup_line_names_contigs(self, text, cid, table, cap_lines=None, cap_names=64, line_idx=None, names=None, meta=None, stream=None):
+        """mpileup_line_names against a ContigTable (nsnp_mpileup_line_names_contigs): cid int32 per line as mpileup_tokenise_contigs wrote it
+        for the same device text -> (line_idx int32 [cap_lines]: -1 where the line's first token is the table name of its contig or the line
+        belongs to no wanted contig, else its entry in names; names uint8 [cap_names, 44]; meta int64 [4] = {lines that differ, status})"""
+        import torch
+        dev = text.device
+        cap_lines = int(cid.numel() if cap_lines is None else cap_lines)
+        if line_idx is None:
+            line_idx = torch.empty(max(cap_lines, 1), dtype=torch.int32, device=dev)
+        if names is None:
+            names = torch.empty((max(int(cap_names), 1), self.NAME_ENTRY), dtype=torch.uint8, device=dev)
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        assert text.dtype == torch.uint8 and text.is_cuda and line_idx.dtype == torch.int32 and line_idx.is_cuda and names.is_cuda
+        if cid.dtype != torch.int32 or not cid.is_cuda or not cid.is_contiguous() or cid.numel() < cap_lines or line_idx.numel() < cap_lines:
+            raise NanoSNPError("line_names_contigs: cid and line_idx must be contiguous device int32 tensors of at least cap_lines entries")
+        check(self.lib.nsnp_mpileup_line_names_contigs(self.handle, _dptr(text), int(text.numel()), _dptr(cid), _dptr(table.names_blob),
+                                                       _dptr(table.name_off), len(table), cap_lines, _dptr(line_idx), _dptr(names),
+                                                       int(names.shape[0]), meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_mpileup_line_names_contigs")
+        return line_idx, names, meta
+
+    def pileup_window_records_keys(self, counts, center_idx, key, table, elem=2, position_matrix=None, position=None, site_key=None, meta=None,
+                                   stream=None, line_names=None, cap_names=None):
+        """pileup_window_records for a chunk of several contigs (nsnp_pileup_window_records_keys): key int64 [M] as mpileup_tokenise_contigs
+        wrote it, table the ContigTable of that call -> (position_matrix [N,33,18], position uint8 [N,83], site_key int64 [N] = key[centre],
+        meta int64 [4] = {N, int16 overflow, status, 0}).  line_names: (line_idx, names) of mpileup_line_names_contigs for the same lines;
+        cap_names: the entries of names that count (default: all it holds).  The four outputs may be given: device or pinned tensors."""
+        import torch
+        n, m = int(center_idx.shape[0]), int(counts.shape[0])
+        dev = counts.device
+        assert counts.dtype == torch.int32 and center_idx.dtype == torch.int64 and key.dtype == torch.int64
+        if key.shape[0] != m or not key.is_contiguous():
+            raise NanoSNPError("window_records_keys: key [M] must match counts [M,18]")
+        dt = {2: torch.int16, 4: torch.int32}.get(elem)
+        if dt is None:
+            raise NanoSNPError("elem: 2 (int16) or 4 (int32)")
+        if position_matrix is None:
+            position_matrix = torch.empty((max(n, 1), 33, 18), dtype=dt, device=dev)
+        if position is None:
+            position = torch.empty((max(n, 1), self.POSITION_WIDTH), dtype=torch.uint8, device=dev)
+        if site_key is None:
+            site_key = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        for t, what in ((position_matrix, "position_matrix"), (position, "position"), (site_key, "site_key"), (meta, "meta")):
+            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
+                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
+        if (position_matrix.dtype != dt or position_matrix.numel() < n * 594 or position.dtype != torch.uint8 or position.numel() < n * self.POSITION_WIDTH
+                or site_key.dtype != torch.int64 or site_key.numel() < n):
+            raise NanoSNPError("window_records_keys: output buffers too small or of the wrong type")
+        line_idx, names = line_names if line_names is not None else (None, None)
+        if line_idx is not None and (line_idx.dtype != torch.int32 or line_idx.numel() < m or not line_idx.is_cuda or not names.is_cuda):
+            raise NanoSNPError("line_names: device int32 [M] and the name table of mpileup_line_names_contigs")
+        n_names = int(names.numel() // self.NAME_ENTRY) if names is not None else 0
+        cap_names = n_names if cap_names is None else int(cap_names)
+        if cap_names < 0 or cap_names > n_names:
+            raise NanoSNPError("window_records_keys: cap_names beyond the name table")
+        check(self.lib.nsnp_pileup_window_records_keys(self.handle, _dptr(counts), _dptr(center_idx), _dptr(key), m, n, _dptr(table.names_blob),
+                                                       _dptr(table.name_off), _dptr(table.genome), _dptr(table.seq_off), len(table), int(elem),
+                                                       _dptr(line_idx), _dptr(names), cap_names, position_matrix.data_ptr(), position.data_ptr(),
+                                                       site_key.data_ptr(), meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_window_records_keys")
+        return (position_matrix.view(-1)[:n * 594].view(n, 33, 18), position.view(-1)[:n * self.POSITION_WIDTH].view(n, self.POSITION_WIDTH),
+                site_key.view(-1)[:n], meta)
+
+    def pileup_alt_info_keys(self, bases, col_off, ref, key, depth, center_idx, table, cap=None, blob=None, offsets=None, meta=None, stream=None):
+        """pileup_alt_info for a chunk of several contigs (nsnp_pileup_alt_info_keys): key int64 [M] for pos, the ContigTable for chr_seq -> (blob
+        uint8 [cap], offsets int64 [N + 1], meta int64 [4] = {bytes needed, status, 0, 0}); everything else as pileup_alt_info."""
+        import torch
+        n, m = int(center_idx.shape[0]), int(ref.shape[0])
+        dev = ref.device
+        assert bases.dtype == torch.uint8 and col_off.dtype == torch.int64 and ref.dtype == torch.uint8 and key.dtype == torch.int64
+        assert depth.dtype == torch.int32 and center_idx.dtype == torch.int64
+        if col_off.shape[0] != m + 1 or key.shape[0] != m or depth.shape[0] != m:
+            raise NanoSNPError("alt_info_keys: col_off [M + 1], key [M] and depth [M] must match ref [M]")
+        retry = cap is None and blob is None
+        cap = int(blob.numel() if blob is not None else (64 * n + 4096 if cap is None else cap))
+        if blob is None:
+            blob = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        for t, what in ((blob, "blob"), (offsets, "offsets"), (meta, "meta")):
+            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
+                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
+        if blob.numel() < cap or offsets.numel() < n + 1:
+            raise NanoSNPError("alt_info_keys: output buffers too small")
+        check(self.lib.nsnp_pileup_alt_info_keys(self.handle, _dptr(bases), int(bases.numel()), _dptr(col_off), _dptr(ref), _dptr(key), _dptr(depth), m,
+                                                 _dptr(center_idx), n, _dptr(table.genome), _dptr(table.seq_off), len(table), blob.data_ptr(), cap,
+                                                 offsets.data_ptr(), meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_alt_info_keys")
+        if retry:
+            (stream or torch.cuda.current_stream(dev)).synchronize()
+            need = int(meta[0])
+            if need > cap:
+                return self.pileup_alt_info_keys(bases, col_off, ref, key, depth, center_idx, table, cap=need, offsets=offsets, meta=meta, stream=stream)
         return blob, offsets[:n + 1], meta
 
     def pileup_gather_windows(self, counts, center_idx, stream=None):

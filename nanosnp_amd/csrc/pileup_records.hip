@@ -86,19 +86,9 @@ __global__ __launch_bounds__(REC_BLOCK) void k_window_matrix(const int32_t* __re
     if (bad) meta[2] = 1;
 }
 
-// byte b of the position string of one site: name ':' decimal(pos) ':' REF33 zeros
-// other: the site's own name entry (NSNP_NAME_ENTRY bytes: 40 name bytes, then the length as int32), or null for the contig's name
-__device__ __forceinline__ int position_byte(const RecName& name, const uint8_t* __restrict__ other, int64_t p, int b,
-                                             const uint8_t* __restrict__ chr_seq, int64_t chr_len, bool& bad)
+// byte b behind "name:" of the position string of one site: decimal(pos) ':' REF33 zeros, the bases from chr_seq[0, chr_len) (chr_len >= 1)
+__device__ __forceinline__ int position_tail(int64_t p, int b, const uint8_t* __restrict__ chr_seq, int64_t chr_len, bool& bad)
 {
-    int nlen = name.len;
-    if (other) {
-        nlen = *reinterpret_cast<const int32_t*>(other + 40);
-        if (nlen < 1 || nlen > REC_NAME_MAX) { bad = true; nlen = nlen < 1 ? 1 : REC_NAME_MAX; }      // (no room for 11 digits and the bases behind it)
-    }
-    if (b < nlen) return other ? other[b] : name.b[b];
-    if (b == nlen) return ':';
-    b -= nlen + 1;
     if (p < 0) { p = 0; bad = true; }
     if (p > 99999999999ll) { p = 99999999999ll; bad = true; }
     int nd = 1;
@@ -116,6 +106,21 @@ __device__ __forceinline__ int position_byte(const RecName& name, const uint8_t*
     if (i >= chr_len) { i = chr_len - 1; bad = true; }
     const int c = chr_seq[i];
     return (c >= 'a' && c <= 'z') ? c - 32 : c;              // toupper in the C locale
+}
+
+// byte b of the position string of one site: name ':' decimal(pos) ':' REF33 zeros
+// other: the site's own name entry (NSNP_NAME_ENTRY bytes: 40 name bytes, then the length as int32), or null for the contig's name
+__device__ __forceinline__ int position_byte(const RecName& name, const uint8_t* __restrict__ other, int64_t p, int b,
+                                             const uint8_t* __restrict__ chr_seq, int64_t chr_len, bool& bad)
+{
+    int nlen = name.len;
+    if (other) {
+        nlen = *reinterpret_cast<const int32_t*>(other + 40);
+        if (nlen < 1 || nlen > REC_NAME_MAX) { bad = true; nlen = nlen < 1 ? 1 : REC_NAME_MAX; }      // (no room for 11 digits and the bases behind it)
+    }
+    if (b < nlen) return other ? other[b] : name.b[b];
+    if (b == nlen) return ':';
+    return position_tail(p, b - nlen - 1, chr_seq, chr_len, bad);
 }
 
 __global__ __launch_bounds__(REC_BLOCK) void k_position_strings(const int64_t* __restrict__ center_idx, const int64_t* __restrict__ pos, int64_t N, int64_t M,
@@ -145,6 +150,78 @@ __global__ __launch_bounds__(REC_BLOCK) void k_position_strings(const int64_t* _
         if (e0 + j < total) {
             w |= (unsigned)position_byte(name, other, p, b, chr_seq, chr_len, bad) << (8 * j);
             if (++b == POSW && n + 1 < N) { b = 0; ++n; c = safe_center(center_idx, n, M, bad); p = pos[c]; other = own_name(c); }
+        }
+    }
+    if (e0 + 4 <= total) *reinterpret_cast<unsigned*>(out + e0) = w;
+    else for (int j = 0; j < 4; ++j) if (e0 + j < total) out[e0 + j] = (uint8_t)(w >> (8 * j));
+    if (bad) meta[2] = 1;
+}
+
+// ---- the same records for a chunk that holds SEVERAL contigs -------------------------------------------------------------------------
+// A site's contig comes out of its key ((cid << NSNP_TOK_KEY_SHIFT) | pos, as nsnp_mpileup_tokenise_contigs leaves it): its reference bases
+// out of the resident genome, bounded by the contig's OWN length, its name out of the table's names.
+constexpr int64_t KEY_POS_MASK = (1ll << NSNP_TOK_KEY_SHIFT) - 1;
+
+// contig and position of a key; a filler key (negative) or a contig outside the table: contig -1, position 0
+__device__ __forceinline__ int64_t key_contig(int64_t key, int64_t n_contigs, int64_t& p)
+{
+    const int64_t cid = key >> NSNP_TOK_KEY_SHIFT;
+    if (key < 0 || cid >= n_contigs) { p = 0; return -1; }
+    p = key & KEY_POS_MASK;
+    return cid;
+}
+
+struct KeySite {                                             // what the position string of one site is made of
+    const uint8_t* nm; int nlen;                             // its name: the table's, or the emitting line's own token
+    const uint8_t* seq; int64_t len;                         // its contig's sequence
+    int64_t p, key;
+};
+
+__global__ __launch_bounds__(REC_BLOCK) void k_position_strings_keys(const int64_t* __restrict__ center_idx, const int64_t* __restrict__ key, int64_t N, int64_t M,
+                                                                     const uint8_t* __restrict__ names_blob, const int64_t* __restrict__ name_off,
+                                                                     const uint8_t* __restrict__ genome, const int64_t* __restrict__ seq_off, int64_t n_contigs,
+                                                                     const int32_t* __restrict__ line_idx, const uint8_t* __restrict__ names, int64_t cap_names,
+                                                                     uint8_t* __restrict__ out, int64_t* __restrict__ site_key, int64_t* __restrict__ meta)
+{
+    bool bad = false;
+    auto site = [&](int64_t n) -> KeySite {
+        KeySite s;
+        const int64_t c = safe_center(center_idx, n, M, bad);
+        s.key = key[c];
+        int64_t cid = key_contig(s.key, n_contigs, s.p);
+        if (cid < 0) { cid = 0; bad = true; }                // (a filler or a contig outside the table: contig 0 at position 0, which clamps)
+        const int64_t o = seq_off[cid];
+        s.seq = genome + o; s.len = seq_off[cid + 1] - o;
+        if (s.len < 1) { s.seq = genome; s.len = 1; bad = true; }      // (an empty contig holds no site: the genome's first byte stands in)
+        const int64_t no = name_off[cid];
+        s.nm = names_blob + no; s.nlen = (int)(name_off[cid + 1] - no);
+        if (s.nlen < 0 || s.nlen > REC_NAME_MAX) { bad = true; s.nlen = s.nlen < 0 ? 0 : REC_NAME_MAX; }
+        // the name of a site is column 0 of the line that EMITS it (main.cpp:248: the line at centre + 16); line_idx[line] < 0: the table's
+        if (line_idx) {
+            const int32_t e = line_idx[c + PCENTER];
+            if (e == 0x7fffffff || (int64_t)e >= cap_names) bad = true;      // (an entry the table had no room for, or one outside it: not followed)
+            else if (e >= 0) {
+                s.nm = names + (int64_t)e * NSNP_NAME_ENTRY;
+                s.nlen = *reinterpret_cast<const int32_t*>(s.nm + 40);
+                if (s.nlen < 1 || s.nlen > REC_NAME_MAX) { bad = true; s.nlen = s.nlen < 1 ? 1 : REC_NAME_MAX; }
+            }
+        }
+        return s;
+    };
+    const int64_t total = N * POSW;
+    const int64_t e0 = ((int64_t)blockIdx.x * REC_BLOCK + threadIdx.x) * 4;
+    if (e0 >= total) return;
+    int64_t n = e0 / POSW;
+    int b = (int)(e0 - n * POSW);
+    KeySite s = site(n);
+    unsigned w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (e0 + j < total) {
+            if (b == 0) site_key[n] = s.key;                 // (the thread that owns a site's first byte: one 8-byte store per site)
+            const int v = b < s.nlen ? s.nm[b] : b == s.nlen ? ':' : position_tail(s.p, b - s.nlen - 1, s.seq, s.len, bad);
+            w |= (unsigned)v << (8 * j);
+            if (++b == POSW && n + 1 < N) { b = 0; ++n; s = site(n); }
         }
     }
     if (e0 + 4 <= total) *reinterpret_cast<unsigned*>(out + e0) = w;
@@ -239,6 +316,54 @@ __global__ __launch_bounds__(REC_BLOCK) void k_names_emit(const uint8_t* __restr
                 }
                 line_idx[line] = idx;
             }
+        }
+        line += text[i] == '\n';
+    }
+}
+
+// k_names_emit against the contig table: the name a line is compared with is the table's name of cid[line] (the contig tokeniser's, for the
+// same text); a line of no wanted contig (cid < 0) never emits a site and keeps -1
+__global__ __launch_bounds__(REC_BLOCK) void k_names_emit_contigs(const uint8_t* __restrict__ text, int64_t len, const int64_t* __restrict__ blk,
+                                                                  const int32_t* __restrict__ cid, const uint8_t* __restrict__ names_blob,
+                                                                  const int64_t* __restrict__ name_off, int64_t n_contigs,
+                                                                  int64_t cap_lines, int32_t* __restrict__ line_idx, uint8_t* __restrict__ names, int64_t cap_names,
+                                                                  unsigned long long* __restrict__ counter)
+{
+    __shared__ int wsum[REC_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t i0 = ((int64_t)blockIdx.x * REC_BLOCK + tid) * NM_PER;
+    const int mine = nm_newlines(text, i0, len);
+    int inc = mine;                                          // inclusive scan over the wave
+    for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(inc, o); if (lane >= o) inc += v; }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int64_t line = blk[blockIdx.x] + inc - mine;             // newlines in front of byte i0
+    for (int w = 0; w < wave; ++w) line += wsum[w];
+    for (int j = 0; j < NM_PER; ++j) {
+        const int64_t i = i0 + j;
+        if (i >= len) break;
+        if ((i == 0 || text[i - 1] == '\n') && line < cap_lines) {
+            const int64_t c = cid[line];
+            int32_t idx = -1;
+            if (c >= 0 && c < n_contigs) {
+                int64_t a = i;
+                while (a < len && text[a] == '\t') ++a;
+                int64_t e = a;
+                while (e < len && text[e] != '\t' && text[e] != '\n') ++e;
+                const int64_t tl = e - a, no = name_off[c], nl = name_off[c + 1] - no;
+                bool same = tl == nl;
+                for (int64_t k = 0; same && k < nl; ++k) same = text[a + k] == names_blob[no + k];
+                if (!same) {
+                    const unsigned long long slot = atomicAdd(counter, 1ull);
+                    idx = slot < (unsigned long long)cap_names ? (int32_t)slot : 0x7fffffff;      // (beyond the table: the caller sees the count and runs again)
+                    if (slot < (unsigned long long)cap_names) {
+                        uint8_t* dst = names + (int64_t)slot * NSNP_NAME_ENTRY;
+                        for (int k = 0; k < 40; ++k) dst[k] = k < tl ? text[a + k] : 0;
+                        *reinterpret_cast<int32_t*>(dst + 40) = (int32_t)(tl > 0x7fffffff ? 0x7fffffff : tl);
+                    }
+                }
+            }
+            line_idx[line] = idx;
         }
         line += text[i] == '\n';
     }
@@ -441,6 +566,58 @@ __global__ __launch_bounds__(ALT_BLOCK) void k_alt_write(const uint8_t* __restri
     alt_text(bases, b0, b1, ref[c], p, depth[c], chr_seq, chr_len, out);
 }
 
+// k_alt_sizes / k_alt_write for a chunk of several contigs: the 'D' keys read the site's OWN contig out of the resident genome and meet
+// NUL at ITS end (the next contig's bases lie right behind it); a filler key or a contig outside the table is a contig of length 0
+__device__ __forceinline__ bool alt_key_site(const int64_t* __restrict__ key, int64_t c, const uint8_t* __restrict__ genome,
+                                             const int64_t* __restrict__ seq_off, int64_t n_contigs, int64_t& p, const uint8_t*& seq, int64_t& len)
+{
+    const int64_t cid = key_contig(key[c], n_contigs, p);
+    seq = genome; len = 0;
+    if (cid < 0) return false;
+    const int64_t o = seq_off[cid];
+    seq = genome + o; len = seq_off[cid + 1] - o;
+    return true;
+}
+
+__global__ __launch_bounds__(ALT_BLOCK) void k_alt_sizes_keys(const uint8_t* __restrict__ bases, int64_t n_bytes, const int64_t* __restrict__ col_off,
+                                                              const uint8_t* __restrict__ ref, const int64_t* __restrict__ key, const int32_t* __restrict__ depth,
+                                                              int64_t M, const int64_t* __restrict__ center_idx, int64_t N,
+                                                              const uint8_t* __restrict__ genome, const int64_t* __restrict__ seq_off, int64_t n_contigs,
+                                                              int64_t* __restrict__ sizes)
+{
+    const int64_t n = (int64_t)blockIdx.x * ALT_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    int64_t c, b0, b1;
+    CountSink out{0, 0};
+    if (alt_column(center_idx, n, M, col_off, n_bytes, c, b0, b1)) {
+        int64_t p, len; const uint8_t* seq;
+        alt_key_site(key, c, genome, seq_off, n_contigs, p, seq, len);
+        alt_text(bases, b0, b1, ref[c], p, depth[c], seq, len, out);
+    }
+    sizes[n] = out.keep;
+}
+
+__global__ __launch_bounds__(ALT_BLOCK) void k_alt_write_keys(const uint8_t* __restrict__ bases, int64_t n_bytes, const int64_t* __restrict__ col_off,
+                                                              const uint8_t* __restrict__ ref, const int64_t* __restrict__ key, const int32_t* __restrict__ depth,
+                                                              int64_t M, const int64_t* __restrict__ center_idx, int64_t N,
+                                                              const uint8_t* __restrict__ genome, const int64_t* __restrict__ seq_off, int64_t n_contigs,
+                                                              const int64_t* __restrict__ scan, int64_t cap, uint8_t* __restrict__ stage,
+                                                              int64_t* __restrict__ offsets, int64_t* __restrict__ meta)
+{
+    const int64_t n = (int64_t)blockIdx.x * ALT_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const int64_t o = scan[n], lim = scan[n + 1] - o;
+    offsets[n] = o;
+    int64_t c, b0, b1;
+    if (!alt_column(center_idx, n, M, col_off, n_bytes, c, b0, b1)) return;
+    int64_t p, len; const uint8_t* seq;
+    if (!alt_key_site(key, c, genome, seq_off, n_contigs, p, seq, len))
+        meta[1] = (scan[N] > cap ? NSNP_TOK_ERANGE : 0) | NSNP_TOK_EPOS;      // (behind k_alt_scan's word; every writer stores the same one)
+    if (scan[N] > cap || lim <= 0) return;
+    WriteSink out{stage + o, 0, lim};
+    alt_text(bases, b0, b1, ref[c], p, depth[c], seq, len, out);
+}
+
 // staging -> blob: whole 16-byte stores where the blob is aligned for them, the total read from the device
 __global__ __launch_bounds__(REC_BLOCK) void k_alt_copy(const uint8_t* __restrict__ stage, const int64_t* __restrict__ total_p, int64_t cap,
                                                         uint8_t* __restrict__ blob)
@@ -550,6 +727,103 @@ extern "C" int nsnp_pileup_alt_info(nsnp_ctx* ctx, const uint8_t* bases, int64_t
     if (N > 0) {
         hipLaunchKernelGGL(k_alt_write, dim3(grid), dim3(ALT_BLOCK), 0, s, bases, n_bytes, col_off, ref, pos, depth, M, center_idx, N, chr_seq, chr_len,
                            (const int64_t*)scan, cap, stage, offsets);
+        if (cap > 0) {
+            int64_t blocks = NSNP_CDIV(cap, (int64_t)REC_BLOCK * 16);
+            if (blocks > 1024) blocks = 1024;
+            hipLaunchKernelGGL(k_alt_copy, dim3((unsigned)blocks), dim3(REC_BLOCK), 0, s, (const uint8_t*)stage, (const int64_t*)(scan + N), cap, blob);
+        }
+    }
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+extern "C" int nsnp_pileup_window_records_keys(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const int64_t* key, int64_t M, int64_t N,
+                                               const uint8_t* names_blob, const int64_t* name_off, const uint8_t* genome, const int64_t* seq_off,
+                                               int64_t n_contigs, int elem, const int32_t* line_idx, const uint8_t* names, int64_t cap_names,
+                                               void* position_matrix, uint8_t* position, int64_t* site_key, int64_t* meta, void* stream)
+{
+    if (line_idx && (!names || cap_names < 1)) return NSNP_EINVAL;
+    if (!ctx || !meta || N < 0 || M < 0 || (elem != 2 && elem != 4) || cap_names < 0 || n_contigs < 0 || n_contigs > NSNP_TOK_MAX_CONTIGS) return NSNP_EINVAL;
+    if (N > 0 && (!counts || !center_idx || !key || !names_blob || !name_off || !genome || !seq_off || n_contigs < 1 || !position_matrix || !position ||
+                  !site_key || M < PW))
+        return NSNP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(position_matrix) & 15) || (reinterpret_cast<uintptr_t>(position) & 3) || (reinterpret_cast<uintptr_t>(site_key) & 7))
+        return NSNP_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_records_meta, dim3(1), dim3(64), 0, s, N, meta);
+    if (N > 0) {
+        const int64_t units = NSNP_CDIV(N * REC_W * elem, (int64_t)16);
+        if (elem == 2)
+            hipLaunchKernelGGL(k_window_matrix<int16_t>, dim3((unsigned)NSNP_CDIV(units, (int64_t)REC_BLOCK)), dim3(REC_BLOCK), 0, s, counts, center_idx, N, M,
+                               (int16_t*)position_matrix, meta);
+        else
+            hipLaunchKernelGGL(k_window_matrix<int32_t>, dim3((unsigned)NSNP_CDIV(units, (int64_t)REC_BLOCK)), dim3(REC_BLOCK), 0, s, counts, center_idx, N, M,
+                               (int32_t*)position_matrix, meta);
+        const int64_t words = NSNP_CDIV(N * POSW, (int64_t)4);
+        hipLaunchKernelGGL(k_position_strings_keys, dim3((unsigned)NSNP_CDIV(words, (int64_t)REC_BLOCK)), dim3(REC_BLOCK), 0, s, center_idx, key, N, M,
+                           names_blob, name_off, genome, seq_off, n_contigs, line_idx, names, cap_names, position, site_key, meta);
+    }
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+extern "C" int nsnp_mpileup_line_names_contigs(nsnp_ctx* ctx, const uint8_t* text, int64_t text_len, const int32_t* cid, const uint8_t* names_blob,
+                                               const int64_t* name_off, int64_t n_contigs, int64_t cap_lines, int32_t* line_idx, uint8_t* names,
+                                               int64_t cap_names, int64_t* meta, void* stream)
+{
+    if (!ctx || !meta || text_len < 0 || cap_lines < 0 || cap_names < 0 || cap_names > 0x7ffffff0 || n_contigs < 0 || n_contigs > NSNP_TOK_MAX_CONTIGS)
+        return NSNP_EINVAL;
+    if ((text_len > 0 && (!text || !line_idx || !cid)) || (cap_names > 0 && !names) || (n_contigs > 0 && (!names_blob || !name_off))) return NSNP_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_blocks = NSNP_CDIV(text_len, (int64_t)NM_TILE);
+    const size_t need = ((size_t)n_blocks + 2) * sizeof(int64_t);
+    if (ctx->rec_tmp_bytes < need) {
+        NSNP_HIP(ctx, hipStreamSynchronize(s));
+        if (ctx->rec_tmp) (void)hipFree(ctx->rec_tmp);
+        ctx->rec_tmp = nullptr; ctx->rec_tmp_bytes = 0;
+        NSNP_HIP(ctx, hipMalloc(&ctx->rec_tmp, need + need / 4));
+        ctx->rec_tmp_bytes = need + need / 4;
+    }
+    int64_t* blk = (int64_t*)ctx->rec_tmp;
+    unsigned long long* counter = (unsigned long long*)(blk + n_blocks);
+    if (n_blocks > 0) hipLaunchKernelGGL(k_names_count, dim3((unsigned)n_blocks), dim3(REC_BLOCK), 0, s, text, text_len, blk);
+    hipLaunchKernelGGL(k_names_scan, dim3(1), dim3(1024), 0, s, blk, n_blocks, counter);
+    if (n_blocks > 0)
+        hipLaunchKernelGGL(k_names_emit_contigs, dim3((unsigned)n_blocks), dim3(REC_BLOCK), 0, s, text, text_len, (const int64_t*)blk, cid, names_blob, name_off,
+                           n_contigs, cap_lines, line_idx, names, cap_names, counter);
+    hipLaunchKernelGGL(k_names_meta, dim3(1), dim3(64), 0, s, (const unsigned long long*)counter, cap_names, meta);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+extern "C" int nsnp_pileup_alt_info_keys(nsnp_ctx* ctx, const uint8_t* bases, int64_t n_bytes, const int64_t* col_off, const uint8_t* ref, const int64_t* key,
+                                         const int32_t* depth, int64_t M, const int64_t* center_idx, int64_t N, const uint8_t* genome,
+                                         const int64_t* seq_off, int64_t n_contigs, uint8_t* blob, int64_t cap, int64_t* offsets, int64_t* meta, void* stream)
+{
+    if (!ctx || !meta || !offsets || N < 0 || M < 0 || cap < 0 || n_bytes < 0 || n_contigs < 0 || n_contigs > NSNP_TOK_MAX_CONTIGS || (cap > 0 && !blob))
+        return NSNP_EINVAL;
+    if (N > 0 && (!col_off || !ref || !key || !depth || !center_idx || (n_bytes > 0 && !bases) || (n_contigs > 0 && (!genome || !seq_off)))) return NSNP_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    // scratch: N + 1 scanned sizes, then the staging blob (16-byte aligned)
+    const size_t scan_bytes = (((size_t)N + 1) * sizeof(int64_t) + 15) & ~(size_t)15;
+    const size_t need = scan_bytes + (size_t)cap + 16;
+    if (ctx->rec_tmp_bytes < need) {
+        NSNP_HIP(ctx, hipStreamSynchronize(s));
+        if (ctx->rec_tmp) (void)hipFree(ctx->rec_tmp);
+        ctx->rec_tmp = nullptr; ctx->rec_tmp_bytes = 0;
+        NSNP_HIP(ctx, hipMalloc(&ctx->rec_tmp, need + need / 4));
+        ctx->rec_tmp_bytes = need + need / 4;
+    }
+    int64_t* scan = (int64_t*)ctx->rec_tmp;
+    uint8_t* stage = (uint8_t*)ctx->rec_tmp + scan_bytes;
+    const unsigned grid = (unsigned)NSNP_CDIV(N, (int64_t)ALT_BLOCK);
+    if (N > 0)
+        hipLaunchKernelGGL(k_alt_sizes_keys, dim3(grid), dim3(ALT_BLOCK), 0, s, bases, n_bytes, col_off, ref, key, depth, M, center_idx, N, genome, seq_off,
+                           n_contigs, scan);
+    hipLaunchKernelGGL(k_alt_scan, dim3(1), dim3(1024), 0, s, scan, N, cap, offsets, meta);
+    if (N > 0) {
+        hipLaunchKernelGGL(k_alt_write_keys, dim3(grid), dim3(ALT_BLOCK), 0, s, bases, n_bytes, col_off, ref, key, depth, M, center_idx, N, genome, seq_off,
+                           n_contigs, (const int64_t*)scan, cap, stage, offsets, meta);
         if (cap > 0) {
             int64_t blocks = NSNP_CDIV(cap, (int64_t)REC_BLOCK * 16);
             if (blocks > 1024) blocks = 1024;

@@ -1471,12 +1471,17 @@ class ContigRuns:
         return started
 
 
-def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stats, on_rows, cap_runs=None):
+def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stats, on_rows, cap_runs=None, indel_min_af=None, records=None,
+                     name_cap=1024):
     """_stream_contig_dev for a text of several contigs: the same chunk loop over the same buffer sets (_run_text_chunks, _text_chunk_sets)
     with nsnp_mpileup_tokenise_contigs in the tokeniser's place and its
     `key` where the per-contig path hands a position to the window rule and the call rows.  The run table of every chunk arrives in pinned
     memory with its counts.  on_rows(rows_k, started): the call rows of a chunk ([n, 13] float64 on the device, column 0 = key) or None, and
-    the wanted contigs that start among the chunk's own lines; called in chunk order as soon as the chunk's last kernels are issued."""
+    the wanted contigs that start among the chunk's own lines; called in chunk order as soon as the chunk's last kernels are issued.
+    records (mpileup_to_bins; None: nothing below changes): the tokenise station also compares column 0 of every line with the table name of
+    its contig while the chunk's text is still resident (nsnp_mpileup_line_names_contigs), and the third station issues no forward -
+    records(k, counts, own centres, _ChunkColumns with the keys as pos, main) is called for every chunk that owns sites; on_rows is not
+    called, the wanted contigs the text holds are tracker.order.  indel_min_af (None: min_af) goes to the encode."""
     import time
     import torch
     ctx = model.ctx
@@ -1502,11 +1507,16 @@ def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stat
         model._ctok_meta_pin = torch.zeros((n_ring, 4), dtype=torch.int64, pin_memory=True)
     meta_pin, tok_pin, run_pin = _count_slots(model, "_meta_pin", len(ranges)), model._ctok_meta_pin, model._run_pin
     started = {}                                           # chunk -> the wanted contigs that start among its own lines
+    names_pin = _count_slots(model, "_names_meta_pin", n_ring) if records is not None else None
+    names_of = {}
 
     def tokenise(k, text_k, cs):
         ks = ksets[k % len(csets)]
         ctx.mpileup_tokenise_contigs_into(text_k, table, cs.pos, cs.off, cs.bases, cs.ref, ks.cid, ks.key, run_pin[k % n_ring],
                                           tok_pin[k % n_ring], stream=main)
+        if records is not None:
+            names_of[k] = ctx.mpileup_line_names_contigs(text_k, ks.cid, table, min(int(text_k.numel()) // 10 + 2, int(ks.cid.numel())), name_cap,
+                                                         meta=names_pin[k % n_ring], stream=main)[:2]
 
     def encode(k, cs, n_lo, n_hi):
         M, nb, status, n_runs = tok_pin[k % n_ring].tolist()
@@ -1529,14 +1539,31 @@ def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stat
         started[k] = tracker.feed(run_pin[k % n_ring, :n_runs].numpy(), M, n_lo, M - n_hi)
         own = M - n_lo - n_hi
         st["columns"] += own
+        names = None
+        if records is not None:
+            names = names_of.pop(k)
+            n_other, n_status, _, _ = names_pin[k % n_ring].tolist()
+            if n_status:
+                raise _NamesOverflow(n_other)
+            if n_other == 0:
+                names = None                                 # (every line names its contig: the records carry the table's names)
         if own <= 0:
             return None
         d_key, d_off, d_bases, d_ref = ksets[k % len(csets)].key[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
-        counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage)
+        counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage, indel_min_af=indel_min_af)
         center = ctx.pileup_select_sites_range(d_key, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
+        if records is not None:
+            return d_key, counts, center, _ChunkColumns(d_bases, d_off, d_ref, d_key, depth, None, names)
         return d_key, counts, center
 
     def calls(k, job):
+        if records is not None:
+            started.pop(k)
+            if job is not None:
+                _, c_lo, c_hi, _ = meta_pin[k].tolist()
+                if c_hi > c_lo:
+                    records(k, job[1], job[2][c_lo:c_hi], job[3], main)
+            return
         rows_k = None
         if job is not None:
             d_key, counts, center = job
@@ -1717,6 +1744,7 @@ class _RecSlot:
         self.position = torch.empty((self.rows, Context.POSITION_WIDTH), dtype=torch.uint8, pin_memory=True)
         self.blob = torch.empty(int(blob_bytes), dtype=torch.uint8, pin_memory=True)
         self.offsets = torch.empty(self.rows + 1, dtype=torch.int64, pin_memory=True)
+        self.site_key = torch.empty(max(self.rows, 1), dtype=torch.int64, pin_memory=True)          # (mpileup_to_bins: the key of every site)
         self.meta = torch.zeros((2, 4), dtype=torch.int64, pin_memory=True)                         # window_records' and alt_info's
         self.busy = None                                                                           # the writer thread's future over this slot
 
@@ -1756,7 +1784,7 @@ def contig_to_bin(model, mpileup_text, contig, chr_seq, path, *, alt_info=True, 
     The name in a position string is column 0 of the line that emits the site (the line at centre + 16), as the reference prints it:
     `contig` in any text samtools or the splitter wrote; a line with another token there has that token (nsnp_mpileup_line_names).  Not
     together with an extended BED (NotImplementedError when such a line is met), and a token longer than 37 bytes is refused.
-    NOT done here: one whole-genome text (call_mpileup-style keys), sharding over a process group, a .pd TEXT writer, the reference's
+    NOT done here: one whole-genome text (mpileup_to_bins does that), sharding over a process group, a .pd TEXT writer, the reference's
     .tensor / .alt_info side files."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
@@ -1918,3 +1946,291 @@ def make_pileup_bins(model, contigs, fasta_path, fai_text, out_dir, **kw):
                     except BufferError:                      # (an exception on its way up still holds views of the mapping)
                         pass
     return out
+
+
+# ---- one whole-genome mpileup text -> every <chr>.pd.bin (make_predict_data.sh:117-234 without the splitter's pass) ------------------------
+def cut_records_by_contig(site_key, alt_offsets=None):
+    """The records of one chunk, cut by contig.  site_key: int64 [n], the key of every site in line order ((contig index << _lib.KEY_SHIFT) |
+    position: nsnp_pileup_window_records_keys); alt_offsets: int64 [n + 1] into the chunk's alt_info blob, or None
+    -> [(contig index, lo, hi, blob_lo, blob_hi, offsets)] in the order the contigs appear: rows [lo, hi), their texts blob[blob_lo:blob_hi]
+    and offsets int64 [hi - lo + 1] REBASED to start at 0 (blob_lo = blob_hi = 0 and offsets None without alt_offsets).  A contig that ends
+    exactly at the chunk's last site is simply the last piece.  NanoSNPError when a contig's rows come in two pieces."""
+    from ._lib import KEY_SHIFT, NanoSNPError
+    k = np.asarray(site_key, np.int64).reshape(-1)
+    if not k.size:
+        return []
+    offs = None if alt_offsets is None else np.asarray(alt_offsets, np.int64).reshape(-1)
+    if offs is not None and offs.size != k.size + 1:
+        raise NanoSNPError("records: alt_offsets must hold one more entry than site_key")
+    cid = k >> KEY_SHIFT
+    edges = np.flatnonzero(cid[1:] != cid[:-1]) + 1
+    lo = np.concatenate([[0], edges]); hi = np.concatenate([edges, [k.size]])
+    out = []
+    for a, b in zip(lo.tolist(), hi.tolist()):
+        if offs is None:
+            out.append((int(cid[a]), a, b, 0, 0, None))
+        else:
+            out.append((int(cid[a]), a, b, int(offs[a]), int(offs[b]), offs[a:b + 1] - offs[a]))
+    if len({c for c, *_ in out}) != len(out):
+        raise NanoSNPError("records: the sites of one contig come in two separate pieces")
+    return out
+
+
+class _BinStaging:
+    """The window files of one mpileup_to_bins call while they are written: every contig's sitefile.PileupBinWriter writes to a staging name
+    inside out_dir, and commit() renames the finished files to <out_dir>/<name>.pd.bin only after the whole text has ended without error;
+    abort() leaves neither a staging nor a .tmp file of this call, and whatever was in out_dir before stays as it was.  The pieces of a
+    contig arrive one after another (a contig is one run of the text), so one writer is open at a time."""
+
+    def __init__(self, out_dir, names, matrix_dtype="int16", alt_info=True):
+        import uuid
+        self.out_dir, self.names, self.matrix_dtype, self.alt_info = out_dir, list(names), matrix_dtype, bool(alt_info)
+        self.tag = f".nsnp-staging-{os.getpid()}-{uuid.uuid4().hex[:12]}"
+        self.cur = self.cur_cid = None
+        self.done = {}                                       # contig index -> sites, of the staging files that are complete
+
+    def staging_path(self, cid):
+        return os.path.join(self.out_dir, f"{self.tag}.{int(cid)}")
+
+    def _finish(self):
+        if self.cur is not None:
+            cur, self.cur = self.cur, None
+            self.done[self.cur_cid] = cur.close()            # (close() removes its .tmp itself when it fails)
+
+    def append(self, cid, x, position, blob=None, offsets=None):
+        """the next piece of contig `cid`, as PileupBinWriter.append takes it"""
+        from ._lib import NanoSNPError
+        if self.cur is None or self.cur_cid != cid:
+            self._finish()
+            if cid in self.done or not 0 <= cid < len(self.names):
+                raise NanoSNPError(f"records: contig index {cid} outside the table or in two separate pieces")
+            from . import sitefile
+            self.cur_cid, self.cur = cid, sitefile.PileupBinWriter(self.staging_path(cid), self.matrix_dtype, self.alt_info)
+        if self.alt_info:
+            self.cur.append(x, position, blob, offsets)
+        else:
+            self.cur.append(x, position)
+
+    def restart(self, matrix_dtype=None):
+        """drops everything written so far: the text is streamed again"""
+        self.abort()
+        self.matrix_dtype = matrix_dtype or self.matrix_dtype
+
+    def commit(self, order):
+        """order: the wanted contigs the text holds, in its order (ContigRuns.order) - one without sites gets its empty file here.
+        -> {name: sites}; the files are in place."""
+        from . import sitefile
+        from ._lib import NanoSNPError
+        self._finish()
+        if set(self.done) - set(order):
+            raise NanoSNPError("records: sites of a contig the text's runs do not hold")
+        for cid in order:
+            if cid not in self.done:
+                self.done[cid] = sitefile.PileupBinWriter(self.staging_path(cid), self.matrix_dtype, self.alt_info).close()
+        out = {}
+        for cid in order:
+            os.replace(self.staging_path(cid), os.path.join(self.out_dir, f"{self.names[cid]}.pd.bin"))
+            out[self.names[cid]] = self.done.pop(cid)
+        return out
+
+    def abort(self):
+        if self.cur is not None:
+            cur, self.cur = self.cur, None
+            cur.abort()
+        for cid in list(self.done):
+            try:
+                os.remove(self.staging_path(cid))
+            except OSError:
+                pass
+        self.done = {}
+
+
+def _staged_bins(out_dir, names, matrix_dtype, alt_info, run_pass, st):
+    """The file side of mpileup_to_bins: run_pass(staging, state) streams the text once, appending to `staging` -> (run again?, the wanted
+    contigs the text holds in its order); state = {elem, blob_min, name_cap} says how the next pass differs.  Every pass but the last is
+    dropped whole; the files are renamed into place when the last one has ended, and on any error nothing of this call is left in out_dir
+    (out_dir itself neither, when this call made it).  -> {name: sites}"""
+    made = not os.path.isdir(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    staging = _BinStaging(out_dir, names, matrix_dtype, alt_info)
+    state = dict(elem=2 if matrix_dtype == "int16" else 4, blob_min=0, name_cap=1024)
+    try:
+        while True:
+            again, order = run_pass(staging, state)
+            if not again:
+                break
+            st["restarts"] = st.get("restarts", 0) + 1
+            staging.restart("int16" if state["elem"] == 2 else "int32")
+        return staging.commit(order)
+    except BaseException:
+        staging.abort()
+        if made:
+            try:
+                os.rmdir(out_dir)
+            except OSError:
+                pass
+        raise
+
+
+def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_af, min_coverage, st, alt_info, state, staging, pool):
+    """one pass of mpileup_to_bins over the text -> (True when it has to be run again - state says how: elem 4, blob_min bytes per slot, or
+    name_cap entries per name table -, the wanted contigs the text holds in its order)"""
+    import torch
+    from ._lib import NanoSNPError
+    elem = state["elem"]
+    text_len = int(_as_bytes_like(text)[1].size)
+    slots = getattr(model, "_rec_slots", None)
+    if slots is None:
+        slots = model._rec_slots = [None, None, None]
+    flag = dict(overflow=False, alt_need=0, status=0)
+    turn, spans = [0], []
+
+    def write_piece(slot, n, done):
+        done.synchronize()
+        m = slot.meta.numpy()
+        if m[0, 1]:
+            flag["overflow"] = True
+        if m[0, 2]:
+            flag["status"] = int(m[0, 2])
+        if alt_info and (m[1, 1] & ctx.TOK_ERANGE):
+            flag["alt_need"] = max(flag["alt_need"], int(m[1, 0]))
+        if alt_info and (m[1, 1] & ~ctx.TOK_ERANGE):
+            flag["status"] = int(m[1, 1])
+        if flag["overflow"] or flag["alt_need"] or flag["status"]:
+            return                                           # (the pass is run again, or refused: nothing more is appended)
+        x = slot.matrix.numpy().view(np.int16 if elem == 2 else np.int32)[:n * 594].reshape(n, 33, 18)
+        position, blob = slot.position.numpy(), slot.blob.numpy()
+        # the rows are ascending in line order: every contig of the chunk is one piece
+        for cid, a, b, b_lo, b_hi, offs in cut_records_by_contig(slot.site_key.numpy()[:n], slot.offsets.numpy()[:n + 1] if alt_info else None):
+            staging.append(cid, x[a:b], position[a:b], blob[b_lo:b_hi] if alt_info else None, offs)
+        st["record_bytes"] = st.get("record_bytes", 0) + n * (594 * elem + 83) + (int(m[1, 0]) + 8 * n if alt_info else 0)
+
+    def records(k, counts, centers, cols, main):
+        if flag["overflow"] or flag["alt_need"] or flag["status"]:
+            return                                           # (this pass is lost: the rest of it only has to end)
+        n = int(centers.shape[0])
+        i = turn[0] % 3
+        turn[0] += 1
+        slot = slots[i]
+        if slot is not None and slot.busy is not None:
+            slot.busy.result()                               # the writer is done with the slot's previous chunk (three chunks back)
+            slot.busy = None
+        want_blob = max(64 * n + (1 << 16), state["blob_min"])
+        if slot is None or slot.rows < n or slot.blob.numel() < want_blob:
+            rows = max(n + n // 4, _cols_for(min(int(chunk_bytes), text_len)) // 64, 1024 if slot is None else slot.rows)
+            slot = slots[i] = _RecSlot(rows, max(64 * rows + (1 << 16), state["blob_min"]))
+        timed = st.get("time_records")                       # (as contig_to_bin: HIP-event time of the record kernels)
+        if timed:
+            t0, t1, t2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            t0.record(main)
+        ctx.pileup_window_records_keys(counts, centers, cols.pos, table, elem, position_matrix=slot.matrix_as(elem), position=slot.position,
+                                       site_key=slot.site_key, meta=slot.meta[0], stream=main, line_names=cols.names)
+        if timed:
+            t1.record(main)
+        if alt_info:
+            ctx.pileup_alt_info_keys(cols.bases, cols.off, cols.ref, cols.pos, cols.depth, centers, table, blob=slot.blob, offsets=slot.offsets,
+                                     meta=slot.meta[1], stream=main)
+        if timed:
+            t2.record(main)
+            spans.append((t0, t1, t2))
+        done = torch.cuda.Event(); done.record(main)
+        slot.busy = pool.submit(write_piece, slot, n, done)
+
+    def drain(swallow):
+        for slot in slots:
+            if slot is not None and slot.busy is not None:
+                busy, slot.busy = slot.busy, None
+                try:
+                    busy.result()
+                except BaseException:
+                    if not swallow:
+                        raise
+
+    try:
+        with host.gc_paused():
+            tracker = _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, st, None, indel_min_af=indel_min_af, records=records,
+                                       name_cap=state["name_cap"])
+        drain(False)
+        for t0, t1, t2 in spans:
+            st["window_records_s"] = st.get("window_records_s", 0.0) + t0.elapsed_time(t1) * 1e-3
+            st["alt_info_s"] = st.get("alt_info_s", 0.0) + t1.elapsed_time(t2) * 1e-3
+            st["record_chunks"] = st.get("record_chunks", 0) + 1
+    except _NamesOverflow as e:
+        drain(True)
+        state["name_cap"] = 2 * e.need + 64
+        return True, None
+    except BaseException:
+        drain(True)                                          # (the streams have been waited for: the writer's pieces end at once)
+        raise
+    if flag["status"]:
+        raise NanoSNPError(f"a selected site outside the columns or its contig, or a name longer than 37 bytes in column 0 (record status {flag['status']})")
+    if flag["overflow"]:
+        if elem == 4:
+            raise NanoSNPError("int16 overflow reported for int32 records")
+        state["elem"] = 4
+        return True, None
+    if flag["alt_need"]:
+        state["blob_min"] = 2 * flag["alt_need"]
+        return True, None
+    return False, list(tracker.order)
+
+
+def mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir, contigs=None, *, alt_info=True, matrix_dtype="int16", min_af=0.12,
+                    indel_min_af=None, min_coverage=6, chunk_bytes=64 << 20, stats=None):
+    """Stage s1 from the file the reference's stage 1 starts from: ONE mpileup text holding every contig (samtools mpileup BAM -o
+    pileup_data, make_predict_data.sh:117) -> <out_dir>/<name>.pd.bin for every wanted contig the text holds, each byte for byte what
+    contig_to_bin writes for the <name>.mpileup the splitter (DNA_ExtractChrPileupData) would have cut - make_predict_data.sh:167-234 in one
+    call, the text read once.  Returns {name: sites} in text order.
+
+    mpileup_path_or_bytes: a path, or bytes / mmap / uint8 array; contigs: the wanted names (None: every name of fai_text); model: only the
+    holder of the context and the buffer sets (no weights needed).  The text is the ONE stream of call_mpileup (_stream_text_dev): the device
+    finds the contig of every line and hands on key = (contig index << 36) | position; where call_mpileup runs the forward, this entry
+    issues nsnp_pileup_window_records_keys and nsnp_pileup_alt_info_keys - reference bases and names out of the resident contig table, every
+    site bounded by its OWN contig - into one of three pinned slots, and a writer thread cuts the slot's rows by contig (the key of every
+    site comes back with them) and appends each piece to that contig's sitefile.PileupBinWriter.  The name in a position string is column
+    0 of the emitting line (nsnp_mpileup_line_names_contigs), as in contig_to_bin.
+    Which contigs get a file: a wanted contig the text holds, even one without a site (its file equals contig_to_bin of its lines); a wanted
+    contig the text does not hold gets none, as the splitter writes none.  A wanted contig in two separate runs raises NanoSNPError, an
+    empty line is refused, as in call_mpileup.
+    The writers write to staging names inside out_dir, renamed into place only after the whole text has ended without error: on any error
+    no staging or .tmp file of this call is left and whatever was in out_dir stays as it was.
+    Restarts are of the WHOLE text: an alt_info text that outgrows its slot or a name table that is too small run it again with larger
+    ones, and a count outside int16 runs it again as int32 - after which EVERY file of the run is int32 (make_pileup_bins over the split
+    files would make only the overflowing contig's file int32).  stats: chunks, columns, sites, record_bytes, restarts; with
+    stats["time_records"] = True also window_records_s / alt_info_s / record_chunks (HIP-event sums), as contig_to_bin reports them.
+    Refused before anything is touched: a process group of more than one rank, NSNP_TOKENISE=host, no GPU (_bins_refusals); ValueError for
+    a wanted name that is empty, holds NUL or is longer than 37 bytes."""
+    from concurrent.futures import ThreadPoolExecutor
+    from . import _lib, sitefile
+    _bins_refusals()
+    if matrix_dtype not in ("int16", "int32"):
+        raise sitefile.SiteFileError("matrix_dtype: 'int16' or 'int32'")
+    names = [str(n) for n in (contigs if contigs is not None else fai_names(fai_text))]
+    for n in names:
+        b = n.encode()
+        if not b or b"\0" in b or len(b) + 1 + 11 + 1 + 33 > sitefile.POSITION_WIDTH:
+            raise ValueError(f"{n!r}: a contig name of 1 to {sitefile.POSITION_WIDTH - 46} bytes without NUL is needed for the "
+                             f"{sitefile.POSITION_WIDTH}-byte position field")
+    table = _lib.ContigTable(fasta=fasta_path, names=names, device=model.ctx.device)
+    st = _stream_stats(stats)
+    g = text = None
+    if isinstance(mpileup_path_or_bytes, (str, os.PathLike)):
+        g = open(mpileup_path_or_bytes, "rb")
+        size = os.fstat(g.fileno()).st_size
+        text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if size else None
+    try:
+        src = (text if text is not None else b"") if g is not None else mpileup_path_or_bytes
+        with ThreadPoolExecutor(max_workers=1) as pool:
+            out = _staged_bins(out_dir, names, matrix_dtype, alt_info,
+                               lambda staging, state: _text_records_pass(model, model.ctx, src, table, chunk_bytes, min_af, indel_min_af, min_coverage,
+                                                                         st, alt_info, state, staging, pool), st)
+        st["sites"] = st.get("sites", 0) + sum(out.values())
+        return out
+    finally:
+        if text is not None:
+            try:
+                text.close()
+            except BufferError:                  # (an exception on its way up still holds views of the mapping)
+                pass
+        if g is not None:
+            g.close()
