@@ -333,6 +333,43 @@ int nsnp_mpileup_tokenise_contigs(nsnp_ctx* ctx, const uint8_t* text, int64_t te
                                   int64_t cap_cols, int64_t cap_bytes, int64_t cap_runs, int64_t* pos, int64_t* col_off, uint8_t* bases,
                                   uint8_t* ref, int32_t* cid, int64_t* key, int64_t* runs, int64_t* meta, void* stream);
 
+/* ---- BED region filters for a chunk that holds SEVERAL contigs (key = (cid << NSNP_TOK_KEY_SHIFT) | pos) -------------------------------
+ * The bitmap TABLE lies beside the contig table of nsnp_mpileup_tokenise_contigs (same n_contigs, same seq_off), all device arrays:
+ *   bed_words uint32 []               the bitmaps of all contigs, back to back
+ *   bed_off   int64 [n_contigs + 1]   ascending word offsets starting at 0: contig c owns words [bed_off[c], bed_off[c + 1]), laid out as the
+ *                                     single bitmaps above - bit i of the contig is bit i & 31 of its word i >> 5
+ * Contig c has min(seq_off[c + 1] - seq_off[c], 32 * (bed_off[c + 1] - bed_off[c])) bits.  A contig the BED does not mention takes ZERO
+ * words and every one of its bits reads 0; bits at or beyond the contig's length read 0 even where the last word has them set; nothing is
+ * read outside a contig's own words, so a range that reaches past the end of contig A never sees the first bits of contig B (the reference's
+ * one list over all contigs does).  A key with cid < 0 (the filler -2^62) or cid >= n_contigs never touches the table and reads 0.  bed_words
+ * may be NULL when no contig owns a word.
+ *
+ * nsnp_pileup_filter_columns_keys = nsnp_pileup_filter_columns for keyed columns: a column stays when cid = key >> NSNP_TOK_KEY_SHIFT lies in
+ * [0, n_contigs) and bit (key & (2^NSNP_TOK_KEY_SHIFT - 1)) - 1 of contig cid is set - filler keys and keys of an unknown cid are dropped
+ * (they separate nothing the high bits of the kept keys do not already separate: no step between two contigs is + 1).  aux / aux_out (both
+ * NULL, or device int32 [M] each): one value per column that is compacted with it, e.g. line_idx of nsnp_mpileup_line_names_contigs - the line
+ * that EMITS a site is the 16th KEPT line behind its centre.  Capacities, the tail [K, M) (key -2^62, reference byte 'N', empty columns,
+ * aux_out -1), meta = { K, kept bytes, image of own_lo, image of own_hi }, the 16 readable bytes in front of bases_out, the three launches and
+ * the scratch in the context: as nsnp_pileup_filter_columns (the count and scatter kernels are the same templates, k_filter_scan the same
+ * kernel).  NSNP_EINVAL: as there (an output that is its input, a NULL array with M > 0, n_contigs < 0, n_contigs > 0 without bed_off /
+ * seq_off), and aux without aux_out or the reverse. */
+int nsnp_pileup_filter_columns_keys(nsnp_ctx* ctx, const int64_t* key, const int64_t* col_off, const uint8_t* bases, const uint8_t* ref,
+                                    const int32_t* aux, int64_t M, const uint32_t* bed_words, const int64_t* bed_off, const int64_t* seq_off,
+                                    int64_t n_contigs, int64_t own_lo, int64_t own_hi,
+                                    int64_t* key_out, int64_t* off_out, uint8_t* bases_out, uint8_t* ref_out, int32_t* aux_out, int64_t* meta,
+                                    void* stream);
+
+/* nsnp_pileup_encode_columns3 with `key` where it takes pos and the bitmap table where it takes conf_bits / conf_n_bits: with a table
+ * (bed_off != NULL) NSNP_FLAG_CANDIDATE additionally needs a set bit in [p - 1, p + max_del_length + 1) of the column's OWN contig, clipped to
+ * that contig's bits - a deletion at the last positions of contig A whose reach passes A's end is tested against A's bits alone; a filler
+ * column or one of an unknown cid is never a candidate.  max_del is optional.  counts, depth, max_del and the other flag bits equal
+ * nsnp_pileup_encode_columns2 / 3 bit for bit; without a table (bed_off NULL: bed_words must be NULL, too) so does NSNP_FLAG_CANDIDATE.
+ * NSNP_EINVAL: a table without seq_off or (M > 0) without key, bed_words without bed_off, n_contigs < 0.  One launch. */
+int nsnp_pileup_encode_columns_keys(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off, const uint8_t* ref, const int64_t* key,
+                                    int64_t M, double snp_min_af, double indel_min_af, int min_coverage, const uint32_t* bed_words,
+                                    const int64_t* bed_off, const int64_t* seq_off, int64_t n_contigs,
+                                    int32_t* counts, int32_t* depth, uint8_t* flags, int32_t* max_del, void* stream);
+
 /* x[n][t][c] = counts[center_idx[n]-16+t][c]; x: device int32 [N,33,18]. */
 int nsnp_pileup_gather_windows(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx,
                                int64_t N, int32_t* x, void* stream);

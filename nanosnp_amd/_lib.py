@@ -52,6 +52,9 @@ _SIGNATURES = {
                                               C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
     "nsnp_pileup_filter_columns": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
+    "nsnp_pileup_filter_columns_keys": (C.c_int, [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 7),
+    "nsnp_pileup_encode_columns_keys": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 3 + [C.c_int64] +
+                                        [C.c_void_p] * 5),
     "nsnp_pileup_select_sites_range_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                      C.c_void_p]),
     "nsnp_pileup_select_sites": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
@@ -175,6 +178,69 @@ class ContigTable:
 
     def __len__(self):
         return len(self.names)
+
+
+
+class BedTable:
+    """The BED bitmaps of a whole-genome call beside its ContigTable (include/nanosnp.h, "the bitmap TABLE"): per BED a pair (words: device
+    int32 tensor of 32-bit words, off: device int64 [n + 1] word offsets), `ext` for -extended_confident_bed and `conf` for -confident_bed, None
+    where there is no such BED.  bed arguments: a path or {contig: intervals} (bed.table_bitmaps says how they are read).  The words travel
+    contig by contig through one pinned buffer: a human genome's bitmap is 390 MB per BED and never exists as one host array, as the
+    ContigTable never holds the genome on the host."""
+    PIN_WORDS = 1 << 22
+
+    def __init__(self, table, extended_bed=None, confident_bed=None, fai=None):
+        self.table = table
+        self.ext = None if extended_bed is None else self._build(table, extended_bed, fai)
+        self.conf = None if confident_bed is None else self._build(table, confident_bed, fai)
+
+    @staticmethod
+    def _build(table, bed, fai):
+        import numpy as np
+        import torch
+        from . import bed as _bed
+        dev = table.seq_off.device
+        iv = _bed.table_intervals(bed, table.names, table.lengths, fai)
+        off = _bed.table_word_offsets(iv, table.lengths)
+        words = torch.empty(max(int(off[-1]), 1), dtype=torch.int32, device=dev)[:int(off[-1])]
+        pin = torch.empty(BedTable.PIN_WORDS, dtype=torch.int32, pin_memory=True)
+        for c, ivc in enumerate(iv):
+            if off[c + 1] == off[c]:
+                continue
+            w = _bed.bed_bitmap(ivc, table.lengths[c]).view(np.int32)
+            for a in range(0, w.size, pin.numel()):
+                n = min(pin.numel(), w.size - a)
+                pin.numpy()[:n] = w[a:a + n]
+                words[int(off[c]) + a:int(off[c]) + a + n].copy_(pin[:n], non_blocking=True)
+                torch.cuda.current_stream(dev).synchronize()         # (the pinned buffer is written again)
+            del w
+        return words, torch.from_numpy(off).to(dev)
+
+    @staticmethod
+    def upload(table, words, off):
+        """host arrays as bed.table_bitmaps returns them -> the device pair (words, off); NanoSNPError unless off is int64 [n + 1], ascending
+        from 0 to the number of words"""
+        import numpy as np
+        import torch
+        words = np.ascontiguousarray(words, np.uint32).reshape(-1)
+        off = np.ascontiguousarray(off, np.int64).reshape(-1)
+        if off.size != len(table) + 1 or off[0] != 0 or bool((np.diff(off) < 0).any()) or int(off[-1]) != words.size:
+            raise NanoSNPError("bed table: off must be int64 [n_contigs + 1], ascending from 0 to the number of words")
+        dev = table.seq_off.device
+        d = torch.empty(max(words.size, 1), dtype=torch.int32, device=dev)[:words.size]
+        if words.size:
+            d.copy_(torch.from_numpy(words.view(np.int32)))
+        return d, torch.from_numpy(off).to(dev)
+
+
+def _check_bed_pair(bed, table, what):
+    import torch
+    words, off = bed
+    if (words.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not words.is_cuda or not words.is_contiguous()
+            or off.dtype != torch.int64 or not off.is_cuda or not off.is_contiguous() or off.numel() != len(table) + 1):
+        raise NanoSNPError(f"{what}: bed = (device 32-bit words, device int64 [n_contigs + 1] word offsets) of this contig table (BedTable)")
+    return words, off
+
 
 _lib = None
 
@@ -465,6 +531,67 @@ class Context:
                                                   _stream_ptr(stream)),
               self.handle, "nsnp_pileup_filter_columns")
         return po[:m], oo[:m + 1], bo[:max(nb, 1)], ro[:m], meta
+
+    def pileup_filter_columns_keys(self, key, col_off, bases, ref, table, bed, aux=None, own_lo=0, own_hi=None, meta=None, out=None, stream=None):
+        """pileup_filter_columns for the keyed columns of a whole-genome chunk (nsnp_pileup_filter_columns_keys): table the ContigTable of the
+        keys, bed = (words, off) of a BedTable (its .ext); a column stays when the bit of its position is set in its OWN contig's bitmap.
+        aux: device int32 [M] compacted with the columns (-1 behind the kept ones), or None -> (key_out [M], off_out [M + 1], bases_out,
+        ref_out [M], aux_out [M] or None, meta).  out: the four (with aux: five) output tensors of an earlier call to reuse."""
+        import torch
+        m = int(key.shape[0])
+        dev = key.device
+        own_hi = m if own_hi is None else own_hi
+        nb = int(bases.numel())
+        words, off = _check_bed_pair(bed, table, "filter_columns_keys")
+        if key.dtype != torch.int64 or not key.is_contiguous() or col_off.shape[0] != m + 1 or ref.shape[0] != m:
+            raise NanoSNPError("filter_columns_keys: col_off [M + 1] and ref [M] must match the contiguous int64 key [M]")
+        if aux is not None and (aux.dtype != torch.int32 or not aux.is_cuda or not aux.is_contiguous() or aux.numel() < m):
+            raise NanoSNPError("filter_columns_keys: aux must be a contiguous device int32 tensor of at least M entries")
+        if out is None:
+            pad = self.FILTER_FRONT_PAD
+            out = (torch.empty(max(m, 1), dtype=torch.int64, device=dev), torch.empty(m + 1, dtype=torch.int64, device=dev),
+                   torch.empty(pad + max(nb, 1), dtype=torch.uint8, device=dev)[pad:], torch.empty(max(m, 1), dtype=torch.uint8, device=dev))
+            if aux is not None:
+                out += (torch.empty(max(m, 1), dtype=torch.int32, device=dev),)
+        ko, oo, bo, ro = out[:4]
+        ao = out[4] if aux is not None and len(out) > 4 else None
+        if ko.numel() < m or oo.numel() < m + 1 or bo.numel() < nb or ro.numel() < m or (aux is not None and (ao is None or ao.numel() < m or ao.dtype != torch.int32)):
+            raise NanoSNPError("filter_columns_keys: output buffers too small")
+        meta = meta if meta is not None else torch.zeros(4, dtype=torch.int64, device=dev)
+        check(self.lib.nsnp_pileup_filter_columns_keys(self.handle, _dptr(key), _dptr(col_off), _dptr(bases), _dptr(ref), _dptr(aux), m,
+                                                       _dptr(words) if words.numel() else None, _dptr(off), _dptr(table.seq_off), len(table),
+                                                       int(own_lo), int(own_hi), _dptr(ko), _dptr(oo), _dptr(bo), _dptr(ro), _dptr(ao),
+                                                       meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_filter_columns_keys")
+        return ko[:m], oo[:m + 1], bo[:max(nb, 1)], ro[:m], (ao[:m] if ao is not None else None), meta
+
+    def pileup_encode_columns_keys(self, bases, col_off, ref, key=None, table=None, bed=None, min_af=0.12, min_coverage=6, stream=None,
+                                   indel_min_af=None, want_max_del=True):
+        """pileup_encode_columns3 for the keyed columns of a whole-genome chunk (nsnp_pileup_encode_columns_keys) -> (counts, depth, flags,
+        max_del int32 [M] or None).  bed = (words, off) of a BedTable (its .conf) with table the ContigTable and key int64 [M]: a candidate
+        then needs a set bit in [p - 1, p + max_del_length + 1) of its OWN contig; bed None: the candidates of pileup_encode_columns."""
+        import torch
+        assert bases.is_cuda and bases.dtype == torch.uint8 and col_off.dtype == torch.int64 and ref.dtype == torch.uint8
+        m = ref.shape[0]
+        dev = ref.device
+        words = off = None
+        if bed is not None:
+            if table is None or key is None:
+                raise NanoSNPError("encode_columns_keys: a bed table is tested at keys: key and table are needed")
+            words, off = _check_bed_pair(bed, table, "encode_columns_keys")
+        if key is not None and (key.dtype != torch.int64 or key.shape[0] != m or not key.is_contiguous()):
+            raise NanoSNPError("key: a contiguous int64 tensor of one key per column")
+        counts = torch.empty((m, 18), dtype=torch.int32, device=dev)
+        depth = torch.empty(m, dtype=torch.int32, device=dev)
+        flags = torch.empty(m, dtype=torch.uint8, device=dev)
+        max_del = torch.empty(m, dtype=torch.int32, device=dev) if want_max_del else None
+        check(self.lib.nsnp_pileup_encode_columns_keys(self.handle, _dptr(bases), _dptr(col_off), _dptr(ref), _dptr(key), m,
+                                                       float(min_af), float(min_af if indel_min_af is None else indel_min_af), int(min_coverage),
+                                                       _dptr(words) if words is not None and words.numel() else None, _dptr(off),
+                                                       _dptr(table.seq_off) if table is not None else None, len(table) if table is not None else 0,
+                                                       _dptr(counts), _dptr(depth), _dptr(flags), _dptr(max_del), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_encode_columns_keys")
+        return counts, depth, flags, max_del
 
     def pileup_select_sites_range_dev(self, pos, flags, own, meta, stream=None):
         """pileup_select_sites_range with the bounds {own_lo, own_hi} read from `own` (int64 [2], device or pinned: e.g. meta[2:] of

@@ -6,6 +6,7 @@ questions of it (make_candidate_snp_tensor/main.cpp:165,194): is bit p - 1 set (
 any bit of [p - 1, p + max_del_length + 1) set (confident BED: the column may be a candidate).  Here the bits of ONE contig are a uint32
 array, bit i = bit (i & 31) of word i >> 5, uploaded once per contig and tested on the device (include/nanosnp.h); bits at or beyond the
 contig length read as 0, where the reference - one list over all contigs - reads the first bits of the next contig.
+A call over one whole-genome text takes the bitmaps of all its contigs as one TABLE (table_bitmaps; _lib.BedTable puts it on the device).
 """
 from __future__ import annotations
 
@@ -122,3 +123,40 @@ def contig_intervals(bed, contig, chr_len, fai=None):
         bed = load_bed(bed, fai) if fai is not None else load_bed(bed, {contig: int(chr_len)}, skip_unknown=True)
     iv = bed.get(contig)
     return np.zeros((0, 2), np.int64) if iv is None else np.asarray(iv, np.int64).reshape(-1, 2)
+
+
+def table_intervals(bed, names, lengths, fai=None):
+    """what a whole-genome call was given as one BED -> the intervals of every contig of `names`, in their order: [int64 [n, 2] or None (the
+    BED holds nothing of this contig)].  bed: a path - read by load_bed against the whole index fai (a dict, .fai text or path: an interval
+    beyond a contig and a contig the index lacks raise, as in the reference), without one against {names: lengths} with other contigs passed
+    over - or a dict {contig: intervals}.  Contigs outside `names` are ignored; every interval must lie inside its contig (bed_bitmap's rule)."""
+    names, lengths = [str(n) for n in names], [int(n) for n in lengths]
+    if len(names) != len(lengths):
+        raise NanoSNPError("table_intervals: one length per name")
+    if not isinstance(bed, dict):
+        bed = load_bed(bed, fai) if fai is not None else load_bed(bed, dict(zip(names, lengths)), skip_unknown=True)
+    out = []
+    for name, n in zip(names, lengths):
+        iv = bed.get(name)
+        iv = None if iv is None else np.asarray(iv, np.int64).reshape(-1, 2)
+        if iv is not None and not iv.size:
+            iv = None
+        if iv is not None and (int(iv.min()) < 0 or int(iv[:, 1].max()) > n or bool((iv[:, 0] >= iv[:, 1]).any())):
+            raise NanoSNPError(f"{name}: an interval must satisfy 0 <= from < to <= contig length ({n})")
+        out.append(iv)
+    return out
+
+
+def table_word_offsets(intervals, lengths):
+    """-> int64 [n + 1]: contig c owns words [off[c], off[c + 1]) - (length + 31) // 32 of them, ZERO for a contig without intervals"""
+    return np.concatenate([[0], np.cumsum([0 if iv is None else (int(n) + 31) // 32 for iv, n in zip(intervals, lengths)])]).astype(np.int64)
+
+
+def table_bitmaps(bed, names, lengths, fai=None):
+    """The bitmap table of a call over several contigs (include/nanosnp.h) -> (words uint32, off int64 [n + 1]): the bed_bitmap of every contig
+    of `names` the BED holds, back to back; contig c owns words [off[c], off[c + 1]) and has min(lengths[c], 32 * its words) bits - a contig
+    without intervals takes zero words, every bit of it reads 0.  bed, fai: as table_intervals reads them."""
+    iv = table_intervals(bed, names, lengths, fai)
+    off = table_word_offsets(iv, lengths)
+    parts = [bed_bitmap(v, n) for v, n in zip(iv, lengths) if v is not None]
+    return (np.concatenate(parts) if parts else np.zeros(0, np.uint32)), off

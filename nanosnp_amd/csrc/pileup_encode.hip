@@ -188,6 +188,24 @@ __device__ __forceinline__ bool bed_any(const uint32_t* __restrict__ bits, int64
     return false;
 }
 
+// The bitmap TABLE of a call over several contigs (include/nanosnp.h): contig c owns words [bed_off[c], bed_off[c + 1]) of bed_words and
+// min(its length, 32 * its words) bits.  A key (cid << 36 | position) is tested against the bits of its OWN contig alone: a filler key
+// (cid < 0) or a cid beyond the table touches nothing and reads 0, so does a contig of zero words.
+constexpr int KEY_SHIFT = 36;
+struct BedTable { const uint32_t* words; const int64_t* bed_off; const int64_t* seq_off; int64_t n_contigs; };
+
+// -> the contig's words and its bit count in n_bits; nullptr (n_bits 0) for a key that names no contig of the table
+__device__ __forceinline__ const uint32_t* bed_table_contig(const BedTable& t, int64_t key, int64_t& n_bits)
+{
+    const int64_t cid = key >> KEY_SHIFT;                  // (arithmetic: the filler -2^62 gives a negative index)
+    n_bits = 0;
+    if (cid < 0 || cid >= t.n_contigs) return nullptr;
+    const int64_t w0 = t.bed_off[cid], cap = (t.bed_off[cid + 1] - w0) * 32, len = t.seq_off[cid + 1] - t.seq_off[cid];
+    n_bits = len < cap ? len : cap;
+    return t.words + w0;
+}
+__device__ __forceinline__ int64_t key_pos(int64_t key) { return key & ((1ll << KEY_SHIFT) - 1); }
+
 // The candidate tests compare (double)count / (double)depth with min_af (tensor_maker.cpp:195-228: float64 division).  For
 // integers count, depth < 2^31 the correctly rounded quotient is >= a double a exactly when count / depth >= the midpoint tau
 // between a and its predecessor (the quotient can never BE that midpoint: tau has an odd 54- or 55-bit mantissa, which a
@@ -280,6 +298,9 @@ static_assert(4 * (ENC_WAVES * (STAGE_BYTES + (ENC_ECAP_BED + P3_STEP) * 8 + 64 
 // what nsnp_pileup_encode_columns3 adds (all optional): max_del[M] receives max_del_length; with bits, NSNP_FLAG_CANDIDATE also needs a set
 // bit in [pos - 1, pos + max_del_length + 1) (main.cpp:194)
 struct EncBed { const int64_t* pos; const uint32_t* bits; int64_t n_bits; int32_t* max_del; };
+// what nsnp_pileup_encode_columns_keys takes in its place: the keys of the columns and the bitmap table (tab.bed_off NULL: no confident test)
+struct EncKeys { const int64_t* key; BedTable tab; int32_t* max_del; };
+enum { ENC_PLAIN = 0, ENC_BED = 1, ENC_KEYS = 2 };
 
 // inclusive prefix sum over the 64 lanes of a wave with DPP row shifts and row broadcasts (no LDS)
 __device__ __forceinline__ int wave_scan_incl(int v)
@@ -297,14 +318,16 @@ __device__ __forceinline__ int wave_scan_incl(int v)
 #ifndef NSNP_ENC_MINW
 #define NSNP_ENC_MINW 4
 #endif
-// BED = false is k_encode_columns as it always was (nothing below depends on `bed` there); BED = true: k_encode_columns_bed
-template <bool BED>
+// MODE ENC_PLAIN is k_encode_columns as it always was (nothing below depends on `bed` there); ENC_BED: k_encode_columns_bed (Bed = EncBed);
+// ENC_KEYS: k_encode_columns_keys (Bed = EncKeys) - the two differ in the confident test of the very last step alone
+template <int MODE, typename Bed>
 __device__ __forceinline__ void encode_columns_body(
     const uint8_t* __restrict__ bases, const int64_t* __restrict__ col_off, const uint8_t* __restrict__ ref,
     int64_t M, const AfThreshold& af, const AfTable& aft, const AfThreshold& afi, const AfTable& afti, int min_cov, int32_t* __restrict__ counts,
     int32_t* __restrict__ depth_out,
-    uint8_t* __restrict__ flags, const EncBed& bed)
+    uint8_t* __restrict__ flags, const Bed& bed)
 {
+    constexpr bool BED = MODE != ENC_PLAIN;
     constexpr int ECAP = BED ? ENC_ECAP_BED : ENC_ECAP;            // opener entries of a segment
     constexpr int NACC = BED ? 9 : 8;
     __shared__ uint32_t af_min[128];          // 256 x uint16: smallest passing count by depth (make_af_table): the SNP threshold
@@ -709,7 +732,17 @@ __device__ __forceinline__ void encode_columns_body(
         bool cand = rb < 4 && pass_af && depth >= min_cov;
         if (BED) {
             if (bed.max_del) (bed.max_del + wave_col0)[lane] = mdel;
-            if (cand && bed.bits) { const int64_t p = (bed.pos + wave_col0)[lane]; cand = bed_any(bed.bits, bed.n_bits, p - 1, p + mdel + 1); }
+            if constexpr (MODE == ENC_KEYS) {
+                if (cand && bed.tab.bed_off) {
+                    const int64_t k = (bed.key + wave_col0)[lane];
+                    int64_t nb;
+                    const uint32_t* w = bed_table_contig(bed.tab, k, nb);     // (nb 0: nothing is read)
+                    const int64_t p = key_pos(k);
+                    cand = bed_any(w, nb, p - 1, p + mdel + 1);
+                }
+            } else {
+                if (cand && bed.bits) { const int64_t p = (bed.pos + wave_col0)[lane]; cand = bed_any(bed.bits, bed.n_bits, p - 1, p + mdel + 1); }
+            }
         }
         if (cand) f |= NSNP_FLAG_CANDIDATE;
         (flags + wave_col0)[lane] = f;
@@ -722,7 +755,7 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns(
     int32_t* __restrict__ depth_out,
     uint8_t* __restrict__ flags)
 {
-    encode_columns_body<false>(bases, col_off, ref, M, af, aft, afi, afti, min_cov, counts, depth_out, flags, EncBed{nullptr, nullptr, 0, nullptr});
+    encode_columns_body<ENC_PLAIN>(bases, col_off, ref, M, af, aft, afi, afti, min_cov, counts, depth_out, flags, EncBed{nullptr, nullptr, 0, nullptr});
 }
 
 __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns_bed(
@@ -731,7 +764,16 @@ __global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns_bed
     int32_t* __restrict__ depth_out,
     uint8_t* __restrict__ flags, const EncBed bed)
 {
-    encode_columns_body<true>(bases, col_off, ref, M, af, aft, afi, afti, min_cov, counts, depth_out, flags, bed);
+    encode_columns_body<ENC_BED>(bases, col_off, ref, M, af, aft, afi, afti, min_cov, counts, depth_out, flags, bed);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK, NSNP_ENC_MINW) void k_encode_columns_keys(
+    const uint8_t* __restrict__ bases, const int64_t* __restrict__ col_off, const uint8_t* __restrict__ ref,
+    int64_t M, AfThreshold af, const AfTable aft, AfThreshold afi, const AfTable afti, int min_cov, int32_t* __restrict__ counts,
+    int32_t* __restrict__ depth_out,
+    uint8_t* __restrict__ flags, const EncKeys bed)
+{
+    encode_columns_body<ENC_KEYS>(bases, col_off, ref, M, af, aft, afi, afti, min_cov, counts, depth_out, flags, bed);
 }
 
 
@@ -841,10 +883,10 @@ __global__ void k_gather_windows(const int32_t* __restrict__ counts, const int64
 
 }  // namespace
 
-// bed == nullptr: k_encode_columns, the launch nsnp_pileup_encode_columns2 always made; else k_encode_columns_bed
+// keys: k_encode_columns_keys; else bed == nullptr: k_encode_columns, the launch nsnp_pileup_encode_columns2 always made; else k_encode_columns_bed
 static int encode_columns_launch(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off,
                                  const uint8_t* ref, int64_t M, double snp_min_af, double indel_min_af, int min_coverage,
-                                 int32_t* counts, int32_t* depth, uint8_t* flags, const EncBed* bed, void* stream)
+                                 int32_t* counts, int32_t* depth, uint8_t* flags, const EncBed* bed, void* stream, const EncKeys* keys = nullptr)
 {
     if (!ctx || M < 0 || (M > 0 && (!bases || !col_off || !ref || !counts || !depth || !flags))) return NSNP_EINVAL;
     if (M == 0) return NSNP_OK;
@@ -870,7 +912,10 @@ static int encode_columns_launch(nsnp_ctx* ctx, const uint8_t* bases, const int6
     }
     AfThreshold af{ctx->af_t, ctx->af_k, ctx->af_mode}, afi{ctx->af2_t, ctx->af2_k, ctx->af2_mode};
     AfTable aft, afti; memcpy(aft.w, ctx->af_table_words, sizeof(aft.w)); memcpy(afti.w, ctx->af2_table_words, sizeof(afti.w));
-    if (bed)
+    if (keys)
+        hipLaunchKernelGGL(k_encode_columns_keys, dim3(grid), dim3(ENC_BLOCK), 0, (hipStream_t)stream,
+                           bases, col_off, ref, M, af, aft, afi, afti, min_coverage, counts, depth, flags, *keys);
+    else if (bed)
         hipLaunchKernelGGL(k_encode_columns_bed, dim3(grid), dim3(ENC_BLOCK), 0, (hipStream_t)stream,
                            bases, col_off, ref, M, af, aft, afi, afti, min_coverage, counts, depth, flags, *bed);
     else
@@ -896,6 +941,18 @@ extern "C" int nsnp_pileup_encode_columns3(nsnp_ctx* ctx, const uint8_t* bases, 
     if (conf_n_bits < 0 || (conf_bits ? (conf_n_bits == 0 || (M > 0 && !pos)) : conf_n_bits != 0)) return NSNP_EINVAL;
     const EncBed bed{pos, conf_bits, conf_n_bits, max_del};
     return encode_columns_launch(ctx, bases, col_off, ref, M, snp_min_af, indel_min_af, min_coverage, counts, depth, flags, &bed, stream);
+}
+
+extern "C" int nsnp_pileup_encode_columns_keys(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off, const uint8_t* ref, const int64_t* key,
+                                               int64_t M, double snp_min_af, double indel_min_af, int min_coverage, const uint32_t* bed_words,
+                                               const int64_t* bed_off, const int64_t* seq_off, int64_t n_contigs,
+                                               int32_t* counts, int32_t* depth, uint8_t* flags, int32_t* max_del, void* stream)
+{
+    // a table is tested at keys: it needs them and the contig lengths; without bed_off there is no table (then no words either).  bed_words
+    // may be NULL beside a table whose contigs all own zero words
+    if (n_contigs < 0 || (bed_off ? (!seq_off || (M > 0 && !key)) : bed_words != nullptr)) return NSNP_EINVAL;
+    const EncKeys keys{key, BedTable{bed_words, bed_off, seq_off, n_contigs}, max_del};
+    return encode_columns_launch(ctx, bases, col_off, ref, M, snp_min_af, indel_min_af, min_coverage, counts, depth, flags, nullptr, stream, &keys);
 }
 
 extern "C" int nsnp_pileup_encode_columns(nsnp_ctx* ctx, const uint8_t* bases, const int64_t* col_off,
@@ -1045,17 +1102,46 @@ __device__ __forceinline__ int64_t wave_scan_incl64(int64_t v, int lane)
     return v;
 }
 
+// The keep rule of the filter, a template parameter of the count and scatter kernels: keep(v) for the column's `pos` entry v, and what the
+// scatter carries along beside the reference byte.  FilPos: one contig, v a position, one bitmap - the kernels of nsnp_pileup_filter_columns as
+// they always were.  A rule reaches a kernel as its two parts A0, A1 - for FilPos the very arguments `bits, n_bits` those kernels took, in their
+// place (handed over as one struct the compiler fetches the kernel arguments in other pieces and numbers the scalar registers otherwise).
+struct FilPos {
+    typedef const uint32_t* __restrict__ A0; typedef int64_t A1;
+    const uint32_t* __restrict__ bits; int64_t n_bits;
+    __device__ __forceinline__ bool keep(int64_t p) const { return bed_bit(bits, n_bits, p - 1); }
+    __device__ __forceinline__ void carry(int64_t, int64_t) const {}
+    __device__ __forceinline__ void fill(int64_t) const {}
+};
+// FilKey (nsnp_pileup_filter_columns_keys): v a key, the bitmap table, every test bounded by the key's OWN contig; aux (optional): one int32
+// per column that travels with it (-1 behind the kept ones)
+struct FilAux { const int32_t* aux; int32_t* aux_out; };
+struct FilKey {
+    typedef BedTable A0; typedef FilAux A1;
+    BedTable tab; FilAux x;
+    __device__ __forceinline__ bool keep(int64_t key) const
+    {
+        int64_t nb;
+        const uint32_t* w = bed_table_contig(tab, key, nb);
+        return bed_bit(w, nb, key_pos(key) - 1);           // (nb 0 - no contig, or one of zero words: nothing is read)
+    }
+    __device__ __forceinline__ void carry(int64_t src, int64_t dst) const { if (x.aux) x.aux_out[dst] = x.aux[src]; }
+    __device__ __forceinline__ void fill(int64_t c) const { if (x.aux) x.aux_out[c] = -1; }
+};
+
+template <typename Rule>
 __global__ __launch_bounds__(FIL_BLOCK) void k_filter_count(const int64_t* __restrict__ pos, const int64_t* __restrict__ col_off,
-                                                             const uint32_t* __restrict__ bits, int64_t n_bits, int64_t M, int64_t n_blocks,
+                                                             typename Rule::A0 r0, typename Rule::A1 r1, int64_t M, int64_t n_blocks,
                                                              int64_t* __restrict__ blk)
 {
+    const Rule rule{r0, r1};
     __shared__ int64_t wsum[2][FIL_BLOCK / 64];
     const int64_t base = (int64_t)blockIdx.x * FIL_TILE + threadIdx.x;
     int64_t n = 0, nb = 0;
 #pragma unroll
     for (int k = 0; k < FIL_PER_THREAD; ++k) {
         const int64_t c = base + (int64_t)k * FIL_BLOCK;
-        if (c < M && bed_bit(bits, n_bits, pos[c] - 1)) { const int64_t l = col_off[c + 1] - col_off[c]; n += 1; nb += l > 0 ? l : 0; }
+        if (c < M && rule.keep(pos[c])) { const int64_t l = col_off[c + 1] - col_off[c]; n += 1; nb += l > 0 ? l : 0; }
     }
     for (int o = 32; o > 0; o >>= 1) { n += __shfl_down(n, o); nb += __shfl_down(nb, o); }
     if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = n; wsum[1][threadIdx.x >> 6] = nb; }
@@ -1103,14 +1189,16 @@ __global__ __launch_bounds__(1024) void k_filter_scan(int64_t* __restrict__ blk,
     }
 }
 
+template <typename Rule>
 __global__ __launch_bounds__(FIL_BLOCK) void k_filter_scatter(
     const int64_t* __restrict__ pos, const int64_t* __restrict__ col_off, const uint8_t* __restrict__ bases, const uint8_t* __restrict__ ref,
-    const uint32_t* __restrict__ bits, int64_t n_bits, int64_t M, int64_t n_blocks, const int64_t* __restrict__ blk, int64_t own_lo, int64_t own_hi,
+    typename Rule::A0 r0, typename Rule::A1 r1, int64_t M, int64_t n_blocks, const int64_t* __restrict__ blk, int64_t own_lo, int64_t own_hi,
     int64_t* __restrict__ pos_out, int64_t* __restrict__ off_out, uint8_t* __restrict__ bases_out, uint8_t* __restrict__ ref_out,
     int64_t* __restrict__ meta)
 {
     // kept column r of the tile: s_out[r] = its first output byte (s_out[kept columns of the tile] = the end of the tile's bytes),
     // s_delta[r] = its first input byte - its first output byte (never decreasing in r: dropped bytes only add to it)
+    const Rule rule{r0, r1};
     __shared__ int64_t s_out[FIL_TILE + 1];
     __shared__ int64_t s_delta[FIL_TILE];
     __shared__ int wcnt[FIL_PER_THREAD][FIL_BLOCK / 64];
@@ -1125,7 +1213,7 @@ __global__ __launch_bounds__(FIL_BLOCK) void k_filter_scatter(
         const int64_t c = base + (int64_t)k * FIL_BLOCK;
         bool keep = false; int64_t len = 0; src[k] = 0;
         if (c < M) {
-            keep = bed_bit(bits, n_bits, pos[c] - 1);
+            keep = rule.keep(pos[c]);
             if (keep) { src[k] = col_off[c]; len = col_off[c + 1] - src[k]; len = len > 0 ? len : 0; }
         }
         const unsigned long long bal = __ballot(keep);
@@ -1147,12 +1235,13 @@ __global__ __launch_bounds__(FIL_BLOCK) void k_filter_scatter(
                 if ((keepm >> k) & 1u) {
                     const int64_t o = byte0 + brun + bbefore[k];
                     pos_out[col0 + r] = pos[c]; ref_out[col0 + r] = ref[c]; off_out[col0 + r] = o;
+                    rule.carry(c, col0 + r);
                     s_out[r] = o; s_delta[r] = src[k] - o;
                 }
                 // the images of the chunk's own range under the compaction: kept columns in front of column own_lo / own_hi
                 if (c == own_lo) meta[2] = col0 + r;
                 if (c == own_hi) meta[3] = col0 + r;
-                if (c < M && c >= K) { pos_out[c] = FIL_POS_NONE; ref_out[c] = 'N'; off_out[c] = kept_bytes; }
+                if (c < M && c >= K) { pos_out[c] = FIL_POS_NONE; ref_out[c] = 'N'; off_out[c] = kept_bytes; rule.fill(c); }
                 if (c == M - 1) off_out[M] = kept_bytes;
             }
             run += wcnt[k][w]; brun += wbytes[k][w];
@@ -1185,13 +1274,12 @@ __global__ __launch_bounds__(FIL_BLOCK) void k_filter_scatter(
 }
 }  // namespace
 
-extern "C" int nsnp_pileup_filter_columns(nsnp_ctx* ctx, const int64_t* pos, const int64_t* col_off, const uint8_t* bases, const uint8_t* ref,
-                                          int64_t M, const uint32_t* bits, int64_t n_bits, int64_t own_lo, int64_t own_hi,
-                                          int64_t* pos_out, int64_t* off_out, uint8_t* bases_out, uint8_t* ref_out, int64_t* meta, void* stream)
+// the three launches of both filter entries (the arguments are checked by the entries; r0, r1: the two parts of the rule)
+template <typename Rule>
+static int filter_columns_launch(nsnp_ctx* ctx, const int64_t* pos, const int64_t* col_off, const uint8_t* bases, const uint8_t* ref, int64_t M,
+                                 typename Rule::A0 r0, typename Rule::A1 r1, int64_t own_lo, int64_t own_hi,
+                                 int64_t* pos_out, int64_t* off_out, uint8_t* bases_out, uint8_t* ref_out, int64_t* meta, void* stream)
 {
-    if (!ctx || M < 0 || n_bits < 0 || !meta || !off_out || (n_bits > 0 && !bits) ||
-        (M > 0 && (!pos || !col_off || !bases || !ref || !pos_out || !bases_out || !ref_out))) return NSNP_EINVAL;
-    if (pos_out == pos || off_out == col_off || bases_out == bases || ref_out == ref) return NSNP_EINVAL;       // not in place
     hipStream_t s = (hipStream_t)stream;
     if (M == 0) {
         NSNP_HIP(ctx, hipMemsetAsync(meta, 0, 4 * sizeof(int64_t), s));
@@ -1208,10 +1296,36 @@ extern "C" int nsnp_pileup_filter_columns(nsnp_ctx* ctx, const int64_t* pos, con
         NSNP_HIP(ctx, hipMalloc((void**)&ctx->fil_tmp, need + need / 4));
         ctx->fil_tmp_bytes = need + need / 4;
     }
-    hipLaunchKernelGGL(k_filter_count, dim3((unsigned)n_blocks), dim3(FIL_BLOCK), 0, s, pos, col_off, bits, n_bits, M, n_blocks, ctx->fil_tmp);
+    hipLaunchKernelGGL(k_filter_count<Rule>, dim3((unsigned)n_blocks), dim3(FIL_BLOCK), 0, s, pos, col_off, r0, r1, M, n_blocks, ctx->fil_tmp);
     hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(1024), 0, s, ctx->fil_tmp, n_blocks, M, own_lo, own_hi, meta);
-    hipLaunchKernelGGL(k_filter_scatter, dim3((unsigned)n_blocks), dim3(FIL_BLOCK), 0, s, pos, col_off, bases, ref, bits, n_bits, M, n_blocks,
+    hipLaunchKernelGGL(k_filter_scatter<Rule>, dim3((unsigned)n_blocks), dim3(FIL_BLOCK), 0, s, pos, col_off, bases, ref, r0, r1, M, n_blocks,
                        (const int64_t*)ctx->fil_tmp, own_lo, own_hi, pos_out, off_out, bases_out, ref_out, meta);
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
+}
+
+extern "C" int nsnp_pileup_filter_columns(nsnp_ctx* ctx, const int64_t* pos, const int64_t* col_off, const uint8_t* bases, const uint8_t* ref,
+                                          int64_t M, const uint32_t* bits, int64_t n_bits, int64_t own_lo, int64_t own_hi,
+                                          int64_t* pos_out, int64_t* off_out, uint8_t* bases_out, uint8_t* ref_out, int64_t* meta, void* stream)
+{
+    if (!ctx || M < 0 || n_bits < 0 || !meta || !off_out || (n_bits > 0 && !bits) ||
+        (M > 0 && (!pos || !col_off || !bases || !ref || !pos_out || !bases_out || !ref_out))) return NSNP_EINVAL;
+    if (pos_out == pos || off_out == col_off || bases_out == bases || ref_out == ref) return NSNP_EINVAL;       // not in place
+    return filter_columns_launch<FilPos>(ctx, pos, col_off, bases, ref, M, bits, n_bits, own_lo, own_hi, pos_out, off_out, bases_out, ref_out, meta,
+                                         stream);
+}
+
+extern "C" int nsnp_pileup_filter_columns_keys(nsnp_ctx* ctx, const int64_t* key, const int64_t* col_off, const uint8_t* bases, const uint8_t* ref,
+                                               const int32_t* aux, int64_t M, const uint32_t* bed_words, const int64_t* bed_off,
+                                               const int64_t* seq_off, int64_t n_contigs, int64_t own_lo, int64_t own_hi,
+                                               int64_t* key_out, int64_t* off_out, uint8_t* bases_out, uint8_t* ref_out, int32_t* aux_out,
+                                               int64_t* meta, void* stream)
+{
+    // (bed_words may be NULL beside a table whose contigs all own zero words: every column is dropped, nothing is read)
+    if (!ctx || M < 0 || n_contigs < 0 || !meta || !off_out || (n_contigs > 0 && (!bed_off || !seq_off)) ||
+        (M > 0 && (!key || !col_off || !bases || !ref || !key_out || !bases_out || !ref_out))) return NSNP_EINVAL;
+    if (key_out == key || off_out == col_off || bases_out == bases || ref_out == ref) return NSNP_EINVAL;       // not in place
+    if ((aux != nullptr) != (aux_out != nullptr) || (aux && aux_out == aux)) return NSNP_EINVAL;
+    return filter_columns_launch<FilKey>(ctx, key, col_off, bases, ref, M, BedTable{bed_words, bed_off, seq_off, n_contigs}, FilAux{aux, aux_out}, own_lo,
+                                         own_hi, key_out, off_out, bases_out, ref_out, meta, stream);
 }

@@ -225,6 +225,16 @@ class _FilSet:
         self.out = (self.pos, self.off, self.bases, self.ref)
 
 
+class _FilKeySet(_FilSet):
+    """_FilSet for the keyed columns of a whole-genome chunk (nsnp_pileup_filter_columns_keys: pos holds keys), plus the int32 per column that
+    is compacted with them (the line_idx of the chunk's name table)"""
+    def __init__(self, cap_cols, cap_bytes, dev):
+        import torch
+        super().__init__(cap_cols, cap_bytes, dev)
+        self.aux = torch.empty(cap_cols, dtype=torch.int32, device=dev)
+        self.out = self.out + (self.aux,)
+
+
 class _TextSet:
     """one chunk of raw mpileup text in flight: pinned on the host (filled by the staging thread, read by the copy engine) or on the device
     (filled by the copy stream, read by the tokeniser)"""
@@ -1472,7 +1482,7 @@ class ContigRuns:
 
 
 def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stats, on_rows, cap_runs=None, indel_min_af=None, records=None,
-                     name_cap=1024):
+                     name_cap=1024, beds=None):
     """_stream_contig_dev for a text of several contigs: the same chunk loop over the same buffer sets (_run_text_chunks, _text_chunk_sets)
     with nsnp_mpileup_tokenise_contigs in the tokeniser's place and its
     `key` where the per-contig path hands a position to the window rule and the call rows.  The run table of every chunk arrives in pinned
@@ -1481,7 +1491,12 @@ def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stat
     records (mpileup_to_bins; None: nothing below changes): the tokenise station also compares column 0 of every line with the table name of
     its contig while the chunk's text is still resident (nsnp_mpileup_line_names_contigs), and the third station issues no forward -
     records(k, counts, own centres, _ChunkColumns with the keys as pos, main) is called for every chunk that owns sites; on_rows is not
-    called, the wanted contigs the text holds are tracker.order.  indel_min_af (None: min_af) goes to the encode."""
+    called, the wanted contigs the text holds are tracker.order.  indel_min_af (None: min_af) goes to the encode.
+    beds (a _lib.BedTable of `table`; None: exactly the launches issued without): with an extended table every chunk's columns pass
+    nsnp_pileup_filter_columns_keys in front of the encode, into one of three filter sets - every line tested against the bitmap of its OWN
+    contig, the images of the chunk's own range kept on the device for the selection - and the chunk's line_idx is compacted with them: the line
+    that emits a site is the 16th KEPT line behind its centre.  With a confident table the encode is nsnp_pileup_encode_columns_keys.  The run
+    tables still describe the unfiltered lines: a wanted contig whose lines are all dropped is still held by the text."""
     import time
     import torch
     ctx = model.ctx
@@ -1509,6 +1524,16 @@ def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stat
     started = {}                                           # chunk -> the wanted contigs that start among its own lines
     names_pin = _count_slots(model, "_names_meta_pin", n_ring) if records is not None else None
     names_of = {}
+    ext_bed = conf_bed = fsets = fmeta = None
+    if beds is not None:
+        ext_bed, conf_bed = beds.ext, beds.conf
+        if ext_bed is not None:
+            fsets = getattr(model, "_filkey_dev_sets", None)
+            if not fsets or fsets[0].pos.device != dev or fsets[0].pos.numel() < csets[0].pos.numel() or fsets[0].bases.numel() < csets[0].bases.numel():
+                fsets = model._filkey_dev_sets = [_FilKeySet(csets[0].pos.numel(), csets[0].bases.numel(), dev) for _ in range(3)]
+                if not sets.fresh:
+                    sets.copy_stream.wait_stream(main)     # (new filter sets are new device sets: _text_chunk_sets says why the copy stream waits)
+            fmeta = torch.zeros((len(ranges), 4), dtype=torch.int64, device=dev)
 
     def tokenise(k, text_k, cs):
         ks = ksets[k % len(csets)]
@@ -1550,8 +1575,24 @@ def _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, stat
         if own <= 0:
             return None
         d_key, d_off, d_bases, d_ref = ksets[k % len(csets)].key[:M], cs.off[:M + 1], cs.bases[:max(nb, 1)], cs.ref[:M]
-        counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage, indel_min_af=indel_min_af)
-        center = ctx.pileup_select_sites_range(d_key, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
+        if ext_bed is not None:
+            # the lines outside the extended BED leave the arrays, the name index of every line with them; where the chunk's own range
+            # [n_lo, M - n_hi) lies among the kept columns stays on the device (fmeta[k][2:])
+            d_key, d_off, d_bases, d_ref, d_idx, _ = ctx.pileup_filter_columns_keys(d_key, d_off, d_bases, d_ref, table, ext_bed,
+                                                                                    aux=None if names is None else names[0], own_lo=n_lo,
+                                                                                    own_hi=M - n_hi, meta=fmeta[k],
+                                                                                    out=fsets[k % len(fsets)].out, stream=main)
+            if names is not None:
+                names = (d_idx, names[1])
+        if conf_bed is not None:
+            counts, depth, flags, _ = ctx.pileup_encode_columns_keys(d_bases, d_off, d_ref, d_key, table, conf_bed, min_af, min_coverage,
+                                                                     want_max_del=False, indel_min_af=indel_min_af)
+        else:
+            counts, depth, flags = ctx.pileup_encode_columns(d_bases, d_off, d_ref, min_af, min_coverage, indel_min_af=indel_min_af)
+        if ext_bed is not None:
+            center = ctx.pileup_select_sites_range_dev(d_key, flags, fmeta[k][2:], meta_pin[k], stream=main)
+        else:
+            center = ctx.pileup_select_sites_range(d_key, flags, n_lo, M - n_hi, meta_pin[k], stream=main)
         if records is not None:
             return d_key, counts, center, _ChunkColumns(d_bases, d_off, d_ref, d_key, depth, None, names)
         return d_key, counts, center
@@ -1628,14 +1669,33 @@ def call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file
     Departures from the splitter: a wanted contig in two separate runs raises NanoSNPError (the splitter would reopen its file with "w" and
     keep only the last run); an empty line is refused as the tokeniser refuses it (the splitter skips it).  NotImplementedError: under a
     process group of more than one rank, with NSNP_TOKENISE=host, with extended_bed= / confident_bed=."""
+    if extended_bed is not None or confident_bed is not None:
+        raise NotImplementedError("call_mpileup: BED region filters over several contigs (call_mpileup_bed takes them)")
+    return _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, None, None, contigs=contigs, batch_size=batch_size,
+                         score_mode=score_mode, chunk_bytes=chunk_bytes, min_af=min_af, min_coverage=min_coverage, stats=stats)
+
+
+def call_mpileup_bed(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, *, extended_bed=None, confident_bed=None, **kw):
+    """call_mpileup with the reference's two region filters (-extended_confident_bed / -confident_bed, make_candidate_snp_tensor/main.cpp:
+    158-201) over ALL contigs of the text: each a path - checked against the whole index fai_text, as the reference reads it - or {contig:
+    intervals}.  A line is read at all only where the extended BED has the bit of its position in its OWN contig; a column is a candidate only
+    where the confident BED has a bit in [p - 1, p + max_del_length + 1) of its own contig (bed.py; a reach past a contig's end never sees the
+    next contig's bits).  For a text whose wanted contigs each form one run the file equals, byte for byte, call_variants(..., extended_bed=,
+    confident_bed=) over the files the splitter would have written, at every chunk_bytes with ascending positions.  The bitmaps are resident
+    beside the sequences (_lib.BedTable: 1 bit per base of every contig a BED mentions).  **kw and the refusals: as call_mpileup (a process
+    group of more than one rank, NSNP_TOKENISE=host); with both BEDs None this IS call_mpileup, launch for launch."""
+    return _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, extended_bed, confident_bed, **kw)
+
+
+def _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, extended_bed, confident_bed, contigs=None, batch_size=1000,
+                  score_mode=host.SCORE_FLOAT64, chunk_bytes=64 << 20, min_af=0.12, min_coverage=6, stats=None):
+    """the one body of call_mpileup and call_mpileup_bed"""
     import time
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
     import torch
     import torch.distributed as tdist
     from . import _lib
-    if extended_bed is not None or confident_bed is not None:
-        raise NotImplementedError("call_mpileup: BED region filters over several contigs (use call_variants on per-contig files)")
     if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
         raise NotImplementedError("call_mpileup: sharding a whole-genome text over ranks")
     if tokenise_mode() != "device":
@@ -1644,6 +1704,7 @@ def call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file
         raise _lib.NanoSNPError("no GPU visible: nanosnp_amd has no CPU fallback")
     names = list(contigs) if contigs is not None else fai_names(fai_text)
     table = _lib.ContigTable(fasta=fasta_path, names=names, device=model.ctx.device)
+    beds = None if extended_bed is None and confident_bed is None else _lib.BedTable(table, extended_bed, confident_bed, fai_text)
     st = stats if stats is not None else {}
     dev = torch.device("cuda", model.ctx.device)
     side = getattr(model, "_rows_stream", None)
@@ -1711,7 +1772,7 @@ def call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file
                     acc.append(rows_k)
 
             try:
-                _stream_text_dev(model, src, table, chunk_bytes, min_af, min_coverage, st, on_rows)
+                _stream_text_dev(model, src, table, chunk_bytes, min_af, min_coverage, st, on_rows, beds=beds)
                 flush(True)
                 while futs:
                     n_rows += futs.popleft().result()
@@ -2072,7 +2133,7 @@ def _staged_bins(out_dir, names, matrix_dtype, alt_info, run_pass, st):
         raise
 
 
-def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_af, min_coverage, st, alt_info, state, staging, pool):
+def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_af, min_coverage, st, alt_info, state, staging, pool, beds=None):
     """one pass of mpileup_to_bins over the text -> (True when it has to be run again - state says how: elem 4, blob_min bytes per slot, or
     name_cap entries per name table -, the wanted contigs the text holds in its order)"""
     import torch
@@ -2149,7 +2210,7 @@ def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_a
     try:
         with host.gc_paused():
             tracker = _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, st, None, indel_min_af=indel_min_af, records=records,
-                                       name_cap=state["name_cap"])
+                                       name_cap=state["name_cap"], beds=beds)
         drain(False)
         for t0, t1, t2 in spans:
             st["window_records_s"] = st.get("window_records_s", 0.0) + t0.elapsed_time(t1) * 1e-3
@@ -2200,6 +2261,24 @@ def mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir,
     stats["time_records"] = True also window_records_s / alt_info_s / record_chunks (HIP-event sums), as contig_to_bin reports them.
     Refused before anything is touched: a process group of more than one rank, NSNP_TOKENISE=host, no GPU (_bins_refusals); ValueError for
     a wanted name that is empty, holds NUL or is longer than 37 bytes."""
+    return _mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir, None, None, contigs=contigs, alt_info=alt_info,
+                            matrix_dtype=matrix_dtype, min_af=min_af, indel_min_af=indel_min_af, min_coverage=min_coverage, chunk_bytes=chunk_bytes,
+                            stats=stats)
+
+
+def mpileup_to_bins_bed(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir, *, extended_bed=None, confident_bed=None, **kw):
+    """mpileup_to_bins with the reference's two region filters over ALL contigs of the text (extended_bed / confident_bed: as call_mpileup_bed
+    takes them): every <name>.pd.bin is byte for byte what make_pileup_bins(..., extended_bed=, confident_bed=) writes for the files the
+    splitter would have cut, and the same set of files - a wanted contig the text holds gets one even when the extended BED drops all its
+    lines (an empty file, as contig_to_bin writes for it).  Under an extended BED the name in a position string is still column 0 of the
+    EMITTING line, the 16th kept line behind the centre: the name index of every line is compacted with the columns, which contig_to_bin
+    does not do (it refuses such a text).  **kw and the refusals: as mpileup_to_bins; with both BEDs None this IS mpileup_to_bins."""
+    return _mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir, extended_bed, confident_bed, **kw)
+
+
+def _mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir, extended_bed, confident_bed, contigs=None, *, alt_info=True,
+                     matrix_dtype="int16", min_af=0.12, indel_min_af=None, min_coverage=6, chunk_bytes=64 << 20, stats=None):
+    """the one body of mpileup_to_bins and mpileup_to_bins_bed"""
     from concurrent.futures import ThreadPoolExecutor
     from . import _lib, sitefile
     _bins_refusals()
@@ -2212,6 +2291,7 @@ def mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir,
             raise ValueError(f"{n!r}: a contig name of 1 to {sitefile.POSITION_WIDTH - 46} bytes without NUL is needed for the "
                              f"{sitefile.POSITION_WIDTH}-byte position field")
     table = _lib.ContigTable(fasta=fasta_path, names=names, device=model.ctx.device)
+    beds = None if extended_bed is None and confident_bed is None else _lib.BedTable(table, extended_bed, confident_bed, fai_text)
     st = _stream_stats(stats)
     g = text = None
     if isinstance(mpileup_path_or_bytes, (str, os.PathLike)):
@@ -2223,7 +2303,7 @@ def mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir,
         with ThreadPoolExecutor(max_workers=1) as pool:
             out = _staged_bins(out_dir, names, matrix_dtype, alt_info,
                                lambda staging, state: _text_records_pass(model, model.ctx, src, table, chunk_bytes, min_af, indel_min_af, min_coverage,
-                                                                         st, alt_info, state, staging, pool), st)
+                                                                         st, alt_info, state, staging, pool, beds), st)
         st["sites"] = st.get("sites", 0) + sum(out.values())
         return out
     finally:
