@@ -465,6 +465,26 @@ int nsnp_pileup_alt_info_keys(nsnp_ctx* ctx, const uint8_t* bases, int64_t n_byt
                               const int32_t* depth, int64_t M, const int64_t* center_idx, int64_t N, const uint8_t* genome,
                               const int64_t* seq_off, int64_t n_contigs, uint8_t* blob, int64_t cap, int64_t* offsets, int64_t* meta, void* stream);
 
+/* ---- training labels of a chunk's selected sites (<chr>.td.bin: make_train_data/main.cpp:251-386, common/genotype.cpp:282-353) ----------
+ * Per site the key of its centre, key[center_idx[n]], is looked up in truth_key (device int64 [T], ascending, no key twice).  On a hit the
+ * site's code is truth_code[hit]; otherwise the homozygous-reference code of toupper(genome[seq_off[cid] + p - 1]): gt21 AA 0 / CC 4 / GG 7 /
+ * TT 9, zygosity 0, both lengths 16.  A code is gt21 | zygosity << 8 | length index 1 << 16 | length index 2 << 24 (gt21 0..20 in the
+ * order of GT21_LABLES, zygosity 0..2, length indices 0..32).  A site is kept when it is a truth site, when keep_thr is NULL, or when
+ * (h >> 11) < keep_thr[cid] with h the splitmix64 finaliser of key + seed * 0x9E3779B97F4A7C15 (mod 2^64): a function of key and seed alone.
+ *   out_center_idx int64 [N]   the centres of the kept sites, in order (device memory; may be NULL when label is NULL)
+ *   label   int32 [N', 90]     one-hot rows of the kept sites: 1 at gt21, 21 + zygosity, 24 + length 1, 57 + length 2; room for N rows, 16-byte
+ *                              aligned, device or pinned host memory; NULL: no row is written
+ *   counts  int64 [n_contigs, 2]  device memory, or NULL: the chunk's { truth sites, other sites } per contig are ADDED to it
+ *   meta    int64 [4] = { N', truth sites among N, other sites among N, status }
+ * status != 0: a centre outside [0, M), a filler key, a cid outside [0, n_contigs), a position outside the site's own contig or a reference
+ * byte other than A/C/G/T/a/c/g/t (the selection emits no such site) - all of them clamped, never followed.  Four launches, no workgroup
+ * waits for another; scratch of its own in the context (16 bytes per site), so it may run beside the record entries on another stream. */
+#define NSNP_LABEL_WIDTH 90
+int nsnp_pileup_label_sites_keys(nsnp_ctx* ctx, const int64_t* key, int64_t M, const int64_t* center_idx, int64_t N, const uint8_t* genome,
+                                 const int64_t* seq_off, int64_t n_contigs, const int64_t* truth_key, const uint32_t* truth_code, int64_t T,
+                                 const uint64_t* keep_thr, uint64_t seed, int64_t* out_center_idx, int32_t* label, int64_t* counts,
+                                 int64_t* meta, void* stream);
+
 /* ---- HaplotypeModel ------------------------------------------------------------------- */
 /* seq/bq/mq/hap: device int32 [N,D,L] planes as write_to_bins.py:44-61 stores them (padding
  * rows are -2); ref_row: device int32 [N,L].  out: device fp32 [N,105,L] -- float64 math as

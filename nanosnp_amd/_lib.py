@@ -76,6 +76,8 @@ _SIGNATURES = {
                                                   C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_alt_info_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                             C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_label_sites_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
     "nsnp_mpileup_tokenise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
     "nsnp_mpileup_tokenise_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 5 + [C.c_void_p] * 9),
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -928,6 +930,54 @@ class Context:
             if need > cap:
                 return self.pileup_alt_info_keys(bases, col_off, ref, key, depth, center_idx, table, cap=need, offsets=offsets, meta=meta, stream=stream)
         return blob, offsets[:n + 1], meta
+
+    LABEL_WIDTH = 90
+
+    def pileup_label_sites_keys(self, key, center_idx, table, truth_key, truth_code, keep_thr=None, seed=0, out_center_idx=None, label=None,
+                                counts=None, meta=None, stream=None, want_label=True):
+        """The training labels of a chunk's selected sites (nsnp_pileup_label_sites_keys): key int64 [M] as mpileup_tokenise_contigs wrote it,
+        center_idx int64 [N], table the ContigTable of that call, truth_key device int64 [T] ascending / truth_code device int32 [T] (the
+        packed codes of truth.load_truth, as int32 bits), keep_thr device int64 [n_contigs] (thresholds below 2^63) or None: every site is
+        kept -> (out_center_idx int64 [N] on the device: the first N' entries are the kept centres in order, label int32 [N, 90]: the first
+        N' rows are theirs, meta int64 [4] = {N', truth sites, other sites, status}).  N' is only known behind the launch: the caller reads
+        it from meta.  want_label=False (count mode): no label and no centre is written; counts: device int64 [n_contigs, 2] to which the
+        chunk's {truth sites, other sites} per contig are added.  label and meta may be given: device or pinned tensors."""
+        import torch
+        n, m = int(center_idx.shape[0]), int(key.shape[0])
+        dev = key.device
+        for t, dt, what in ((key, torch.int64, "key"), (center_idx, torch.int64, "center_idx"), (truth_key, torch.int64, "truth_key"),
+                            (truth_code, torch.int32, "truth_code"), (keep_thr, torch.int64, "keep_thr"), (counts, torch.int64, "counts"),
+                            (out_center_idx, torch.int64, "out_center_idx")):
+            if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous()):
+                raise NanoSNPError(f"label_sites_keys: {what} must be a contiguous device tensor of {dt}")
+        if truth_code.numel() != truth_key.numel():
+            raise NanoSNPError("label_sites_keys: one truth_code per truth_key")
+        if (keep_thr is not None and keep_thr.numel() != len(table)) or (counts is not None and counts.numel() != 2 * len(table)):
+            raise NanoSNPError("label_sites_keys: keep_thr [n_contigs] and counts [n_contigs, 2] belong to the contig table")
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        if want_label:
+            if out_center_idx is None:
+                out_center_idx = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+            if label is None:
+                label = torch.empty((max(n, 1), self.LABEL_WIDTH), dtype=torch.int32, device=dev)
+            if label.dtype != torch.int32 or label.numel() < n * self.LABEL_WIDTH or out_center_idx.numel() < n:
+                raise NanoSNPError("label_sites_keys: output buffers too small or of the wrong type")
+        else:
+            out_center_idx = label = None
+        for t, what in ((label, "label"), (meta, "meta")):
+            if t is not None and (not (t.is_cuda or t.is_pinned()) or not t.is_contiguous()):
+                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
+        if meta.dtype != torch.int64 or meta.numel() < 4:
+            raise NanoSNPError("label_sites_keys: meta int64 [4]")
+        check(self.lib.nsnp_pileup_label_sites_keys(self.handle, _dptr(key), m, _dptr(center_idx), n, _dptr(table.genome), _dptr(table.seq_off),
+                                                    len(table), _dptr(truth_key), _dptr(truth_code), int(truth_key.numel()), _dptr(keep_thr),
+                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, _dptr(out_center_idx), _dptr(label), _dptr(counts),
+                                                    meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_label_sites_keys")
+        if not want_label:
+            return None, None, meta
+        return out_center_idx.view(-1)[:n], label.view(-1)[:n * self.LABEL_WIDTH].view(n, self.LABEL_WIDTH), meta
 
     def pileup_gather_windows(self, counts, center_idx, stream=None):
         import torch

@@ -256,6 +256,7 @@ extern "C" int nsnp_ctx_destroy(nsnp_ctx* ctx)
     if (ctx->sel_tmp) (void)hipFree(ctx->sel_tmp);
     if (ctx->fil_tmp) (void)hipFree(ctx->fil_tmp);
     if (ctx->rec_tmp) (void)hipFree(ctx->rec_tmp);
+    if (ctx->lab_tmp) (void)hipFree(ctx->lab_tmp);
     nsnp_tok_free(ctx);
     (void)nsnp_comm_destroy(ctx);
     nsnp_hap_free(ctx);

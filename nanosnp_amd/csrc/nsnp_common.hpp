@@ -129,6 +129,7 @@ struct nsnp_ctx {
     int64_t* sel_tmp; size_t sel_tmp_bytes;   // select_sites scratch
     int64_t* fil_tmp; size_t fil_tmp_bytes;   // filter_columns scratch: kept columns and bytes per tile (pileup_encode.hip)
     void* rec_tmp; size_t rec_tmp_bytes;      // nsnp_pileup_alt_info scratch: scanned sizes + the staging blob (pileup_records.hip)
+    void* lab_tmp; size_t lab_tmp_bytes;      // nsnp_pileup_label_sites_keys scratch: scanned flags + two words per site (pileup_labels.hip)
     void* tok_ws; size_t tok_ws_bytes;        // mpileup tokeniser scratch: 4,112 bytes per 8 KB tile of text (mpileup_tokenise.hip)
     void* ctg_ws; size_t ctg_ws_bytes;        // nsnp_mpileup_tokenise_contigs scratch: 8 bytes per line + 16 per 256 lines (mpileup_tokenise.hip)
     int tok_fused;      // mpileup tokeniser: 0 = three launches (default), 1 = one launch, chained scan (opt-in: its tiles spin on their predecessors)

@@ -2050,8 +2050,14 @@ class _BinStaging:
         self.cur = self.cur_cid = None
         self.done = {}                                       # contig index -> sites, of the staging files that are complete
 
+    suffix = ".pd.bin"
+
     def staging_path(self, cid):
         return os.path.join(self.out_dir, f"{self.tag}.{int(cid)}")
+
+    def _writer(self, cid):
+        from . import sitefile
+        return sitefile.PileupBinWriter(self.staging_path(cid), self.matrix_dtype, self.alt_info)
 
     def _finish(self):
         if self.cur is not None:
@@ -2065,8 +2071,7 @@ class _BinStaging:
             self._finish()
             if cid in self.done or not 0 <= cid < len(self.names):
                 raise NanoSNPError(f"records: contig index {cid} outside the table or in two separate pieces")
-            from . import sitefile
-            self.cur_cid, self.cur = cid, sitefile.PileupBinWriter(self.staging_path(cid), self.matrix_dtype, self.alt_info)
+            self.cur_cid, self.cur = cid, self._writer(cid)
         if self.alt_info:
             self.cur.append(x, position, blob, offsets)
         else:
@@ -2080,17 +2085,16 @@ class _BinStaging:
     def commit(self, order):
         """order: the wanted contigs the text holds, in its order (ContigRuns.order) - one without sites gets its empty file here.
         -> {name: sites}; the files are in place."""
-        from . import sitefile
         from ._lib import NanoSNPError
         self._finish()
         if set(self.done) - set(order):
             raise NanoSNPError("records: sites of a contig the text's runs do not hold")
         for cid in order:
             if cid not in self.done:
-                self.done[cid] = sitefile.PileupBinWriter(self.staging_path(cid), self.matrix_dtype, self.alt_info).close()
+                self.done[cid] = self._writer(cid).close()
         out = {}
         for cid in order:
-            os.replace(self.staging_path(cid), os.path.join(self.out_dir, f"{self.names[cid]}.pd.bin"))
+            os.replace(self.staging_path(cid), os.path.join(self.out_dir, f"{self.names[cid]}{self.suffix}"))
             out[self.names[cid]] = self.done.pop(cid)
         return out
 
@@ -2106,14 +2110,14 @@ class _BinStaging:
         self.done = {}
 
 
-def _staged_bins(out_dir, names, matrix_dtype, alt_info, run_pass, st):
+def _staged_bins(out_dir, names, matrix_dtype, alt_info, run_pass, st, staging_cls=None):
     """The file side of mpileup_to_bins: run_pass(staging, state) streams the text once, appending to `staging` -> (run again?, the wanted
     contigs the text holds in its order); state = {elem, blob_min, name_cap} says how the next pass differs.  Every pass but the last is
     dropped whole; the files are renamed into place when the last one has ended, and on any error nothing of this call is left in out_dir
     (out_dir itself neither, when this call made it).  -> {name: sites}"""
     made = not os.path.isdir(out_dir)
     os.makedirs(out_dir, exist_ok=True)
-    staging = _BinStaging(out_dir, names, matrix_dtype, alt_info)
+    staging = (staging_cls or _BinStaging)(out_dir, names, matrix_dtype, alt_info)
     state = dict(elem=2 if matrix_dtype == "int16" else 4, blob_min=0, name_cap=1024)
     try:
         while True:
@@ -2133,16 +2137,22 @@ def _staged_bins(out_dir, names, matrix_dtype, alt_info, run_pass, st):
         raise
 
 
-def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_af, min_coverage, st, alt_info, state, staging, pool, beds=None):
+def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_af, min_coverage, st, alt_info, state, staging, pool, beds=None,
+                       train=None):
     """one pass of mpileup_to_bins over the text -> (True when it has to be run again - state says how: elem 4, blob_min bytes per slot, or
-    name_cap entries per name table -, the wanted contigs the text holds in its order)"""
+    name_cap entries per name table -, the wanted contigs the text holds in its order).
+    train (a _TrainLabels of mpileup_to_train_bins; None: exactly the launches issued without): its slots carry the label rows, its
+    label() runs in front of the record kernels and says which centres they get, and the writer hands the staging the label rows and the
+    site keys of every piece."""
     import torch
     from ._lib import NanoSNPError
     elem = state["elem"]
     text_len = int(_as_bytes_like(text)[1].size)
-    slots = getattr(model, "_rec_slots", None)
+    slots_attr = "_rec_slots" if train is None else "_train_slots"
+    slots = getattr(model, slots_attr, None)
     if slots is None:
-        slots = model._rec_slots = [None, None, None]
+        slots = [None, None, None]
+        setattr(model, slots_attr, slots)
     flag = dict(overflow=False, alt_need=0, status=0)
     turn, spans = [0], []
 
@@ -2153,6 +2163,8 @@ def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_a
             flag["overflow"] = True
         if m[0, 2]:
             flag["status"] = int(m[0, 2])
+        if train is not None and int(slot.lmeta[3]):
+            flag["status"] = flag["status"] or 1
         if alt_info and (m[1, 1] & ctx.TOK_ERANGE):
             flag["alt_need"] = max(flag["alt_need"], int(m[1, 0]))
         if alt_info and (m[1, 1] & ~ctx.TOK_ERANGE):
@@ -2162,9 +2174,14 @@ def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_a
         x = slot.matrix.numpy().view(np.int16 if elem == 2 else np.int32)[:n * 594].reshape(n, 33, 18)
         position, blob = slot.position.numpy(), slot.blob.numpy()
         # the rows are ascending in line order: every contig of the chunk is one piece
-        for cid, a, b, b_lo, b_hi, offs in cut_records_by_contig(slot.site_key.numpy()[:n], slot.offsets.numpy()[:n + 1] if alt_info else None):
-            staging.append(cid, x[a:b], position[a:b], blob[b_lo:b_hi] if alt_info else None, offs)
-        st["record_bytes"] = st.get("record_bytes", 0) + n * (594 * elem + 83) + (int(m[1, 0]) + 8 * n if alt_info else 0)
+        keys = slot.site_key.numpy()
+        for cid, a, b, b_lo, b_hi, offs in cut_records_by_contig(keys[:n], slot.offsets.numpy()[:n + 1] if alt_info else None):
+            if train is None:
+                staging.append(cid, x[a:b], position[a:b], blob[b_lo:b_hi] if alt_info else None, offs)
+            else:
+                staging.append(cid, x[a:b], position[a:b], slot.label.numpy()[a:b], blob[b_lo:b_hi] if alt_info else None, offs, keys=keys[a:b])
+        st["record_bytes"] = (st.get("record_bytes", 0) + n * (594 * elem + 83 + (0 if train is None else 360))
+                              + (int(m[1, 0]) + 8 * n if alt_info else 0))
 
     def records(k, counts, centers, cols, main):
         if flag["overflow"] or flag["alt_need"] or flag["status"]:
@@ -2179,7 +2196,13 @@ def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_a
         want_blob = max(64 * n + (1 << 16), state["blob_min"])
         if slot is None or slot.rows < n or slot.blob.numel() < want_blob:
             rows = max(n + n // 4, _cols_for(min(int(chunk_bytes), text_len)) // 64, 1024 if slot is None else slot.rows)
-            slot = slots[i] = _RecSlot(rows, max(64 * rows + (1 << 16), state["blob_min"]))
+            blob_bytes = max(64 * rows + (1 << 16), state["blob_min"])
+            slot = slots[i] = _RecSlot(rows, blob_bytes) if train is None else train.new_slot(rows, blob_bytes, main)
+        if train is not None:
+            centers = train.label(slot, centers, cols, main, st, flag)
+            if centers is None:
+                return                                       # (no site of the chunk is kept, or a status that ends the pass)
+            n = int(centers.shape[0])
         timed = st.get("time_records")                       # (as contig_to_bin: HIP-event time of the record kernels)
         if timed:
             t0, t1, t2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
@@ -2224,7 +2247,8 @@ def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_a
         drain(True)                                          # (the streams have been waited for: the writer's pieces end at once)
         raise
     if flag["status"]:
-        raise NanoSNPError(f"a selected site outside the columns or its contig, or a name longer than 37 bytes in column 0 (record status {flag['status']})")
+        raise NanoSNPError("a selected site outside the columns or its contig, " + ("" if train is None else "at a reference byte other than A/C/G/T, ")
+                           + f"or a name longer than 37 bytes in column 0 (record status {flag['status']})")
     if flag["overflow"]:
         if elem == 4:
             raise NanoSNPError("int16 overflow reported for int32 records")
@@ -2306,6 +2330,238 @@ def _mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir
                                                                          st, alt_info, state, staging, pool, beds), st)
         st["sites"] = st.get("sites", 0) + sum(out.values())
         return out
+    finally:
+        if text is not None:
+            try:
+                text.close()
+            except BufferError:                  # (an exception on its way up still holds views of the mapping)
+                pass
+        if g is not None:
+            g.close()
+
+
+# ---- one whole-genome mpileup text + a truth VCF -> every <chr>.td.bin (make_train_data.sh steps 4, 6 and 7) --------------------------------
+class _TrainSlot(_RecSlot):
+    """a _RecSlot with the labels of its rows (pinned), the label entry's counts (pinned) and the kept centres (device)"""
+    def __init__(self, rows, blob_bytes, dev):
+        import torch
+        from ._lib import Context
+        super().__init__(rows, blob_bytes)
+        self.label = torch.empty((self.rows, Context.LABEL_WIDTH), dtype=torch.int32, pin_memory=True)
+        self.lmeta = torch.zeros(4, dtype=torch.int64, pin_memory=True)
+        self.kept = torch.empty(max(self.rows, 1), dtype=torch.int64, device=dev)
+
+
+class _TrainStaging(_BinStaging):
+    """_BinStaging for <name>.td.bin: sitefile.TrainBinWriter, and what only the rows themselves can say - that the sites of a contig are
+    strictly ascending (NanoSNPError otherwise), and how many of the rows written are truth sites."""
+    suffix = ".td.bin"
+
+    def __init__(self, out_dir, names, matrix_dtype="int16", alt_info=True, truth_keys=None):
+        super().__init__(out_dir, names, matrix_dtype, alt_info)
+        self.truth_keys = np.zeros(0, np.int64) if truth_keys is None else truth_keys
+        self.last, self.variants = {}, {}
+
+    def _writer(self, cid):
+        from . import sitefile
+        return sitefile.TrainBinWriter(self.staging_path(cid), self.matrix_dtype, self.alt_info)
+
+    def append(self, cid, x, position, label, blob=None, offsets=None, keys=None):
+        from ._lib import KEY_SHIFT, NanoSNPError
+        k = np.asarray(keys, np.int64)
+        if k.size:
+            back = np.flatnonzero(k[1:] <= k[:-1])
+            at = int(k[0]) if (cid in self.last and k[0] <= self.last[cid]) else int(k[back[0] + 1]) if back.size else None
+            if at is not None:
+                raise NanoSNPError(f"{self.names[cid] if 0 <= cid < len(self.names) else cid}: the sites of a contig must be strictly ascending "
+                                   f"(position {at & ((1 << KEY_SHIFT) - 1)} repeats or goes back)")
+        if self.cur is None or self.cur_cid != cid:
+            self._finish()
+            if cid in self.done or not 0 <= cid < len(self.names):
+                raise NanoSNPError(f"records: contig index {cid} outside the table or in two separate pieces")
+            self.cur_cid, self.cur = cid, self._writer(cid)
+        if self.alt_info:
+            self.cur.append(x, position, label, blob, offsets)
+        else:
+            self.cur.append(x, position, label)
+        if k.size:
+            self.last[cid] = int(k[-1])
+            at = np.searchsorted(self.truth_keys, k)
+            hit = (at < self.truth_keys.size) & (self.truth_keys[np.minimum(at, max(self.truth_keys.size - 1, 0))] == k) if self.truth_keys.size else np.zeros(k.size, bool)
+            self.variants[cid] = self.variants.get(cid, 0) + int(hit.sum())
+
+    def abort(self):
+        super().abort()
+        self.last, self.variants = {}, {}
+
+
+def _train_count_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_af, min_coverage, beds, truth, seed, state):
+    """the count pass of mpileup_to_train_bins: the stream of the text with nothing but the count-mode label launch behind every chunk's
+    selection -> int64 [n_contigs, 2] = {truth sites, other sites} per contig, or None when the pass has to be run again (state: name_cap)"""
+    import torch
+    from ._lib import NanoSNPError
+    dev = torch.device("cuda", ctx.device)
+    totals = torch.zeros((len(table), 2), dtype=torch.int64, device=dev)
+    metas = []
+
+    def records(k, counts, centers, cols, main):
+        metas.append(ctx.pileup_label_sites_keys(cols.pos, centers, table, truth[0], truth[1], None, seed, counts=totals, stream=main,
+                                                 want_label=False)[2])
+
+    try:
+        with host.gc_paused():
+            _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, {}, None, indel_min_af=indel_min_af, records=records,
+                             name_cap=state["name_cap"], beds=beds)
+    except _NamesOverflow as e:
+        state["name_cap"] = 2 * e.need + 64
+        return None
+    if metas and int(torch.stack(metas)[:, 3].max().item()):
+        raise NanoSNPError("a selected site outside the columns or its contig, or at a reference byte other than A/C/G/T (label status)")
+    return totals.cpu().numpy()
+
+
+class _TrainLabels:
+    """What _text_records_pass does differently for mpileup_to_train_bins: truth = (device keys, device codes); thr: the device thresholds,
+    or None - then every site is kept, N' == N is known on the host and the label launch simply goes in front of the record kernels on the
+    compute stream.  With thresholds the label launch runs on a side stream (the chunk's selection is complete: its count has been
+    read), the issuing thread waits for ITS event alone and reads N' from pinned memory, and the compute stream waits for that event -
+    whatever else is queued on the compute stream (the record kernels of the chunk before) keeps running meanwhile."""
+
+    def __init__(self, model, ctx, table, truth, thr, seed):
+        import torch
+        self.ctx, self.table, self.truth, self.thr, self.seed = ctx, table, truth, thr, seed
+        self.dev = torch.device("cuda", ctx.device)
+        self.side = None
+        if thr is not None:
+            self.side = getattr(model, "_label_stream", None)
+            if self.side is None or self.side.device != self.dev:
+                self.side = model._label_stream = torch.cuda.Stream(self.dev)
+
+    def new_slot(self, rows, blob_bytes, main):
+        slot = _TrainSlot(rows, blob_bytes, self.dev)
+        if self.side is not None:
+            # slot.kept comes out of the compute stream's pool: its block may be one a previous chunk's tensors (counts, depth, centres)
+            # gave back while that chunk's record kernels are still queued on the compute stream and still read them.  The compute
+            # stream's own later work is ordered behind those kernels; the side stream is not, and its first write into the new buffer
+            # would be - so it waits once for everything queued on the compute stream so far (_text_chunk_sets does the same for the
+            # copy stream).  Nothing in the steady state: a slot that is kept is not new.
+            self.side.wait_stream(main)
+        return slot
+
+    def label(self, slot, centers, cols, main, st, flag):
+        """the label launch of one chunk -> the centres the record kernels get (None: none)"""
+        import time
+        import torch
+        ctx, truth = self.ctx, self.truth
+        if self.thr is None:
+            return ctx.pileup_label_sites_keys(cols.pos, centers, self.table, truth[0], truth[1], None, self.seed, out_center_idx=slot.kept,
+                                               label=slot.label, meta=slot.lmeta, stream=main)[0]
+        ctx.pileup_label_sites_keys(cols.pos, centers, self.table, truth[0], truth[1], self.thr, self.seed, out_center_idx=slot.kept,
+                                    label=slot.label, meta=slot.lmeta, stream=self.side)
+        labelled = torch.cuda.Event(); labelled.record(self.side)
+        t_w = time.perf_counter()
+        labelled.synchronize()
+        st["wait_labels_s"] = st.get("wait_labels_s", 0.0) + time.perf_counter() - t_w
+        main.wait_event(labelled)
+        n_kept, _, _, status = slot.lmeta.tolist()
+        if status:
+            flag["status"] = 1
+            return None
+        st["dropped_sites"] = st.get("dropped_sites", 0) + int(centers.shape[0]) - n_kept
+        return slot.kept[:n_kept] if n_kept else None
+
+
+def mpileup_to_train_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, truth_vcf, out_dir, contigs=None, *, extended_bed=None,
+                          confident_bed=None, max_non_variant_ratio=5.0, seed=0, alt_info=True, matrix_dtype="int16", min_af=0.12,
+                          indel_min_af=None, min_coverage=6, chunk_bytes=64 << 20, stats=None):
+    """The training set of the PileupModel from the two files the reference's make_train_data.sh starts from: ONE mpileup text holding every
+    contig and the truth VCF -> <out_dir>/<name>.td.bin for every wanted contig the text holds (sitefile.TrainBinWriter: position_matrix,
+    position, label int32 [N,90], alt_info) - steps 4, 6 and 7 of that script (DNA_SplitVcf, DNA_CreateTrainData, make_bin_train_data.py)
+    behind the steps mpileup_to_bins_bed already runs; with max_non_variant_ratio=None byte for byte sitefile.td_to_bin of the reference's
+    <name>.td at -shuffle_tensors 0.
+
+    truth_vcf: a path or the bytes of the VCF (truth.load_truth says how a row becomes a label, every quirk of the reference kept).  The
+    text is the stream of mpileup_to_bins_bed; behind every chunk's selection nsnp_pileup_label_sites_keys looks every site up among the
+    truth keys (resident on the device), labels it - a site no truth row names gets the homozygous-reference label of its base -, drops
+    the surplus of such sites and hands the record kernels the centres that are left.
+    max_non_variant_ratio (the reference's -maxinum_non_variant_ratio): None keeps every site in ONE pass.  A number runs a count pass over
+    the text first (the same stream, only the counting launch behind each selection); per contig max_nv = int(variants * ratio), and a
+    contig with more non-variant sites than that keeps such a site when (hash(key, seed) >> 11) < (max_nv << 53) // non_variants - a
+    contig with sites but without a truth site keeps nothing, as the reference's arithmetic gives.
+    Where this departs from the reference: rows stay in text order (no shuffle); the subsample is a seeded function of
+    the key, the same set for every chunk layout and run; the sites of a contig must be strictly ascending (NanoSNPError); the
+    confident_* recall line of the reference's log is not computed.
+    Everything else - contigs, the BEDs, alt_info, matrix_dtype, the staging names renamed only on success, restarts of the whole text, the
+    set of files, the refusals (_bins_refusals) - as mpileup_to_bins_bed.  stats: as there, plus count_pass_s, wait_labels_s, dropped_sites.
+    Returns {name: dict(sites=, variants=, non_variants=, kept=, ratio=, truth=, recall=)} in text order: the numbers of the reference's two
+    log lines (candidate sites that are / are not truth variants, the subsample ratio, the contig's truth variants and the share of them
+    among the sites) and the rows written."""
+    import time
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from . import _lib, sitefile
+    from . import truth as _truth
+    _bins_refusals()
+    if matrix_dtype not in ("int16", "int32"):
+        raise sitefile.SiteFileError("matrix_dtype: 'int16' or 'int32'")
+    if max_non_variant_ratio is not None and not float(max_non_variant_ratio) >= 0.0:
+        raise ValueError("max_non_variant_ratio: None or a number >= 0")
+    names = [str(n) for n in (contigs if contigs is not None else fai_names(fai_text))]
+    for n in names:
+        b = n.encode()
+        if not b or b"\0" in b or len(b) + 1 + 11 + 1 + 33 > sitefile.POSITION_WIDTH:
+            raise ValueError(f"{n!r}: a contig name of 1 to {sitefile.POSITION_WIDTH - 46} bytes without NUL is needed for the "
+                             f"{sitefile.POSITION_WIDTH}-byte position field")
+    ctx = model.ctx
+    dev = torch.device("cuda", ctx.device)
+    table = _lib.ContigTable(fasta=fasta_path, names=names, device=ctx.device)
+    t_keys, t_codes, t_counts = _truth.load_truth(truth_vcf, table)
+    truth = (torch.from_numpy(t_keys).to(dev), torch.from_numpy(t_codes.view(np.int32)).to(dev))
+    beds = None if extended_bed is None and confident_bed is None else _lib.BedTable(table, extended_bed, confident_bed, fai_text)
+    st = _stream_stats(stats)
+    g = text = None
+    if isinstance(mpileup_path_or_bytes, (str, os.PathLike)):
+        g = open(mpileup_path_or_bytes, "rb")
+        size = os.fstat(g.fileno()).st_size
+        text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if size else None
+    try:
+        src = (text if text is not None else b"") if g is not None else mpileup_path_or_bytes
+        counted = thr = ratios = None
+        if max_non_variant_ratio is not None:
+            t0 = time.perf_counter()
+            cstate = dict(name_cap=1024)
+            while counted is None:
+                counted = _train_count_pass(model, ctx, src, table, chunk_bytes, min_af, indel_min_af, min_coverage, beds, truth, seed, cstate)
+            st["count_pass_s"] = st.get("count_pass_s", 0.0) + time.perf_counter() - t0
+            thr_list, ratios = _truth.keep_thresholds(counted[:, 0], counted[:, 1], max_non_variant_ratio)
+            thr = torch.tensor(thr_list, dtype=torch.int64, device=dev) if thr_list else None
+        labels = _TrainLabels(model, ctx, table, truth, thr, seed)
+        made = []
+
+        def staging_of(*a):
+            made.append(_TrainStaging(*a, truth_keys=t_keys))
+            return made[-1]
+
+        with ThreadPoolExecutor(max_workers=1) as pool:
+            out = _staged_bins(out_dir, names, matrix_dtype, alt_info,
+                               lambda staging, state: _text_records_pass(model, ctx, src, table, chunk_bytes, min_af, indel_min_af, min_coverage,
+                                                                         st, alt_info, state, staging, pool, beds, train=labels),
+                               st, staging_cls=staging_of)
+        st["sites"] = st.get("sites", 0) + sum(out.values())
+        result = {}
+        for name, kept in out.items():
+            cid = names.index(name)
+            variants = made[-1].variants.get(cid, 0)
+            if counted is None:
+                sites, non_variants, ratio = kept, kept - variants, 1.0
+            else:
+                if int(counted[cid, 0]) != variants:
+                    raise _lib.NanoSNPError(f"{name}: the count pass saw {int(counted[cid, 0])} truth sites, the write pass wrote {variants}")
+                sites, non_variants, ratio = int(counted[cid].sum()), int(counted[cid, 1]), ratios[cid]
+            n_truth = int(t_counts[cid])
+            result[name] = dict(sites=sites, variants=variants, non_variants=non_variants, kept=kept, ratio=ratio, truth=n_truth,
+                                recall=variants / n_truth if n_truth else float("nan"))
+        return result
     finally:
         if text is not None:
             try:

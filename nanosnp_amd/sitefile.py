@@ -348,6 +348,128 @@ def pd_to_bin(pd_text: bytes, path, matrix_dtype="int16"):
     return len(xs)
 
 
+# ---- <chr>.td.bin ------------------------------------------------------------------------------------------------
+LABEL_WIDTH = 90                  # make_bin_train_data.py: label_size = 21 + 3 + 33 + 33 (common/genotype.cpp:264-274)
+
+
+def _label_rows(label, n):
+    y = np.asarray(label)
+    if y.dtype.kind not in "iu" or y.shape != (n, LABEL_WIDTH):
+        raise SiteFileError(f"label must hold integers [N,{LABEL_WIDTH}] with one row per site")
+    return np.ascontiguousarray(y, dtype=np.int32)
+
+
+def write_train_bin(path, position_matrix, position, label, alt_info=None, matrix_dtype="int16"):
+    """The training file the reference's make_bin_train_data.py:101-105 leaves behind, under its array names: position_matrix, position and
+    alt_info exactly as write_pileup_bin stores them, and label int32 [N,90] (the reference's Int32Atom) behind position."""
+    import os
+    tmp = f"{path}.pd.tmp"
+    write_pileup_bin(tmp, position_matrix, position, alt_info, matrix_dtype=matrix_dtype)
+    try:
+        a = read_arrays(tmp, mmap=False)
+    finally:
+        os.remove(tmp)
+    arrays = {"position_matrix": a["position_matrix"], "position": a["position"], "label": _label_rows(label, a["position"].shape[0])}
+    arrays.update({k: a[k] for k in ("alt_info", "alt_info_offsets") if k in a})
+    write_arrays(path, arrays)
+
+
+class TrainBinWriter(PileupBinWriter):
+    """A <chr>.td.bin written piece by piece (pipeline.mpileup_to_train_bins): PileupBinWriter with one more array, label int32 [N,90], held
+    back with the other small arrays and written behind `position`.  close() leaves a file byte-identical to write_train_bin of the same
+    rows in one call."""
+
+    def _start(self, matrix_dtype):
+        super()._start(matrix_dtype)
+        self._labels = []
+        n_arrays = 5 if self.alt_info else 3
+        self._x_off = (len(MAGIC) + 8 + _REC.size * n_arrays + 63) & ~63
+        self._f.seek(self._x_off)
+
+    def append(self, position_matrix_rows, position_rows, label_rows, alt_blob=None, alt_offsets=None):
+        """as PileupBinWriter.append, with label_rows: integer [n,90]"""
+        y = _label_rows(label_rows, np.asarray(position_matrix_rows).shape[0])
+        before = self.n
+        super().append(position_matrix_rows, position_rows, alt_blob, alt_offsets)
+        if self.n != before:
+            self._labels.append(np.array(y, np.int32, copy=True))
+
+    def close(self):
+        import os
+        if self._f is None:
+            raise SiteFileError("close() of a writer that was closed or aborted")
+        f, n = self._f, self.n
+        # (name, dtype, shape, the pieces held back: written one after another, never joined - the labels are 360 bytes a site)
+        small = [("position", np.dtype(np.uint8), (n, POSITION_WIDTH), self._positions), ("label", np.dtype(np.int32), (n, LABEL_WIDTH), self._labels)]
+        if self.alt_info:
+            offs = np.zeros(n + 1, np.int64)
+            if self._lens:
+                np.cumsum(np.concatenate(self._lens), out=offs[1:])
+            small.append(("alt_info", np.dtype(np.uint8), (int(offs[-1]),), self._blobs))
+            small.append(("alt_info_offsets", offs.dtype, offs.shape, [offs]))
+        recs = [_REC.pack(b"position_matrix", self.matrix_dtype.str.encode(), 3, 0, n, 33, 18, 0, self._x_off, n * 594 * self.matrix_dtype.itemsize)]
+        try:
+            off = self._x_off + n * 594 * self.matrix_dtype.itemsize
+            if f.tell() != off:
+                raise SiteFileError("internal: matrix bytes written do not match the site count")
+            for name, dt, shape, pieces in small:
+                o = (off + 63) & ~63
+                f.write(b"\0" * (o - off))
+                nbytes = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+                for piece in pieces:
+                    f.write(memoryview(np.ascontiguousarray(piece, dt)).cast("B"))
+                if f.tell() != o + nbytes:
+                    raise SiteFileError(f"internal: {name} bytes written do not match the site count")
+                recs.append(_REC.pack(name.encode(), dt.str.encode(), len(shape), 0, *(list(shape) + [0] * (4 - len(shape))), o, nbytes))
+                off = o + nbytes
+            f.truncate(off)                                # (empty arrays at the end still count their padding, as write_arrays writes it)
+            f.seek(0)
+            f.write(MAGIC + struct.pack("<II", len(recs), 0))
+            for r in recs:
+                f.write(r)
+            f.close()
+            self._f = None
+            os.replace(self.tmp, self.path)
+        except BaseException:
+            self.abort()
+            raise
+        return n
+
+
+def read_train_bin(path, mmap=True):
+    """-> (contig_names, positions int64 [N], reference_bases uint8 [N], position_matrix int32 [N,33,18], label int32 [N,90]): read_pileup_bin
+    plus the labels"""
+    a = read_arrays(path, mmap)
+    if "label" not in a or tuple(a["label"].shape[1:]) != (LABEL_WIDTH,):
+        raise SiteFileError(f"{path}: not a training site file")
+    return (*read_pileup_bin(path, mmap), a["label"])
+
+
+def td_to_bin(td_text: bytes, path, matrix_dtype="int16"):
+    """``.td`` text (DNA_CreateTrainData, make_train_data/main.cpp:369-382) -> training site file: ``transform_one_input`` of
+    make_bin_train_data.py:61-81 - columns 0-3 of a line are the 594 ints, the 90 label ints, the position string and alt_info; a fifth
+    (the truth row the reference appends to a variant's line) is ignored, as there."""
+    xs, ys, positions, alts = [], [], [], []
+    for ln, line in enumerate(td_text.split(b"\n")):
+        line = line.strip()
+        if not line:
+            continue
+        fields = line.split(b"\t")
+        if len(fields) < 4:
+            raise SiteFileError(f".td line {ln + 1}: expected tensor, label, position and alt_info fields")
+        vals, lab = np.array(fields[0].split(), dtype=np.int64), np.array(fields[1].split(), dtype=np.int64)
+        if vals.size != 33 * 18 or lab.size != LABEL_WIDTH:
+            raise SiteFileError(f".td line {ln + 1}: {vals.size} tensor and {lab.size} label values, expected 594 and {LABEL_WIDTH}")
+        xs.append(vals.astype(np.int32).reshape(33, 18))
+        ys.append(lab.astype(np.int32))
+        positions.append(fields[2].strip())
+        alts.append(fields[3].strip())
+    x = np.stack(xs) if xs else np.empty((0, 33, 18), np.int32)
+    y = np.stack(ys) if ys else np.empty((0, LABEL_WIDTH), np.int32)
+    write_train_bin(path, x, positions, y, alts, matrix_dtype=matrix_dtype)
+    return len(xs)
+
+
 # ---- haplotype bins ---------------------------------------------------------------------------------------------------
 HAP_PLANES = ("haplotype_sequences", "haplotype_hap", "haplotype_baseq", "haplotype_mapq",
               "pileup_sequences", "pileup_hap", "pileup_baseq", "pileup_mapq")
