@@ -128,11 +128,13 @@ int nsnp_ctx_reserve(nsnp_ctx* ctx, int64_t max_sites);
  *   kernels, bit-identical to each other), "l1_register_stationary" 1 four waves x four gate
  *   tiles (default) | 2 eight waves x two tiles | 0 LDS-image kernels with the Xp1 round trip, "l1_site_groups" 0 | 1 | 2 | 4,
  *   "l1_stagger" 0 (default) | 1 (eight-wave kernel: waves 4-7 issue a group's next input part ahead of its cell),
+ *   "l1_weave" 1 (default) | 0 (four-wave kernel, one site group: the step software-pipelined - the next step's input projection
+ *   is issued in front of the barrier with the cell placed inside its MFMA burst, half of W_hh in LDS; bit-identical to 0),
  *   "head_split" 1 (default) | 0 heads with the output tiles split over eight waves, "static_priority" 0..3 (f16x3
  *   register-stationary kernels: s_setprio 1 for waves 4-7 of layer 1 / odd workgroups of layer 0; measured without effect),
  *   "l0_input_weights_in_lds" 0 (default) | 1 (fp32 layer 0, 16-site workgroups: input-part weight fragments in LDS, 128
  *   VGPRs; measured without gain).  Combinations without effect are accepted and ignored: "l1_site_groups" under
- *   "l1_register_stationary" 1 (its workgroups are always one 16-site group), "l1_stagger" outside the eight-wave kernel,
+ *   "l1_register_stationary" 1 (its workgroups are always one 16-site group), "l1_stagger" outside the eight-wave kernel, "l1_weave" outside fp32 / "l1_register_stationary" 1 / one site group,
  *   "static_priority" and "fused_*" / "proj1_tiles" on the fp32 path.
  *   bf16x3 path (pileup_precision 2): "l0_site_groups" 0 auto | 1/2/4 and "l1_site_groups" 0 auto | 1/2/4 (16-site groups per
  *   workgroup of its layer-0 / layer-1 kernel); every combination returns the same bits.

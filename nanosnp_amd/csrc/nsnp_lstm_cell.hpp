@@ -42,4 +42,52 @@ __device__ __forceinline__ float lstm_cell(float zi, float zf, float zg, float z
     return (1.0f - ec) * __builtin_amdgcn_rcpf(__builtin_fmaf(eo, tc, tc));
 }
 
+// The same cell for FOUR units, one instruction at a time, for kernels that place the cell into the gaps of an MFMA burst by hand:
+// slice I = 4 stage + unit, 20 stages per unit, 80 slices.  A stage is one instruction of lstm_cell above with the same operands in
+// the same order, so the bits are lstm_cell's; consecutive slices belong to different units, a dependent instruction follows its
+// operand four slices later.  z[u] holds the pre-activations (i f g o) of unit u, c[u] its state (updated by stage 12), h[u]
+// receives h' (stage 19).
+struct CellSlices { float ei[4], ef[4], eo[4], eg[4], t[4], d[4], m[4], fg[4]; };
+constexpr int CELL_SLICES = 80;
+
+template <int I, typename Z4>
+__device__ __forceinline__ void lstm_cell_slice(CellSlices& w, const Z4 (&z)[4], float (&c)[4], Z4& h)
+{
+    static_assert(I >= 0 && I < CELL_SLICES, "slice index");
+    constexpr int st = I >> 2, u = I & 3;
+    constexpr float K = -2.0f * LOG2E;
+    if constexpr (st == 0) w.ei[u] = __builtin_amdgcn_exp2f(z[u][0]);
+    else if constexpr (st == 1) w.ef[u] = __builtin_amdgcn_exp2f(z[u][1]);
+    else if constexpr (st == 2) w.eo[u] = __builtin_amdgcn_exp2f(z[u][3]);
+    else if constexpr (st == 3) w.t[u] = cap64(z[u][2]);
+    else if constexpr (st == 4) w.eg[u] = __builtin_amdgcn_exp2f(w.t[u]);
+    else if constexpr (st == 5) w.t[u] = 1.0f + w.eg[u];                                   // tg
+    else if constexpr (st == 6) w.d[u] = __builtin_fmaf(w.ei[u], w.t[u], w.t[u]);
+    else if constexpr (st == 7) w.d[u] = __builtin_amdgcn_rcpf(w.d[u]);
+    else if constexpr (st == 8) w.m[u] = __builtin_fmaf(-K, w.eg[u], K);
+    else if constexpr (st == 9) w.m[u] = w.m[u] * w.d[u];                                  // ig
+    else if constexpr (st == 10) w.fg[u] = 1.0f + w.ef[u];
+    else if constexpr (st == 11) w.fg[u] = __builtin_amdgcn_rcpf(w.fg[u]);
+    else if constexpr (st == 12) c[u] = __builtin_fmaf(w.fg[u], c[u], w.m[u]);             // cn
+    else if constexpr (st == 13) w.t[u] = cap64(c[u]);
+    else if constexpr (st == 14) w.eg[u] = __builtin_amdgcn_exp2f(w.t[u]);                 // ec
+    else if constexpr (st == 15) w.t[u] = 1.0f + w.eg[u];                                  // tc
+    else if constexpr (st == 16) w.d[u] = __builtin_fmaf(w.eo[u], w.t[u], w.t[u]);
+    else if constexpr (st == 17) w.d[u] = __builtin_amdgcn_rcpf(w.d[u]);
+    else if constexpr (st == 18) w.m[u] = 1.0f - w.eg[u];
+    else h[u] = w.m[u] * w.d[u];
+    // the result is made opaque where it is written: hipcc otherwise packs two units' slices into one v_pk_* instruction and sinks
+    // the dependent chain to the end of the burst
+    if constexpr (st == 0) asm volatile("" : "+v"(w.ei[u]));
+    else if constexpr (st == 1) asm volatile("" : "+v"(w.ef[u]));
+    else if constexpr (st == 2) asm volatile("" : "+v"(w.eo[u]));
+    else if constexpr (st == 4 || st == 14) asm volatile("" : "+v"(w.eg[u]));
+    else if constexpr (st == 3 || st == 5 || st == 13 || st == 15) asm volatile("" : "+v"(w.t[u]));
+    else if constexpr (st == 6 || st == 7 || st == 16 || st == 17) asm volatile("" : "+v"(w.d[u]));
+    else if constexpr (st == 8 || st == 9 || st == 18) asm volatile("" : "+v"(w.m[u]));
+    else if constexpr (st == 10 || st == 11) asm volatile("" : "+v"(w.fg[u]));
+    else if constexpr (st == 12) asm volatile("" : "+v"(c[u]));
+    else { float v = h[u]; asm volatile("" : "+v"(v)); h[u] = v; }
+}
+
 }  // namespace nsnp_cell

@@ -1040,8 +1040,221 @@ __global__ __launch_bounds__(256, 2) void k_pileup_l1_rs4(
     NSNP_DEVCLK_STOP(1)
 }
 
+// K23r4w: K23r4 for one site group with the step software-pipelined ("l1_weave" 1).  The input projection of step s+1 reads only
+// h0 rows that were staged ahead, so it is issued in step s into a second accumulator set, and the 80 vector instructions of the
+// cell of step s (nsnp_cell::lstm_cell_slice) are placed into the gaps between its 128 MFMAs: CELL_PER_GAP vector instructions
+// behind each MFMA from gap CELL_FIRST_GAP on, then the ds_write of h1, the h0 staging, the rest of the burst and the barrier.
+// A step is then 64 recurrent MFMAs, the cell, 127 MFMAs that wait for nothing, and the barrier, which every wave reaches with
+// its h1 row long written.  What measured (docs/rounds/r19.md): the cell in ONE piece is the gain (K23r4's first half of the cell
+// is mixed into its last ten MFMAs by hipcc); spread thinly over the burst it is a loss.  Per accumulator the chain is still
+// bias -> W_ih K-steps 0..31 -> W_hh K-steps 0..15: bit-identical to K23r4.
+// The order is written out slot by slot and held by a sched_barrier behind every slot: sched_group_barrier pipelines over the
+// whole burst were dropped by hipcc in the loop block (source order came back, docs/rounds/r19.md).
+// Registers: the second accumulator set does not fit beside 192 weight registers, so K blocks 2 and 3 of W_hh live in LDS
+// ([wave][tile][2][lane] f32x4, 32 KB, written once from the same packed image) and are read as A operands behind the barrier,
+// under the 32 MFMAs of K blocks 0 and 1.  h0 rows are staged two steps ahead: buffer u % 2 holds step u, step s stores the rows
+// of step s+2 over those of step s (read by the projection issued in step s-1) and loads those of step s+3; beyond the last step
+// both repeat the last rows into a buffer nobody reads again, so that the burst has no branch.
+constexpr int rs4w_l1_lds_bytes() { return rs4_l1_lds_bytes(1) + 4 * 4 * 2 * 64 * 16; }
+
+template <int... I, class F>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_seq(std::make_integer_sequence<int, N>{}, f); }
+
+template <int CELL_PER_GAP, int CELL_FIRST_GAP>
+__global__ __launch_bounds__(256, 2) void k_pileup_l1_rs4w(
+    const float* __restrict__ H0, int64_t N,
+    const float* __restrict__ wih0, const float* __restrict__ wih1,
+    const float* __restrict__ whh0, const float* __restrict__ whh1,
+    const float* __restrict__ bias0, const float* __restrict__ bias1,
+    float* __restrict__ H1c)
+{
+    extern __shared__ f32x4 lds[];
+    float* const h0s = reinterpret_cast<float*>(lds);                  // [2][16][RS_H0ROW]
+    float* const h1x = h0s + 2 * 16 * RS_H0ROW;                         // [2][16][RS_XROW]
+    f32x4* const lbias = reinterpret_cast<f32x4*>(h1x + 2 * 16 * RS_XROW);   // [16 tiles][4 q]
+    f32x4* const lwhh = lbias + 64;                                     // [4 waves][4 tiles][2 K blocks][64 lanes]
+    const int dir = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 15, q = lane >> 4;
+    NSNP_DEVCLK_START
+    const int64_t base_site = (int64_t)blockIdx.x * 16;
+
+    f32x4 Wih[4][8], Whh[4][2];
+    f32x4* const lw = lwhh + wave * (4 * 2 * 64) + lane;
+    {
+        const f32x4* __restrict__ gih = reinterpret_cast<const f32x4*>(dir ? wih1 : wih0);      // [tile][j4 8][lane]
+        const f32x4* __restrict__ ghh = reinterpret_cast<const f32x4*>(dir ? whh1 : whh0);      // [tile][j4 4][lane]
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) Wih[u][j] = gih[((4 * wave + u) * 8 + j) * 64 + lane];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) Whh[u][j] = ghh[((4 * wave + u) * 4 + j) * 64 + lane];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) lw[(2 * u + j) * 64] = ghh[((4 * wave + u) * 4 + 2 + j) * 64 + lane];
+        }
+        if (tid < 64) lbias[tid] = reinterpret_cast<const f32x4*>(dir ? bias1 : bias0)[(tid >> 2) * 64 + 16 * (tid & 3)];
+    }
+
+    // ---- h0 staging as in K23r4: thread (row = tid / 32 + 8 k, chunk = tid % 32) moves 2 chunks per step ----
+    const int cid = tid & 31;                                            // H0 order: 16 d + 4 q' + c
+    const int slot = (cid & 16) + 4 * (cid & 3) + ((cid >> 2) & 3);      // LDS order: 16 d + 4 c + q'
+    // (the global address is the workgroup's scalar base + t * 128 floats and a 32-bit byte offset per thread, made opaque in every
+    // step as in k_pileup_l0_rsx's flush: folded into a 64-bit address per thread it costs six vector instructions a step)
+    f32x4 sreg[2];
+    const float* const h0wg = H0 + base_site * (PW * 128);
+    unsigned hoff[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int64_t site = base_site + (tid >> 5) + 8 * k;
+        const int64_t sc = site < N ? site : N - 1;                     // rows past N restage the last site
+        hoff[k] = (unsigned)((int)(sc - base_site) * (PW * 128) + 4 * cid) * 4u;
+    }
+    auto tpos = [&](int u) { return dir ? PW - 1 - u : u; };
+    auto load_h0 = [&](int t) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            asm volatile("" : "+v"(hoff[k]));
+            sreg[k] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h0wg + t * 128) + hoff[k]);
+        }
+    };
+    auto store_h0 = [&](int buf) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            *reinterpret_cast<f32x4*>(h0s + ((size_t)buf * 16 + (tid >> 5) + 8 * k) * RS_H0ROW + 4 * slot) = sreg[k];
+    };
+    static_assert(PSTEPS1 >= 3, "the pipeline stages three steps in its prologue");
+    load_h0(tpos(0)); store_h0(0);
+    load_h0(tpos(1)); store_h0(1);
+    __syncthreads();
+    load_h0(tpos(2));
+
+    float c[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) c[u] = 0.f;
+
+    // input projection of the step staged in buffer buf.  project_reads: the biases and the first B fragment (issued ahead of the
+    // burst, under the last recurrent K block).  project: the burst; with CELL the cell of (a, c) goes into its gaps, the h1 row
+    // is written to hout, the staged h0 rows go to the other buffer and the rows of step tnext are loaded.
+    auto project_reads = [&](int buf, f32x4 (&p)[4], f32x4& b0) __attribute__((always_inline)) {
+        b0 = *reinterpret_cast<const f32x4*>(h0s + ((size_t)buf * 16 + n) * RS_H0ROW + 4 * q);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p[u] = lbias[(4 * wave + u) * 4 + q];
+    };
+    auto project = [&](int buf, f32x4 (&p)[4], const f32x4& b0, auto cell_tag, f32x4 (&a)[4], float* hout, int tnext)
+                       __attribute__((always_inline)) {
+        constexpr bool CELL = decltype(cell_tag)::value;
+        constexpr int NGAPS = (nsnp_cell::CELL_SLICES + CELL_PER_GAP - 1) / CELL_PER_GAP, CELL_END = CELL_FIRST_GAP + NGAPS;
+        static_assert(CELL_END + 8 <= 128, "the cell, the h1 row and the h0 staging end inside the burst");
+        const float* r0 = h0s + ((size_t)buf * 16 + n) * RS_H0ROW + 4 * q;
+        f32x4 b4[2];
+        b4[0] = b0;
+        nsnp_cell::CellSlices w;
+        f32x4 hn;
+        // slot g = 16 j + 4 e + u: K block j (direction j / 4, chunk j % 4), K-step 4 j + e, tile u -- today's order per accumulator.
+        // The B fragment of K block j+1 is read in front of the first MFMA of K block j.
+        static_for<128>([&](auto gc) __attribute__((always_inline)) {
+            constexpr int g = decltype(gc)::value, j = g >> 4, e = (g >> 2) & 3, u = g & 3;
+            if constexpr ((g & 15) == 0 && j + 1 < 8)
+                b4[(j + 1) & 1] = *reinterpret_cast<const f32x4*>(r0 + 64 * ((j + 1) >> 2) + 16 * ((j + 1) & 3));
+            p[u] = mfma4(Wih[u][j][e], b4[j & 1][e], p[u]);
+            if constexpr (CELL) {
+                static_for<CELL_PER_GAP>([&](auto kc) __attribute__((always_inline)) {
+                    constexpr int i = (g - CELL_FIRST_GAP) * CELL_PER_GAP + decltype(kc)::value;
+                    if constexpr (g >= CELL_FIRST_GAP && i < nsnp_cell::CELL_SLICES) nsnp_cell::lstm_cell_slice<i>(w, a, c, hn);
+                });
+                // cell: lane (n, q) holds unit 4 (4 wave + u) + q -> exchange positions 16 wave + 4 q + u
+                if constexpr (g == CELL_END) *reinterpret_cast<f32x4*>(hout) = hn;
+                if constexpr (g == CELL_END + 2) store_h0(buf ^ 1);
+                if constexpr (g == CELL_END + 4) load_h0(tnext);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    };
+
+    f32x4 accA[4], accB[4], bfirst;
+    project_reads(0, accA, bfirst);
+    project(0, accA, bfirst, std::false_type{}, accA, nullptr, 0);
+    // step 0 stores the rows of step 2 over those of step 0: every wave must have read them
+    lds_barrier();
+
+    // step s: acc holds bias + input projection of step s and leaves through the cell; nxt receives that of step s+1
+    auto step = [&](int s, f32x4 (&acc)[4], f32x4 (&nxt)[4], auto first_tag, auto last_tag) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
+        const int cur = s & 1;
+        float* const hw = h1x + ((size_t)cur * 16 + n) * RS_XROW + 16 * wave + 4 * q;         // h1_s
+        f32x4 b0;
+        if constexpr (!FIRST) {
+            // recurrent B fragments one K block ahead of their MFMAs; the A fragments of K blocks 2 and 3 come from LDS under K
+            // blocks 0 and 1
+            const float* r1 = h1x + ((size_t)(cur ^ 1) * 16 + n) * RS_XROW + 4 * q;           // h1_{s-1}
+            f32x4 hb0 = *reinterpret_cast<const f32x4*>(r1), hb1 = *reinterpret_cast<const f32x4*>(r1 + 16), A2[4], A3[4];
+#define RS4W_KBLOCK(A, HB)                                                                             \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e)                                              \
+                _Pragma("unroll") for (int u = 0; u < 4; ++u) acc[u] = mfma4(A[e], HB[e], acc[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) A2[u] = lw[(2 * u) * 64];
+            __builtin_amdgcn_sched_barrier(0);
+            RS4W_KBLOCK(Whh[u][0], hb0)
+            __builtin_amdgcn_sched_barrier(0);
+            hb0 = *reinterpret_cast<const f32x4*>(r1 + 32);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) A3[u] = lw[(2 * u + 1) * 64];
+            RS4W_KBLOCK(Whh[u][1], hb1)
+            __builtin_amdgcn_sched_barrier(0);
+            hb1 = *reinterpret_cast<const f32x4*>(r1 + 48);
+            RS4W_KBLOCK(A2[u], hb0)
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!LAST) project_reads(cur ^ 1, nxt, b0);
+            RS4W_KBLOCK(A3[u], hb1)
+            __builtin_amdgcn_sched_barrier(0);
+#undef RS4W_KBLOCK
+        } else {
+            project_reads(cur ^ 1, nxt, b0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (!LAST) {
+            project(cur ^ 1, nxt, b0, std::true_type{}, acc, hw, tpos(s + 3 < PSTEPS1 ? s + 3 : PSTEPS1 - 1));
+        } else {
+            f32x4 hn;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) hn[u] = lstm_cell(acc[u][0], acc[u][1], acc[u][2], acc[u][3], c[u]);
+            *reinterpret_cast<f32x4*>(hw) = hn;
+        }
+        lds_barrier();
+    };
+    // the two accumulator sets change roles from step to step: steps 1 .. PSTEPS1 - 3 run in pairs
+    static_assert(PSTEPS1 % 2 == 1, "the step loop is unrolled by two");
+    step(0, accA, accB, std::true_type{}, std::false_type{});
+    for (int s = 1; s < PSTEPS1 - 2; s += 2) {
+        step(s, accB, accA, std::false_type{}, std::false_type{});
+        step(s + 1, accA, accB, std::false_type{}, std::false_type{});
+    }
+    step(PSTEPS1 - 2, accB, accA, std::false_type{}, std::false_type{});
+    step(PSTEPS1 - 1, accA, accB, std::false_type{}, std::true_type{});
+
+    // h1 at position 16 -> H1c[site][dir][q][16]: entries 4 wave .. 4 wave + 3 of row q (read back from the exchange rows)
+    const int64_t site = base_site + n;
+    if (site < N)
+        *reinterpret_cast<f32x4*>(H1c + site * 128 + dir * 64 + q * 16 + 4 * wave) =
+            *reinterpret_cast<const f32x4*>(h1x + ((size_t)((PSTEPS1 - 1) & 1) * 16 + n) * RS_XROW + 16 * wave + 4 * q);
+    NSNP_DEVCLK_STOP(1)
+}
+// the placement that is built: vector instructions of the cell per MFMA gap, and the gap of the burst in which the cell starts.
+// Measured (docs/rounds/r19.md): one per gap is 3 % SLOWER than K23r4, two per gap equal, eight or more - up to the whole cell in
+// one piece - 2.5 % faster, wherever the piece stands in the burst; the whole cell behind the first MFMA sends h1 out earliest.
+#ifndef RS4W_PER_GAP
+#define RS4W_PER_GAP 80
+#endif
+#ifndef RS4W_FIRST_GAP
+#define RS4W_FIRST_GAP 0
+#endif
+static_assert(rs4w_l1_lds_bytes() <= 80 * 1024, "two workgroups per CU");
+
 // ---------------------------------------------------------------------------------------------
-// K4: heads.  block = 256 (4 waves x 16 sites), weights streamed from L2 (216 KB of images).
+// K4: heads. block = 256 (4 waves x 16 sites), weights streamed from L2 (216 KB of images).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pileup_head(
     const float* __restrict__ H1c, int64_t N,
@@ -1485,6 +1698,7 @@ static int set_lds_attr_once(nsnp_ctx* ctx)
     NSNP_HIP(ctx, hipFuncSetAttribute((const void*)k_pileup_l1<1>, hipFuncAttributeMaxDynamicSharedMemorySize, L1_LDS_BYTES));
     NSNP_HIP(ctx, hipFuncSetAttribute((const void*)k_pileup_l1_rs4<1>, hipFuncAttributeMaxDynamicSharedMemorySize, rs4_l1_lds_bytes(1)));
     NSNP_HIP(ctx, hipFuncSetAttribute((const void*)k_pileup_l1_rs4<2>, hipFuncAttributeMaxDynamicSharedMemorySize, rs4_l1_lds_bytes(2)));
+    NSNP_HIP(ctx, hipFuncSetAttribute((const void*)k_pileup_l1_rs4w<RS4W_PER_GAP, RS4W_FIRST_GAP>, hipFuncAttributeMaxDynamicSharedMemorySize, rs4w_l1_lds_bytes()));
     NSNP_HIP(ctx, hipFuncSetAttribute((const void*)k_pileup_l1_rs32<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, rs32_l1_lds_bytes(4)));
     NSNP_HIP(ctx, hipFuncSetAttribute((const void*)k_pileup_l1_rs32<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, rs32_l1_lds_bytes(2)));
     NSNP_HIP(ctx, hipFuncSetAttribute((const void*)k_pileup_l1_rs32<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, rs32_l1_lds_bytes(4)));
@@ -1549,7 +1763,12 @@ int nsnp_pileup_forward_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* cen
             if (ctx->l1_rs_groups == 1 || ctx->l1_rs_groups == 2) g1 = ctx->l1_rs_groups;
 #define LAUNCH_R4(G) hipLaunchKernelGGL(k_pileup_l1_rs4<G>, dim3((unsigned)NSNP_CDIV(n, 16 * G), 2), dim3(256), rs4_l1_lds_bytes(G), s, \
                            ctx->ws_h0, n, pw.l1_wih[0], pw.l1_wih[1], pw.l1_whh[0], pw.l1_whh[1], pw.l1_bias[0], pw.l1_bias[1], ctx->ws_h1c)
-            if (g1 == 2) LAUNCH_R4(2); else LAUNCH_R4(1);
+            if (g1 == 2) LAUNCH_R4(2);
+            else if (ctx->l1_weave)
+                hipLaunchKernelGGL((k_pileup_l1_rs4w<RS4W_PER_GAP, RS4W_FIRST_GAP>), dim3((unsigned)NSNP_CDIV(n, 16), 2), dim3(256),
+                                   rs4w_l1_lds_bytes(), s, ctx->ws_h0, n, pw.l1_wih[0], pw.l1_wih[1], pw.l1_whh[0], pw.l1_whh[1],
+                                   pw.l1_bias[0], pw.l1_bias[1], ctx->ws_h1c);
+            else LAUNCH_R4(1);
 #undef LAUNCH_R4
         } else if (ctx->l1_rs == 2) {
             ScopedKernelTimer tm(ctx, NSNP_K_L1, s);

@@ -22,6 +22,7 @@ ctx.set_option("l0_site_groups", int(os.environ.get("L0SG", "0")))
 ctx.set_option("l1_register_stationary", int(os.environ.get("L1RS", "1")))
 ctx.set_option("l1_site_groups", int(os.environ.get("L1SG", "0")))
 ctx.set_option("l1_stagger", int(os.environ.get("STAG", "0")))
+ctx.set_option("l1_weave", int(os.environ.get("WEAVE", "0")))
 ctx.set_option("head_split", int(os.environ.get("HEADS", "1")))
 ctx.set_option("static_priority", int(os.environ.get("PRIO", "0")))
 ctx.set_option("l0_input_weights_in_lds", int(os.environ.get("WXL", "0")))
