@@ -487,6 +487,42 @@ int nsnp_pileup_label_sites_keys(nsnp_ctx* ctx, const int64_t* key, int64_t M, c
                                  const uint64_t* keep_thr, uint64_t seed, int64_t* out_center_idx, int32_t* label, int64_t* counts,
                                  int64_t* meta, void* stream);
 
+/* ---- scoring a checkpoint on training windows (PileupModel/train.py:93-150, its eval()) -------------------------------------------------
+ * fp32 only: with pileup_precision 1 or 2 every entry of this block that runs the network returns NSNP_EINVAL.  Head rows at the ABI, as the
+ * label row of a <chr>.td.bin orders them: 0-20 genotype, 21-23 zygosity, 24-56 indel1, 57-89 indel2.
+ *
+ * nsnp_pileup_load_indel_heads: host_tensors = { indel1_layer.weight [33,256], .bias [33], indel2_layer.weight [33,256], .bias [33] } (n >= 4),
+ * valid only after nsnp_pileup_load_weights (NSNP_ENOWEIGHTS before); packs the six-tile image of all 90 head rows.  A later
+ * nsnp_pileup_load_weights invalidates it. */
+int nsnp_pileup_load_indel_heads(nsnp_ctx* ctx, const float* const* host_tensors, int n);
+
+/* The classes of label rows (PileupModel/dataset.py:78-82,98-104): per family the index of the first maximum of its slice (np.argmax; an
+ * all-zero slice gives 0).  With variants_only != 0 only rows of zygosity class > 0 are kept.  Kept rows, compacted and in their order:
+ *   cls        uint8 [N,4]   { gt, zy, id1, id2 }                       (device)
+ *   center_idx int64 [N]     33 * n + 16 of row n: the centre of its window in a pass flattened to [N * 33, 18]   (device)
+ *   meta       int64 [4]   = { kept, rows of N that are not one-hot in some family, status (always 0), 0 }; device or pinned host memory
+ * Nothing is written behind the kept rows.  Three launches (flags, one-workgroup exclusive scan, compaction), no workgroup waits for
+ * another; scratch of its own in the context (12 bytes per row). */
+int nsnp_pileup_label_classes(nsnp_ctx* ctx, const int32_t* label, int64_t N, int variants_only, uint8_t* cls, int64_t* center_idx,
+                              int64_t* meta, void* stream);
+
+/* LSTMNetwork.forward without its loss (PileupModel/model.py:97-100,66-73): layers 0 and 1 as nsnp_pileup_forward_windows launches them, then
+ * all four heads as raw logits, fp32 [N,90].  center_idx NULL: counts is [N,33,18].  NSNP_ENOWEIGHTS without the indel heads. */
+int nsnp_pileup_forward_logits(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, int64_t N, float* logits, void* stream);
+
+/* The same forward with the label-smoothed loss (PileupModel/optim.py:137-144 before its mean), the argmax and the confusion counts in the heads
+ * kernel.  cls uint8 [N,4]: the target classes (a class outside its head counts as the head's last).  Per site and head h with C classes:
+ *   lp = z - logsumexp(z);  site_loss[n,h] = -(0.9 lp[t] + 0.1 / (C - 1) (sum(lp) - lp[t]));  pred[n,h] = first maximum of z
+ *   counters int64 [NSNP_EVAL_COUNTERS]: four matrices [target][predicted], 21x21, 3x3, 33x33, 33x33 back to back; ADDED to (device memory)
+ *   logits   NULL, or fp32 [N,90]: with NULL no logit reaches memory. */
+#define NSNP_EVAL_COUNTERS 2628
+int nsnp_pileup_eval_windows(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
+                             uint8_t* pred, int64_t* counters, float* logits, void* stream);
+
+/* batch_sum[b,h] = the float64 sum of site_loss[n,h] over the rows n of batch b (rows b * batch_size ..), double [ceil(N / batch_size), 4]: one
+ * workgroup per batch, a fixed tree - the same bits whatever the launch and the run.  The caller divides by the batch's size. */
+int nsnp_pileup_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream);
+
 /* ---- HaplotypeModel ------------------------------------------------------------------- */
 /* seq/bq/mq/hap: device int32 [N,D,L] planes as write_to_bins.py:44-61 stores them (padding
  * rows are -2); ref_row: device int32 [N,L].  out: device fp32 [N,105,L] -- float64 math as

@@ -3,13 +3,15 @@
 The compute path is the HIP library behind include/nanosnp.h (``nanosnp_amd/_lib.py`` binds it);
 this package holds only the host-side mirror of the reference's interface for that path:
 
-    pileup_model.LSTMNetwork     PileupModel/model.py LSTMNetwork (predict only)
+    pileup_model.LSTMNetwork     PileupModel/model.py LSTMNetwork (predict; forward with its loss, no backward)
     haplotype_model.LSTMNetwork  HaplotypeModel/model_dev.py LSTMNetwork (predict only)
     cat_model.CatModel           HaplotypeModel/model.py CatModel, the legacy path (predict only)
     pipeline                     mpileup text -> column encode -> windows -> PileupModel -> pileup.vcf in one pass
                                  (dna_sv_tensor make_candidate_snp_tensor + make_predict_data + predict.py)
                                  and .pd.bin window files -> pinned staging / H2D / PileupModel -> pileup.vcf, streamed
                                  (PileupModel/predict.py + dataset.py PredictDataset behind a DataLoader)
+    evaluate                     <chr>.td.bin training window files -> loss, accuracies, confusion matrices of a checkpoint
+                                 (PileupModel/train.py eval() + dataset.py TrainDataset(for_evaluate=True))
     hap_pipeline                 haplotype site files -> pinned staging / H2D / features + HaplotypeModel -> haplotype.csv, streamed
                                  (HaplotypeModel/predict_dev.py + dataset_dev.py TestDataset behind a DataLoader)
     predict                      PileupModel/predict.py / HaplotypeModel/predict_dev.py loops on arrays

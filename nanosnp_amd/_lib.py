@@ -78,6 +78,11 @@ _SIGNATURES = {
                                             C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_label_sites_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
+    "nsnp_pileup_load_indel_heads": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
+    "nsnp_pileup_label_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_forward_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_eval_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "nsnp_pileup_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_mpileup_tokenise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
     "nsnp_mpileup_tokenise_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 5 + [C.c_void_p] * 9),
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -978,6 +983,98 @@ class Context:
         if not want_label:
             return None, None, meta
         return out_center_idx.view(-1)[:n], label.view(-1)[:n * self.LABEL_WIDTH].view(n, self.LABEL_WIDTH), meta
+
+    # ---- scoring on labelled windows (include/nanosnp.h; fp32 only) ----
+    EVAL_COUNTERS = 2628
+    EVAL_HEADS = ((0, 21, 0), (21, 3, 441), (24, 33, 450), (57, 33, 1539))      # (first head row, classes, first counter) of gt, zy, id1, id2
+
+    def pileup_load_indel_heads(self, tensors):
+        """tensors: indel1_layer.weight [33,256], .bias [33], indel2_layer.weight [33,256], .bias [33]; after pileup_load_weights"""
+        import numpy as np
+        arrs = [np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32) for t in tensors]
+        if [a.shape for a in arrs] != [(33, 256), (33,), (33, 256), (33,)]:
+            raise NanoSNPError(f"expected the four indel tensors [33,256], [33], [33,256], [33], got {[a.shape for a in arrs]}")
+        ptrs = (C.c_void_p * 4)(*[a.ctypes.data for a in arrs])
+        check(self.lib.nsnp_pileup_load_indel_heads(self.handle, ptrs, 4), self.handle, "nsnp_pileup_load_indel_heads")
+
+    def pileup_label_classes(self, label, variants_only=True, cls=None, center_idx=None, meta=None, stream=None):
+        """label: device int32 [N,90] -> (cls uint8 [N,4], center_idx int64 [N], meta int64 [4]): the first meta[0] rows of cls / center_idx
+        are the kept rows' classes {gt, zy, id1, id2} and centres 33 n + 16, in order; meta[1] = rows that are not one-hot in some family.
+        meta may be pinned host memory; the count is only known behind the launch."""
+        import torch
+        if label.dtype != torch.int32 or not label.is_cuda or not label.is_contiguous() or label.dim() != 2 or label.shape[1] != self.LABEL_WIDTH:
+            raise NanoSNPError(f"label_classes: label must be a contiguous device int32 [N,{self.LABEL_WIDTH}]")
+        n, dev = int(label.shape[0]), label.device
+        cls = cls if cls is not None else torch.empty((max(n, 1), 4), dtype=torch.uint8, device=dev)
+        center_idx = center_idx if center_idx is not None else torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        meta = meta if meta is not None else torch.zeros(4, dtype=torch.int64, device=dev)
+        if (cls.dtype != torch.uint8 or cls.numel() < 4 * n or not cls.is_cuda or not cls.is_contiguous() or center_idx.dtype != torch.int64
+                or center_idx.numel() < n or not center_idx.is_cuda or not center_idx.is_contiguous()):
+            raise NanoSNPError("label_classes: cls uint8 [N,4] and center_idx int64 [N] on the device")
+        if meta.dtype != torch.int64 or meta.numel() < 4 or not (meta.is_cuda or meta.is_pinned()) or not meta.is_contiguous():
+            raise NanoSNPError("label_classes: meta int64 [4] on the device or in pinned memory")
+        check(self.lib.nsnp_pileup_label_classes(self.handle, _dptr(label), n, int(bool(variants_only)), _dptr(cls), _dptr(center_idx),
+                                                 meta.data_ptr(), _stream_ptr(stream)), self.handle, "nsnp_pileup_label_classes")
+        return cls, center_idx, meta
+
+    @staticmethod
+    def _eval_inputs(counts, center_idx, what):
+        import torch
+        if counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous():
+            raise NanoSNPError(f"{what}: counts must be a contiguous device int32 tensor")
+        if center_idx is None:
+            if counts.dim() != 3 or tuple(counts.shape[1:]) != (33, 18):
+                raise NanoSNPError(f"{what}: without center_idx counts is [N,33,18]")
+            return int(counts.shape[0])
+        if center_idx.dtype != torch.int64 or not center_idx.is_cuda or not center_idx.is_contiguous():
+            raise NanoSNPError(f"{what}: center_idx must be a contiguous device int64 tensor")
+        return int(center_idx.shape[0])
+
+    def pileup_forward_logits(self, counts, center_idx=None, logits=None, stream=None):
+        """all four heads as raw logits, fp32 [N,90] (rows 0-20 gt, 21-23 zy, 24-56 indel1, 57-89 indel2); center_idx None: counts is [N,33,18]"""
+        import torch
+        n = self._eval_inputs(counts, center_idx, "forward_logits")
+        logits = logits if logits is not None else torch.empty((n, self.LABEL_WIDTH), dtype=torch.float32, device=counts.device)
+        if logits.dtype != torch.float32 or logits.numel() < n * self.LABEL_WIDTH or not logits.is_cuda or not logits.is_contiguous():
+            raise NanoSNPError("forward_logits: logits fp32 [N,90] on the device")
+        check(self.lib.nsnp_pileup_forward_logits(self.handle, _dptr(counts), _dptr(center_idx), n, _dptr(logits), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_forward_logits")
+        return logits
+
+    def pileup_eval_windows(self, counts, center_idx, cls, counters, n=None, site_loss=None, pred=None, want_logits=False, stream=None):
+        """forward + label-smoothed loss + argmax + confusion counts -> (site_loss fp32 [n,4], pred uint8 [n,4], logits fp32 [n,90] or None).
+        cls: device uint8 [>= n, 4]; counters: device int64 [EVAL_COUNTERS], added to; n: the sites to run (default: all of center_idx / counts)"""
+        import torch
+        n_all = self._eval_inputs(counts, center_idx, "eval_windows")
+        n = n_all if n is None else int(n)
+        dev = counts.device
+        if n < 0 or n > n_all or cls.dtype != torch.uint8 or cls.numel() < 4 * n or not cls.is_cuda or not cls.is_contiguous():
+            raise NanoSNPError("eval_windows: cls uint8 [N,4] on the device, one row per site")
+        if counters.dtype != torch.int64 or counters.numel() != self.EVAL_COUNTERS or not counters.is_cuda or not counters.is_contiguous():
+            raise NanoSNPError(f"eval_windows: counters int64 [{self.EVAL_COUNTERS}] on the device")
+        site_loss = site_loss if site_loss is not None else torch.empty((n, 4), dtype=torch.float32, device=dev)
+        pred = pred if pred is not None else torch.empty((n, 4), dtype=torch.uint8, device=dev)
+        if (site_loss.dtype != torch.float32 or site_loss.numel() < 4 * n or not site_loss.is_cuda or not site_loss.is_contiguous()
+                or pred.dtype != torch.uint8 or pred.numel() < 4 * n or not pred.is_cuda or not pred.is_contiguous()):
+            raise NanoSNPError("eval_windows: site_loss fp32 [N,4] and pred uint8 [N,4] on the device")
+        logits = torch.empty((n, self.LABEL_WIDTH), dtype=torch.float32, device=dev) if want_logits else None
+        check(self.lib.nsnp_pileup_eval_windows(self.handle, _dptr(counts), _dptr(center_idx), _dptr(cls), n, _dptr(site_loss), _dptr(pred),
+                                                _dptr(counters), _dptr(logits), _stream_ptr(stream)), self.handle, "nsnp_pileup_eval_windows")
+        return site_loss, pred, logits
+
+    def pileup_batch_loss(self, site_loss, batch_size, n=None, stream=None):
+        """float64 sums of site_loss fp32 [n,4] per batch of batch_size rows -> device float64 [ceil(n / batch_size), 4]"""
+        import torch
+        if site_loss.dtype != torch.float32 or not site_loss.is_cuda or not site_loss.is_contiguous():
+            raise NanoSNPError("batch_loss: site_loss fp32 [N,4] on the device")
+        n = int(site_loss.numel() // 4) if n is None else int(n)
+        if int(batch_size) < 1 or n < 0 or 4 * n > site_loss.numel():
+            raise NanoSNPError("batch_loss: batch_size >= 1 and n rows within site_loss")
+        nb = -(-n // int(batch_size))
+        out = torch.empty((nb, 4), dtype=torch.float64, device=site_loss.device)
+        check(self.lib.nsnp_pileup_batch_loss(self.handle, _dptr(site_loss), n, int(batch_size), _dptr(out), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_batch_loss")
+        return out
 
     def pileup_gather_windows(self, counts, center_idx, stream=None):
         import torch

@@ -263,6 +263,9 @@ extern "C" int nsnp_ctx_destroy(nsnp_ctx* ctx)
     if (ctx->fil_tmp) (void)hipFree(ctx->fil_tmp);
     if (ctx->rec_tmp) (void)hipFree(ctx->rec_tmp);
     if (ctx->lab_tmp) (void)hipFree(ctx->lab_tmp);
+    if (ctx->evl_tmp) (void)hipFree(ctx->evl_tmp);
+    if (ctx->pw.head6_w) (void)hipFree(ctx->pw.head6_w);
+    if (ctx->pw.head6_b) (void)hipFree(ctx->pw.head6_b);
     nsnp_tok_free(ctx);
     (void)nsnp_comm_destroy(ctx);
     nsnp_hap_free(ctx);
@@ -312,6 +315,30 @@ extern "C" int nsnp_pileup_load_weights(nsnp_ctx* ctx, const float* const* host_
     int rc = nsnp_pileup_pack_weights(ctx, host_tensors);
     if (!rc) rc = nsnp_pileup_pack_weights_f16(ctx, host_tensors);
     return rc ? rc : nsnp_pileup_pack_weights_bf16(ctx, host_tensors);
+}
+
+extern "C" int nsnp_pileup_load_indel_heads(nsnp_ctx* ctx, const float* const* host_tensors, int n)
+{
+    if (!ctx || !host_tensors || n < 4) return NSNP_EINVAL;
+    for (int i = 0; i < 4; ++i) if (!host_tensors[i]) return NSNP_EINVAL;
+    if (!ctx->pw.loaded) return NSNP_ENOWEIGHTS;
+    NSNP_HIP(ctx, hipSetDevice(ctx->device));
+    return nsnp_pileup_pack_indel_heads(ctx, host_tensors);
+}
+
+extern "C" int nsnp_pileup_forward_logits(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, int64_t N, float* logits, void* stream)
+{
+    if (!ctx || N < 0 || (N > 0 && (!counts || !logits))) return NSNP_EINVAL;
+    if (ctx->precision != 0) return NSNP_EINVAL;           // fp32 only: the split-precision modes have no such heads kernel
+    return nsnp_pileup_eval_impl(ctx, counts, center_idx, nullptr, N, nullptr, nullptr, nullptr, logits, (hipStream_t)stream);
+}
+
+extern "C" int nsnp_pileup_eval_windows(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const uint8_t* cls, int64_t N,
+                                        float* site_loss, uint8_t* pred, int64_t* counters, float* logits, void* stream)
+{
+    if (!ctx || N < 0 || (N > 0 && (!counts || !cls || !site_loss || !pred || !counters))) return NSNP_EINVAL;
+    if (ctx->precision != 0) return NSNP_EINVAL;
+    return nsnp_pileup_eval_impl(ctx, counts, center_idx, cls, N, site_loss, pred, counters, logits, (hipStream_t)stream);
 }
 
 // one dispatch for the three arithmetic modes; post / post_written as in nsnp_common.hpp

@@ -48,6 +48,11 @@ struct PileupWeightsDev {
     float* arena;       // one allocation holding all of the above
     size_t arena_bytes;
     bool   loaded;
+    // all 90 head rows (genotype 0..20, zygosity 21..23, indel1 24..56, indel2 57..89, rest 0) for the heads kernel of pileup_eval.hip:
+    // an allocation of its own, made by nsnp_pileup_load_indel_heads, invalidated by nsnp_pileup_load_weights
+    float* head6_w;     // [6][16][64][4]  96 KB
+    float* head6_b;     // [6][64][4]
+    bool   indel_loaded;
 };
 
 // fp16 hi/lo images of the same weights for the f16x3 path (pileup_forward_f16x3.hip)
@@ -130,6 +135,7 @@ struct nsnp_ctx {
     int64_t* sel_tmp; size_t sel_tmp_bytes;   // select_sites scratch
     int64_t* fil_tmp; size_t fil_tmp_bytes;   // filter_columns scratch: kept columns and bytes per tile (pileup_encode.hip)
     void* rec_tmp; size_t rec_tmp_bytes;      // nsnp_pileup_alt_info scratch: scanned sizes + the staging blob (pileup_records.hip)
+    void* evl_tmp; size_t evl_tmp_bytes;      // nsnp_pileup_label_classes scratch: scanned flags + the four classes per row (pileup_eval.hip)
     void* lab_tmp; size_t lab_tmp_bytes;      // nsnp_pileup_label_sites_keys scratch: scanned flags + two words per site (pileup_labels.hip)
     void* tok_ws; size_t tok_ws_bytes;        // mpileup tokeniser scratch: 4,112 bytes per 8 KB tile of text (mpileup_tokenise.hip)
     void* ctg_ws; size_t ctg_ws_bytes;        // nsnp_mpileup_tokenise_contigs scratch: 8 bytes per line + 16 per 256 lines (mpileup_tokenise.hip)
@@ -168,6 +174,13 @@ int nsnp_ctx_need_xp1(nsnp_ctx* ctx);   // legacy unfused layer-1 path only (syn
 int nsnp_pileup_forward_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx,
                              int64_t N, float* gt, float* zy, const PostOut* post, bool* post_written, hipStream_t s);
 int nsnp_pileup_pack_weights(nsnp_ctx* ctx, const float* const* w);
+// scoring (include/nanosnp.h): the dispatch stands beside nsnp_pileup_forward_impl and launches the same layers 0 and 1; the heads kernel
+// and its launcher are pileup_eval.hip's.  cls NULL: logits only (site_loss, pred, counters unused)
+int nsnp_pileup_pack_indel_heads(nsnp_ctx* ctx, const float* const* w);
+int nsnp_pileup_eval_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
+                          uint8_t* pred, int64_t* counters, float* logits, hipStream_t s);
+void nsnp_pileup_eval_heads_launch(nsnp_ctx* ctx, int64_t n, const uint8_t* cls, float* site_loss, uint8_t* pred, int64_t* counters,
+                                   float* logits, hipStream_t s);
 int nsnp_pileup_forward_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx,
                               int64_t N, float* gt, float* zy, hipStream_t s);
 int nsnp_pileup_pack_weights_f16(nsnp_ctx* ctx, const float* const* w);

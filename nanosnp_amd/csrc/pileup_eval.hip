@@ -1,0 +1,331 @@
+// pileup_eval.hip -- scoring a checkpoint on labelled windows (<chr>.td.bin): what PileupModel/train.py:93-150, its eval(), computes.
+//
+// Replaces, for windows and label rows that are already in HBM,
+//   the label decode and the variant filter of TrainDataset(for_evaluate=True)   PileupModel/dataset.py:78-82,98-104
+//   ForwardLayer.forward with all four heads as raw logits                       PileupModel/model.py:66-73
+//   LabelSmoothingLoss.forward before its mean                                   PileupModel/optim.py:137-144
+//   the argmax behind torchmetrics' Accuracy / ConfusionMatrix updates           PileupModel/train.py:125-134
+//
+// nsnp_pileup_label_classes, three launches:
+//   k_evl_flags    one lane per label row: the first maximum of each family, whether the row is one-hot, whether it is kept  -> scratch
+//   k_evl_scan     exclusive prefix sums of the kept flags, int64, by ONE workgroup of 1024 lanes.  Levels: a lane sums its own run of
+//                  ceil(N / 1024) consecutive rows serially; the 1024 run sums are scanned in LDS (Hillis-Steele, 10 rounds); each lane
+//                  then writes the running offsets of its rows.  There is no carry between workgroups because there is one workgroup,
+//                  so the scan is exact for any N and no workgroup waits for another.  The same lanes count the malformed rows; meta.
+//   k_evl_compact  the kept rows' classes and centres, in order                                                              -> cls, center_idx
+// k_pileup_head_eval: the heads kernel (below).  k_evl_batch_loss: float64 sums of the per-site losses of a batch, one workgroup each.
+#include "nsnp_common.hpp"
+
+namespace {
+
+constexpr float LOG2E = 1.4426950408889634f;
+
+// the two device functions of pileup_forward.hip the heads use, restated: the accumulators of rows 0..23 must be the bits of k_pileup_head_rs
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ float tanh_f(float x)
+{
+    return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((2.0f * LOG2E) * x)), 1.0f);
+}
+
+constexpr int EV_W = NSNP_LABEL_WIDTH;                       // 90 head rows = 21 + 3 + 33 + 33
+constexpr int EV_ZLD = 97;                                   // floats per site of the logit exchange (odd: 16 sites hit 16 banks)
+constexpr int EV_COUNTERS = NSNP_EVAL_COUNTERS;
+__device__ __forceinline__ int head_row0(int h) { return h == 0 ? 0 : (h == 1 ? 21 : (h == 2 ? 24 : 57)); }
+__device__ __forceinline__ int head_classes(int h) { return h == 0 ? 21 : (h == 1 ? 3 : 33); }
+__device__ __forceinline__ int head_counter0(int h) { return h == 0 ? 0 : (h == 1 ? 441 : (h == 2 ? 450 : 1539)); }
+static_assert(441 + 9 + 1089 + 1089 == EV_COUNTERS, "four confusion matrices");
+
+// ---------------------------------------------------------------------------------------------
+// K4e: k_pileup_head_rs with all 90 head rows, raw logits, and the loss / argmax / confusion counts of a scoring pass.
+// 512 threads, a persistent loop over groups of 16 sites; wave w owns output_proj tile w and dense tiles 2w, 2w+1 with their weights in
+// VGPRs across the loop - the code of k_pileup_head_rs to the letter up to x2.  Then waves 0..5 each own one head tile (64 VGPRs of
+// weights, as waves 0 and 1 there), and the K order, the bias start and the MFMA chain of every accumulator are those of k_pileup_head_rs.
+//
+// Row map.  Head row r (0..20 genotype, 21..23 zygosity, 24..56 indel1, 57..89 indel2, 90..95 zero padding) is accumulator
+//   tile r / 16  (= the wave that computes it),  lane (site n, q = (r % 16) / 4) = n + 16 q,  register g = r % 4,
+// and lands in LDS at z[n][r] (6.1 KB, 97 floats per site).  Heads straddle tiles: genotype = tile 0 + tile 1 rows 16..20, zygosity = tile 1
+// rows 21..23, indel1 = tile 1 rows 24..31 + tiles 2, 3 rows 32..56 (q = 0, 1 and g = 0 of q = 2), indel2 = tile 3 rows 57..63 + tiles 4, 5.
+// Behind one barrier wave h (0..3) finishes head h for the 16 sites: lane (n, q) reads classes c = q, q + 4, ... of z[n][row0(h) + c];
+// maximum / first argmax / sum of exponentials / sum of logits meet over the four q lanes of a site (16 lanes apart) by two butterfly
+// steps whose operands commute, so the four lanes hold the same bits.  Lane q = 0 stores loss and argmax and counts [target][predicted]
+// in a 32-bit LDS counter (10.5 KB per workgroup, integer adds: order-free); the counters leave once, behind the loop, as 64-bit adds.
+// No float is ever added atomically.  With `logits` all 512 lanes copy z (1,440 contiguous floats of a full group) to HBM.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512, 2) void k_pileup_head_eval(
+    const float* __restrict__ H1c, int64_t N,
+    const float* __restrict__ proj_w, const float* __restrict__ proj_b,
+    const float* __restrict__ dense_w, const float* __restrict__ dense_b,
+    const float* __restrict__ head_w, const float* __restrict__ head_b,
+    const uint8_t* __restrict__ cls, float* __restrict__ site_loss, uint8_t* __restrict__ pred,
+    unsigned long long* __restrict__ counters, float* __restrict__ logits)
+{
+    __shared__ float x1[32][64];          // output_proj results as dense K-steps
+    __shared__ float x2[64][64];          // tanh(dense) as head K-steps
+    __shared__ float z[16][EV_ZLD];       // the 90 logits of the group's 16 sites
+    __shared__ unsigned int cnt[EV_COUNTERS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = lane >> 4;
+    for (int i = tid; i < EV_COUNTERS; i += 512) cnt[i] = 0;
+    // weights of this wave
+    f32x4 Wp[8], Wd[2][8], Wh[16], bp, bd[2], bh;
+    {
+        const f32x4* pw = reinterpret_cast<const f32x4*>(proj_w);      // [8 tiles][8 j4][lane]
+        const f32x4* dw = reinterpret_cast<const f32x4*>(dense_w);     // [16][8][lane]
+        const f32x4* hw = reinterpret_cast<const f32x4*>(head_w);      // [6][16][lane]
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            Wp[j] = pw[(wave * 8 + j) * 64 + lane];
+            Wd[0][j] = dw[((2 * wave) * 8 + j) * 64 + lane];
+            Wd[1][j] = dw[((2 * wave + 1) * 8 + j) * 64 + lane];
+        }
+        bp = reinterpret_cast<const f32x4*>(proj_b)[wave * 64 + lane];
+        bd[0] = reinterpret_cast<const f32x4*>(dense_b)[(2 * wave) * 64 + lane];
+        bd[1] = reinterpret_cast<const f32x4*>(dense_b)[(2 * wave + 1) * 64 + lane];
+        if (wave < 6) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) Wh[j] = hw[(wave * 16 + j) * 64 + lane];
+            bh = reinterpret_cast<const f32x4*>(head_b)[wave * 64 + lane];
+        }
+    }
+    const int64_t n_groups = NSNP_CDIV(N, 16);
+    for (int64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+        const int64_t site = grp * 16 + (lane & 15);
+        const bool live = site < N;
+        const int64_t sc = live ? site : N - 1;
+        const f32x4* __restrict__ hin = reinterpret_cast<const f32x4*>(H1c + sc * 128 + q * 16);
+        // output_proj 128 -> 128 (model.py:37): tile `wave`
+        f32x4 ap = bp;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const f32x4 b4 = hin[(j >> 2) * 16 + (j & 3)];            // fwd half, then reverse half (+64 floats)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ap = mfma4(Wp[j][e], b4[e], ap);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) x1[4 * wave + g][lane] = ap[g];
+        __syncthreads();
+        // dense 128 -> 256 + tanh (model.py:67): tiles 2 wave, 2 wave + 1
+        f32x4 ad[2] = {bd[0], bd[1]};
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float b = x1[4 * j + e][lane];
+                ad[0] = mfma4(Wd[0][j][e], b, ad[0]);
+                ad[1] = mfma4(Wd[1][j][e], b, ad[1]);
+            }
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) x2[4 * (2 * wave + u) + g][lane] = tanh_f(ad[u][g]);
+        __syncthreads();
+        // the four heads (model.py:69-72): tile `wave` of the 90-row image in waves 0..5
+        if (wave < 6) {
+            f32x4 ah = bh;
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ah = mfma4(Wh[j][e], x2[4 * j + e][lane], ah);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) z[lane & 15][16 * wave + 4 * q + g] = ah[g];
+        }
+        __syncthreads();
+        if (logits)
+            for (int i = tid; i < 16 * EV_W; i += 512) {
+                const int n = i / EV_W, r = i - n * EV_W;
+                if (grp * 16 + n < N) logits[(grp * 16 + n) * EV_W + r] = z[n][r];
+            }
+        if (cls && wave < 4) {
+            const int C = head_classes(wave);
+            const float* zr = &z[lane & 15][head_row0(wave)];
+            const float NEG = -3.0e38f;
+            float v[9], bv = NEG;
+            int bi = 0x7fffffff;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                const int c = q + 4 * i;
+                v[i] = c < C ? zr[c] : NEG;
+                if (c < C && v[i] > bv) { bv = v[i]; bi = c; }          // ascending classes within a lane: the first maximum
+            }
+#pragma unroll
+            for (int o = 16; o <= 32; o <<= 1) {
+                const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
+                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            }
+            float se = 0.f, sz = 0.f;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                const bool ok = q + 4 * i < C;
+                se += ok ? expf(v[i] - bv) : 0.f;
+                sz += ok ? v[i] : 0.f;
+            }
+            se += __shfl_xor(se, 16); se += __shfl_xor(se, 32);
+            sz += __shfl_xor(sz, 16); sz += __shfl_xor(sz, 32);
+            if (live && q == 0) {
+                int t = cls[site * 4 + wave];
+                if (t >= C) t = C - 1;
+                if (bi >= C) bi = 0;                                   // (no maximum among NaN logits: class 0, as np.argmax of a NaN at 0)
+                // lp = z - logsumexp(z); loss = -(0.9 lp[t] + 0.1 / (C - 1) (sum(lp) - lp[t]))      optim.py:138-144
+                const float lse = bv + logf(se);
+                const float lpt = zr[t] - lse;
+                const float slp = sz - (float)C * lse;
+                site_loss[site * 4 + wave] = -(0.9f * lpt + (0.1f / (float)(C - 1)) * (slp - lpt));
+                pred[site * 4 + wave] = (uint8_t)bi;
+                atomicAdd(&cnt[head_counter0(wave) + t * C + bi], 1u);
+            }
+        }
+        // (x1 / x2 / z of this group are not touched again before the next group's first / second / third barrier)
+    }
+    if (cls) {
+        __syncthreads();
+        for (int i = tid; i < EV_COUNTERS; i += 512)
+            if (cnt[i]) atomicAdd(counters + i, (unsigned long long)cnt[i]);
+    }
+}
+
+// ---- label rows -> classes --------------------------------------------------------------------
+constexpr int EVL_BLOCK = 256;
+constexpr uint32_t EVL_BAD = 0x80u;                          // beside the genotype class (0..20) in byte 0 of a row's scratch word
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_evl_flags(const int32_t* __restrict__ label, int64_t N, int variants_only,
+                                                         int64_t* __restrict__ keep, uint32_t* __restrict__ word)
+{
+    const int64_t n = (int64_t)blockIdx.x * EVL_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const int32_t* y = label + n * EV_W;
+    uint32_t w = 0;
+    bool bad = false;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int r0 = head_row0(h), C = head_classes(h);
+        int best = y[r0], bi = 0, ones = best == 1, nonzero = best != 0;
+        for (int c = 1; c < C; ++c) {
+            const int v = y[r0 + c];
+            if (v > best) { best = v; bi = c; }              // the first maximum, as np.argmax
+            ones += v == 1; nonzero += v != 0;
+        }
+        bad |= ones != 1 || nonzero != 1;
+        w |= (uint32_t)bi << (8 * h);
+    }
+    keep[n] = (!variants_only || ((w >> 8) & 0xff) > 0) ? 1 : 0;
+    word[n] = w | (bad ? EVL_BAD : 0u);
+}
+
+__global__ __launch_bounds__(1024) void k_evl_scan(int64_t* __restrict__ keep, const uint32_t* __restrict__ word, int64_t N, int64_t* __restrict__ meta)
+{
+    __shared__ int64_t part[1024];
+    __shared__ unsigned long long n_bad;
+    const int tid = threadIdx.x;
+    if (tid == 0) n_bad = 0;
+    const int64_t per = NSNP_CDIV(N, (int64_t)1024);
+    const int64_t n0 = tid * per < N ? tid * per : N, n1 = n0 + per < N ? n0 + per : N;
+    int64_t s = 0, b = 0;
+    for (int64_t n = n0; n < n1; ++n) { s += keep[n]; b += (word[n] & EVL_BAD) ? 1 : 0; }
+    part[tid] = s;
+    __syncthreads();
+    if (b) atomicAdd(&n_bad, (unsigned long long)b);
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int64_t v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int64_t run = tid ? part[tid - 1] : 0;
+    for (int64_t n = n0; n < n1; ++n) { const int64_t v = keep[n]; keep[n] = run; run += v; }
+    if (tid == 1023) {
+        keep[N] = part[1023];
+        meta[0] = part[1023]; meta[1] = (int64_t)n_bad; meta[2] = 0; meta[3] = 0;
+    }
+}
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_evl_compact(const int64_t* __restrict__ scan, const uint32_t* __restrict__ word, int64_t N,
+                                                           uint32_t* __restrict__ cls, int64_t* __restrict__ center_idx)
+{
+    const int64_t n = (int64_t)blockIdx.x * EVL_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const int64_t o = scan[n];
+    if (scan[n + 1] == o || o < 0 || o >= N) return;         // (o lies in [0, N) by construction)
+    cls[o] = word[n] & ~EVL_BAD;                             // bytes gt, zy, id1, id2 of row o
+    center_idx[o] = (int64_t)NSNP_PILEUP_WINDOW * n + 16;
+}
+
+// ---- per-batch loss sums ----------------------------------------------------------------------
+// one workgroup of 256 lanes per batch: lane t adds rows t, t + 256, ... of the batch in that order (float64), then the 256 partial sums of
+// each head meet in a fixed binary tree in LDS.  Nothing depends on the grid or on timing.
+__global__ __launch_bounds__(256) void k_evl_batch_loss(const float* __restrict__ site_loss, int64_t N, int64_t B, double* __restrict__ batch_sum)
+{
+    __shared__ double part[4][256];
+    const int tid = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * B, r1 = r0 + B < N ? r0 + B : N;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t r = r0 + tid; r < r1; r += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(site_loss + r * 4);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) s[h] += (double)v[h];
+    }
+#pragma unroll
+    for (int h = 0; h < 4; ++h) part[h][tid] = s[h];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+#pragma unroll
+            for (int h = 0; h < 4; ++h) part[h][tid] += part[h][tid + o];
+        }
+        __syncthreads();
+    }
+    if (tid < 4) batch_sum[(int64_t)blockIdx.x * 4 + tid] = part[tid][0];
+}
+
+}  // namespace
+
+void nsnp_pileup_eval_heads_launch(nsnp_ctx* ctx, int64_t n, const uint8_t* cls, float* site_loss, uint8_t* pred, int64_t* counters,
+                                   float* logits, hipStream_t s)
+{
+    const PileupWeightsDev& pw = ctx->pw;
+    int64_t gh = NSNP_CDIV(n, 16);
+    if (gh > 2 * (int64_t)ctx->n_cu) gh = 2 * (int64_t)ctx->n_cu;          // persistent, as k_pileup_head_rs
+    hipLaunchKernelGGL(k_pileup_head_eval, dim3((unsigned)gh), dim3(512), 0, s, ctx->ws_h1c, n, pw.proj_w, pw.proj_b, pw.dense_w, pw.dense_b,
+                       pw.head6_w, pw.head6_b, cls, site_loss, pred, reinterpret_cast<unsigned long long*>(counters), logits);
+}
+
+extern "C" int nsnp_pileup_label_classes(nsnp_ctx* ctx, const int32_t* label, int64_t N, int variants_only, uint8_t* cls, int64_t* center_idx,
+                                         int64_t* meta, void* stream)
+{
+    if (!ctx || !meta || N < 0 || (N > 0 && (!label || !cls || !center_idx))) return NSNP_EINVAL;
+    if (reinterpret_cast<uintptr_t>(cls) & 3) return NSNP_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t scan_bytes = (((size_t)N + 1) * sizeof(int64_t) + 15) & ~(size_t)15;
+    const size_t need = scan_bytes + (size_t)N * sizeof(uint32_t) + 16;
+    if (ctx->evl_tmp_bytes < need) {
+        NSNP_HIP(ctx, hipStreamSynchronize(s));
+        if (ctx->evl_tmp) (void)hipFree(ctx->evl_tmp);
+        ctx->evl_tmp = nullptr; ctx->evl_tmp_bytes = 0;
+        NSNP_HIP(ctx, hipMalloc(&ctx->evl_tmp, need + need / 4));
+        ctx->evl_tmp_bytes = need + need / 4;
+    }
+    int64_t* scan = (int64_t*)ctx->evl_tmp;
+    uint32_t* word = (uint32_t*)((uint8_t*)ctx->evl_tmp + scan_bytes);
+    const unsigned grid = (unsigned)NSNP_CDIV(N, (int64_t)EVL_BLOCK);
+    if (N > 0) hipLaunchKernelGGL(k_evl_flags, dim3(grid), dim3(EVL_BLOCK), 0, s, label, N, variants_only, scan, word);
+    hipLaunchKernelGGL(k_evl_scan, dim3(1), dim3(1024), 0, s, scan, (const uint32_t*)word, N, meta);
+    if (N > 0)
+        hipLaunchKernelGGL(k_evl_compact, dim3(grid), dim3(EVL_BLOCK), 0, s, (const int64_t*)scan, (const uint32_t*)word, N,
+                           reinterpret_cast<uint32_t*>(cls), center_idx);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+extern "C" int nsnp_pileup_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream)
+{
+    if (!ctx || N < 0 || batch_size < 1 || (N > 0 && (!site_loss || !batch_sum))) return NSNP_EINVAL;
+    if (reinterpret_cast<uintptr_t>(site_loss) & 15) return NSNP_EINVAL;
+    if (N == 0) return NSNP_OK;
+    const int64_t nb = NSNP_CDIV(N, batch_size);
+    if (nb > 0x7fffffffll) return NSNP_EINVAL;
+    hipLaunchKernelGGL(k_evl_batch_loss, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, site_loss, N, batch_size, batch_sum);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}

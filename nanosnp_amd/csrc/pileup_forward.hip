@@ -1678,6 +1678,40 @@ int nsnp_pileup_pack_weights(nsnp_ctx* ctx, const float* const* w)
     pw.proj_w = dev(h_proj); pw.proj_b = dev(h_pb); pw.dense_w = dev(h_dense); pw.dense_b = dev(h_db);
     pw.head_w = dev(h_head); pw.head_b = dev(h_hb);
     pw.loaded = true;
+    pw.indel_loaded = false;        // (the six-tile image repeats the genotype / zygosity rows of the weights it was packed behind)
+    return NSNP_OK;
+}
+
+// nsnp_pileup_load_indel_heads: the image of all 90 head rows for the heads kernel of pileup_eval.hip, in the K order of f_head.  Rows 0..23
+// (tile 0, and lanes of tile 1 whose row is below 24) are read back from the two-tile image nsnp_pileup_pack_weights uploaded, so the
+// accumulators of those rows see the very floats k_pileup_head_rs sees; rows 24..89 come from w, rows 90..95 are 0.
+int nsnp_pileup_pack_indel_heads(nsnp_ctx* ctx, const float* const* w)
+{
+    PileupWeightsDev& pw = ctx->pw;
+    constexpr size_t n_w = 6 * 16 * 256, n_b = 6 * 256;
+    std::vector<float> img(n_w), bias(n_b), old_w(2 * 16 * 256), old_b(2 * 256);
+    NSNP_HIP(ctx, hipDeviceSynchronize());
+    NSNP_HIP(ctx, hipMemcpy(old_w.data(), pw.head_w, old_w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    NSNP_HIP(ctx, hipMemcpy(old_b.data(), pw.head_b, old_b.size() * sizeof(float), hipMemcpyDeviceToHost));
+    struct IndelRef { const float* w1; const float* w2; } ir{w[0], w[2]};
+    nsnp_pack_image(img.data(), 6, 16, [](const void* u, int row, int k) -> float {
+        const IndelRef* m = (const IndelRef*)u;
+        if (row >= 24 && row < 57) return m->w1[(row - 24) * 256 + acc_col(k)];
+        if (row >= 57 && row < 90) return m->w2[(row - 57) * 256 + acc_col(k)];
+        return 0.f;
+    }, &ir);
+    for (int tile = 0; tile < 2; ++tile) for (int j4 = 0; j4 < 16; ++j4) for (int lane = 0; lane < 64; ++lane)
+        if (16 * tile + (lane & 15) < 24)
+            for (int e = 0; e < 4; ++e) img[((tile * 16 + j4) * 64 + lane) * 4 + e] = old_w[((tile * 16 + j4) * 64 + lane) * 4 + e];
+    for (int tile = 0; tile < 6; ++tile) for (int lane = 0; lane < 64; ++lane) for (int g = 0; g < 4; ++g) {
+        const int row = 16 * tile + 4 * (lane >> 4) + g;
+        bias[(tile * 64 + lane) * 4 + g] = row < 24 ? old_b[(tile * 64 + lane) * 4 + g] : (row < 57 ? w[1][row - 24] : (row < 90 ? w[3][row - 57] : 0.f));
+    }
+    if (!pw.head6_w) NSNP_HIP(ctx, hipMalloc((void**)&pw.head6_w, n_w * sizeof(float)));
+    if (!pw.head6_b) NSNP_HIP(ctx, hipMalloc((void**)&pw.head6_b, n_b * sizeof(float)));
+    NSNP_HIP(ctx, hipMemcpy(pw.head6_w, img.data(), n_w * sizeof(float), hipMemcpyHostToDevice));
+    NSNP_HIP(ctx, hipMemcpy(pw.head6_b, bias.data(), n_b * sizeof(float), hipMemcpyHostToDevice));
+    pw.indel_loaded = true;
     return NSNP_OK;
 }
 
@@ -1707,19 +1741,12 @@ static int set_lds_attr_once(nsnp_ctx* ctx)
     return NSNP_OK;
 }
 
-int nsnp_pileup_forward_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx,
-                             int64_t N, float* gt, float* zy, const PostOut* post, bool* post_written, hipStream_t s)
+// layers 0 and 1 of one chunk of n <= chunk_sites sites: H1c of the chunk in ctx->ws_h1c.  The ONE place these launches are made - the
+// probability forward below and the scoring forward behind it (nsnp_pileup_eval_impl) differ in their heads kernel only.
+static int launch_layers(nsnp_ctx* ctx, const int32_t* xc, const int64_t* cc, int64_t n, hipStream_t s)
 {
-    if (!ctx->pw.loaded) return NSNP_ENOWEIGHTS;
-    if (N == 0) return NSNP_OK;
-    int rc = set_lds_attr_once(ctx);
-    if (rc) return rc;
-    if (!ctx->ws_h0) { rc = nsnp_ctx_reserve(ctx, ctx->chunk_sites); if (rc) return rc; }
     const PileupWeightsDev& pw = ctx->pw;
-    for (int64_t base = 0; base < N; base += ctx->chunk_sites) {
-        const int64_t n = (N - base < ctx->chunk_sites) ? N - base : ctx->chunk_sites;
-        const int32_t* xc = center_idx ? x : x + base * (PW * PC);
-        const int64_t* cc = center_idx ? center_idx + base : nullptr;
+    {
         // waves per recurrence workgroup: the largest of 8/4/2/1 that still yields a workgroup for every
         // second CU (LDS admits two workgroups per CU whatever their size): a 4096-site batch runs as
         // 128 four-wave workgroups, which measured best when several batches are in flight on
@@ -1798,6 +1825,25 @@ int nsnp_pileup_forward_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* cen
 #undef LAUNCH_L1
         }
         }
+    }
+    return NSNP_OK;
+}
+
+int nsnp_pileup_forward_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx,
+                             int64_t N, float* gt, float* zy, const PostOut* post, bool* post_written, hipStream_t s)
+{
+    if (!ctx->pw.loaded) return NSNP_ENOWEIGHTS;
+    if (N == 0) return NSNP_OK;
+    int rc = set_lds_attr_once(ctx);
+    if (rc) return rc;
+    if (!ctx->ws_h0) { rc = nsnp_ctx_reserve(ctx, ctx->chunk_sites); if (rc) return rc; }
+    const PileupWeightsDev& pw = ctx->pw;
+    for (int64_t base = 0; base < N; base += ctx->chunk_sites) {
+        const int64_t n = (N - base < ctx->chunk_sites) ? N - base : ctx->chunk_sites;
+        const int32_t* xc = center_idx ? x : x + base * (PW * PC);
+        const int64_t* cc = center_idx ? center_idx + base : nullptr;
+        rc = launch_layers(ctx, xc, cc, n, s);
+        if (rc) return rc;
         ScopedKernelTimer tm_head(ctx, NSNP_K_HEAD, s);
         if (ctx->head_rs) {
             int64_t gh = NSNP_CDIV(n, 16);
@@ -1813,6 +1859,28 @@ int nsnp_pileup_forward_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* cen
         hipLaunchKernelGGL(k_pileup_head, dim3((unsigned)NSNP_CDIV(n, 64)), dim3(256), 0, s, ctx->ws_h1c, n,
                            pw.proj_w, pw.proj_b, pw.dense_w, pw.dense_b, pw.head_w, pw.head_b,
                            gt + base * NSNP_GT_CLASSES, zy + base * NSNP_ZY_CLASSES);
+    }
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+// nsnp_pileup_forward_logits / nsnp_pileup_eval_windows: the chunk loop and the layers of nsnp_pileup_forward_impl, then the six-tile heads
+// kernel of pileup_eval.hip on the chunk's H1c
+int nsnp_pileup_eval_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
+                          uint8_t* pred, int64_t* counters, float* logits, hipStream_t s)
+{
+    if (!ctx->pw.loaded || !ctx->pw.indel_loaded) return NSNP_ENOWEIGHTS;
+    if (N == 0) return NSNP_OK;
+    int rc = set_lds_attr_once(ctx);
+    if (rc) return rc;
+    if (!ctx->ws_h0) { rc = nsnp_ctx_reserve(ctx, ctx->chunk_sites); if (rc) return rc; }
+    for (int64_t base = 0; base < N; base += ctx->chunk_sites) {
+        const int64_t n = (N - base < ctx->chunk_sites) ? N - base : ctx->chunk_sites;
+        rc = launch_layers(ctx, center_idx ? x : x + base * (PW * PC), center_idx ? center_idx + base : nullptr, n, s);
+        if (rc) return rc;
+        ScopedKernelTimer tm_head(ctx, NSNP_K_HEAD, s);
+        nsnp_pileup_eval_heads_launch(ctx, n, cls ? cls + base * 4 : nullptr, cls ? site_loss + base * 4 : nullptr, cls ? pred + base * 4 : nullptr,
+                                      counters, logits ? logits + base * NSNP_LABEL_WIDTH : nullptr, s);
     }
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;

@@ -16,6 +16,8 @@ ENCODER_KEYS = [f"lstm.{n}_l{l}{d}" for l in (0, 1) for d in ("", "_reverse")
                ["output_proj.weight", "output_proj.bias"]
 FORWARD_KEYS = ["dense.weight", "dense.bias", "genotype_layer.weight", "genotype_layer.bias",
                 "zygosity_layer.weight", "zygosity_layer.bias"]
+# kept when a state dict has all four: only forward() and nanosnp_amd.evaluate need them (nsnp_pileup_load_indel_heads)
+INDEL_KEYS = ["indel1_layer.weight", "indel1_layer.bias", "indel2_layer.weight", "indel2_layer.bias"]
 
 # PileupModel/config/ont_pileup.yaml:6-20 -- the only architecture the kernels are built for
 EXPECTED_MODEL_CONFIG = {"feature_dim": 18, "gt_num_class": 21, "zy_num_class": 3,
@@ -44,17 +46,18 @@ class _SubModule:
     ``pred_model.encoder.load_state_dict(checkpoint['encoder'])`` lines keep working
     (PileupModel/predict.py:213-214)."""
 
-    def __init__(self, owner, keys, prefix):
-        self._owner, self._keys, self._prefix = owner, keys, prefix
+    def __init__(self, owner, keys, prefix, optional=()):
+        self._owner, self._keys, self._prefix, self._optional = owner, keys, prefix, list(optional)
         self.state = None
+        self.optional_state = None
 
     def load_state_dict(self, sd):
         missing = [k for k in self._keys if k not in sd]
         if missing:
             raise KeyError(f"{self._prefix}: missing keys {missing}")
-        self.state = [np.ascontiguousarray(
-            sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], dtype=np.float32)
-            for k in self._keys]
+        arr = lambda k: np.ascontiguousarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], dtype=np.float32)
+        self.state = [arr(k) for k in self._keys]
+        self.optional_state = [arr(k) for k in self._optional] if self._optional and all(k in sd for k in self._optional) else None
         self._owner._maybe_upload()
 
 
@@ -66,8 +69,9 @@ class LSTMNetwork:
         _check_config(config)
         self.ctx = ctx if ctx is not None else _lib.Context(device, chunk_sites)
         self.encoder = _SubModule(self, ENCODER_KEYS, "encoder")
-        self.forward_layer = _SubModule(self, FORWARD_KEYS, "forward_layer")
+        self.forward_layer = _SubModule(self, FORWARD_KEYS, "forward_layer", optional=INDEL_KEYS)
         self._loaded = False
+        self._indel_loaded = False
 
     # torch.nn.Module look-alikes used by the reference's predict.py
     def to(self, device):
@@ -80,11 +84,22 @@ class LSTMNetwork:
         if self.encoder.state is not None and self.forward_layer.state is not None:
             self.ctx.pileup_load_weights(self.encoder.state + self.forward_layer.state)
             self._loaded = True
+            self._indel_loaded = False                  # (a new load invalidates the six-tile head image)
+            if self.forward_layer.optional_state is not None:
+                self.ctx.pileup_load_indel_heads(self.forward_layer.optional_state)
+                self._indel_loaded = True
 
     def load_weight_list(self, tensors):
         """24 arrays in state-dict order (nanosnp_amd/data/ont_pileup_weights.npz order)."""
         self.ctx.pileup_load_weights(tensors)
         self._loaded = True
+        self._indel_loaded = False
+        return self
+
+    def load_indel_heads(self, tensors):
+        """the four indel tensors in INDEL_KEYS order, behind load_weight_list"""
+        self.ctx.pileup_load_indel_heads(tensors)
+        self._indel_loaded = True
         return self
 
     @classmethod
@@ -102,7 +117,7 @@ class LSTMNetwork:
         z = np.load(path)
         m = cls(None, device, **kw)
         m.encoder.load_state_dict({k: z["encoder." + k] for k in ENCODER_KEYS})
-        m.forward_layer.load_state_dict({k: z["forward_layer." + k] for k in FORWARD_KEYS})
+        m.forward_layer.load_state_dict({k: z["forward_layer." + k] for k in FORWARD_KEYS + INDEL_KEYS if "forward_layer." + k in z.files})
         return m
 
     def predict(self, inputs, stream=None):
@@ -117,3 +132,29 @@ class LSTMNetwork:
             raise _lib.NanoSNPError("inputs must live on the GPU (no CPU path)")
         x = inputs if inputs.dtype == torch.int32 else inputs.to(torch.int32)
         return self.ctx.pileup_forward(x.contiguous(), stream=stream)
+
+    def forward(self, inputs, gt_target, zy_target, id1_target, id2_target, stream=None):
+        """``LSTMNetwork.forward`` (PileupModel/model.py:97-112), argument for argument: inputs as predict takes them, the four targets
+        integer cuda tensors [N] -> (loss, gt_logits [N,21], zy_logits [N,3], id1_logits [N,33], id2_logits [N,33]).  loss = mean(gt) +
+        mean(zy) of the label-smoothed losses (optim.py:137-144) as an fp32 scalar tensor: the indel losses are not in it, as
+        model.py:109-110.  fp32 only; needs the indel heads (a forward_layer state dict that had them, or load_indel_heads)."""
+        import torch
+        if not self._loaded or not self._indel_loaded:
+            raise _lib.NanoSNPError("weights not loaded" if not self._loaded else "indel heads not loaded (the forward_layer state dict had none)")
+        if inputs.dim() != 3 or tuple(inputs.shape[1:]) != (33, 18):
+            raise ValueError(f"expected [N,33,18], got {tuple(inputs.shape)}")
+        if not inputs.is_cuda:
+            raise _lib.NanoSNPError("inputs must live on the GPU (no CPU path)")
+        n = int(inputs.shape[0])
+        x = (inputs if inputs.dtype == torch.int32 else inputs.to(torch.int32)).contiguous()
+        cls = torch.stack([t.reshape(-1).to(device=x.device, dtype=torch.uint8) for t in (gt_target, zy_target, id1_target, id2_target)], dim=1)
+        if tuple(cls.shape) != (n, 4):
+            raise ValueError(f"expected four targets of {n} classes")
+        counters = torch.zeros(self.ctx.EVAL_COUNTERS, dtype=torch.int64, device=x.device)
+        site_loss, _, z = self.ctx.pileup_eval_windows(x, None, cls.contiguous(), counters, want_logits=True, stream=stream)
+        if n == 0:
+            loss = torch.full((), float("nan"), dtype=torch.float32, device=x.device)          # (torch.mean of nothing)
+        else:
+            s = self.ctx.pileup_batch_loss(site_loss, n, stream=stream)[0]
+            loss = ((s[0] + s[1]) / n).to(torch.float32)
+        return loss, z[:, :21], z[:, 21:24], z[:, 24:57], z[:, 57:90]
