@@ -125,7 +125,9 @@ int nsnp_ctx_reserve(nsnp_ctx* ctx, int64_t max_sites);
  *   "proj1_tiles"             1..64                            row tiles per wave of the unfused projection kernel
  *   fp32 path (pileup_precision 0): "l0_register_stationary" 2 (default: the input block of layer 0 as exact bf16 partial products,
  *   16-site workgroups; "l0_site_groups" and "l0_input_weights_in_lds" shape the kernels of 1 only) | 1 | 0 (the fp32-MFMA
- *   kernels, bit-identical to each other), "l1_register_stationary" 1 four waves x four gate
+ *   kernels, bit-identical to each other), "l0_weave" 1 (default) | 0 (the kernel of "l0_register_stationary" 2 with the step
+ *   software-pipelined - the next step's count projection is issued under this step's cell, in front of the barrier;
+ *   bit-identical to 0, accepted and ignored elsewhere), "l1_register_stationary" 1 four waves x four gate
  *   tiles (default) | 2 eight waves x two tiles | 0 LDS-image kernels with the Xp1 round trip, "l1_site_groups" 0 | 1 | 2 | 4,
  *   "l1_stagger" 0 (default) | 1 (eight-wave kernel: waves 4-7 issue a group's next input part ahead of its cell),
  *   "l1_weave" 1 (default) | 0 (four-wave kernel, one site group: the step software-pipelined - the next step's input projection

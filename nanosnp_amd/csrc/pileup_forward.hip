@@ -760,6 +760,298 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsx(
     NSNP_DEVCLK_STOP(0)
 }
 
+template <int... I, class F>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_seq(std::make_integer_sequence<int, N>{}, f); }
+
+// K1xw: K1x with the step software-pipelined ("l0_weave" 1, docs/rounds/r21.md).  The count projection of step s+1 depends on
+// nothing the barrier of step s protects, and its bf16 MFMAs - unlike the fp32 ones of the recurrent block - leave the vector ALU
+// free for half of their cycles.  So they are issued in step s, behind the part of the cell that reads the pre-activations and in
+// front of the barrier, with the rest of the cell in their gaps:
+//   prologue  stage x of steps 0 and 1, load step 2, project step 0 into acc, barrier
+//   step s    ds_reads of h[s-1] and of plane 0 and the split level of step s+1; 64 recurrent MFMAs onto acc (s > 0);
+//             cell slices 0..19 (nsnp_cell::lstm_cell_slice stages 0-4: 16 v_exp_f32, 4 v_med3_f32), after which acc is dead;
+//             the 12 bf16 MFMAs of step s+1 from a zero C operand into acc (planes w2, w1, w0, four tiles each) with cell
+//             slices 20..79 placed between them by GAP_T / GAP_V; ds_write of h[s]; stage x of step s+2, load x of step s+3;
+//             barrier
+// Per accumulator the chain stays 0 -> count planes (level .. 0) x (w2, w1, w0) -> W_hh K blocks 0..3 and the cell's instructions
+// are lstm_cell's: the bits are K1x's (tests/test_gpu_l0_weave.py).
+// Placement: walking slices 20..79 in the order of rsxw_late_slice, an MFMA of the burst is issued in front of a transcendental slice once GAP_T
+// transcendentals (in front of a plain slice once GAP_V plain instructions) have followed the previous MFMA, from the GAP_FIRST-th
+// of these 60 slices on; what is left of the burst follows slice 79.  GAP_T = GAP_V = 0: the cell in one piece, then the burst.  LATE_W0 moves the last plane (w0 c0, four
+// MFMAs) behind the barrier, in front of the first recurrent MFMA, where it covers the ds_reads of h[s]; w0 c0 is last in the
+// chain of every level either way.  The order is written out slot by slot and held by a sched_barrier behind every slot, as
+// in K23r4w.
+// Split levels 1 and 2 of step s+1 (known in step s) run the cell in one piece and their 24 / 36 MFMAs as a plain block.
+// x buffers: buffer u % 2 holds step u.  Step s reads buffer (s+1) % 2 (staged in step s-1, in front of barrier s-1) and
+// stores step s+2 into buffer s % 2, whose last readers - the projection of step s - ran in step s-1 in front of barrier s-1
+// (step 0: in the prologue, in front of its barrier).  Buffer (s+1) % 2 is next written in step s+1, behind barrier s.  Two
+// buffers suffice.  Past the last step the staging repeats the last column into a buffer nobody reads again.
+constexpr bool rsxw_slice_is_trans(int i)
+{
+    const int st = i >> 2;
+    return st == 0 || st == 1 || st == 2 || st == 4 || st == 7 || st == 11 || st == 14 || st == 17;
+}
+// the k-th of the 60 late slices: lstm_cell_slice's order (stage by stage, four units each) except that stages 5 and 6 run unit by
+// unit (tg dies at once and d takes the place of e_i: seven registers fewer at the cell's widest point; a plain instruction may
+// follow its operand directly)
+constexpr int rsxw_late_slice(int k) { return k < 8 ? 4 * (5 + (k & 1)) + (k >> 1) : 20 + k; }
+// MFMAs of a burst of nm, paced from late slice `first` on, issued in front of late slices 0 .. last
+constexpr int rsxw_mfmas_upto(int gap_t, int gap_v, int first, int nm, int last)
+{
+    int m = 0, run = 0;
+    for (int k = first; k <= last; ++k) {
+        const int quota = rsxw_slice_is_trans(rsxw_late_slice(k)) ? gap_t : gap_v;
+        if (quota == 0) continue;
+        if (m < nm && (m == 0 || run >= quota)) { ++m; run = 0; }
+        ++run;
+    }
+    return m;
+}
+
+template <int GAP_T, int GAP_V, int GAP_FIRST, bool LATE_W0>
+__global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
+    const int32_t* __restrict__ x, const int64_t* __restrict__ center_idx, int64_t N,
+    const float* __restrict__ whh0, const float* __restrict__ whh1,
+    const __bf16* __restrict__ wx0, const __bf16* __restrict__ wx1,
+    float* __restrict__ H0)
+{
+    static_assert(GAP_T == 0 || GAP_V == 0, "one class of cell instruction paces the burst");
+    static_assert(PW >= 3, "the pipeline stages three steps in its prologue");
+    // hx[2]: the staging threads' 64-bit element offsets at t = 0 (contiguous windows and center_idx alike: no register holds an
+    // offset).  Thread tid keeps its offset at the position of its flush chunk in an exchange buffer, so that ONE address register
+    // serves the flush and the window loads
+    __shared__ __attribute__((aligned(16))) float hx[3][16][RS_XROW];
+    __shared__ __attribute__((aligned(16))) __bf16 xx[2][3][RX_PLANE];
+    __shared__ __attribute__((aligned(16))) int xlvl[2][4];             // [buf][staging wave]: split level
+    const int dir = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = lane & 15, q = lane >> 4;
+    NSNP_DEVCLK_START
+    const int64_t base_site = (int64_t)blockIdx.x * 16;
+    const int nrows = (int)min((int64_t)16, N - base_site);
+
+    // ---- weights, x staging and the H0 flush: K1x's ----
+    f32x4 Whh[4][4];
+    b8 Wx[4][3];
+    {
+        const f32x4* __restrict__ ghh = reinterpret_cast<const f32x4*>(dir ? whh1 : whh0);     // [tile][j4 4][lane]
+        const b8* __restrict__ gx = reinterpret_cast<const b8*>(dir ? wx1 : wx0);              // [tile][plane 3][lane]
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) Whh[u][j] = ghh[((4 * wave + u) * 4 + j) * 64 + lane];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) Wx[u][p] = gx[((4 * wave + u) * 3 + p) * 64 + lane];
+        }
+    }
+    const bool xon = tid < 9 * 16;
+    const int xrow = min(wave < 2 ? lane >> 2 : n, nrows - 1);          // (rows past N restage the last site: never stored)
+    const int piece = wave < 2 ? 4 * wave + (lane & 3) : 8;
+    const int xdst = wave < 2 ? 128 * wave + 2 * lane : 256 + 8 * n;    // K position 2 piece of the staged row
+    const int frow = tid >> 4, fcid = tid & 15;
+    float* const fl = &hx[0][frow][16 * (fcid & 3) + 4 * (fcid >> 2)];
+    int64_t* const xofs = reinterpret_cast<int64_t*>(fl + 2 * 16 * RS_XROW);
+    if (xon) *xofs = (center_idx ? (center_idx[base_site + xrow] - PCENTER) * PC : (base_site + xrow) * (PW * PC)) + 2 * piece;
+    int2 xi = int2{0, 0};
+    auto tpos = [&](int u) { return dir ? PW - 1 - u : u; };
+    auto load_x = [&](int t) {
+        if (!xon) return;
+        xi = *reinterpret_cast<const int2*>(x + *xofs + t * PC);
+    };
+    auto stage_x_split = [&](b2* d, int* lv) {
+        __bf16 a0, a1, a2, c0, c1, c2;
+        split3((float)xi.x, a0, a1, a2); split3((float)xi.y, c0, c1, c2);
+        d[0] = b2{a0, c0}; d[RX_PLANE / 2] = b2{a1, c1}; d[RX_PLANE] = b2{a2, c2};
+        const bool nz1 = (float)a1 != 0.f || (float)c1 != 0.f, nz2 = (float)a2 != 0.f || (float)c2 != 0.f;
+        const int lvl = __ballot(nz2) != 0ull ? 2 : (__ballot(nz1) != 0ull ? 1 : 0);
+        if (lane == 0) *lv = lvl;
+    };
+    auto stage_x = [&](int buf) {
+        if (!xon) return;
+        b2* const d = reinterpret_cast<b2*>(&xx[buf][0][xdst]);
+        const bool big = (unsigned)xi.x + 256u > 512u || (unsigned)xi.y + 256u > 512u;
+        if (__builtin_expect(__ballot(big) == 0ull, 1)) {
+            d[0] = __builtin_convertvector(f32x2{(float)xi.x, (float)xi.y}, b2);       // predict.py:49 int -> float; exact: |c| <= 256
+            d[RX_PLANE / 2] = b2{0, 0};                                  // planes 1 and 2 always hold this step's terms
+            d[RX_PLANE] = b2{0, 0};
+            if (lane == 0) xlvl[buf][wave] = 0;
+        } else {
+            stage_x_split(d, &xlvl[buf][wave]);
+        }
+    };
+    for (int i = tid; i < 2 * 3 * RX_PLANE / 8; i += 256) reinterpret_cast<b8*>(&xx[0][0][0])[i] = b8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (tid < 8) xlvl[tid >> 2][tid & 3] = 0;
+    __syncthreads();
+    if (tid < 32) xx[tid >> 4][0][2 * 128 + (tid & 15) * 8 + 2] = (__bf16)1.0f;
+    load_x(tpos(0)); stage_x(0);
+    load_x(tpos(1)); stage_x(1);
+    load_x(tpos(2));
+    __syncthreads();
+
+    float c[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) c[u] = 0.f;
+
+    float* const h0wg = H0 + (base_site * PW * 2 + dir) * 64;
+    unsigned foff = (unsigned)(frow * (PW * 128) + 4 * fcid) * 4u;
+    const bool fon = frow < nrows;
+    auto flush_h = [&](int buf, int t) {
+        asm volatile("" : "+v"(foff));
+        if (fon)
+            *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(h0wg + t * 128) + foff) =
+                *reinterpret_cast<const f32x4*>(fl + buf * (16 * RS_XROW));
+    };
+
+    // ---- the projection of the step staged in buffer buf, from a zero C operand ----
+    // NM: bf16 MFMAs of a level-0 burst issued in front of the barrier (the last plane waits behind it under LATE_W0)
+    constexpr int NM = LATE_W0 ? 8 : 12;
+    auto read_x = [&](int buf, b8& xb0, int& lvl) __attribute__((always_inline)) {
+        // (plane 0 is read beside the level: one LDS round trip)
+        xb0 = *reinterpret_cast<const b8*>(&xx[buf][0][q * 128 + n * 8]);
+        const i32x4 lv = *reinterpret_cast<const i32x4*>(xlvl[buf]);
+        lvl = __builtin_amdgcn_readfirstlane(max(max(lv[0], lv[1]), max(lv[2], lv[3])));
+    };
+    // levels 1 and 2, and level 0 in the prologue: count planes smallest first, each with w2, w1, w0, as one block
+    auto project_block = [&](int buf, const b8& xb0, f32x4 (&acc)[4], auto lvl_tag) __attribute__((always_inline)) {
+        constexpr int LVL = decltype(lvl_tag)::value;
+        const __bf16* xr = &xx[buf][0][q * 128 + n * 8];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int p = LVL; p >= 0; --p) {
+            const b8 b = p ? *reinterpret_cast<const b8*>(xr + p * RX_PLANE) : xb0;
+#pragma unroll
+            for (int wp = 2; wp >= (LATE_W0 && p == 0 ? 1 : 0); --wp)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Wx[u][wp], b, acc[u], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);                  // (source order: one B fragment live, every sum in place)
+                }
+        }
+    };
+    auto project_any = [&](int buf, const b8& xb0, int lvl, f32x4 (&acc)[4]) __attribute__((always_inline)) {
+        if (__builtin_expect(lvl == 0, 1)) project_block(buf, xb0, acc, std::integral_constant<int, 0>{});
+        else if (lvl == 1)                 project_block(buf, xb0, acc, std::integral_constant<int, 1>{});
+        else                               project_block(buf, xb0, acc, std::integral_constant<int, 2>{});
+    };
+
+    f32x4 acc[4];
+    b8 xb;                                                              // plane 0 of the step acc holds (read again behind the barrier under LATE_W0)
+    {
+        int lvl0;
+        read_x(0, xb, lvl0);
+        project_any(0, xb, lvl0, acc);
+    }
+    // step 0 stores x of step 2 over that of step 0: every wave must have read it
+    lds_barrier();
+
+    auto step = [&](int s, auto first_tag, auto last_tag) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
+        const int t = tpos(s);
+        const int cur = s & 1;
+        const float* hr = &hx[cur ^ 1][n][4 * q];
+        f32x4 hb0, hb1;
+        if constexpr (!FIRST) { hb0 = *reinterpret_cast<const f32x4*>(hr); hb1 = *reinterpret_cast<const f32x4*>(hr + 16); }
+        if constexpr (LATE_W0) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Wx[u][0], xb, acc[u], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        int lvln = 0;
+        if constexpr (FIRST) read_x(cur ^ 1, xb, lvln);
+        else {
+            // recurrent B fragments one K block ahead of their MFMAs, two in flight, as in K1r.  acc is live across the barrier
+            // here, so plane 0 of step s+1 is read once K block 0 has released its fragment, and h[s-1] leaves for H0 through the
+            // registers K block 2 releases
+#define RSXW_KBLOCK(J, HB)                                                                             \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e)                                              \
+                _Pragma("unroll") for (int u = 0; u < 4; ++u) acc[u] = mfma4(Whh[u][J][e], HB[e], acc[u]);
+            __builtin_amdgcn_sched_barrier(0);
+            RSXW_KBLOCK(0, hb0)
+            __builtin_amdgcn_sched_barrier(0);
+            hb0 = *reinterpret_cast<const f32x4*>(hr + 32);
+            RSXW_KBLOCK(1, hb1)
+            __builtin_amdgcn_sched_barrier(0);
+            hb1 = *reinterpret_cast<const f32x4*>(hr + 48);
+            if constexpr (!LAST) read_x(cur ^ 1, xb, lvln);
+            RSXW_KBLOCK(2, hb0)
+            __builtin_amdgcn_sched_barrier(0);
+            flush_h(cur ^ 1, dir ? t + 1 : t - 1);
+            RSXW_KBLOCK(3, hb1)
+#undef RSXW_KBLOCK
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // cell: lane (n, q) holds the four gates of unit 4 (4 wave + u) + q in acc[u]
+        nsnp_cell::CellSlices w;
+        f32x4 hn;
+        // (unit by unit, so that acc[u] dies with unit u: stage 3, v_med3_f32, first and its v_exp_f32, stage 4, last)
+        static_for<20>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int k = decltype(ic)::value, u = k / 5, st = k % 5 == 0 ? 3 : k % 5 == 4 ? 4 : k % 5 - 1;
+            nsnp_cell::lstm_cell_slice<4 * st + u>(w, acc, c, hn);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        // MFMA m of the level-0 burst: plane w(2 - m / 4), tile m % 4; none behind the last step
+        auto burst = [&](auto from_tag, auto to_tag) __attribute__((always_inline)) {
+            constexpr int FROM = decltype(from_tag)::value, TO = decltype(to_tag)::value;
+            if constexpr (!LAST)
+                static_for<TO - FROM>([&](auto mc) __attribute__((always_inline)) {
+                    constexpr int m = FROM + decltype(mc)::value, u = m & 3, wp = 2 - (m >> 2);
+                    if constexpr (m < 4) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Wx[u][wp], xb, acc[u], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+        };
+        static_for<60>([&](auto kc) __attribute__((always_inline)) {
+            constexpr int k = decltype(kc)::value;
+            constexpr int before = rsxw_mfmas_upto(GAP_T, GAP_V, GAP_FIRST, NM, k - 1), upto = rsxw_mfmas_upto(GAP_T, GAP_V, GAP_FIRST, NM, k);
+            burst(std::integral_constant<int, before>{}, std::integral_constant<int, upto>{});
+            nsnp_cell::lstm_cell_slice<rsxw_late_slice(k)>(w, acc, c, hn);
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        *reinterpret_cast<f32x4*>(&hx[cur][n][16 * wave + 4 * q]) = hn;
+        __builtin_amdgcn_sched_barrier(0);
+        burst(std::integral_constant<int, rsxw_mfmas_upto(GAP_T, GAP_V, GAP_FIRST, NM, 59)>{}, std::integral_constant<int, NM>{});
+        // counts beyond +-256 in step s+1 (no pileup has them): the burst above held plane 0 only, so its sums are dropped and the
+        // step's 24 / 36 MFMAs run as one block from zero.  (A second copy of the cell in this branch, in one piece in front of the
+        // block, costs the kernel its registers: docs/rounds/r21.md)
+        if constexpr (!LAST) {
+            if (__builtin_expect(lvln != 0, 0)) {
+                if (lvln == 1) project_block(cur ^ 1, xb, acc, std::integral_constant<int, 1>{});
+                else           project_block(cur ^ 1, xb, acc, std::integral_constant<int, 2>{});
+            }
+        }
+        if constexpr (!LAST) {
+            stage_x(cur);                                               // x of step s+2 over that of step s
+            load_x(tpos(s + 3 < PW ? s + 3 : PW - 1));
+        }
+        lds_barrier();
+    };
+    step(0, std::true_type{}, std::false_type{});
+    for (int s = 1; s < PW - 1; ++s) step(s, std::false_type{}, std::false_type{});
+    step(PW - 1, std::false_type{}, std::true_type{});
+    flush_h((PW - 1) & 1, dir ? 0 : PW - 1);
+    NSNP_DEVCLK_STOP(0)
+}
+// the placement that is built.  Measured (docs/rounds/r21.md): on the headline every placement of this kernel is 1.4 - 1.7 % above
+// k_pileup_l0_rsx and they differ among themselves by less than a run does; one transcendental behind each of eight MFMAs, from the
+// reciprocal of the forget gate on (late slice 24, where the cell holds the fewest registers), with the last plane behind the
+// barrier, is the highest and the steadiest.  Two plain instructions per gap from slice 0 on (0, 2, 0, 0) is 5 % slower per launch.
+#ifndef RSXW_GAP_T
+#define RSXW_GAP_T 1
+#endif
+#ifndef RSXW_GAP_V
+#define RSXW_GAP_V 0
+#endif
+#ifndef RSXW_GAP_FIRST
+#define RSXW_GAP_FIRST 24
+#endif
+#ifndef RSXW_LATE_W0
+#define RSXW_LATE_W0 1
+#endif
+
 // K23r: layer 1,input projection FUSED into the recurrence (no Xp1 round trip: 70 KB/site less HBM traffic than K2 + K3).
 // grid = (ceil(N / (16 NSG)), 2), block = 512: wave w owns gate tiles 2w, 2w+1 (W_ih1 K = 128 and W_hh1 K = 64: 96 VGPRs).
 // LDS: the h0_t rows of the workgroup's sites copied from H0 one step ahead (double-buffered; the 16-byte chunk (d, q, c) of
@@ -1056,11 +1348,6 @@ __global__ __launch_bounds__(256, 2) void k_pileup_l1_rs4(
 // of step s+2 over those of step s (read by the projection issued in step s-1) and loads those of step s+3; beyond the last step
 // both repeat the last rows into a buffer nobody reads again, so that the burst has no branch.
 constexpr int rs4w_l1_lds_bytes() { return rs4_l1_lds_bytes(1) + 4 * 4 * 2 * 64 * 16; }
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_seq(std::make_integer_sequence<int, N>{}, f); }
 
 template <int CELL_PER_GAP, int CELL_FIRST_GAP>
 __global__ __launch_bounds__(256, 2) void k_pileup_l1_rs4w(
@@ -1760,6 +2047,10 @@ static int launch_layers(nsnp_ctx* ctx, const int32_t* xc, const int64_t* cc, in
             ScopedKernelTimer tm(ctx, NSNP_K_L0, s);
             // 16 sites per workgroup, three workgroups per SIMD set ("l0_site_groups" and "l0_input_weights_in_lds" shape the
             // kernels of value 1 only)
+            if (ctx->l0_weave)
+                hipLaunchKernelGGL((k_pileup_l0_rsxw<RSXW_GAP_T, RSXW_GAP_V, RSXW_GAP_FIRST, RSXW_LATE_W0 != 0>), dim3((unsigned)NSNP_CDIV(n, 16), 2), dim3(256), 0, s,
+                                   xc, cc, n, pw.l0_whh[0], pw.l0_whh[1], (const __bf16*)pw.l0_wx[0], (const __bf16*)pw.l0_wx[1], ctx->ws_h0);
+            else
             hipLaunchKernelGGL(k_pileup_l0_rsx, dim3((unsigned)NSNP_CDIV(n, 16), 2), dim3(256), 0, s, xc, cc, n,
                                pw.l0_whh[0], pw.l0_whh[1], (const __bf16*)pw.l0_wx[0], (const __bf16*)pw.l0_wx[1], ctx->ws_h0);
         } else if (ctx->l0_rs) {
