@@ -151,7 +151,8 @@ int nsnp_ctx_set_option(nsnp_ctx* ctx, const char* name, int64_t value);
  * 4 column encode, 5 haplotype features) and resets the counter.  Ids 6-8 bracket a whole CHAIN of launches of one
  * internal pass with one event pair each: 6 the fused LSTM step launches of a HaplotypeModel pass (83 launches of
  * k_hap_gemm), 7 the convolution GEMM + pooling launches of a CatModel pass (12 + 4), 8 a whole CatModel pass;
- * `launches` then counts passes.  Synchronous. */
+ * `launches` then counts passes.  Id 9: the heads launch of a HaplotypeModel pass (the softmax heads of nsnp_hap_forward or the scoring
+ * heads of nsnp_hap_eval).  Synchronous. */
 int nsnp_ctx_enable_timing(nsnp_ctx* ctx, int enable);
 int nsnp_ctx_read_timing(nsnp_ctx* ctx, int kernel, double* total_ms, int64_t* launches);
 
@@ -572,6 +573,37 @@ int nsnp_hap_load_weights(nsnp_ctx* ctx, const float* const* host_tensors, int n
 /* xp: device fp32 [N,105,33], xh: device fp32 [N,105,11] -> gt [N,n_gt], zy [N,n_zy]. */
 int nsnp_hap_forward(nsnp_ctx* ctx, const float* xp, const float* xh, int64_t N,
                      float* gt_prob, float* zy_prob, void* stream);
+
+/* ---- scoring a HaplotypeModel checkpoint on labelled sites (HaplotypeModel/evaluate_dev.py:16-86, its eval()) ----------------------------
+ * All three arithmetics of the option "hap_precision".  Inference with labels attached: no backward pass.
+ *
+ * LabelField and EvaluateDataset's target rule (dataset_dev.py:174-187,320) on candidate_labels rows { confident, gt21, zygosity }, device
+ * int32 [N,3].  A row is kept when confident == 1 and it is a refcall (zygosity == -1, gt21 < 10) or a variant (0 < zygosity < 10, gt21 < 10);
+ * zygosity 0 is in neither list and is dropped, as there.  Of those rows the ones the loaded heads cannot score (gt21 < 0, gt21 >= n_gt,
+ * zygosity >= n_zy: where the reference's scatter_ fails) are counted and dropped.  Kept rows, compacted and in their order:
+ *   cls   uint8 [N,2]   { gt21, max(zygosity, 0) }          (device)
+ *   rows  int64 [N]     the row's index in the pass         (device)
+ *   meta  int64 [4]   = { kept, unscorable, refcalls kept, variants kept }; device or pinned host memory
+ * Nothing is written behind the kept rows.  Three launches (flags, one-workgroup exclusive scan, compaction), no workgroup waits for another;
+ * the scratch is nsnp_pileup_label_classes' (12 bytes per row).  NSNP_ENOWEIGHTS before nsnp_hap_load_weights.  The reference's order -
+ * refcalls, then variants, then an unseeded shuffle - is not reproduced: every result that does not depend on the order equals its own. */
+int nsnp_hap_label_classes(nsnp_ctx* ctx, const int32_t* label, int64_t N, uint8_t* cls, int64_t* rows, int64_t* meta, void* stream);
+
+/* LSTMNetwork.forward (model_dev.py:120-131) before the two means: the launches of nsnp_hap_forward with a scoring heads kernel as the last.
+ * The logit of a head row is computed exactly as nsnp_hap_forward computes it in front of its softmax.  cls uint8 [N,2]: the target classes
+ * { gt, zy } (a class outside its head counts as the head's last).  Per site and head h with C classes:
+ *   lp = z - logsumexp(z);  site_loss[n,h] = -(0.9 lp[t] + 0.1 / (C - 1) (sum(lp) - lp[t]));  pred[n,h] = first maximum of z
+ *   (C == 1: loss 0, pred 0)
+ *   counters int64 [n_gt * n_gt + n_zy * n_zy]: two matrices [target][predicted], genotype then zygosity; ADDED to (device memory)
+ *   logits   NULL, or fp32 [N, n_gt + n_zy] (genotype rows first): with NULL no logit reaches memory.
+ * The heads kernel is persistent: at most NSNP_HAP_EVAL_WAVES_PER_CU waves per compute unit, one site per wave and trip.  Counts are 32-bit
+ * integers in LDS, flushed once per workgroup as 64-bit integer adds; no float is added atomically: the same bits from run to run. */
+#define NSNP_HAP_EVAL_WAVES_PER_CU 32
+int nsnp_hap_eval(nsnp_ctx* ctx, const float* xp, const float* xh, const uint8_t* cls, int64_t N, float* site_loss, uint8_t* pred,
+                  int64_t* counters, float* logits, void* stream);
+
+/* nsnp_pileup_batch_loss for rows of two heads: site_loss fp32 [N,2] (8-byte aligned) -> batch_sum double [ceil(N / batch_size), 2]. */
+int nsnp_hap_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream);
 
 /* ---- legacy haplotype caller (HaplotypeModel/predict.py -> model.CatModel; not run by run_caller.sh) ---- */
 /* host_tensors: the 132 floating-point tensors of CatModel(nc0=5,nc1=5,nc2=2,nclass=10,nh=256).state_dict()

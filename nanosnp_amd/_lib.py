@@ -92,6 +92,9 @@ _SIGNATURES = {
     "nsnp_hap_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int] + [C.c_int] * 5),
     "nsnp_hap_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "nsnp_hap_label_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nsnp_hap_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "nsnp_hap_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_cat_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
     "nsnp_cat_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_comm_unique_id": (C.c_int, [C.c_void_p]),
@@ -323,7 +326,7 @@ class Context:
 
     # ids of nsnp_ctx_read_timing; the last three are ONE event pair around a chain of launches of a pass (include/nanosnp.h)
     KERNELS = ("pileup_l0", "pileup_proj1", "pileup_l1", "pileup_head", "encode_columns", "hap_features",
-               "hap_lstm_chain", "cat_conv_chain", "cat_forward_pass")
+               "hap_lstm_chain", "cat_conv_chain", "cat_forward_pass", "hap_head")
 
     def enable_timing(self, enable=True):
         check(self.lib.nsnp_ctx_enable_timing(self.handle, int(bool(enable))), self.handle, "nsnp_ctx_enable_timing")
@@ -1174,3 +1177,76 @@ class Context:
                                         _stream_ptr(stream)),
               self.handle, "nsnp_hap_forward")
         return gt, zy
+
+    # ---- scoring a HaplotypeModel checkpoint on labelled sites (include/nanosnp.h; every hap_precision) ----
+    HAP_EVAL_WAVES_PER_CU = 32                  # NSNP_HAP_EVAL_WAVES_PER_CU: the persistent heads kernel takes one site per wave and trip
+
+    def hap_label_classes(self, label, cls=None, rows=None, meta=None, stream=None):
+        """label: device int32 [N,3] = {confident, gt21, zygosity} -> (cls uint8 [N,2], rows int64 [N], meta int64 [4]): the first meta[0]
+        rows of cls / rows are the kept rows' classes {gt, max(zy, 0)} and their indices, in order; meta = {kept, unscorable, refcalls kept,
+        variants kept}.  meta may be pinned host memory; the count is only known behind the launch."""
+        import torch
+        if label.dtype != torch.int32 or not label.is_cuda or not label.is_contiguous() or label.dim() != 2 or label.shape[1] != 3:
+            raise NanoSNPError("hap_label_classes: label must be a contiguous device int32 [N,3]")
+        n, dev = int(label.shape[0]), label.device
+        cls = cls if cls is not None else torch.empty((max(n, 1), 2), dtype=torch.uint8, device=dev)
+        rows = rows if rows is not None else torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        meta = meta if meta is not None else torch.zeros(4, dtype=torch.int64, device=dev)
+        if (cls.dtype != torch.uint8 or cls.numel() < 2 * n or not cls.is_cuda or not cls.is_contiguous() or rows.dtype != torch.int64
+                or rows.numel() < n or not rows.is_cuda or not rows.is_contiguous()):
+            raise NanoSNPError("hap_label_classes: cls uint8 [N,2] and rows int64 [N] on the device")
+        if meta.dtype != torch.int64 or meta.numel() < 4 or not (meta.is_cuda or meta.is_pinned()) or not meta.is_contiguous():
+            raise NanoSNPError("hap_label_classes: meta int64 [4] on the device or in pinned memory")
+        check(self.lib.nsnp_hap_label_classes(self.handle, _dptr(label), n, _dptr(cls), _dptr(rows), meta.data_ptr(), _stream_ptr(stream)),
+              self.handle, "nsnp_hap_label_classes")
+        return cls, rows, meta
+
+    def hap_eval_counters(self, device=None):
+        """a zeroed counter tensor for hap_eval: int64 [n_gt * n_gt + n_zy * n_zy]"""
+        import torch
+        n_gt, n_zy = self._hap_dims
+        return torch.zeros(n_gt * n_gt + n_zy * n_zy, dtype=torch.int64, device=device if device is not None else torch.device("cuda", self.device))
+
+    def hap_eval(self, xp, xh, cls, counters, n=None, site_loss=None, pred=None, want_logits=False, stream=None):
+        """forward + label-smoothed loss + argmax + confusion counts -> (site_loss fp32 [n,2], pred uint8 [n,2], logits fp32 [n, n_gt + n_zy] or
+        None).  xp [N,F,33], xh [N,F,11] contiguous device fp32; cls: device uint8 [>= n, 2]; counters: device int64 [n_gt^2 + n_zy^2], added
+        to; n: the sites to run (default: all of xp)"""
+        import torch
+        if not hasattr(self, "_hap_dims"):
+            raise NanoSNPError("hap_eval: weights not loaded")
+        n_gt, n_zy = self._hap_dims
+        for t, l, what in ((xp, 33, "xp"), (xh, 11, "xh")):
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape[2] != l:
+                raise NanoSNPError(f"hap_eval: {what} must be a contiguous device fp32 [N,F,{l}]")
+        n_all = int(xp.shape[0])
+        n = n_all if n is None else int(n)
+        dev = xp.device
+        if n < 0 or n > n_all or xh.shape[0] < n or xh.shape[1] != xp.shape[1]:
+            raise NanoSNPError("hap_eval: n sites within xp and xh, which share their feature count")
+        if cls.dtype != torch.uint8 or cls.numel() < 2 * n or not cls.is_cuda or not cls.is_contiguous():
+            raise NanoSNPError("hap_eval: cls uint8 [N,2] on the device, one row per site")
+        if counters.dtype != torch.int64 or counters.numel() != n_gt * n_gt + n_zy * n_zy or not counters.is_cuda or not counters.is_contiguous():
+            raise NanoSNPError(f"hap_eval: counters int64 [{n_gt * n_gt + n_zy * n_zy}] on the device")
+        site_loss = site_loss if site_loss is not None else torch.empty((n, 2), dtype=torch.float32, device=dev)
+        pred = pred if pred is not None else torch.empty((n, 2), dtype=torch.uint8, device=dev)
+        if (site_loss.dtype != torch.float32 or site_loss.numel() < 2 * n or not site_loss.is_cuda or not site_loss.is_contiguous()
+                or pred.dtype != torch.uint8 or pred.numel() < 2 * n or not pred.is_cuda or not pred.is_contiguous()):
+            raise NanoSNPError("hap_eval: site_loss fp32 [N,2] and pred uint8 [N,2] on the device")
+        logits = torch.empty((n, n_gt + n_zy), dtype=torch.float32, device=dev) if want_logits else None
+        check(self.lib.nsnp_hap_eval(self.handle, _dptr(xp), _dptr(xh), _dptr(cls), n, _dptr(site_loss), _dptr(pred), _dptr(counters),
+                                     _dptr(logits), _stream_ptr(stream)), self.handle, "nsnp_hap_eval")
+        return site_loss, pred, logits
+
+    def hap_batch_loss(self, site_loss, batch_size, n=None, stream=None):
+        """float64 sums of site_loss fp32 [n,2] per batch of batch_size rows -> device float64 [ceil(n / batch_size), 2]"""
+        import torch
+        if site_loss.dtype != torch.float32 or not site_loss.is_cuda or not site_loss.is_contiguous():
+            raise NanoSNPError("hap_batch_loss: site_loss fp32 [N,2] on the device")
+        n = int(site_loss.numel() // 2) if n is None else int(n)
+        if int(batch_size) < 1 or n < 0 or 2 * n > site_loss.numel():
+            raise NanoSNPError("hap_batch_loss: batch_size >= 1 and n rows within site_loss")
+        nb = -(-n // int(batch_size))
+        out = torch.empty((nb, 2), dtype=torch.float64, device=site_loss.device)
+        check(self.lib.nsnp_hap_batch_loss(self.handle, _dptr(site_loss), n, int(batch_size), _dptr(out), _stream_ptr(stream)),
+              self.handle, "nsnp_hap_batch_loss")
+        return out

@@ -14,6 +14,10 @@
 // tile-image layout that the next step / next layer loads back with linear 8 KB copies.  Both
 // directions (and both encoders while the short one is still running) share a launch through
 // gridDim.z.  Only what position L/2 needs is computed in the last layer (17 of 33 / 6 of 11 steps).
+//
+// nsnp_hap_eval is the same forward with labels attached (LSTMNetwork.forward, model_dev.py:120-131, as evaluate_dev.py:45 calls it): every
+// launch up to the dense layer is shared (hap_forward_t takes the heads launch as a parameter), k_hap_head_eval ends it with raw logits,
+// the two label-smoothed losses, the argmax and the confusion counts.
 #include "nsnp_common.hpp"
 
 #include <new>
@@ -85,6 +89,31 @@ __global__ __launch_bounds__(256) void k_hap_pack_input(const float* __restrict_
     }
 }
 
+// the dense output of site n as a wave holds it for the heads: lane k has features k, k + 64, k + 128, k + 192 of the image (natural order)
+template <bool F16>
+__device__ __forceinline__ void hap_inner_of_site(const float* __restrict__ inner, int64_t n, int lane, float v[4])
+{
+    const int64_t tile = n / TS; const int site = (int)(n % TS);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int f = lane + 64 * j;
+        const float* row = inner + (tile * 16 + (f >> 4)) * TILE_F + site * BK;
+        if (F16) { const _Float16* hr = reinterpret_cast<const _Float16*>(row); v[j] = (float)hr[f & 15] + (float)hr[16 + (f & 15)]; }
+        else v[j] = row[f & 15];
+    }
+}
+
+// one head row of a site: the lane's four products in order, the xor tree over the wave (every lane ends with the same bits: the operands of
+// each level commute), the bias last.  The ONE definition of a logit: k_hap_heads and k_hap_head_eval agree on what the model said.
+__device__ __forceinline__ float hap_head_logit(const float* __restrict__ wrow, const float v[4], float bias)
+{
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += wrow[64 * j] * v[j];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    return s + bias;
+}
+
 // heads: logits = W[rows x 256] . inner + b over the dense output image (natural order), softmax
 template <bool F16>
 __global__ __launch_bounds__(256) void k_hap_heads(const float* __restrict__ inner, int64_t N,
@@ -95,24 +124,11 @@ __global__ __launch_bounds__(256) void k_hap_heads(const float* __restrict__ inn
     const int lane = threadIdx.x & 63;
     const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
-    const int64_t tile = n / TS; const int site = (int)(n % TS);
     float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int f = lane + 64 * j;
-        const float* row = inner + (tile * 16 + (f >> 4)) * TILE_F + site * BK;
-        if (F16) { const _Float16* hr = reinterpret_cast<const _Float16*>(row); v[j] = (float)hr[f & 15] + (float)hr[16 + (f & 15)]; }
-        else v[j] = row[f & 15];
-    }
+    hap_inner_of_site<F16>(inner, n, lane, v);
     const int rows = n_gt + n_zy;
     float logit[16];
-    for (int r = 0; r < rows; ++r) {
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s += w[r * 256 + lane + 64 * j] * v[j];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        logit[r] = s + b[r];
-    }
+    for (int r = 0; r < rows; ++r) logit[r] = hap_head_logit(w + r * 256 + lane, v, b[r]);
     if (lane == 0) {
         float m = logit[0];
         for (int r = 1; r < n_gt; ++r) m = fmaxf(m, logit[r]);
@@ -125,6 +141,77 @@ __global__ __launch_bounds__(256) void k_hap_heads(const float* __restrict__ inn
         for (int r = 0; r < n_zy; ++r) { logit[n_gt + r] = __expf(logit[n_gt + r] - m); sum += logit[n_gt + r]; }
         for (int r = 0; r < n_zy; ++r) zy[n * n_zy + r] = logit[n_gt + r] / sum;
     }
+}
+
+// heads of a scoring pass (nsnp_hap_eval): the raw logits of k_hap_heads, then per head the label-smoothed loss (optim.py:137-144 before its
+// mean), the first maximum and one count [target][predicted].
+// A persistent grid: wave g of the launch takes sites g, g + waves, ... .  Per site every lane ends hap_head_logit with the logit of each row
+// r; lane c of the first 16-lane group keeps genotype class c, lane c of the second group zygosity class c (a head has at most 15 classes).
+// Maximum / first argmax / sum of exponentials / sum of logits of BOTH heads then meet in the same four butterfly steps (xor 1, 2, 4, 8 stay
+// inside a group; lanes outside the head carry the neutral element; the operands of every step commute, so the 16 lanes of a group hold the
+// same bits); the target's logit comes by one shuffle.  Lanes 0 and 16 store loss and argmax of their head and count in a 32-bit LDS counter
+// (at most 15 * 15 + 1 of them: integer adds, order-free); the counters leave once, behind the loop, as 64-bit adds.  No float is ever
+// added atomically.
+constexpr int HE_MAX_COUNTERS = 15 * 15 + 1;
+constexpr int HE_WAVES_PER_CU = NSNP_HAP_EVAL_WAVES_PER_CU; // the grid: 2 workgroups of 16 waves per CU, fewer when the pass has fewer sites
+constexpr int HE_WAVES = 16, HE_BLOCK = 64 * HE_WAVES;      // (large workgroups: every workgroup flushes its counters once, to the same words)
+static_assert(HE_WAVES_PER_CU % HE_WAVES == 0, "whole workgroups per CU");
+template <bool F16>
+__global__ __launch_bounds__(HE_BLOCK) void k_hap_head_eval(const float* __restrict__ inner, int64_t N,
+                                                        const float* __restrict__ w, const float* __restrict__ b, int n_gt, int n_zy,
+                                                        const uint8_t* __restrict__ cls, float* __restrict__ site_loss, uint8_t* __restrict__ pred,
+                                                        unsigned long long* __restrict__ counters, float* __restrict__ logits)
+{
+    __shared__ unsigned int cnt[HE_MAX_COUNTERS];
+    const int lane = threadIdx.x & 63;
+    const int rows = n_gt + n_zy, n_cnt = n_gt * n_gt + n_zy * n_zy;
+    for (int i = threadIdx.x; i < n_cnt; i += HE_BLOCK) cnt[i] = 0;
+    __syncthreads();
+    const int head = (lane >> 4) & 1;                        // 16-lane group 0: genotype, group 1: zygosity (groups 2 and 3 only help with the logits)
+    const int c = lane & 15;                                 // the class this lane keeps
+    const int C = head ? n_zy : n_gt;
+    const bool mine = lane < 32 && c < C;
+    const int myrow = head ? n_gt + c : c;
+    const int cnt0 = head ? n_gt * n_gt : 0;
+    const float NEG = -3.0e38f;
+    const int64_t n_waves = (int64_t)gridDim.x * HE_WAVES;
+    for (int64_t n = (int64_t)blockIdx.x * HE_WAVES + (threadIdx.x >> 6); n < N; n += n_waves) {
+        float v[4];
+        hap_inner_of_site<F16>(inner, n, lane, v);
+        float z = NEG;
+        for (int r = 0; r < rows; ++r) {
+            const float zr = hap_head_logit(w + r * 256 + lane, v, b[r]);
+            if (mine && myrow == r) z = zr;
+        }
+        if (logits && mine) logits[n * rows + myrow] = z;
+        const bool cand = mine && z > NEG;                                       // (a NaN logit is no maximum)
+        float bv = cand ? z : NEG;
+        int bi = cand ? c : 0x7fffffff;
+#pragma unroll
+        for (int o = 1; o <= 8; o <<= 1) {                                       // (xor below 16: the two heads' groups never mix)
+            const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        float se = mine ? expf(z - bv) : 0.f, sz = mine ? z : 0.f;
+#pragma unroll
+        for (int o = 1; o <= 8; o <<= 1) { se += __shfl_xor(se, o); sz += __shfl_xor(sz, o); }
+        int t = cls[n * 2 + head];
+        if (t >= C) t = C - 1;                                                   // (the pileup entry's rule: nanosnp.h)
+        const float zt = __shfl(z, (lane & 48) + t);                             // the target's logit: lane t of this lane's group
+        if (bi >= C) bi = 0;                                                     // (no maximum among NaN logits: class 0, as np.argmax of a NaN at 0)
+        if (lane < 32 && c == 0) {
+            // lp = z - logsumexp(z); loss = -(0.9 lp[t] + 0.1 / (C - 1) (sum(lp) - lp[t]))      optim.py:138-144
+            const float lse = bv + logf(se);
+            const float lpt = zt - lse;
+            const float slp = sz - (float)C * lse;
+            site_loss[n * 2 + head] = C > 1 ? -(0.9f * lpt + (0.1f / (float)(C - 1)) * (slp - lpt)) : 0.f;
+            pred[n * 2 + head] = (uint8_t)bi;
+            atomicAdd(&cnt[cnt0 + t * C + bi], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_cnt; i += HE_BLOCK)
+        if (cnt[i]) atomicAdd(counters + i, (unsigned long long)cnt[i]);
 }
 
 }  // namespace
@@ -342,12 +429,14 @@ extern "C" int nsnp_hap_load_weights(nsnp_ctx* ctx, const float* const* t, int n
 }
 
 // AR: 0 exact fp32, 1 f16x3 (activation images hold (hi, lo) fp16 pairs), 2 bf16x3 (weights AND activation images as three bf16 planes)
-template <int AR>
-static int hap_forward_t(nsnp_ctx* ctx, const float* xp, const float* xh, int64_t N, float* gt_prob, float* zy_prob, hipStream_t s)
+// heads(inner, n0, n): the last launch of a pass of n sites that starts at site n0 - the softmax heads of nsnp_hap_forward or the scoring
+// heads of nsnp_hap_eval; every launch in front of it is shared.  `inner` holds (hi, lo) fp16 pairs when AR == 1, fp32 otherwise.
+template <int AR, typename HeadsFn>
+static int hap_forward_t(nsnp_ctx* ctx, const float* xp, const float* xh, int64_t N, hipStream_t s, HeadsFn heads)
 {
     const HapWeightsDev& hw = *ctx->hw;
     const int H = hw.H, F = hw.F;
-    constexpr bool F16 = AR == 1;                              // element format of the activation images: (hi, lo) fp16 pairs ...
+    // element format of the activation images: (hi, lo) fp16 pairs (AR == 1) ...
     constexpr bool BS = AR == 2 && NSNP_HAP_BS;                // ... or three bf16 planes (written by the producing epilogue: hap_gemm.hpp)
     constexpr size_t TILE_A = BS ? TILE_F3 : TILE_F;           // floats of one [128][16] activation tile image
     const WeightMap wm{hw.arena, AR == 1 ? (const void*)hw.arena16 : (const void*)hw.arena_b3, AR};
@@ -438,11 +527,21 @@ static int hap_forward_t(nsnp_ctx* ctx, const float* xp, const float* xh, int64_
             a.cstate = nullptr; a.c_tile_stride = 0; a.first = 0;
             launch_hap_gemm<MODE_LINEAR_TANH, AR, false, BS, false>(ctx, s, L, (int)(n_tiles), H / TR, 1);      // (its output feeds the heads kernel: fp32)
         }
-        hipLaunchKernelGGL(k_hap_heads<F16>, dim3((unsigned)NSNP_CDIV(n, 4)), dim3(256), 0, s, inner, n, hw.head_w, hw.head_b,
-                           hw.n_gt, hw.n_zy, gt_prob + n0 * hw.n_gt, zy_prob + n0 * hw.n_zy);
+        ScopedKernelTimer tm_heads(ctx, NSNP_K_HAPHEAD, s);
+        heads(inner, n0, n);
+        tm_heads.stop();
     }
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
+}
+
+// the arithmetic selected by the option "hap_precision"
+template <typename HeadsFn>
+static int hap_forward_dispatch(nsnp_ctx* ctx, const float* xp, const float* xh, int64_t N, hipStream_t s, HeadsFn heads)
+{
+    if (ctx->hap_precision == 1) return hap_forward_t<1>(ctx, xp, xh, N, s, heads);
+    if (ctx->hap_precision == 2) return hap_forward_t<2>(ctx, xp, xh, N, s, heads);
+    return hap_forward_t<0>(ctx, xp, xh, N, s, heads);
 }
 
 extern "C" int nsnp_hap_forward(nsnp_ctx* ctx, const float* xp, const float* xh, int64_t N,
@@ -452,9 +551,45 @@ extern "C" int nsnp_hap_forward(nsnp_ctx* ctx, const float* xp, const float* xh,
     if (!ctx->hw) return NSNP_ENOWEIGHTS;
     if (N == 0) return NSNP_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (ctx->hap_precision == 1) return hap_forward_t<1>(ctx, xp, xh, N, gt_prob, zy_prob, s);
-    if (ctx->hap_precision == 2) return hap_forward_t<2>(ctx, xp, xh, N, gt_prob, zy_prob, s);
-    return hap_forward_t<0>(ctx, xp, xh, N, gt_prob, zy_prob, s);
+    const HapWeightsDev& hw = *ctx->hw;
+    const bool f16 = ctx->hap_precision == 1;               // the dense output image holds (hi, lo) fp16 pairs
+    return hap_forward_dispatch(ctx, xp, xh, N, s, [&](const float* inner, int64_t n0, int64_t n) {
+        const dim3 grid((unsigned)NSNP_CDIV(n, 4));
+        float* gt = gt_prob + n0 * hw.n_gt; float* zy = zy_prob + n0 * hw.n_zy;
+        if (f16) hipLaunchKernelGGL(k_hap_heads<true>, grid, dim3(256), 0, s, inner, n, hw.head_w, hw.head_b, hw.n_gt, hw.n_zy, gt, zy);
+        else hipLaunchKernelGGL(k_hap_heads<false>, grid, dim3(256), 0, s, inner, n, hw.head_w, hw.head_b, hw.n_gt, hw.n_zy, gt, zy);
+    });
+}
+
+int nsnp_hap_dims(const nsnp_ctx* ctx, int* n_gt, int* n_zy)
+{
+    if (!ctx->hw) return NSNP_ENOWEIGHTS;
+    *n_gt = ctx->hw->n_gt; *n_zy = ctx->hw->n_zy;
+    return NSNP_OK;
+}
+
+extern "C" int nsnp_hap_eval(nsnp_ctx* ctx, const float* xp, const float* xh, const uint8_t* cls, int64_t N, float* site_loss, uint8_t* pred,
+                             int64_t* counters, float* logits, void* stream)
+{
+    if (!ctx || N < 0 || (N > 0 && (!xp || !xh || !cls || !site_loss || !pred || !counters))) return NSNP_EINVAL;
+    if (!ctx->hw) return NSNP_ENOWEIGHTS;
+    if (N == 0) return NSNP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const HapWeightsDev& hw = *ctx->hw;
+    const bool f16 = ctx->hap_precision == 1;
+    const int rows = hw.n_gt + hw.n_zy;
+    const int64_t max_wgs = (int64_t)ctx->n_cu * (HE_WAVES_PER_CU / HE_WAVES);
+    return hap_forward_dispatch(ctx, xp, xh, N, s, [&](const float* inner, int64_t n0, int64_t n) {
+        const int64_t want = NSNP_CDIV(n, (int64_t)HE_WAVES);
+        const int64_t wgs = want < max_wgs ? want : max_wgs;                              // persistent: sized to the chip, not to n
+        const dim3 grid((unsigned)wgs);
+        unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
+        float* lg = logits ? logits + n0 * rows : nullptr;
+        if (f16) hipLaunchKernelGGL(k_hap_head_eval<true>, grid, dim3(HE_BLOCK), 0, s, inner, n, hw.head_w, hw.head_b, hw.n_gt, hw.n_zy,
+                                    cls + n0 * 2, site_loss + n0 * 2, pred + n0 * 2, cnt, lg);
+        else hipLaunchKernelGGL(k_hap_head_eval<false>, grid, dim3(HE_BLOCK), 0, s, inner, n, hw.head_w, hw.head_b, hw.n_gt, hw.n_zy,
+                                cls + n0 * 2, site_loss + n0 * 2, pred + n0 * 2, cnt, lg);
+    });
 }
 
 NSNP_DEVCLK_READER(nsnp_devclk_read_hap)

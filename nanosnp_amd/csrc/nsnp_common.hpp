@@ -81,6 +81,7 @@ struct CatWeightsDev;   // cat_forward.hip
 // NSNP_K_HAPLSTM / NSNP_K_CATCONV / NSNP_K_CAT bracket a whole chain of launches of one pass with ONE event pair (the fused
 // LSTM step launches of a HaplotypeModel pass; the conv GEMM + pool launches of a CatModel pass; a whole CatModel pass)
 enum { NSNP_K_L0 = 0, NSNP_K_PROJ1, NSNP_K_L1, NSNP_K_HEAD, NSNP_K_ENCODE, NSNP_K_HAPFEAT, NSNP_K_HAPLSTM, NSNP_K_CATCONV, NSNP_K_CAT,
+       NSNP_K_HAPHEAD,     // the heads launch of a HaplotypeModel pass: k_hap_heads or k_hap_head_eval
        NSNP_K_COUNT };
 struct KernelTimer {
     std::vector<hipEvent_t> start[NSNP_K_COUNT], stop[NSNP_K_COUNT];
@@ -182,6 +183,9 @@ int nsnp_pileup_eval_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center
                           uint8_t* pred, int64_t* counters, float* logits, hipStream_t s);
 void nsnp_pileup_eval_heads_launch(nsnp_ctx* ctx, int64_t n, const uint8_t* cls, float* site_loss, uint8_t* pred, int64_t* counters,
                                    float* logits, hipStream_t s);
+// the class counts of the loaded HaplotypeModel heads (hap_forward.hip; NSNP_ENOWEIGHTS without weights): what nsnp_hap_label_classes
+// (pileup_eval.hip) can score
+int nsnp_hap_dims(const nsnp_ctx* ctx, int* n_gt, int* n_zy);
 int nsnp_pileup_forward_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx,
                               int64_t N, float* gt, float* zy, hipStream_t s);
 int nsnp_pileup_pack_weights_f16(nsnp_ctx* ctx, const float* const* w);

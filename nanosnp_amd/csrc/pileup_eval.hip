@@ -14,6 +14,11 @@
 //                  so the scan is exact for any N and no workgroup waits for another.  The same lanes count the malformed rows; meta.
 //   k_evl_compact  the kept rows' classes and centres, in order                                                              -> cls, center_idx
 // k_pileup_head_eval: the heads kernel (below).  k_evl_batch_loss: float64 sums of the per-site losses of a batch, one workgroup each.
+//
+// The HaplotypeModel's scoring (HaplotypeModel/evaluate_dev.py:16-86) shares the scan, the scratch and the batch sums:
+//   nsnp_hap_label_classes   k_hapl_flags (LabelField + the target rule, dataset_dev.py:174-187,320), k_evl_scan, k_hapl_compact
+//   nsnp_hap_batch_loss      k_evl_batch_loss over rows of two heads
+// Its heads kernel, k_hap_head_eval, lives beside the forward it ends (hap_forward.hip).
 #include "nsnp_common.hpp"
 
 namespace {
@@ -214,19 +219,27 @@ __global__ __launch_bounds__(EVL_BLOCK) void k_evl_flags(const int32_t* __restri
     word[n] = w | (bad ? EVL_BAD : 0u);
 }
 
+// (shared with nsnp_hap_label_classes, whose words carry two more flags to count: EVL_M2 / EVL_M3 -> meta[2] / meta[3].  The label rows of a
+// .td.bin never set them - byte 1 of their word is the zygosity class, 0..2 - so those two stay 0 there.)
+constexpr uint32_t EVL_M2 = 0x4000u, EVL_M3 = 0x8000u;
 __global__ __launch_bounds__(1024) void k_evl_scan(int64_t* __restrict__ keep, const uint32_t* __restrict__ word, int64_t N, int64_t* __restrict__ meta)
 {
     __shared__ int64_t part[1024];
-    __shared__ unsigned long long n_bad;
+    __shared__ unsigned long long n_bad, n_m2, n_m3;
     const int tid = threadIdx.x;
-    if (tid == 0) n_bad = 0;
+    if (tid == 0) { n_bad = 0; n_m2 = 0; n_m3 = 0; }
     const int64_t per = NSNP_CDIV(N, (int64_t)1024);
     const int64_t n0 = tid * per < N ? tid * per : N, n1 = n0 + per < N ? n0 + per : N;
-    int64_t s = 0, b = 0;
-    for (int64_t n = n0; n < n1; ++n) { s += keep[n]; b += (word[n] & EVL_BAD) ? 1 : 0; }
+    int64_t s = 0, b = 0, m2 = 0, m3 = 0;
+    for (int64_t n = n0; n < n1; ++n) {
+        const uint32_t w = word[n];
+        s += keep[n]; b += (w & EVL_BAD) ? 1 : 0; m2 += (w & EVL_M2) ? 1 : 0; m3 += (w & EVL_M3) ? 1 : 0;
+    }
     part[tid] = s;
     __syncthreads();
     if (b) atomicAdd(&n_bad, (unsigned long long)b);
+    if (m2) atomicAdd(&n_m2, (unsigned long long)m2);
+    if (m3) atomicAdd(&n_m3, (unsigned long long)m3);
     for (int o = 1; o < 1024; o <<= 1) {
         const int64_t v = tid >= o ? part[tid - o] : 0;
         __syncthreads();
@@ -237,8 +250,41 @@ __global__ __launch_bounds__(1024) void k_evl_scan(int64_t* __restrict__ keep, c
     for (int64_t n = n0; n < n1; ++n) { const int64_t v = keep[n]; keep[n] = run; run += v; }
     if (tid == 1023) {
         keep[N] = part[1023];
-        meta[0] = part[1023]; meta[1] = (int64_t)n_bad; meta[2] = 0; meta[3] = 0;
+        meta[0] = part[1023]; meta[1] = (int64_t)n_bad; meta[2] = (int64_t)n_m2; meta[3] = (int64_t)n_m3;
     }
+}
+
+// ---- HaplotypeModel: candidate_labels rows {confident, gt21, zygosity} -> classes (LabelField, HaplotypeModel/dataset_dev.py:174-187,320) ----
+// word of a row: gt in byte 0 (with EVL_BAD: kept by the filter but not scorable by the loaded model), max(zy, 0) in byte 1 with EVL_M2 for a
+// kept refcall and EVL_M3 for a kept variant.  The scan and its meta are k_evl_scan's.
+__global__ __launch_bounds__(EVL_BLOCK) void k_hapl_flags(const int32_t* __restrict__ label, int64_t N, int n_gt, int n_zy,
+                                                          int64_t* __restrict__ keep, uint32_t* __restrict__ word)
+{
+    const int64_t n = (int64_t)blockIdx.x * EVL_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const int32_t cf = label[n * 3], gt = label[n * 3 + 1], zy = label[n * 3 + 2];
+    const bool refcall = cf == 1 && zy == -1 && gt < 10;            // dataset_dev.py:185
+    const bool variant = cf == 1 && zy > 0 && zy < 10 && gt < 10;   // :180,187 (zy == 0 passes valid_idx and is in neither list)
+    const bool scorable = gt >= 0 && gt < n_gt && zy < n_zy;        // (what scatter_ of the smoothed loss accepts)
+    const bool kept = (refcall || variant) && scorable;
+    uint32_t w = 0;
+    if (kept) w = (uint32_t)gt | (uint32_t)(zy > 0 ? zy : 0) << 8 | (refcall ? EVL_M2 : EVL_M3);
+    else if (refcall || variant) w = EVL_BAD;
+    keep[n] = kept ? 1 : 0;
+    word[n] = w;
+}
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_hapl_compact(const int64_t* __restrict__ scan, const uint32_t* __restrict__ word, int64_t N,
+                                                            uint8_t* __restrict__ cls, int64_t* __restrict__ rows)
+{
+    const int64_t n = (int64_t)blockIdx.x * EVL_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const int64_t o = scan[n];
+    if (scan[n + 1] == o || o < 0 || o >= N) return;         // (o lies in [0, N) by construction)
+    const uint32_t w = word[n];
+    cls[o * 2] = (uint8_t)(w & 0x7fu);
+    cls[o * 2 + 1] = (uint8_t)((w >> 8) & 0x3fu);
+    rows[o] = n;
 }
 
 __global__ __launch_bounds__(EVL_BLOCK) void k_evl_compact(const int64_t* __restrict__ scan, const uint32_t* __restrict__ word, int64_t N,
@@ -255,28 +301,63 @@ __global__ __launch_bounds__(EVL_BLOCK) void k_evl_compact(const int64_t* __rest
 // ---- per-batch loss sums ----------------------------------------------------------------------
 // one workgroup of 256 lanes per batch: lane t adds rows t, t + 256, ... of the batch in that order (float64), then the 256 partial sums of
 // each head meet in a fixed binary tree in LDS.  Nothing depends on the grid or on timing.
+// W: the heads of a row - 4 for the PileupModel (rows of 16 bytes), 2 for the HaplotypeModel (rows of 8 bytes); a row is one vector load.
+template <int W>
 __global__ __launch_bounds__(256) void k_evl_batch_loss(const float* __restrict__ site_loss, int64_t N, int64_t B, double* __restrict__ batch_sum)
 {
-    __shared__ double part[4][256];
+    typedef float __attribute__((ext_vector_type(W))) row_t;
+    __shared__ double part[W][256];
     const int tid = threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * B, r1 = r0 + B < N ? r0 + B : N;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t r = r0 + tid; r < r1; r += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(site_loss + r * 4);
+    double s[W];
 #pragma unroll
-        for (int h = 0; h < 4; ++h) s[h] += (double)v[h];
+    for (int h = 0; h < W; ++h) s[h] = 0.0;
+    for (int64_t r = r0 + tid; r < r1; r += 256) {
+        const row_t v = *reinterpret_cast<const row_t*>(site_loss + r * W);
+#pragma unroll
+        for (int h = 0; h < W; ++h) s[h] += (double)v[h];
     }
 #pragma unroll
-    for (int h = 0; h < 4; ++h) part[h][tid] = s[h];
+    for (int h = 0; h < W; ++h) part[h][tid] = s[h];
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (tid < o) {
 #pragma unroll
-            for (int h = 0; h < 4; ++h) part[h][tid] += part[h][tid + o];
+            for (int h = 0; h < W; ++h) part[h][tid] += part[h][tid + o];
         }
         __syncthreads();
     }
-    if (tid < 4) batch_sum[(int64_t)blockIdx.x * 4 + tid] = part[tid][0];
+    if (tid < W) batch_sum[(int64_t)blockIdx.x * W + tid] = part[tid][0];
+}
+
+template <int W>
+int batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream)
+{
+    if (!ctx || N < 0 || batch_size < 1 || (N > 0 && (!site_loss || !batch_sum))) return NSNP_EINVAL;
+    if (reinterpret_cast<uintptr_t>(site_loss) & (W * sizeof(float) - 1)) return NSNP_EINVAL;
+    if (N == 0) return NSNP_OK;
+    const int64_t nb = NSNP_CDIV(N, batch_size);
+    if (nb > 0x7fffffffll) return NSNP_EINVAL;
+    hipLaunchKernelGGL(k_evl_batch_loss<W>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, site_loss, N, batch_size, batch_sum);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+// scratch of a label pass: the int64 scan (N + 1 entries) and one word per row; grown behind a stream synchronisation
+int label_scratch(nsnp_ctx* ctx, int64_t N, hipStream_t s, int64_t** scan, uint32_t** word)
+{
+    const size_t scan_bytes = (((size_t)N + 1) * sizeof(int64_t) + 15) & ~(size_t)15;
+    const size_t need = scan_bytes + (size_t)N * sizeof(uint32_t) + 16;
+    if (ctx->evl_tmp_bytes < need) {
+        NSNP_HIP(ctx, hipStreamSynchronize(s));
+        if (ctx->evl_tmp) (void)hipFree(ctx->evl_tmp);
+        ctx->evl_tmp = nullptr; ctx->evl_tmp_bytes = 0;
+        NSNP_HIP(ctx, hipMalloc(&ctx->evl_tmp, need + need / 4));
+        ctx->evl_tmp_bytes = need + need / 4;
+    }
+    *scan = (int64_t*)ctx->evl_tmp;
+    *word = (uint32_t*)((uint8_t*)ctx->evl_tmp + scan_bytes);
+    return NSNP_OK;
 }
 
 }  // namespace
@@ -297,17 +378,8 @@ extern "C" int nsnp_pileup_label_classes(nsnp_ctx* ctx, const int32_t* label, in
     if (!ctx || !meta || N < 0 || (N > 0 && (!label || !cls || !center_idx))) return NSNP_EINVAL;
     if (reinterpret_cast<uintptr_t>(cls) & 3) return NSNP_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const size_t scan_bytes = (((size_t)N + 1) * sizeof(int64_t) + 15) & ~(size_t)15;
-    const size_t need = scan_bytes + (size_t)N * sizeof(uint32_t) + 16;
-    if (ctx->evl_tmp_bytes < need) {
-        NSNP_HIP(ctx, hipStreamSynchronize(s));
-        if (ctx->evl_tmp) (void)hipFree(ctx->evl_tmp);
-        ctx->evl_tmp = nullptr; ctx->evl_tmp_bytes = 0;
-        NSNP_HIP(ctx, hipMalloc(&ctx->evl_tmp, need + need / 4));
-        ctx->evl_tmp_bytes = need + need / 4;
-    }
-    int64_t* scan = (int64_t*)ctx->evl_tmp;
-    uint32_t* word = (uint32_t*)((uint8_t*)ctx->evl_tmp + scan_bytes);
+    int64_t* scan; uint32_t* word;
+    if (const int rc = label_scratch(ctx, N, s, &scan, &word)) return rc;
     const unsigned grid = (unsigned)NSNP_CDIV(N, (int64_t)EVL_BLOCK);
     if (N > 0) hipLaunchKernelGGL(k_evl_flags, dim3(grid), dim3(EVL_BLOCK), 0, s, label, N, variants_only, scan, word);
     hipLaunchKernelGGL(k_evl_scan, dim3(1), dim3(1024), 0, s, scan, (const uint32_t*)word, N, meta);
@@ -320,12 +392,27 @@ extern "C" int nsnp_pileup_label_classes(nsnp_ctx* ctx, const int32_t* label, in
 
 extern "C" int nsnp_pileup_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream)
 {
-    if (!ctx || N < 0 || batch_size < 1 || (N > 0 && (!site_loss || !batch_sum))) return NSNP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(site_loss) & 15) return NSNP_EINVAL;
-    if (N == 0) return NSNP_OK;
-    const int64_t nb = NSNP_CDIV(N, batch_size);
-    if (nb > 0x7fffffffll) return NSNP_EINVAL;
-    hipLaunchKernelGGL(k_evl_batch_loss, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, site_loss, N, batch_size, batch_sum);
+    return batch_loss<4>(ctx, site_loss, N, batch_size, batch_sum, stream);
+}
+
+// ---- HaplotypeModel (include/nanosnp.h) --------------------------------------------------------
+extern "C" int nsnp_hap_label_classes(nsnp_ctx* ctx, const int32_t* label, int64_t N, uint8_t* cls, int64_t* rows, int64_t* meta, void* stream)
+{
+    if (!ctx || !meta || N < 0 || (N > 0 && (!label || !cls || !rows))) return NSNP_EINVAL;
+    int n_gt = 0, n_zy = 0;
+    if (const int rc = nsnp_hap_dims(ctx, &n_gt, &n_zy)) return rc;           // (what is scorable depends on the loaded heads)
+    hipStream_t s = (hipStream_t)stream;
+    int64_t* scan; uint32_t* word;
+    if (const int rc = label_scratch(ctx, N, s, &scan, &word)) return rc;
+    const unsigned grid = (unsigned)NSNP_CDIV(N, (int64_t)EVL_BLOCK);
+    if (N > 0) hipLaunchKernelGGL(k_hapl_flags, dim3(grid), dim3(EVL_BLOCK), 0, s, label, N, n_gt, n_zy, scan, word);
+    hipLaunchKernelGGL(k_evl_scan, dim3(1), dim3(1024), 0, s, scan, (const uint32_t*)word, N, meta);
+    if (N > 0) hipLaunchKernelGGL(k_hapl_compact, dim3(grid), dim3(EVL_BLOCK), 0, s, (const int64_t*)scan, (const uint32_t*)word, N, cls, rows);
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
+}
+
+extern "C" int nsnp_hap_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream)
+{
+    return batch_loss<2>(ctx, site_loss, N, batch_size, batch_sum, stream);
 }

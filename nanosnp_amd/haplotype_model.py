@@ -85,8 +85,7 @@ class LSTMNetwork:
         self._loaded = True
         return self
 
-    def predict(self, pileup_x, haplotype_x, stream=None):
-        """pileup_x [N,105,33], haplotype_x [N,105,11] cuda tensors (any float dtype: predict_dev.py:35-36 casts to float32)"""
+    def _inputs(self, pileup_x, haplotype_x):
         import torch
         if not self._loaded:
             raise _lib.NanoSNPError("weights not loaded")
@@ -97,6 +96,29 @@ class LSTMNetwork:
                              f"{tuple(pileup_x.shape)} and {tuple(haplotype_x.shape)}")
         if not (pileup_x.is_cuda and haplotype_x.is_cuda):
             raise _lib.NanoSNPError("inputs must live on the GPU (no CPU path)")
-        xp = pileup_x.to(torch.float32).contiguous()
-        xh = haplotype_x.to(torch.float32).contiguous()
+        return pileup_x.to(torch.float32).contiguous(), haplotype_x.to(torch.float32).contiguous()
+
+    def predict(self, pileup_x, haplotype_x, stream=None):
+        """pileup_x [N,105,33], haplotype_x [N,105,11] cuda tensors (any float dtype: predict_dev.py:35-36 casts to float32)"""
+        xp, xh = self._inputs(pileup_x, haplotype_x)
         return self.ctx.hap_forward(xp, xh, stream=stream)
+
+    def forward(self, pileup_x, haplotype_x, gt_target, zy_target, stream=None):
+        """``LSTMNetwork.forward`` (HaplotypeModel/model_dev.py:120-131), argument for argument: the inputs as predict takes them, the two
+        targets integer cuda tensors [N] -> (loss, gt_logits [N,n_gt], zy_logits [N,n_zy]).  loss = mean(gt) + mean(zy) of the two
+        label-smoothed losses (LabelSmoothingLoss(C, 0.1)) as an fp32 scalar tensor made from the float64 batch sum; NaN for N == 0
+        (torch.mean of nothing).  Runs under every hap_precision."""
+        import torch
+        xp, xh = self._inputs(pileup_x, haplotype_x)
+        n, d = int(xp.shape[0]), self.dims
+        cls = torch.stack([t.reshape(-1).to(device=xp.device, dtype=torch.uint8) for t in (gt_target, zy_target)], dim=1)
+        if tuple(cls.shape) != (n, 2):
+            raise ValueError(f"expected two targets of {n} classes")
+        counters = self.ctx.hap_eval_counters(xp.device)
+        site_loss, _, z = self.ctx.hap_eval(xp, xh, cls.contiguous(), counters, want_logits=True, stream=stream)
+        if n == 0:
+            loss = torch.full((), float("nan"), dtype=torch.float32, device=xp.device)
+        else:
+            s = self.ctx.hap_batch_loss(site_loss, n, stream=stream)[0]
+            loss = ((s[0] + s[1]) / n).to(torch.float32)
+        return loss, z[:, :d["gt_num_class"]], z[:, d["gt_num_class"]:]

@@ -475,15 +475,8 @@ HAP_PLANES = ("haplotype_sequences", "haplotype_hap", "haplotype_baseq", "haplot
               "pileup_sequences", "pileup_hap", "pileup_baseq", "pileup_mapq")
 
 
-def write_haplotype_bin(path, candidate_positions, haplotype_positions, planes: dict, max_haplotype_depth=None,
-                        max_pileup_depth=None, plane_dtype="int8"):
-    """planes: the eight padded integer arrays of write_to_bins.py (``haplotype_*`` [N,Dh,11], ``pileup_*`` [N,Dp,33], padding
-    -2).  Sites are sorted by the integer position of ``ctg:pos`` (write_to_bins.py:5-8; stable here) and depth is cut to
-    ``max_*_depth`` (:39-42,54-61).
-    plane_dtype: "int8" (default) stores the read planes as int8 when EVERY value of all eight fits (base codes -2..4, HP -2..3, base
-    qualities <= 93, mapping qualities <= 60 from minimap2: they do; a plane holding e.g. mapq 255 makes the whole file int32) - a
-    quarter of the file, of the bytes over PCIe and of the feature kernel's HBM reads, same features bit for bit
-    (nsnp_hap_features_i8); "int32" writes the reference's dtype (write_to_bins.py:44-47).  Readers accept both."""
+def _haplotype_arrays(candidate_positions, haplotype_positions, planes, max_haplotype_depth, max_pileup_depth, plane_dtype):
+    """-> (the arrays of a haplotype bin in file order, the stable position order they were permuted by)"""
     cand = [c if isinstance(c, str) else bytes(c).decode() for c in candidate_positions]
     n = len(cand)
     order = np.argsort(np.array([int(c.split(":")[1]) for c in cand], np.int64), kind="stable") if n else np.empty(0, np.int64)
@@ -514,6 +507,19 @@ def write_haplotype_bin(path, candidate_positions, haplotype_positions, planes: 
         for k, p in enumerate(hp[j]):
             b = p.encode(); hpa[i, k, :len(b)] = np.frombuffer(b, np.uint8)
     arrays["haplotype_positions"] = hpa
+    return arrays, order
+
+
+def write_haplotype_bin(path, candidate_positions, haplotype_positions, planes: dict, max_haplotype_depth=None,
+                        max_pileup_depth=None, plane_dtype="int8"):
+    """planes: the eight padded integer arrays of write_to_bins.py (``haplotype_*`` [N,Dh,11], ``pileup_*`` [N,Dp,33], padding
+    -2).  Sites are sorted by the integer position of ``ctg:pos`` (write_to_bins.py:5-8; stable here) and depth is cut to
+    ``max_*_depth`` (:39-42,54-61).
+    plane_dtype: "int8" (default) stores the read planes as int8 when EVERY value of all eight fits (base codes -2..4, HP -2..3, base
+    qualities <= 93, mapping qualities <= 60 from minimap2: they do; a plane holding e.g. mapq 255 makes the whole file int32) - a
+    quarter of the file, of the bytes over PCIe and of the feature kernel's HBM reads, same features bit for bit
+    (nsnp_hap_features_i8); "int32" writes the reference's dtype (write_to_bins.py:44-47).  Readers accept both."""
+    arrays, _ = _haplotype_arrays(candidate_positions, haplotype_positions, planes, max_haplotype_depth, max_pileup_depth, plane_dtype)
     write_arrays(path, arrays)
 
 
@@ -527,3 +533,40 @@ def read_haplotype_bin(path, mmap=True):
     cand = [dec(r) for r in np.asarray(a["candidate_positions"])]
     hpos = [[dec(p) for p in row] for row in np.asarray(a["haplotype_positions"])]
     return cand, hpos, {k: a[k] for k in HAP_PLANES}
+
+
+# ---- labelled haplotype bins (HaplotypeModel/make_train_bins.py) -------------------------------------------------------
+HAP_LABEL_WIDTH = 3               # make_train_bins.py:123-127,246,258: candidate_labels = {confident, gt21, zygosity} per site
+
+
+def _hap_label_rows(candidate_labels, n):
+    """any integer or float array [N,3] (the reference's is float64, cast by the PyTables Int32Atom) -> int32 [N,3]; a value that is not an
+    integer or lies outside int32 is refused instead of truncated"""
+    y = np.asarray(candidate_labels)
+    if y.dtype.kind not in "iuf" or y.shape != (n, HAP_LABEL_WIDTH):
+        raise SiteFileError(f"candidate_labels must hold numbers [N,{HAP_LABEL_WIDTH}] with one row per site")
+    if y.dtype.kind == "f":
+        if not np.all(np.isfinite(y)) or np.any(y != np.floor(y)):
+            raise SiteFileError("candidate_labels holds a value that is not an integer")
+    if y.size and (y.min() < np.iinfo(np.int32).min or y.max() > np.iinfo(np.int32).max):
+        raise SiteFileError("candidate_labels holds a value outside int32")
+    return np.ascontiguousarray(y.astype(np.int32))
+
+
+def write_haplotype_train_bin(path, candidate_positions, haplotype_positions, planes: dict, candidate_labels, max_haplotype_depth=None,
+                              max_pileup_depth=None, plane_dtype="int8"):
+    """write_haplotype_bin's arrays plus ``candidate_labels`` int32 [N,3] = {confident, gt21, zygosity} (make_train_bins.py:123-127,246,258),
+    permuted by the same stable position order as every other array.  The file stays a valid input of read_haplotype_bin, HapBinSource and
+    predict_haplotype_bins, which ignore the extra array."""
+    arrays, order = _haplotype_arrays(candidate_positions, haplotype_positions, planes, max_haplotype_depth, max_pileup_depth, plane_dtype)
+    arrays["candidate_labels"] = _hap_label_rows(candidate_labels, len(order))[order]
+    write_arrays(path, arrays)
+
+
+def read_haplotype_train_bin(path, mmap=True):
+    """-> (candidate_positions, haplotype_positions, planes, candidate_labels int32 [N,3]): read_haplotype_bin plus the labels"""
+    a = read_arrays(path, mmap)
+    y = a.get("candidate_labels")
+    if y is None or y.dtype != np.dtype(np.int32) or y.ndim != 2 or y.shape[1] != HAP_LABEL_WIDTH:
+        raise SiteFileError(f"{path}: not a labelled haplotype bin (no candidate_labels int32 [N,{HAP_LABEL_WIDTH}])")
+    return (*read_haplotype_bin(path, mmap), y)

@@ -202,3 +202,188 @@ def keep_thresholds(variants, non_variants, max_non_variant_ratio):
             thr.append(1 << 53)
             ratio.append(1.0)
     return thr, ratio
+
+
+# ---- HaplotypeModel: the per-contig truth table of get_truth.py and the label rows of make_train_bins.py ----------------------------
+class ContigTruth:
+    """One contig of get_truth.get_truth_variants (HaplotypeModel/get_truth.py:258-277), compact: the reference bytes (the non-variant
+    gt21 is a function of them), the confident marks as a bitmap (np.packbits, bit n = base index n) and the truth rows that landed on a
+    marked base as a sparse map - sorted 0-based indices with their gt21 and zygosity.  The reference keeps float64 [len, 3]."""
+    __slots__ = ("ref", "confident", "index", "gt21", "zygosity")
+
+    def __init__(self, ref):
+        self.ref = np.frombuffer(bytes(ref), np.uint8)
+        self.confident = np.zeros((self.ref.size + 7) // 8, np.uint8)
+        self.index, self.gt21, self.zygosity = np.empty(0, np.int64), np.empty(0, np.int32), np.empty(0, np.int32)
+
+    def __len__(self):
+        return int(self.ref.size)
+
+    def marked(self, idx):
+        idx = np.asarray(idx, np.int64)
+        return (self.confident[idx >> 3] >> (7 - (idx & 7)).astype(np.uint8)) & 1
+
+
+_NONVARIANT_GT21 = np.arange(256, dtype=np.int32)            # get_truth.py:267-270,273: A/a 0, C/c 4, G/g 7, T/t 9, any other byte its code
+for _b, _v in ((65, 0), (97, 0), (67, 4), (99, 4), (71, 7), (103, 7), (84, 9), (116, 9)):
+    _NONVARIANT_GT21[_b] = _v
+
+
+def _wrapped(i, n, what, line):
+    """index i of a numpy array of n rows as numpy reads it: [-n, -1] wraps round, anything else outside [0, n) raises"""
+    from ._lib import NanoSNPError
+    if i < -n or i >= n:
+        raise NanoSNPError(f"{what}: base index {i} outside a contig of {n} bases in {line[:200]!r}")
+    return i + n if i < 0 else i
+
+
+def haplotype_vcf_labels(columns, line=""):
+    """output_labels_from_vcf_columns (get_truth.py:219-239) of the tab-separated columns (str) of a VCF row -> (gt21, zygosity).  The
+    genotype is the LAST column in front of its first ':', '/' read as '|': exactly two integers (no '.', unlike the PileupModel's
+    splitter).  One ALT pairs with REF when a genotype is 0 and with itself otherwise; of more ALTs the first two count.  zygosity: 0/0 ->
+    0, equal -> 1, anything else -> 2 (1/2 counts as heterozygous).  NanoSNPError where the reference raises."""
+    from ._lib import NanoSNPError
+    try:
+        ref, alt = columns[3], columns[4]
+        g1, g2 = [int(v) for v in columns[-1].split(":")[0].replace("/", "|").split("|")]
+    except (ValueError, IndexError):
+        raise NanoSNPError(f"truth VCF: fewer than five columns or a genotype that is not two integers in {line[:200]!r}") from None
+    arr = alt.split(",")
+    if len(arr) == 1:
+        arr = [ref, alt] if (g1 == 0 or g2 == 0) else [alt, alt]
+    parts = []
+    for a in arr[:2]:
+        if len(ref) == len(a) and not a:
+            raise NanoSNPError(f"truth VCF: an empty allele in {line[:200]!r}")
+        parts.append("Del" if len(ref) > len(a) else "Ins" if len(ref) < len(a) else a[0])
+    name = _mix(parts[0], parts[1])
+    if name not in _GT21:
+        raise NanoSNPError(f"truth VCF: REF {ref!r} ALT {alt!r} gives {name!r}, which is no gt21 label, in {line[:200]!r}")
+    return _GT21[name], 0 if (g1 == 0 and g2 == 0) else 1 if g1 == g2 else 2
+
+
+def _text_lines(path_or_bytes):
+    return read_vcf(path_or_bytes).decode("latin-1").split("\n")
+
+
+def haplotype_truth_table(reference, confident_bed, truth_vcf, contigs=None):
+    """get_truth.get_truth_variants (HaplotypeModel/get_truth.py:258-277) -> {contig: ContigTruth}.
+
+    reference: a FASTA path (read as host.load_reference_file does; with a ``.fai`` beside it the contigs and their lengths are the index's,
+    get_truth.py:262-271) or a dict {contig: sequence}.  confident_bed, truth_vcf: paths (plain or gzip) or bytes.  contigs: keep only
+    these (BED and VCF lines of other contigs are passed over); None: every contig of the reference.
+
+    Quirks kept.  load_confident_bed (:118-126) marks 0-based index i - 1 for i in [start, end): a BED start is read as if it were 1-based,
+    and a start of 0 marks index -1, which numpy reads as the contig's LAST base.  load_truth_vcf (:242-255) passes over a row whose base is
+    not marked; a row on a marked base overwrites gt21 and zygosity, later rows win.  NanoSNPError with the line where the reference raises:
+    a contig absent from the reference, a BED line that is not three tab-separated columns of which the last two are integers, an index
+    outside the contig, a genotype that is not two integers, a pair of alleles that is no gt21 label."""
+    from . import host
+    from ._lib import NanoSNPError
+    if isinstance(reference, dict):
+        refs = {str(k): (v.encode() if isinstance(v, str) else bytes(v)) for k, v in reference.items()}
+    else:
+        refs = host.load_reference_file(reference)
+        fai = f"{os.fspath(reference)}.fai"
+        if os.path.exists(fai):
+            with open(fai) as f:
+                lens = {ln.strip().split("\t")[0]: int(ln.strip().split("\t")[1]) for ln in f if ln.strip()}
+            for c, n in lens.items():
+                if c not in refs or len(refs[c]) != n:
+                    raise NanoSNPError(f"{fai}: contig {c!r} of {n} bases is not in the FASTA with that length")
+            refs = {c: refs[c] for c in lens}
+    if contigs is not None:
+        want = [c if isinstance(c, str) else bytes(c).decode() for c in contigs]
+        missing = [c for c in want if c not in refs]
+        if missing:
+            raise NanoSNPError(f"contigs {missing[:4]} are not in the reference")
+        skip = set(refs) - set(want)
+        refs = {c: refs[c] for c in want}
+    else:
+        skip = set()
+    table = {c: ContigTruth(s) for c, s in refs.items()}
+    for line in _text_lines(confident_bed):
+        if not line:
+            continue
+        cols = line.strip().split("\t")
+        if cols and cols[0] in skip:
+            continue
+        try:
+            ctg, start, end = cols
+            start, end = int(start), int(end)
+        except ValueError:
+            raise NanoSNPError(f"confident BED: not three tab-separated columns with two integers in {line[:200]!r}") from None
+        if ctg not in table:
+            raise NanoSNPError(f"confident BED: contig {ctg!r} is not in the reference, in {line[:200]!r}")
+        t = table[ctg]
+        if end > start:
+            n = len(t)
+            idx = np.arange(start - 1, end - 1, dtype=np.int64)
+            if idx[0] < -n or idx[-1] >= n:
+                _wrapped(int(idx[0]) if idx[0] < -n else int(idx[-1]), n, "confident BED", line)
+            idx = np.where(idx < 0, idx + n, idx)
+            np.bitwise_or.at(t.confident, idx >> 3, (np.uint8(128) >> (idx & 7).astype(np.uint8)))
+    rows = {c: {} for c in table}
+    for line in _text_lines(truth_vcf):
+        if line.startswith("#") or not line:
+            continue
+        fields = line.strip().split("\t")
+        if fields[0] in skip:
+            continue
+        if fields[0] not in table:
+            raise NanoSNPError(f"truth VCF: contig {fields[0]!r} is not in the reference, in {line[:200]!r}")
+        t = table[fields[0]]
+        try:
+            pos = int(fields[1])
+        except (ValueError, IndexError):
+            raise NanoSNPError(f"truth VCF: no integer POS in {line[:200]!r}") from None
+        i = _wrapped(pos - 1, len(t), "truth VCF", line)
+        if not t.marked(i):
+            continue
+        rows[fields[0]][i] = haplotype_vcf_labels(fields, line)
+    for c, t in table.items():
+        if rows[c]:
+            t.index = np.array(sorted(rows[c]), np.int64)
+            t.gt21 = np.array([rows[c][i][0] for i in t.index.tolist()], np.int32)
+            t.zygosity = np.array([rows[c][i][1] for i in t.index.tolist()], np.int32)
+    return table
+
+
+def haplotype_label_rows(table, candidate_positions):
+    """The candidate_labels of make_train_bins.py:123-127: per "ctg:pos" the row [pos - 1] of the contig's truth array -> int32 [N,3] =
+    {confident, gt21, zygosity}.  A base no truth row overwrote has gt21 0 / 4 / 7 / 9 by its upper- or lower-case reference base, the
+    byte's ASCII code otherwise, and zygosity -1.  pos 0 reads index -1, the LAST base, as numpy does there.  table: haplotype_truth_table's
+    dict, or one ContigTruth for candidates of one contig (the reference hands one contig's array to its workers)."""
+    from ._lib import NanoSNPError
+    cand = [c if isinstance(c, str) else bytes(c).rstrip(b"\0").decode() for c in candidate_positions]
+    out = np.empty((len(cand), 3), np.int32)
+    by_ctg = {}
+    for n, c in enumerate(cand):
+        try:
+            ctg, p = c.split(":")
+            p = int(p)
+        except ValueError:
+            raise NanoSNPError(f"candidate position {c!r} is not 'ctg:pos'") from None
+        by_ctg.setdefault(ctg, ([], []))
+        by_ctg[ctg][0].append(n); by_ctg[ctg][1].append(p - 1)
+    for ctg, (rows, idx) in by_ctg.items():
+        if isinstance(table, ContigTruth):
+            t = table
+        elif ctg in table:
+            t = table[ctg]
+        else:
+            raise NanoSNPError(f"candidate contig {ctg!r} is not in the truth table")
+        n = len(t)
+        idx = np.array(idx, np.int64)
+        bad = np.flatnonzero((idx < -n) | (idx >= n))
+        if bad.size:
+            _wrapped(int(idx[bad[0]]), n, "candidate position", cand[rows[bad[0]]])
+        idx = np.where(idx < 0, idx + n, idx)
+        gt = _NONVARIANT_GT21[t.ref[idx]].copy()
+        zy = np.full(idx.size, -1, np.int32)
+        if t.index.size:
+            k = np.minimum(np.searchsorted(t.index, idx), t.index.size - 1)
+            hit = t.index[k] == idx
+            gt[hit] = t.gt21[k[hit]]; zy[hit] = t.zygosity[k[hit]]
+        out[rows, 0] = t.marked(idx); out[rows, 1] = gt; out[rows, 2] = zy
+    return out
