@@ -152,7 +152,8 @@ int nsnp_ctx_set_option(nsnp_ctx* ctx, const char* name, int64_t value);
  * internal pass with one event pair each: 6 the fused LSTM step launches of a HaplotypeModel pass (83 launches of
  * k_hap_gemm), 7 the convolution GEMM + pooling launches of a CatModel pass (12 + 4), 8 a whole CatModel pass;
  * `launches` then counts passes.  Id 9: the heads launch of a HaplotypeModel pass (the softmax heads of nsnp_hap_forward or the scoring
- * heads of nsnp_hap_eval).  Synchronous. */
+ * heads of nsnp_hap_eval).  Ids 10-12: the forward, backward and weight-gradient launches of a chunk of nsnp_pileup_loss_grad, one event
+ * pair per phase; `launches` counts chunks.  Synchronous. */
 int nsnp_ctx_enable_timing(nsnp_ctx* ctx, int enable);
 int nsnp_ctx_read_timing(nsnp_ctx* ctx, int kernel, double* total_ms, int64_t* launches);
 
@@ -525,6 +526,34 @@ int nsnp_pileup_eval_windows(nsnp_ctx* ctx, const int32_t* counts, const int64_t
 /* batch_sum[b,h] = the float64 sum of site_loss[n,h] over the rows n of batch b (rows b * batch_size ..), double [ceil(N / batch_size), 4]: one
  * workgroup per batch, a fixed tree - the same bits whatever the launch and the run.  The caller divides by the batch's size. */
 int nsnp_pileup_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream);
+
+/* ---- training the PileupModel: the loss gradients of a batch (PileupModel/train.py:56-59, model(...) and loss.backward()) ---------------
+ * fp32 only and one device: with pileup_precision 1 or 2 nsnp_pileup_loss_grad returns NSNP_EINVAL.  The entries need no
+ * nsnp_pileup_load_weights: the parameters are the caller's device tensors in plain state-dict layout, because they change every step; the
+ * packed images of the inference entries are not read and not refreshed (upload a trained state again to score or call with it).
+ *
+ * nsnp_pileup_train_reserve allocates the workspace of the saved activations and gate gradients, about 194 KB per site (rounded up to 16
+ * sites) plus 128 KB per 1,024 (site, step) rows; synchronous.  NSNP_ENOMEM: the previous reservation stays in force.  A batch larger than
+ * the reservation runs in chunks of that size, in order, adding into the same gradients.
+ *
+ * nsnp_pileup_loss_grad, asynchronous on `stream`:
+ *   params     HOST array of 24 DEVICE pointers, the tensors, order and shapes of nsnp_pileup_load_weights
+ *   counts, center_idx, cls   as nsnp_pileup_eval_windows takes them (center_idx NULL: counts is [N,33,18]); cls uint8 [N,4], columns 0
+ *              (genotype) and 1 (zygosity) used, a class outside its head counts as the head's last
+ *   keep_mask  NULL (no dropout), or device uint8 [N,33,128] of 0 / 1 in h0's order [forward 64 | reverse 64]: layer 1 sees
+ *              h0 * keep_mask * keep_scale (keep_scale = 1 / (1 - p) of nn.LSTM(dropout=p)), the backward pass applies the same factor
+ *   grads      HOST array of 24 device pointers, same shapes: OVERWRITTEN with d(mean gt loss + mean zy loss) / d(param), the means over all
+ *              N sites.  bias_ih and bias_hh of a layer and direction receive the same values.  The indel heads are not in the loss.
+ *   site_loss  NULL, or device fp32 [N,2]: the label-smoothed losses of nsnp_pileup_eval_windows, genotype and zygosity
+ *   pred       NULL, or device uint8 [N,2]: the first maximum of the genotype / zygosity logits
+ * N == 0 is a no-op (grads untouched).  NSNP_EINVAL for null arguments and without a reservation.  The network runs the reduced schedule
+ * of the inference entries (layer 1: 17 steps per direction, dense layers and heads at position 16), which is exact for the gradient too
+ * because the loss reads position 16 only.  Every matrix product is fp32 MFMA; no floating-point atomics: the same call gives the same
+ * bits twice.  nsnp_ctx_read_timing ids 10, 11, 12: the forward, backward and weight-gradient phases of a chunk, one event pair each. */
+int nsnp_pileup_train_reserve(nsnp_ctx* ctx, int64_t max_sites);
+int nsnp_pileup_loss_grad(nsnp_ctx* ctx, const float* const* params, const int32_t* counts, const int64_t* center_idx, const uint8_t* cls,
+                          int64_t N, const uint8_t* keep_mask, float keep_scale, float* const* grads, float* site_loss, uint8_t* pred,
+                          void* stream);
 
 /* ---- HaplotypeModel ------------------------------------------------------------------- */
 /* seq/bq/mq/hap: device int32 [N,D,L] planes as write_to_bins.py:44-61 stores them (padding

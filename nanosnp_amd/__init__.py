@@ -3,7 +3,7 @@
 The compute path is the HIP library behind include/nanosnp.h (``nanosnp_amd/_lib.py`` binds it);
 this package holds only the host-side mirror of the reference's interface for that path:
 
-    pileup_model.LSTMNetwork     PileupModel/model.py LSTMNetwork (predict; forward with its loss, no backward)
+    pileup_model.LSTMNetwork     PileupModel/model.py LSTMNetwork (predict; forward with its loss; the backward pass is train.PileupTrainer's)
     haplotype_model.LSTMNetwork  HaplotypeModel/model_dev.py LSTMNetwork (predict only)
     cat_model.CatModel           HaplotypeModel/model.py CatModel, the legacy path (predict only)
     pipeline                     mpileup text -> column encode -> windows -> PileupModel -> pileup.vcf in one pass
@@ -12,6 +12,8 @@ this package holds only the host-side mirror of the reference's interface for th
                                  (PileupModel/predict.py + dataset.py PredictDataset behind a DataLoader)
     evaluate                     <chr>.td.bin training window files -> loss, accuracies, confusion matrices of a checkpoint
                                  (PileupModel/train.py eval() + dataset.py TrainDataset(for_evaluate=True))
+    train                        <chr>.td.bin training window files -> one epoch of gradient steps on the PileupModel; the loss gradients
+                                 of a batch are one C-ABI call (PileupModel/train.py train() + model forward / loss.backward())
     hap_pipeline                 haplotype site files -> pinned staging / H2D / features + HaplotypeModel -> haplotype.csv, streamed
                                  (HaplotypeModel/predict_dev.py + dataset_dev.py TestDataset behind a DataLoader)
     predict                      PileupModel/predict.py / HaplotypeModel/predict_dev.py loops on arrays

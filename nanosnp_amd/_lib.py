@@ -83,6 +83,9 @@ _SIGNATURES = {
     "nsnp_pileup_forward_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_eval_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
     "nsnp_pileup_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_train_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
+    "nsnp_pileup_loss_grad": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
+                                        C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_mpileup_tokenise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
     "nsnp_mpileup_tokenise_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 5 + [C.c_void_p] * 9),
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -326,7 +329,7 @@ class Context:
 
     # ids of nsnp_ctx_read_timing; the last three are ONE event pair around a chain of launches of a pass (include/nanosnp.h)
     KERNELS = ("pileup_l0", "pileup_proj1", "pileup_l1", "pileup_head", "encode_columns", "hap_features",
-               "hap_lstm_chain", "cat_conv_chain", "cat_forward_pass", "hap_head")
+               "hap_lstm_chain", "cat_conv_chain", "cat_forward_pass", "hap_head", "train_forward", "train_backward", "train_wgrad")
 
     def enable_timing(self, enable=True):
         check(self.lib.nsnp_ctx_enable_timing(self.handle, int(bool(enable))), self.handle, "nsnp_ctx_enable_timing")
@@ -1078,6 +1081,49 @@ class Context:
         check(self.lib.nsnp_pileup_batch_loss(self.handle, _dptr(site_loss), n, int(batch_size), _dptr(out), _stream_ptr(stream)),
               self.handle, "nsnp_pileup_batch_loss")
         return out
+
+    # ---- training (include/nanosnp.h; fp32 only) ----
+    TRAIN_SHAPES = ([(256, 18), (256, 64), (256,), (256,)] * 2 + [(256, 128), (256, 64), (256,), (256,)] * 2 +
+                    [(128, 128), (128,), (256, 128), (256,), (21, 256), (21,), (3, 256), (3,)])        # the 24 tensors of pileup_load_weights
+
+    def pileup_train_reserve(self, max_sites):
+        """workspace of pileup_loss_grad for chunks of max_sites sites (about 194 KB per site); synchronous"""
+        check(self.lib.nsnp_pileup_train_reserve(self.handle, int(max_sites)), self.handle, "nsnp_pileup_train_reserve")
+
+    def _train_tensors(self, tensors, what):
+        import torch
+        if len(tensors) != 24:
+            raise NanoSNPError(f"loss_grad: expected 24 {what}, got {len(tensors)}")
+        for t, shape in zip(tensors, self.TRAIN_SHAPES):
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise NanoSNPError(f"loss_grad: {what} must be contiguous device fp32 tensors in state-dict shapes, got {tuple(t.shape)} for {shape}")
+        return (C.c_void_p * 24)(*[t.data_ptr() for t in tensors])
+
+    def pileup_loss_grad(self, params, counts, center_idx, cls, grads, keep_mask=None, keep_scale=1.0, n=None, site_loss=None, pred=None,
+                         stream=None):
+        """forward, label-smoothed loss and backward of a batch: grads (24 device fp32 tensors in the shapes of params) are OVERWRITTEN with
+        d(mean gt + mean zy) / d(param) -> (site_loss fp32 [n,2], pred uint8 [n,2]).  params: the 24 device tensors in state-dict order;
+        cls: device uint8 [>= n, 4]; keep_mask: None or device uint8 [n,33,128], layer 1 sees h0 * keep_mask * keep_scale; n: the sites to
+        run (default: all of center_idx / counts).  Needs pileup_train_reserve; a larger batch runs in chunks of the reservation."""
+        import torch
+        n_all = self._eval_inputs(counts, center_idx, "loss_grad")
+        n = n_all if n is None else int(n)
+        dev = counts.device
+        if n < 0 or n > n_all or cls.dtype != torch.uint8 or cls.numel() < 4 * n or not cls.is_cuda or not cls.is_contiguous():
+            raise NanoSNPError("loss_grad: cls uint8 [N,4] on the device, one row per site")
+        pp, gp = self._train_tensors(params, "parameters"), self._train_tensors(grads, "gradients")
+        if keep_mask is not None and (keep_mask.dtype != torch.uint8 or not keep_mask.is_cuda or not keep_mask.is_contiguous()
+                                      or keep_mask.numel() < n * 33 * 128 or (keep_mask.dim() == 3 and tuple(keep_mask.shape[1:]) != (33, 128))):
+            raise NanoSNPError("loss_grad: keep_mask uint8 [N,33,128] on the device")
+        site_loss = site_loss if site_loss is not None else torch.empty((n, 2), dtype=torch.float32, device=dev)
+        pred = pred if pred is not None else torch.empty((n, 2), dtype=torch.uint8, device=dev)
+        if (site_loss.dtype != torch.float32 or site_loss.numel() < 2 * n or not site_loss.is_cuda or not site_loss.is_contiguous()
+                or pred.dtype != torch.uint8 or pred.numel() < 2 * n or not pred.is_cuda or not pred.is_contiguous()):
+            raise NanoSNPError("loss_grad: site_loss fp32 [N,2] and pred uint8 [N,2] on the device")
+        check(self.lib.nsnp_pileup_loss_grad(self.handle, pp, _dptr(counts), _dptr(center_idx), _dptr(cls), n, _dptr(keep_mask),
+                                             float(keep_scale), gp, _dptr(site_loss), _dptr(pred), _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_loss_grad")
+        return site_loss, pred
 
     def pileup_gather_windows(self, counts, center_idx, stream=None):
         import torch

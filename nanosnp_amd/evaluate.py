@@ -3,8 +3,8 @@
 ``evaluate_train_bins`` reads the files pipeline.mpileup_to_train_bins / sitefile.td_to_bin write, keeps the variant sites as
 ``TrainDataset(for_evaluate=True)`` does (dataset.py:98-104), runs the forward with all four heads and the label-smoothed loss
 (model.py:97-112, optim.py:137-144) and returns what eval() accumulates: the loss, the accuracies and the confusion matrices of genotype
-and zygosity - plus those of the two indel heads, which eval() computes logits for and then ignores.  Training itself is out of scope
-(DESIGN.md section 9): this is inference with labels attached.  fp32 only.
+and zygosity - plus those of the two indel heads, which eval() computes logits for and then ignores.  Training is nanosnp_amd.train's:
+this is inference with labels attached.  fp32 only.
 
 ``evaluate_haplotype_bins`` is the HaplotypeModel's counterpart, ``eval()`` of HaplotypeModel/evaluate_dev.py:16-86 over labelled haplotype
 site files (sitefile.write_haplotype_train_bin), under every ``hap_precision``.
