@@ -127,7 +127,10 @@ int nsnp_ctx_reserve(nsnp_ctx* ctx, int64_t max_sites);
  *   16-site workgroups; "l0_site_groups" and "l0_input_weights_in_lds" shape the kernels of 1 only) | 1 | 0 (the fp32-MFMA
  *   kernels, bit-identical to each other), "l0_weave" 1 (default) | 0 (the kernel of "l0_register_stationary" 2 with the step
  *   software-pipelined - the next step's count projection is issued under this step's cell, in front of the barrier;
- *   bit-identical to 0, accepted and ignored elsewhere), "l1_register_stationary" 1 four waves x four gate
+ *   bit-identical to 0, accepted and ignored elsewhere), "l0_prestage" 1 (default) | 0 (the kernel of "l0_weave" 1 with the
+ *   workgroup's 16 windows converted once to a read-only LDS image in front of the step loop, and the loop without staging; a
+ *   workgroup with a count beyond +-256 runs the loop of 0; bit-identical to 0, accepted and ignored where
+ *   "l0_register_stationary" is not 2 or "l0_weave" is 0; any other value returns NSNP_EINVAL), "l1_register_stationary" 1 four waves x four gate
  *   tiles (default) | 2 eight waves x two tiles | 0 LDS-image kernels with the Xp1 round trip, "l1_site_groups" 0 | 1 | 2 | 4,
  *   "l1_stagger" 0 (default) | 1 (eight-wave kernel: waves 4-7 issue a group's next input part ahead of its cell),
  *   "l1_weave" 1 (default) | 0 (four-wave kernel, one site group: the step software-pipelined - the next step's input projection

@@ -52,6 +52,7 @@ extern "C" int nsnp_ctx_create(int device, nsnp_ctx** out)
     ctx->fused_l1 = 1;
     ctx->l0_rs = 2;             // fp32 layer 0 with the exact bf16 input block (k_pileup_l0_rsx); the other modes treat 2 as 1
     ctx->l0_weave = 1;          // fp32 layer 0 software-pipelined (k_pileup_l0_rsxw): measured on the headline in docs/rounds/r21.md
+    ctx->l0_prestage = 1;       // fp32 layer 0 with the whole window staged once (k_pileup_l0_rsxp): docs/rounds/r24.md
     ctx->l1_rs = 1;
     ctx->l1_stagger = 0;
     ctx->l1_weave = 1;          // fp32 layer 1 software-pipelined (k_pileup_l1_rs4w): measured on the headline in docs/rounds/r19.md
@@ -188,6 +189,11 @@ extern "C" int nsnp_ctx_set_option(nsnp_ctx* ctx, const char* name, int64_t valu
     if (strcmp(name, "l0_weave") == 0) {
         if (value != 0 && value != 1) return NSNP_EINVAL;
         ctx->l0_weave = (int)value;
+        return NSNP_OK;
+    }
+    if (strcmp(name, "l0_prestage") == 0) {
+        if (value != 0 && value != 1) return NSNP_EINVAL;
+        ctx->l0_prestage = (int)value;
         return NSNP_OK;
     }
     if (strcmp(name, "l1_site_groups") == 0) {

@@ -120,6 +120,7 @@ struct nsnp_ctx {
     int head_rs;        // fp32 heads: 1 = output tiles split over the 8 waves of a workgroup, weights in VGPRs (default); 0 = one wave per 16 sites
     int l1_stagger;     // fp32 register-stationary layer 1: waves 4-7 run a group's next-step input part ahead of its cell (default 0)
     int l0_weave;       // fp32 layer 0 at l0_rs 2: the next step's count projection is issued under this step's cell, in front of the barrier (k_pileup_l0_rsxw)
+    int l0_prestage;    // fp32 layer 0 at l0_rs 2, l0_weave 1: the workgroup's windows staged once in front of the step loop (k_pileup_l0_rsxp)
     int l1_weave;       // fp32 four-wave layer 1, one site group: the cell runs in the MFMA gaps of the next step's input projection (k_pileup_l1_rs4w)
     // workspace (sized by nsnp_ctx_reserve)
     int64_t chunk_sites;

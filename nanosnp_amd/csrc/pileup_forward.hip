@@ -810,8 +810,26 @@ constexpr int rsxw_mfmas_upto(int gap_t, int gap_v, int first, int nm, int last)
     return m;
 }
 
-template <int GAP_T, int GAP_V, int GAP_FIRST, bool LATE_W0>
-__global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
+//
+// K1xp: K1xw with the input staging taken out of the step loop ("l0_prestage" 1, docs/rounds/r24.md).  Nothing the staging does
+// depends on the recurrence, so the prologue does it once for all 33 steps: the 256 threads read the workgroup's 16 windows (2,376
+// contiguous bytes a site, as 8-byte pieces: a window starts 8-byte aligned and no byte outside it is read), convert the counts to
+// bf16 and write the read-only LDS image [t 33][quarter 3][site 16][8 bf16] - K1x's B-fragment layout by window position, K
+// position 18 the constant 1, 19..23 zero; quarter 3 (K 24..31) is zero for every step and is a register constant of the lanes
+// q = 3, which never read the image.  Every thread ORs "some |count| > 256" over its pieces; one word per wave, published by the
+// barrier that publishes the image, makes it a workgroup-uniform bit, and the choice between two loops is made once:
+//   clear (every pileup: the depth cap is 144)  the fast loop: K1xw's level-0 step with the same placement, in which plane 0 of
+//          step s+1 is one ds_read_b128 from the image at tpos(s+1) where K1xw reads its staged buffer - no global load, no range
+//          test, no conversion, no ds_write of x, no split level, no side block
+//   set    K1xw's own prologue and step loop (per-step staging from global memory, split levels 0/1/2), the image unused
+// Both loops are instantiations of the one step body below (FAST), and a fast step is the arithmetic of a level-0 step of K1xw:
+// the bits are K1xw's (tests/test_gpu_l0_prestage.py).
+constexpr int RXP_IMAGE = PW * 3 * 16 * 8;    // bf16 of the window image
+// hx[3], xx, xlvl (K1xw's 20,000 bytes), the image and the wave words
+static_assert(3 * 16 * RS_XROW * 4 + 2 * 3 * RX_PLANE * 2 + 32 + RXP_IMAGE * 2 + 16 + 64 <= 160 * 1024 / 3, "three workgroups in a CU's 160 KB of LDS");
+
+template <int GAP_T, int GAP_V, int GAP_FIRST, bool LATE_W0, bool PRESTAGE>
+__device__ __forceinline__ void pileup_l0_rsxw_body(
     const int32_t* __restrict__ x, const int64_t* __restrict__ center_idx, int64_t N,
     const float* __restrict__ whh0, const float* __restrict__ whh1,
     const __bf16* __restrict__ wx0, const __bf16* __restrict__ wx1,
@@ -822,12 +840,15 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
     // hx[2]: the staging threads' 64-bit element offsets at t = 0 (contiguous windows and center_idx alike: no register holds an
     // offset).  Thread tid keeps its offset at the position of its flush chunk in an exchange buffer, so that ONE address register
     // serves the flush and the window loads
-    __shared__ __attribute__((aligned(16))) float hx[3][16][RS_XROW];
-    __shared__ __attribute__((aligned(16))) __bf16 xx[2][3][RX_PLANE];
-    __shared__ __attribute__((aligned(16))) int xlvl[2][4];             // [buf][staging wave]: split level
+    // (K1xp: the larger alignment places these three in front of the image, at the offsets they have in K1xw: with the image in
+    // front the per-step staging loop needs more address registers than there are)
+    constexpr int LDS_ALIGN = PRESTAGE ? 64 : 16;
+    __shared__ __attribute__((aligned(LDS_ALIGN))) float hx[3][16][RS_XROW];
+    __shared__ __attribute__((aligned(LDS_ALIGN))) __bf16 xx[2][3][RX_PLANE];
+    __shared__ __attribute__((aligned(LDS_ALIGN))) int xlvl[2][4];      // [buf][staging wave]: split level
     const int dir = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 15, q = lane >> 4;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int lane = tid & 63, n = lane & 15, q = lane >> 4;                  // (not const: K1xp's fast loop derives its own)
     NSNP_DEVCLK_START
     const int64_t base_site = (int64_t)blockIdx.x * 16;
     const int nrows = (int)min((int64_t)16, N - base_site);
@@ -835,9 +856,9 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
     // ---- weights, x staging and the H0 flush: K1x's ----
     f32x4 Whh[4][4];
     b8 Wx[4][3];
-    {
-        const f32x4* __restrict__ ghh = reinterpret_cast<const f32x4*>(dir ? whh1 : whh0);     // [tile][j4 4][lane]
-        const b8* __restrict__ gx = reinterpret_cast<const b8*>(dir ? wx1 : wx0);              // [tile][plane 3][lane]
+    const f32x4* __restrict__ ghh = reinterpret_cast<const f32x4*>(dir ? whh1 : whh0);         // [tile][j4 4][lane]
+    const b8* __restrict__ gx = reinterpret_cast<const b8*>(dir ? wx1 : wx0);                  // [tile][plane 3][lane]
+    if constexpr (!PRESTAGE) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
 #pragma unroll
@@ -850,12 +871,66 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
     const int xrow = min(wave < 2 ? lane >> 2 : n, nrows - 1);          // (rows past N restage the last site: never stored)
     const int piece = wave < 2 ? 4 * wave + (lane & 3) : 8;
     const int xdst = wave < 2 ? 128 * wave + 2 * lane : 256 + 8 * n;    // K position 2 piece of the staged row
-    const int frow = tid >> 4, fcid = tid & 15;
-    float* const fl = &hx[0][frow][16 * (fcid & 3) + 4 * (fcid >> 2)];
+    int frow = tid >> 4, fcid = tid & 15;
+    float* fl = &hx[0][frow][16 * (fcid & 3) + 4 * (fcid >> 2)];
     int64_t* const xofs = reinterpret_cast<int64_t*>(fl + 2 * 16 * RS_XROW);
-    if (xon) *xofs = (center_idx ? (center_idx[base_site + xrow] - PCENTER) * PC : (base_site + xrow) * (PW * PC)) + 2 * piece;
     int2 xi = int2{0, 0};
     auto tpos = [&](int u) { return dir ? PW - 1 - u : u; };
+
+    // ---- K1xp: the window image and the workgroup's "some count beyond +-256" bit ----
+    // Thread (row = tid / 16, k = tid % 16) moves pieces k, k + 16, .. of its site's 297 (piece p = channels 2 (p % 9), + 1 of
+    // window position p / 9): pieces 0..7 of a position are bf16 pairs of quarters 0 and 1, piece 8 writes the whole 16-byte row
+    // of quarter 2 (its two counts, the constant 1, five zeros), so the image needs no clearing.  Rows past N restage the last site.
+    // Order: the 19 window loads, the W_hh loads, the image (which releases the window's registers), the input-block loads - all
+    // of them at once would not fit in 168 registers.
+    const __bf16* ximg0 = nullptr, * ximg = nullptr;                    // the image; this lane's fragment of window position 0
+    bool fast = false;
+    if constexpr (PRESTAGE) {
+        __shared__ __attribute__((aligned(16))) __bf16 img[RXP_IMAGE];
+        __shared__ __attribute__((aligned(16))) int wbig[4];            // [wave]: some count beyond +-256
+        const int prow = min(frow, nrows - 1);
+        const int2* const src = reinterpret_cast<const int2*>(
+            x + (center_idx ? (center_idx[base_site + prow] - PCENTER) * PC : (base_site + prow) * (PW * PC)));
+        constexpr int NP = (PW * 9 + 15) / 16;
+        int2 wv[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int p = fcid + 16 * i;
+            wv[i] = (16 * i + 15 < PW * 9 || p < PW * 9) ? src[p] : int2{0, 0};
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) Whh[u][j] = ghh[((4 * wave + u) * 4 + j) * 64 + lane];
+        __builtin_amdgcn_sched_barrier(0);
+        bool big = false;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int p = fcid + 16 * i;
+            if (16 * i + 15 < PW * 9 || p < PW * 9) {
+                const int2 v = wv[i];
+                const int pt = p / 9, pc = p - 9 * pt;
+                big |= (unsigned)v.x + 256u > 512u || (unsigned)v.y + 256u > 512u;
+                const b2 cv = __builtin_convertvector(f32x2{(float)v.x, (float)v.y}, b2);      // exact where the image is used: |c| <= 256
+                __bf16* const d = &img[(pt * 3 + (pc >> 2)) * 128 + frow * 8];
+                if (pc < 8) *reinterpret_cast<b2*>(d + 2 * (pc & 3)) = cv;
+                else        *reinterpret_cast<b8*>(d) = b8{cv[0], cv[1], (__bf16)1.0f, 0, 0, 0, 0, 0};
+            }
+        }
+        const bool wave_big = __ballot(big) != 0ull;
+        if (lane == 0) wbig[wave] = wave_big;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) Wx[u][p] = gx[((4 * wave + u) * 3 + p) * 64 + lane];
+        lds_barrier();
+        const i32x4 wb = *reinterpret_cast<const i32x4*>(wbig);
+        fast = __builtin_amdgcn_readfirstlane(wb[0] | wb[1] | wb[2] | wb[3]) == 0;
+        ximg0 = img;
+    }
+    bool qimg = q < 3;                                                  // (K 24..31: lanes q = 3 keep a zero fragment)
     auto load_x = [&](int t) {
         if (!xon) return;
         xi = *reinterpret_cast<const int2*>(x + *xofs + t * PC);
@@ -881,14 +956,18 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
             stage_x_split(d, &xlvl[buf][wave]);
         }
     };
-    for (int i = tid; i < 2 * 3 * RX_PLANE / 8; i += 256) reinterpret_cast<b8*>(&xx[0][0][0])[i] = b8{0, 0, 0, 0, 0, 0, 0, 0};
-    if (tid < 8) xlvl[tid >> 2][tid & 3] = 0;
-    __syncthreads();
-    if (tid < 32) xx[tid >> 4][0][2 * 128 + (tid & 15) * 8 + 2] = (__bf16)1.0f;
-    load_x(tpos(0)); stage_x(0);
-    load_x(tpos(1)); stage_x(1);
-    load_x(tpos(2));
-    __syncthreads();
+    // per-step staging (K1xw, and K1xp with a count beyond +-256): x of steps 0 and 1 staged, step 2 loaded
+    auto stage_prologue = [&]() __attribute__((always_inline)) {
+        if (xon) *xofs = (center_idx ? (center_idx[base_site + xrow] - PCENTER) * PC : (base_site + xrow) * (PW * PC)) + 2 * piece;
+        for (int i = tid; i < 2 * 3 * RX_PLANE / 8; i += 256) reinterpret_cast<b8*>(&xx[0][0][0])[i] = b8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (tid < 8) xlvl[tid >> 2][tid & 3] = 0;
+        __syncthreads();
+        if (tid < 32) xx[tid >> 4][0][2 * 128 + (tid & 15) * 8 + 2] = (__bf16)1.0f;
+        load_x(tpos(0)); stage_x(0);
+        load_x(tpos(1)); stage_x(1);
+        load_x(tpos(2));
+        __syncthreads();
+    };
 
     float c[4];
 #pragma unroll
@@ -896,7 +975,7 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
 
     float* const h0wg = H0 + (base_site * PW * 2 + dir) * 64;
     unsigned foff = (unsigned)(frow * (PW * 128) + 4 * fcid) * 4u;
-    const bool fon = frow < nrows;
+    bool fon = frow < nrows;
     auto flush_h = [&](int buf, int t) {
         asm volatile("" : "+v"(foff));
         if (fon)
@@ -937,18 +1016,15 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
         else                               project_block(buf, xb0, acc, std::integral_constant<int, 2>{});
     };
 
+    // K1xp's fast loop: plane 0 of window position t, one ds_read_b128 from the image
+    auto read_image = [&](int t, b8& xb0) __attribute__((always_inline)) {
+        if (qimg) xb0 = *reinterpret_cast<const b8*>(ximg + t * (3 * 128));
+    };
+
     f32x4 acc[4];
     b8 xb;                                                              // plane 0 of the step acc holds (read again behind the barrier under LATE_W0)
-    {
-        int lvl0;
-        read_x(0, xb, lvl0);
-        project_any(0, xb, lvl0, acc);
-    }
-    // step 0 stores x of step 2 over that of step 0: every wave must have read it
-    lds_barrier();
-
-    auto step = [&](int s, auto first_tag, auto last_tag) __attribute__((always_inline)) {
-        constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
+    auto step = [&](int s, auto first_tag, auto last_tag, auto fast_tag) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value, FAST = decltype(fast_tag)::value;
         const int t = tpos(s);
         const int cur = s & 1;
         const float* hr = &hx[cur ^ 1][n][4 * q];
@@ -961,8 +1037,10 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
             __builtin_amdgcn_sched_barrier(0);
         }
         int lvln = 0;
-        if constexpr (FIRST) read_x(cur ^ 1, xb, lvln);
-        else {
+        if constexpr (FIRST) {
+            if constexpr (FAST) read_image(tpos(s + 1), xb);
+            else read_x(cur ^ 1, xb, lvln);
+        } else {
             // recurrent B fragments one K block ahead of their MFMAs, two in flight, as in K1r.  acc is live across the barrier
             // here, so plane 0 of step s+1 is read once K block 0 has released its fragment, and h[s-1] leaves for H0 through the
             // registers K block 2 releases
@@ -976,7 +1054,10 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
             RSXW_KBLOCK(1, hb1)
             __builtin_amdgcn_sched_barrier(0);
             hb1 = *reinterpret_cast<const f32x4*>(hr + 48);
-            if constexpr (!LAST) read_x(cur ^ 1, xb, lvln);
+            if constexpr (!LAST) {
+                if constexpr (FAST) read_image(tpos(s + 1), xb);
+                else read_x(cur ^ 1, xb, lvln);
+            }
             RSXW_KBLOCK(2, hb0)
             __builtin_amdgcn_sched_barrier(0);
             flush_h(cur ^ 1, dir ? t + 1 : t - 1);
@@ -1017,23 +1098,78 @@ __global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
         // counts beyond +-256 in step s+1 (no pileup has them): the burst above held plane 0 only, so its sums are dropped and the
         // step's 24 / 36 MFMAs run as one block from zero.  (A second copy of the cell in this branch, in one piece in front of the
         // block, costs the kernel its registers: docs/rounds/r21.md)
-        if constexpr (!LAST) {
+        if constexpr (!LAST && !FAST) {
             if (__builtin_expect(lvln != 0, 0)) {
                 if (lvln == 1) project_block(cur ^ 1, xb, acc, std::integral_constant<int, 1>{});
                 else           project_block(cur ^ 1, xb, acc, std::integral_constant<int, 2>{});
             }
         }
-        if constexpr (!LAST) {
+        if constexpr (!LAST && !FAST) {
             stage_x(cur);                                               // x of step s+2 over that of step s
             load_x(tpos(s + 3 < PW ? s + 3 : PW - 1));
         }
         lds_barrier();
     };
-    step(0, std::true_type{}, std::false_type{});
-    for (int s = 1; s < PW - 1; ++s) step(s, std::false_type{}, std::false_type{});
-    step(PW - 1, std::false_type{}, std::true_type{});
-    flush_h((PW - 1) & 1, dir ? 0 : PW - 1);
+    // the prologue's projection of step 0 and the 33 steps, per-step staging or the image: chosen once
+    auto run = [&](auto fast_tag) __attribute__((always_inline)) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        if constexpr (FAST) {
+            // The two loops are siblings under a uniform branch, but with the lane-dependent branches inside them the compiler
+            // lays them out one behind the other, and whatever the second needs of the lane's position would stay live through
+            // the first, which has no register to spare.  So the fast loop derives its lane values again, from the lane's number in
+            // the wave.
+            const int tid2 = 64 * wave + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            lane = tid2 & 63; n = lane & 15; q = lane >> 4;
+            frow = tid2 >> 4; fcid = tid2 & 15;
+            fl = &hx[0][frow][16 * (fcid & 3) + 4 * (fcid >> 2)];
+            foff = (unsigned)(frow * (PW * 128) + 4 * fcid) * 4u;
+            fon = frow < nrows;
+            qimg = q < 3;
+            ximg = ximg0 + q * 128 + n * 8;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xb[j] = (__bf16)0.0f;                // (lanes q = 3 keep it)
+            read_image(tpos(0), xb);
+            project_block(0, xb, acc, std::integral_constant<int, 0>{});
+        } else {
+            stage_prologue();
+            int lvl0;
+            read_x(0, xb, lvl0);
+            project_any(0, xb, lvl0, acc);
+            // step 0 stores x of step 2 over that of step 0: every wave must have read it
+            lds_barrier();
+        }
+        step(0, std::true_type{}, std::false_type{}, fast_tag);
+        for (int s = 1; s < PW - 1; ++s) step(s, std::false_type{}, std::false_type{}, fast_tag);
+        step(PW - 1, std::false_type{}, std::true_type{}, fast_tag);
+        flush_h((PW - 1) & 1, dir ? 0 : PW - 1);
+    };
+    if constexpr (PRESTAGE) {
+        if (__builtin_expect(fast, 1)) run(std::true_type{});
+        else      run(std::false_type{});
+    } else {
+        run(std::false_type{});
+    }
     NSNP_DEVCLK_STOP(0)
+}
+
+template <int GAP_T, int GAP_V, int GAP_FIRST, bool LATE_W0>
+__global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxw(
+    const int32_t* __restrict__ x, const int64_t* __restrict__ center_idx, int64_t N,
+    const float* __restrict__ whh0, const float* __restrict__ whh1,
+    const __bf16* __restrict__ wx0, const __bf16* __restrict__ wx1,
+    float* __restrict__ H0)
+{
+    pileup_l0_rsxw_body<GAP_T, GAP_V, GAP_FIRST, LATE_W0, false>(x, center_idx, N, whh0, whh1, wx0, wx1, H0);
+}
+
+template <int GAP_T, int GAP_V, int GAP_FIRST, bool LATE_W0>
+__global__ __launch_bounds__(256, 3) void k_pileup_l0_rsxp(
+    const int32_t* __restrict__ x, const int64_t* __restrict__ center_idx, int64_t N,
+    const float* __restrict__ whh0, const float* __restrict__ whh1,
+    const __bf16* __restrict__ wx0, const __bf16* __restrict__ wx1,
+    float* __restrict__ H0)
+{
+    pileup_l0_rsxw_body<GAP_T, GAP_V, GAP_FIRST, LATE_W0, true>(x, center_idx, N, whh0, whh1, wx0, wx1, H0);
 }
 // the placement that is built.  Measured (docs/rounds/r21.md): on the headline every placement of this kernel is 1.4 - 1.7 % above
 // k_pileup_l0_rsx and they differ among themselves by less than a run does; one transcendental behind each of eight MFMAs, from the
@@ -2047,7 +2183,10 @@ static int launch_layers(nsnp_ctx* ctx, const int32_t* xc, const int64_t* cc, in
             ScopedKernelTimer tm(ctx, NSNP_K_L0, s);
             // 16 sites per workgroup, three workgroups per SIMD set ("l0_site_groups" and "l0_input_weights_in_lds" shape the
             // kernels of value 1 only)
-            if (ctx->l0_weave)
+            if (ctx->l0_weave && ctx->l0_prestage)
+                hipLaunchKernelGGL((k_pileup_l0_rsxp<RSXW_GAP_T, RSXW_GAP_V, RSXW_GAP_FIRST, RSXW_LATE_W0 != 0>), dim3((unsigned)NSNP_CDIV(n, 16), 2), dim3(256), 0, s,
+                                   xc, cc, n, pw.l0_whh[0], pw.l0_whh[1], (const __bf16*)pw.l0_wx[0], (const __bf16*)pw.l0_wx[1], ctx->ws_h0);
+            else if (ctx->l0_weave)
                 hipLaunchKernelGGL((k_pileup_l0_rsxw<RSXW_GAP_T, RSXW_GAP_V, RSXW_GAP_FIRST, RSXW_LATE_W0 != 0>), dim3((unsigned)NSNP_CDIV(n, 16), 2), dim3(256), 0, s,
                                    xc, cc, n, pw.l0_whh[0], pw.l0_whh[1], (const __bf16*)pw.l0_wx[0], (const __bf16*)pw.l0_wx[1], ctx->ws_h0);
             else
