@@ -25,8 +25,8 @@ def _layer(inp, w, base):
     outs = []
     for d in range(2):
         wih, whh, b = w[base + 4 * d], w[base + 4 * d + 1], w[base + 4 * d + 2] + w[base + 4 * d + 3]
-        h = torch.zeros((n, H), dtype=torch.float64)
-        c = torch.zeros((n, H), dtype=torch.float64)
+        h = torch.zeros((n, H), dtype=inp.dtype)
+        c = torch.zeros((n, H), dtype=inp.dtype)
         hs = [None] * T
         for s in range(T):
             t = T - 1 - s if d else s
@@ -39,13 +39,14 @@ def _layer(inp, w, base):
     return torch.cat(outs, dim=2)
 
 
-def forward(w, x, cls, keep_mask=None, keep_scale=1.0):
-    """w: 24 float64 tensors; x [N,33,18]; cls integer [N, >= 2] -> (loss scalar tensor, site_loss [N,2] tensor, logits [N,24] tensor).
-    A class outside its head counts as the head's last class."""
-    x = torch.as_tensor(np.asarray(x, np.float64))
+def forward(w, x, cls, keep_mask=None, keep_scale=1.0, dtype=torch.float64):
+    """w: 24 tensors of `dtype`; x [N,33,18]; cls integer [N, >= 2] -> (loss scalar tensor, site_loss [N,2] tensor, logits [N,24] tensor).
+    A class outside its head counts as the head's last class.  dtype torch.float32: the same restatement in fp32 torch on the CPU, the
+    yardstick of what fp32 arithmetic costs on an input the fixture did not measure."""
+    x = torch.as_tensor(np.asarray(x, np.float64)).to(dtype)
     h0 = _layer(x, w, 0)
     if keep_mask is not None:
-        h0 = h0 * torch.as_tensor(np.asarray(keep_mask, np.float64)) * float(keep_scale)
+        h0 = h0 * torch.as_tensor(np.asarray(keep_mask, np.float64)).to(dtype) * float(keep_scale)
     h1 = _layer(h0, w, 8)
     enc = h1[:, 16] @ w[16].T + w[17]
     mid = torch.tanh(enc @ w[18].T + w[19])
@@ -62,15 +63,15 @@ def forward(w, x, cls, keep_mask=None, keep_scale=1.0):
     return site[:, 0].mean() + site[:, 1].mean(), site, z
 
 
-def tensors(weights, requires_grad=True):
-    return [torch.tensor(np.asarray(t, np.float64), requires_grad=requires_grad) for t in weights]
+def tensors(weights, requires_grad=True, dtype=torch.float64):
+    return [torch.tensor(np.asarray(t, np.float64), dtype=dtype, requires_grad=requires_grad) for t in weights]
 
 
-def loss_and_grad(weights, x, cls, keep_mask=None, keep_scale=1.0):
-    """-> dict: grads (24 float64 arrays in state-dict order), loss (float), site_loss float64 [N,2], pred uint8 [N,2] (first maximum),
-    logits float64 [N,24]"""
-    w = tensors(weights)
-    loss, site, z = forward(w, x, cls, keep_mask, keep_scale)
+def loss_and_grad(weights, x, cls, keep_mask=None, keep_scale=1.0, dtype=torch.float64):
+    """-> dict: grads (24 arrays of `dtype` in state-dict order), loss (float), site_loss [N,2], pred uint8 [N,2] (first maximum),
+    logits [N,24]; float64 unless dtype says otherwise"""
+    w = tensors(weights, dtype=dtype)
+    loss, site, z = forward(w, x, cls, keep_mask, keep_scale, dtype)
     loss.backward()
     zn = z.detach().numpy()
     pred = np.stack([zn[:, r0:r0 + c].argmax(1) for r0, c in HEADS], axis=1).astype(np.uint8)

@@ -5,7 +5,9 @@ Parity bound: for every one of the 24 tensors max |g_dev - g_f64| / max |g_f64| 
 fp32 distance from float64 recorded in tests/golden/pileup_grad.npz (5.6e-6): the factor the project grants its forward (1e-4 against inputs
 admissible at 2.5e-5).  Loss and site_loss: 1e-4 absolute; pred: equal wherever the float64 top-two logits differ by more than 1e-4.
 Inputs: eval_rules.synthetic_windows with the weights of nanosnp_amd/data/ont_pileup_weights.npz.  No kernel of pileup_train.hip is
-persistent (no grid is capped by the CU count), so there is no case sized by the CU count.
+persistent (no grid is capped by the CU count), so there is no case sized by the CU count.  The sizes that DO select other paths - more
+than one slice of 1,024 reduction rows for the dense layers and heads (N >= 1025), every starting phase of a slice against the 33 and 17
+steps of a site, a reservation that is no multiple of 16, chunks with a mask and centre indices - are in tests/test_gpu_train_batches.py.
 
 Distances measured on an MI355X: docs/rounds/r23.md has the table per tensor."""
 import ctypes as C
@@ -90,14 +92,16 @@ def _run(ctx, params, x, cls, mask=None, scale=1.0, center_idx=None, fill=None):
 
 
 def _check(got, ref, n, bound, what):
+    """bound: one number for every tensor, or 24 of them"""
     grads, site_loss, pred = got
+    bounds = np.broadcast_to(np.asarray(bound, np.float64), (24,))
     dist = [gr.rel_dist(g, r) for g, r in zip(grads, ref["grads"])]
     loss = float(site_loss.astype(np.float64).sum() / n)
     dl, ds = abs(loss - ref["loss"]), float(np.abs(site_loss - ref["site_loss"]).max())
-    print(f"{what}: max rel dist {max(dist):.3e} (bound {bound:.3e}) per tensor " + " ".join(f"{d:.1e}" for d in dist) +
+    print(f"{what}: max rel dist {max(dist):.3e} (bound {bounds.min():.3e}) per tensor " + " ".join(f"{d:.1e}" for d in dist) +
           f"; |loss - f64| {dl:.2e}, site_loss {ds:.2e}")
     for i, d in enumerate(dist):
-        assert np.isfinite(grads[i]).all() and d <= bound, (what, i, d, bound)
+        assert np.isfinite(grads[i]).all() and d <= bounds[i], (what, i, d, bounds[i])
     assert dl <= ATOL and ds <= ATOL, (what, dl, ds)
     clear = gr.top_two_gap(ref["logits"]) > ATOL
     assert np.array_equal(pred[clear], ref["pred"][clear]), what

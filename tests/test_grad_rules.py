@@ -63,6 +63,44 @@ def test_sampled_batches_match_the_reference(gold, base, weights, n):
         assert abs(gold[f"l2_{n}"][i] - np.sqrt((g ** 2).sum())) <= bound * top * np.sqrt(g.size), i
 
 
+def test_float32_restatement_is_as_close_as_the_reference(gold, base, weights):
+    """grad_rules with dtype=torch.float32 (the yardstick tests/test_gpu_train_batches.py uses on inputs the fixture did not measure) is
+    fp32 arithmetic of the reference's kind: within ref_rel_max of the reference's own fp32 gradients at N = 17; float64 is the default"""
+    import torch
+    x, cls = er.synthetic_windows(base, FULL)
+    f32 = gr.loss_and_grad(weights, x, cls, dtype=torch.float32)
+    assert all(g.dtype == np.float32 for g in f32["grads"]) and f32["site_loss"].dtype == np.float32
+    assert all(g.dtype == np.float64 for g in gr.loss_and_grad(weights, x[:1], cls[:1])["grads"])
+    dist = [gr.rel_dist(g, gold[f"g{FULL}_{i:02d}"]) for i, g in enumerate(f32["grads"])]
+    print("float32 restatement against the reference's fp32 gradients, N = 17: " + " ".join(f"{d:.1e}" for d in dist))
+    assert max(dist) <= float(gold["ref_rel_max"]), dist
+    assert abs(f32["loss"] - float(gold[f"loss_{FULL}"])) <= 1e-4
+
+
+def test_a_lost_site_is_visible_at_a_large_batch(gold, base, weights):
+    """What the parity bound of the GPU tests (max |diff| / max |tensor| <= 4 x ref_rel_max per tensor) can see at N = 1040.  With g the
+    gradient of the batch and g_j that of site j alone (N = 1), a kernel that loses site j changes a tensor by g_j / N.  For the sites
+    next to the cuts of the 1,024-row slices (31: layer-0 rows 1023 | 1024; 60: layer-1 rows 1020..1036; 62: layer-0 row 2048; 1023 and
+    1024: the dense layers' and heads' cut; 0, 1039: the ends) and nine seeded others, max |g_j| / (N max |g|) is at least four times
+    the bound for tensors 0 to 21: a lost site fails the GPU test with room to spare.
+
+    NOT so for the zygosity head (tensors 22 and 23): three classes, so a site whose prediction is confident contributes little, and the
+    ratio falls to the bound's own size for some sites (1.1e-5 measured over 80 sites).  A single lost site can hide there; only the
+    median over the chosen sites is asserted.  What guards those two tensors against a lost slice is that a slice holds 16 to 1,024
+    sites, not one."""
+    n = 1040
+    bound = 4.0 * float(gold["ref_rel_max"])
+    x, cls = er.synthetic_windows(base, n)
+    sites = [0, 30, 31, 32, 60, 62, 1023, 1024, 1039] + sorted(np.random.default_rng(1040).choice(n, 7, replace=False).tolist())
+    assert len(sites) == 16
+    top = np.array([np.abs(g).max() for g in gr.loss_and_grad(weights, x, cls)["grads"]])
+    ratio = np.array([[np.abs(g).max() for g in gr.loss_and_grad(weights, x[j:j + 1], cls[j:j + 1])["grads"]] for j in sites]) / (n * top)
+    print("lost-site ratio max |g_j| / (N max |g|), smallest over the sites per tensor: " + " ".join(f"{v:.1e}" for v in ratio.min(0)) +
+          "; median of tensors 22, 23: " + " ".join(f"{v:.1e}" for v in np.median(ratio[:, 22:], axis=0)) + f"; bound {bound:.3e}")
+    assert ratio[:, :22].min() >= 4.0 * bound, ratio[:, :22].min(0)
+    assert (np.median(ratio[:, 22:], axis=0) >= 4.0 * bound).all()
+
+
 def test_bias_gradients_are_equal_pairs(base, weights):
     x, cls = er.synthetic_windows(base, 5)
     g = gr.loss_and_grad(weights, x, cls)["grads"]
