@@ -10,6 +10,7 @@ everything between lives in HBM.
 """
 from __future__ import annotations
 
+import contextlib
 import mmap
 import os
 from collections import deque, namedtuple
@@ -56,6 +57,26 @@ class _MvFind:
                 return s0 + int(w[-1])
             e = s0
         return -1
+
+
+@contextlib.contextmanager
+def _mapped(path):
+    """the bytes of a file, mapped and never copied (b"" for an empty file: nothing to map); unmapped behind the block"""
+    with open(path, "rb") as g:
+        text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if os.fstat(g.fileno()).st_size else None
+        try:
+            yield text if text is not None else b""
+        finally:
+            if text is not None:
+                try:
+                    text.close()
+                except BufferError:                          # (an exception on its way up still holds views of the mapping)
+                    pass
+
+
+def _text_of(path_or_bytes):
+    """context manager: a path -> _mapped(path); bytes / mmap / uint8 array -> the object itself, left as it is"""
+    return _mapped(path_or_bytes) if isinstance(path_or_bytes, (str, os.PathLike)) else contextlib.nullcontext(path_or_bytes)
 
 
 def line_cuts(text, n_parts, lo=0, hi=None):
@@ -1713,17 +1734,9 @@ def _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_fil
         model._rows_ctx = _lib.Context(model.ctx.device)     # the writer thread's own context (call_contigs)
     wctx = model._rows_ctx
     few = max(1, host.lib().nsnp_host_threads() // 4)
-    g = text = None
-    if isinstance(mpileup_path_or_bytes, (str, os.PathLike)):
-        g = open(mpileup_path_or_bytes, "rb")
-        size = os.fstat(g.fileno()).st_size
-        text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if size else None
-    f = None
     n_rows = 0
-    try:
-        f = open(output_file, "wb")
+    with _text_of(mpileup_path_or_bytes) as src, open(output_file, "wb") as f:
         f.write(host.vcf_header(fai_text).encode())
-        src = (text if text is not None else b"") if g is not None else mpileup_path_or_bytes
         acc, futs, carry = [], deque(), []
 
         def finish(pieces, done, last):
@@ -1782,16 +1795,6 @@ def _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_fil
                 raise
         st["vcf_rows"] = st.get("vcf_rows", 0) + n_rows
         return n_rows
-    finally:
-        if f:
-            f.close()
-        if text is not None:
-            try:
-                text.close()
-            except BufferError:                  # (an exception on its way up still holds views of the mapping)
-                pass
-        if g is not None:
-            g.close()
 
 
 # ---- <chr>.mpileup text -> <chr>.pd.bin: stage s1 alone (make_predict_data.sh:167-234) ------------------------------------------------
@@ -1827,6 +1830,39 @@ def _bins_refusals():
         raise NanoSNPError("no GPU visible: nanosnp_amd has no CPU fallback")
 
 
+def _check_matrix_dtype(matrix_dtype):
+    from . import sitefile
+    if matrix_dtype not in ("int16", "int32"):
+        raise sitefile.SiteFileError("matrix_dtype: 'int16' or 'int32'")
+
+
+def _position_name(contig):
+    """a contig name (str or bytes) -> the bytes a position string begins with; ValueError for one the position field has no room for"""
+    from . import sitefile
+    name = contig.encode() if isinstance(contig, str) else bytes(contig)
+    if not name or b"\0" in name or len(name) + 1 + 11 + 1 + 33 > sitefile.POSITION_WIDTH:
+        raise ValueError(f"{contig!r}: a contig name of 1 to {sitefile.POSITION_WIDTH - 46} bytes without NUL is needed for the "
+                         f"{sitefile.POSITION_WIDTH}-byte position field")
+    return name
+
+
+def _run_passes(sink, matrix_dtype, run_pass, st, finish):
+    """The restart loop of the window writers: run_pass(state) streams the text once into `sink` -> (run again?, result); state = {elem,
+    blob_min, name_cap} says how the next pass differs (_records_pass).  Every pass but the last is dropped whole (sink.restart);
+    -> finish(the last pass's result); on any error sink.abort() before it leaves."""
+    state = dict(elem=2 if matrix_dtype == "int16" else 4, blob_min=0, name_cap=1024)
+    try:
+        while True:
+            again, result = run_pass(state)
+            if not again:
+                return finish(result)
+            st["restarts"] = st.get("restarts", 0) + 1
+            sink.restart("int16" if state["elem"] == 2 else "int32")
+    except BaseException:
+        sink.abort()
+        raise
+
+
 def contig_to_bin(model, mpileup_text, contig, chr_seq, path, *, alt_info=True, matrix_dtype="int16", min_af=0.12, indel_min_af=None,
                   min_coverage=6, chunk_bytes=64 << 20, stats=None, extended_bed=None, confident_bed=None, fai=None):
     """Stage s1 alone: one contig's samtools-mpileup text -> its <chr>.pd.bin (sitefile: position_matrix, position, alt_info,
@@ -1847,47 +1883,35 @@ def contig_to_bin(model, mpileup_text, contig, chr_seq, path, *, alt_info=True, 
     together with an extended BED (NotImplementedError when such a line is met), and a token longer than 37 bytes is refused.
     NOT done here: one whole-genome text (mpileup_to_bins does that), sharding over a process group, a .pd TEXT writer, the reference's
     .tensor / .alt_info side files."""
-    import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import sitefile
     _bins_refusals()
-    name = contig.encode() if isinstance(contig, str) else bytes(contig)
-    if not name or b"\0" in name or len(name) + 1 + 11 + 1 + 33 > sitefile.POSITION_WIDTH:
-        raise ValueError(f"{contig!r}: a contig name of 1 to {sitefile.POSITION_WIDTH - 46} bytes without NUL is needed for the "
-                         f"{sitefile.POSITION_WIDTH}-byte position field")
-    if matrix_dtype not in ("int16", "int32"):
-        raise sitefile.SiteFileError("matrix_dtype: 'int16' or 'int32'")
-    ctx = model.ctx
+    name = _position_name(contig)
+    _check_matrix_dtype(matrix_dtype)
     beds = _contig_beds(extended_bed, confident_bed, contig, chr_seq, fai)
     st = _stream_stats(stats)
-    state = dict(elem=2 if matrix_dtype == "int16" else 4, blob_min=0)
     writer = sitefile.PileupBinWriter(path, matrix_dtype, alt_info)
+    source = _ContigRecords(model.ctx, name, contig, chr_seq, beds, writer, alt_info)
     with ThreadPoolExecutor(max_workers=1) as pool:
-        try:
-            while True:
-                again = _contig_records_pass(model, ctx, mpileup_text, name, contig, chr_seq, chunk_bytes, min_af, indel_min_af, min_coverage, st, beds,
-                                             alt_info, state, writer, pool)
-                if not again:
-                    break
-                st["restarts"] = st.get("restarts", 0) + 1
-                writer.restart("int16" if state["elem"] == 2 else "int32")
-            n = writer.close()
-        except BaseException:
-            writer.abort()
-            raise
+        n = _run_passes(writer, matrix_dtype, lambda state: _records_pass(model, source, mpileup_text, chunk_bytes, min_af, indel_min_af, min_coverage,
+                                                                          st, state, pool), st, lambda _: writer.close())
     st["sites"] = st.get("sites", 0) + n
     return n
 
 
-def _contig_records_pass(model, ctx, text, name, contig, chr_seq, chunk_bytes, min_af, indel_min_af, min_coverage, st, beds, alt_info, state, writer, pool):
-    """one pass of contig_to_bin over the text -> True when it has to be run again (state says how: elem 4, or blob_min bytes per slot)"""
+def _records_pass(model, source, text, chunk_bytes, min_af, indel_min_af, min_coverage, st, state, pool):
+    """One pass of contig_to_bin / mpileup_to_bins / mpileup_to_train_bins over the text -> (True when it has to be run again - state says how:
+    elem 4, blob_min bytes per slot, or name_cap entries per name table -, what source.stream returned).
+    source (_ContigRecords / _KeyedRecords) says how the text is streamed, which two record kernels fill a slot, where a finished slot is
+    appended and how a refusal reads; the three pinned slots taken in turn, the writer thread's pieces and the restart decisions are here."""
     import torch
     from ._lib import NanoSNPError
-    elem = state["elem"]
+    ctx, alt_info, elem = source.ctx, source.alt_info, state["elem"]
     text_len = int(_as_bytes_like(text)[1].size)
-    slots = getattr(model, "_rec_slots", None)
+    slots = getattr(model, source.slots_attr, None)
     if slots is None:
-        slots = model._rec_slots = [None, None, None]
+        slots = [None, None, None]
+        setattr(model, source.slots_attr, slots)
     flag = dict(overflow=False, alt_need=0, status=0)
     turn, spans = [0], []
 
@@ -1898,16 +1922,17 @@ def _contig_records_pass(model, ctx, text, name, contig, chr_seq, chunk_bytes, m
             flag["overflow"] = True
         if m[0, 2]:
             flag["status"] = int(m[0, 2])
+        if source.label_status(slot):
+            flag["status"] = flag["status"] or 1
         if alt_info and (m[1, 1] & ctx.TOK_ERANGE):
             flag["alt_need"] = max(flag["alt_need"], int(m[1, 0]))
+        if alt_info and (m[1, 1] & ~ctx.TOK_ERANGE):         # (a key outside the table: only nsnp_pileup_alt_info_keys reports another bit)
+            flag["status"] = int(m[1, 1])
         if flag["overflow"] or flag["alt_need"] or flag["status"]:
             return                                           # (the pass is run again, or refused: nothing more is appended)
         x = slot.matrix.numpy().view(np.int16 if elem == 2 else np.int32)[:n * 594].reshape(n, 33, 18)
-        if alt_info:
-            writer.append(x, slot.position.numpy()[:n], slot.blob.numpy()[:int(m[1, 0])], slot.offsets.numpy()[:n + 1])
-        else:
-            writer.append(x, slot.position.numpy()[:n])
-        st["record_bytes"] = st.get("record_bytes", 0) + n * (594 * elem + 83) + (int(m[1, 0]) + 8 * n if alt_info else 0)
+        source.append(slot, n, x, int(m[1, 0]))
+        st["record_bytes"] = st.get("record_bytes", 0) + n * (594 * elem + 83 + source.label_bytes) + (int(m[1, 0]) + 8 * n if alt_info else 0)
 
     def records(k, counts, centers, cols, main):
         if flag["overflow"] or flag["alt_need"] or flag["status"]:
@@ -1923,18 +1948,20 @@ def _contig_records_pass(model, ctx, text, name, contig, chr_seq, chunk_bytes, m
         if slot is None or slot.rows < n or slot.blob.numel() < want_blob:
             # (a 30x chunk selects 3-4 % of its columns and budgets one column per 24 bytes: 1 / 64 of them is about as many rows as it fills)
             rows = max(n + n // 4, _cols_for(min(int(chunk_bytes), text_len)) // 64, 1024 if slot is None else slot.rows)
-            slot = slots[i] = _RecSlot(rows, max(64 * rows + (1 << 16), state["blob_min"]))
+            slot = slots[i] = source.new_slot(rows, max(64 * rows + (1 << 16), state["blob_min"]), main)
+        centers = source.label(slot, centers, cols, main, st, flag)
+        if centers is None:
+            return                                           # (no site of the chunk is kept, or a status that ends the pass)
+        n = int(centers.shape[0])
         timed = st.get("time_records")                       # (stats["time_records"] = True: HIP-event time of the record kernels -> stats["window_records_s"], ["alt_info_s"])
         if timed:
             t0, t1, t2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
             t0.record(main)
-        ctx.pileup_window_records(counts, centers, cols.pos, cols.seq, name, elem, position_matrix=slot.matrix_as(elem), position=slot.position,
-                                  meta=slot.meta[0], stream=main, line_names=cols.names)
+        source.window_records(slot, counts, centers, cols, elem, main)
         if timed:
             t1.record(main)
         if alt_info:
-            ctx.pileup_alt_info(cols.bases, cols.off, cols.ref, cols.pos, cols.depth, centers, cols.seq, blob=slot.blob, offsets=slot.offsets,
-                                meta=slot.meta[1], stream=main)
+            source.alt_records(slot, centers, cols, main)
         if timed:
             t2.record(main)
             spans.append((t0, t1, t2))
@@ -1953,8 +1980,7 @@ def _contig_records_pass(model, ctx, text, name, contig, chr_seq, chunk_bytes, m
 
     try:
         with host.gc_paused():
-            _stream_contig_dev(model, text, contig, chr_seq, 0, None, chunk_bytes, min_af, min_coverage, st, None, beds=beds,
-                               indel_min_af=indel_min_af, records=records, name_cap=state.get("name_cap", 1024))
+            result = source.stream(model, text, chunk_bytes, min_af, indel_min_af, min_coverage, st, records, state["name_cap"])
         drain(False)
         for t0, t1, t2 in spans:
             st["window_records_s"] = st.get("window_records_s", 0.0) + t0.elapsed_time(t1) * 1e-3
@@ -1963,21 +1989,62 @@ def _contig_records_pass(model, ctx, text, name, contig, chr_seq, chunk_bytes, m
     except _NamesOverflow as e:
         drain(True)
         state["name_cap"] = 2 * e.need + 64
-        return True
+        return True, None
     except BaseException:
         drain(True)                                          # (the streams have been waited for: the writer's pieces end at once)
         raise
     if flag["status"]:
-        raise NanoSNPError(f"{contig}: a selected site outside the columns or the contig (record status {flag['status']})")
+        raise NanoSNPError(source.status_text(flag["status"]))
     if flag["overflow"]:
         if elem == 4:
-            raise NanoSNPError(f"{contig}: int16 overflow reported for int32 records")
+            raise NanoSNPError(source.overflow_text)
         state["elem"] = 4
-        return True
+        return True, None
     if flag["alt_need"]:
         state["blob_min"] = 2 * flag["alt_need"]
-        return True
-    return False
+        return True, None
+    return False, result
+
+
+class _ContigRecords:
+    """What _records_pass asks of contig_to_bin: one contig's text through _stream_contig_dev, the record kernels that take the contig's one
+    name and sequence, every finished slot straight into the one PileupBinWriter.  Nothing of a chunk is labelled or dropped."""
+    slots_attr = "_rec_slots"
+    label_bytes = 0
+
+    def __init__(self, ctx, name, contig, chr_seq, beds, writer, alt_info):
+        self.ctx, self.name, self.contig, self.chr_seq, self.beds, self.writer, self.alt_info = ctx, name, contig, chr_seq, beds, writer, alt_info
+        self.overflow_text = f"{contig}: int16 overflow reported for int32 records"
+
+    def status_text(self, status):
+        return f"{self.contig}: a selected site outside the columns or the contig (record status {status})"
+
+    def stream(self, model, text, chunk_bytes, min_af, indel_min_af, min_coverage, st, records, name_cap):
+        _stream_contig_dev(model, text, self.contig, self.chr_seq, 0, None, chunk_bytes, min_af, min_coverage, st, None, beds=self.beds,
+                           indel_min_af=indel_min_af, records=records, name_cap=name_cap)
+
+    def new_slot(self, rows, blob_bytes, main):
+        return _RecSlot(rows, blob_bytes)
+
+    def label(self, slot, centers, cols, main, st, flag):
+        return centers
+
+    def label_status(self, slot):
+        return 0
+
+    def window_records(self, slot, counts, centers, cols, elem, main):
+        self.ctx.pileup_window_records(counts, centers, cols.pos, cols.seq, self.name, elem, position_matrix=slot.matrix_as(elem), position=slot.position,
+                                       meta=slot.meta[0], stream=main, line_names=cols.names)
+
+    def alt_records(self, slot, centers, cols, main):
+        self.ctx.pileup_alt_info(cols.bases, cols.off, cols.ref, cols.pos, cols.depth, centers, cols.seq, blob=slot.blob, offsets=slot.offsets,
+                                 meta=slot.meta[1], stream=main)
+
+    def append(self, slot, n, x, blob_bytes):
+        if self.alt_info:
+            self.writer.append(x, slot.position.numpy()[:n], slot.blob.numpy()[:blob_bytes], slot.offsets.numpy()[:n + 1])
+        else:
+            self.writer.append(x, slot.position.numpy()[:n])
 
 
 def make_pileup_bins(model, contigs, fasta_path, fai_text, out_dir, **kw):
@@ -1995,17 +2062,8 @@ def make_pileup_bins(model, contigs, fasta_path, fai_text, out_dir, **kw):
     out = {}
     for name, path in contigs:
         seq = host.fasta_load_contig(fasta_path, name)
-        with open(path, "rb") as g:
-            size = os.fstat(g.fileno()).st_size
-            text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if size else b""
-            try:
-                out[name] = contig_to_bin(model, text, name, seq, os.path.join(out_dir, f"{name}.pd.bin"), **kw)
-            finally:
-                if size:
-                    try:
-                        text.close()
-                    except BufferError:                      # (an exception on its way up still holds views of the mapping)
-                        pass
+        with _mapped(path) as text:
+            out[name] = contig_to_bin(model, text, name, seq, os.path.join(out_dir, f"{name}.pd.bin"), **kw)
     return out
 
 
@@ -2118,17 +2176,9 @@ def _staged_bins(out_dir, names, matrix_dtype, alt_info, run_pass, st, staging_c
     made = not os.path.isdir(out_dir)
     os.makedirs(out_dir, exist_ok=True)
     staging = (staging_cls or _BinStaging)(out_dir, names, matrix_dtype, alt_info)
-    state = dict(elem=2 if matrix_dtype == "int16" else 4, blob_min=0, name_cap=1024)
     try:
-        while True:
-            again, order = run_pass(staging, state)
-            if not again:
-                break
-            st["restarts"] = st.get("restarts", 0) + 1
-            staging.restart("int16" if state["elem"] == 2 else "int32")
-        return staging.commit(order)
+        return _run_passes(staging, matrix_dtype, lambda state: run_pass(staging, state), st, staging.commit)
     except BaseException:
-        staging.abort()
         if made:
             try:
                 os.rmdir(out_dir)
@@ -2137,127 +2187,55 @@ def _staged_bins(out_dir, names, matrix_dtype, alt_info, run_pass, st, staging_c
         raise
 
 
-def _text_records_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_af, min_coverage, st, alt_info, state, staging, pool, beds=None,
-                       train=None):
-    """one pass of mpileup_to_bins over the text -> (True when it has to be run again - state says how: elem 4, blob_min bytes per slot, or
-    name_cap entries per name table -, the wanted contigs the text holds in its order).
+class _KeyedRecords:
+    """What _records_pass asks of mpileup_to_bins: the whole text through _stream_text_dev (-> the wanted contigs it holds, in its order),
+    the record kernels that take names and bases out of the resident contig table and hand back every site's key, every finished slot cut
+    by contig into the staging.
     train (a _TrainLabels of mpileup_to_train_bins; None: exactly the launches issued without): its slots carry the label rows, its
-    label() runs in front of the record kernels and says which centres they get, and the writer hands the staging the label rows and the
-    site keys of every piece."""
-    import torch
-    from ._lib import NanoSNPError
-    elem = state["elem"]
-    text_len = int(_as_bytes_like(text)[1].size)
-    slots_attr = "_rec_slots" if train is None else "_train_slots"
-    slots = getattr(model, slots_attr, None)
-    if slots is None:
-        slots = [None, None, None]
-        setattr(model, slots_attr, slots)
-    flag = dict(overflow=False, alt_need=0, status=0)
-    turn, spans = [0], []
+    label() runs in front of the record kernels and says which centres they get, and the staging gets the label rows and the site keys of
+    every piece."""
 
-    def write_piece(slot, n, done):
-        done.synchronize()
-        m = slot.meta.numpy()
-        if m[0, 1]:
-            flag["overflow"] = True
-        if m[0, 2]:
-            flag["status"] = int(m[0, 2])
-        if train is not None and int(slot.lmeta[3]):
-            flag["status"] = flag["status"] or 1
-        if alt_info and (m[1, 1] & ctx.TOK_ERANGE):
-            flag["alt_need"] = max(flag["alt_need"], int(m[1, 0]))
-        if alt_info and (m[1, 1] & ~ctx.TOK_ERANGE):
-            flag["status"] = int(m[1, 1])
-        if flag["overflow"] or flag["alt_need"] or flag["status"]:
-            return                                           # (the pass is run again, or refused: nothing more is appended)
-        x = slot.matrix.numpy().view(np.int16 if elem == 2 else np.int32)[:n * 594].reshape(n, 33, 18)
-        position, blob = slot.position.numpy(), slot.blob.numpy()
+    def __init__(self, ctx, table, beds, staging, alt_info, train=None):
+        self.ctx, self.table, self.beds, self.staging, self.alt_info, self.train = ctx, table, beds, staging, alt_info, train
+        self.slots_attr = "_rec_slots" if train is None else "_train_slots"
+        self.label_bytes = 0 if train is None else 360
+        self.overflow_text = "int16 overflow reported for int32 records"
+
+    def status_text(self, status):
+        return ("a selected site outside the columns or its contig, " + ("" if self.train is None else "at a reference byte other than A/C/G/T, ")
+                + f"or a name longer than 37 bytes in column 0 (record status {status})")
+
+    def stream(self, model, text, chunk_bytes, min_af, indel_min_af, min_coverage, st, records, name_cap):
+        tracker = _stream_text_dev(model, text, self.table, chunk_bytes, min_af, min_coverage, st, None, indel_min_af=indel_min_af, records=records,
+                                   name_cap=name_cap, beds=self.beds)
+        return list(tracker.order)
+
+    def new_slot(self, rows, blob_bytes, main):
+        return _RecSlot(rows, blob_bytes) if self.train is None else self.train.new_slot(rows, blob_bytes, main)
+
+    def label(self, slot, centers, cols, main, st, flag):
+        return centers if self.train is None else self.train.label(slot, centers, cols, main, st, flag)
+
+    def label_status(self, slot):
+        return self.train is not None and int(slot.lmeta[3])
+
+    def window_records(self, slot, counts, centers, cols, elem, main):
+        self.ctx.pileup_window_records_keys(counts, centers, cols.pos, self.table, elem, position_matrix=slot.matrix_as(elem), position=slot.position,
+                                            site_key=slot.site_key, meta=slot.meta[0], stream=main, line_names=cols.names)
+
+    def alt_records(self, slot, centers, cols, main):
+        self.ctx.pileup_alt_info_keys(cols.bases, cols.off, cols.ref, cols.pos, cols.depth, centers, self.table, blob=slot.blob, offsets=slot.offsets,
+                                      meta=slot.meta[1], stream=main)
+
+    def append(self, slot, n, x, blob_bytes):
+        alt_info, position, blob = self.alt_info, slot.position.numpy(), slot.blob.numpy()
         # the rows are ascending in line order: every contig of the chunk is one piece
         keys = slot.site_key.numpy()
         for cid, a, b, b_lo, b_hi, offs in cut_records_by_contig(keys[:n], slot.offsets.numpy()[:n + 1] if alt_info else None):
-            if train is None:
-                staging.append(cid, x[a:b], position[a:b], blob[b_lo:b_hi] if alt_info else None, offs)
+            if self.train is None:
+                self.staging.append(cid, x[a:b], position[a:b], blob[b_lo:b_hi] if alt_info else None, offs)
             else:
-                staging.append(cid, x[a:b], position[a:b], slot.label.numpy()[a:b], blob[b_lo:b_hi] if alt_info else None, offs, keys=keys[a:b])
-        st["record_bytes"] = (st.get("record_bytes", 0) + n * (594 * elem + 83 + (0 if train is None else 360))
-                              + (int(m[1, 0]) + 8 * n if alt_info else 0))
-
-    def records(k, counts, centers, cols, main):
-        if flag["overflow"] or flag["alt_need"] or flag["status"]:
-            return                                           # (this pass is lost: the rest of it only has to end)
-        n = int(centers.shape[0])
-        i = turn[0] % 3
-        turn[0] += 1
-        slot = slots[i]
-        if slot is not None and slot.busy is not None:
-            slot.busy.result()                               # the writer is done with the slot's previous chunk (three chunks back)
-            slot.busy = None
-        want_blob = max(64 * n + (1 << 16), state["blob_min"])
-        if slot is None or slot.rows < n or slot.blob.numel() < want_blob:
-            rows = max(n + n // 4, _cols_for(min(int(chunk_bytes), text_len)) // 64, 1024 if slot is None else slot.rows)
-            blob_bytes = max(64 * rows + (1 << 16), state["blob_min"])
-            slot = slots[i] = _RecSlot(rows, blob_bytes) if train is None else train.new_slot(rows, blob_bytes, main)
-        if train is not None:
-            centers = train.label(slot, centers, cols, main, st, flag)
-            if centers is None:
-                return                                       # (no site of the chunk is kept, or a status that ends the pass)
-            n = int(centers.shape[0])
-        timed = st.get("time_records")                       # (as contig_to_bin: HIP-event time of the record kernels)
-        if timed:
-            t0, t1, t2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-            t0.record(main)
-        ctx.pileup_window_records_keys(counts, centers, cols.pos, table, elem, position_matrix=slot.matrix_as(elem), position=slot.position,
-                                       site_key=slot.site_key, meta=slot.meta[0], stream=main, line_names=cols.names)
-        if timed:
-            t1.record(main)
-        if alt_info:
-            ctx.pileup_alt_info_keys(cols.bases, cols.off, cols.ref, cols.pos, cols.depth, centers, table, blob=slot.blob, offsets=slot.offsets,
-                                     meta=slot.meta[1], stream=main)
-        if timed:
-            t2.record(main)
-            spans.append((t0, t1, t2))
-        done = torch.cuda.Event(); done.record(main)
-        slot.busy = pool.submit(write_piece, slot, n, done)
-
-    def drain(swallow):
-        for slot in slots:
-            if slot is not None and slot.busy is not None:
-                busy, slot.busy = slot.busy, None
-                try:
-                    busy.result()
-                except BaseException:
-                    if not swallow:
-                        raise
-
-    try:
-        with host.gc_paused():
-            tracker = _stream_text_dev(model, text, table, chunk_bytes, min_af, min_coverage, st, None, indel_min_af=indel_min_af, records=records,
-                                       name_cap=state["name_cap"], beds=beds)
-        drain(False)
-        for t0, t1, t2 in spans:
-            st["window_records_s"] = st.get("window_records_s", 0.0) + t0.elapsed_time(t1) * 1e-3
-            st["alt_info_s"] = st.get("alt_info_s", 0.0) + t1.elapsed_time(t2) * 1e-3
-            st["record_chunks"] = st.get("record_chunks", 0) + 1
-    except _NamesOverflow as e:
-        drain(True)
-        state["name_cap"] = 2 * e.need + 64
-        return True, None
-    except BaseException:
-        drain(True)                                          # (the streams have been waited for: the writer's pieces end at once)
-        raise
-    if flag["status"]:
-        raise NanoSNPError("a selected site outside the columns or its contig, " + ("" if train is None else "at a reference byte other than A/C/G/T, ")
-                           + f"or a name longer than 37 bytes in column 0 (record status {flag['status']})")
-    if flag["overflow"]:
-        if elem == 4:
-            raise NanoSNPError("int16 overflow reported for int32 records")
-        state["elem"] = 4
-        return True, None
-    if flag["alt_need"]:
-        state["blob_min"] = 2 * flag["alt_need"]
-        return True, None
-    return False, list(tracker.order)
+                self.staging.append(cid, x[a:b], position[a:b], slot.label.numpy()[a:b], blob[b_lo:b_hi] if alt_info else None, offs, keys=keys[a:b])
 
 
 def mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir, contigs=None, *, alt_info=True, matrix_dtype="int16", min_af=0.12,
@@ -2304,40 +2282,21 @@ def _mpileup_to_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, out_dir
                      matrix_dtype="int16", min_af=0.12, indel_min_af=None, min_coverage=6, chunk_bytes=64 << 20, stats=None):
     """the one body of mpileup_to_bins and mpileup_to_bins_bed"""
     from concurrent.futures import ThreadPoolExecutor
-    from . import _lib, sitefile
+    from . import _lib
     _bins_refusals()
-    if matrix_dtype not in ("int16", "int32"):
-        raise sitefile.SiteFileError("matrix_dtype: 'int16' or 'int32'")
+    _check_matrix_dtype(matrix_dtype)
     names = [str(n) for n in (contigs if contigs is not None else fai_names(fai_text))]
     for n in names:
-        b = n.encode()
-        if not b or b"\0" in b or len(b) + 1 + 11 + 1 + 33 > sitefile.POSITION_WIDTH:
-            raise ValueError(f"{n!r}: a contig name of 1 to {sitefile.POSITION_WIDTH - 46} bytes without NUL is needed for the "
-                             f"{sitefile.POSITION_WIDTH}-byte position field")
+        _position_name(n)
     table = _lib.ContigTable(fasta=fasta_path, names=names, device=model.ctx.device)
     beds = None if extended_bed is None and confident_bed is None else _lib.BedTable(table, extended_bed, confident_bed, fai_text)
     st = _stream_stats(stats)
-    g = text = None
-    if isinstance(mpileup_path_or_bytes, (str, os.PathLike)):
-        g = open(mpileup_path_or_bytes, "rb")
-        size = os.fstat(g.fileno()).st_size
-        text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if size else None
-    try:
-        src = (text if text is not None else b"") if g is not None else mpileup_path_or_bytes
-        with ThreadPoolExecutor(max_workers=1) as pool:
-            out = _staged_bins(out_dir, names, matrix_dtype, alt_info,
-                               lambda staging, state: _text_records_pass(model, model.ctx, src, table, chunk_bytes, min_af, indel_min_af, min_coverage,
-                                                                         st, alt_info, state, staging, pool, beds), st)
-        st["sites"] = st.get("sites", 0) + sum(out.values())
-        return out
-    finally:
-        if text is not None:
-            try:
-                text.close()
-            except BufferError:                  # (an exception on its way up still holds views of the mapping)
-                pass
-        if g is not None:
-            g.close()
+    with _text_of(mpileup_path_or_bytes) as src, ThreadPoolExecutor(max_workers=1) as pool:
+        out = _staged_bins(out_dir, names, matrix_dtype, alt_info,
+                           lambda staging, state: _records_pass(model, _KeyedRecords(model.ctx, table, beds, staging, alt_info), src, chunk_bytes,
+                                                                min_af, indel_min_af, min_coverage, st, state, pool), st)
+    st["sites"] = st.get("sites", 0) + sum(out.values())
+    return out
 
 
 # ---- one whole-genome mpileup text + a truth VCF -> every <chr>.td.bin (make_train_data.sh steps 4, 6 and 7) --------------------------------
@@ -2421,7 +2380,7 @@ def _train_count_pass(model, ctx, text, table, chunk_bytes, min_af, indel_min_af
 
 
 class _TrainLabels:
-    """What _text_records_pass does differently for mpileup_to_train_bins: truth = (device keys, device codes); thr: the device thresholds,
+    """What _KeyedRecords does differently for mpileup_to_train_bins: truth = (device keys, device codes); thr: the device thresholds,
     or None - then every site is kept, N' == N is known on the host and the label launch simply goes in front of the record kernels on the
     compute stream.  With thresholds the label launch runs on a side stream (the chunk's selection is complete: its count has been
     read), the issuing thread waits for ITS event alone and reads N' from pinned memory, and the compute stream waits for that event -
@@ -2499,19 +2458,15 @@ def mpileup_to_train_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, tr
     import time
     import torch
     from concurrent.futures import ThreadPoolExecutor
-    from . import _lib, sitefile
+    from . import _lib
     from . import truth as _truth
     _bins_refusals()
-    if matrix_dtype not in ("int16", "int32"):
-        raise sitefile.SiteFileError("matrix_dtype: 'int16' or 'int32'")
+    _check_matrix_dtype(matrix_dtype)
     if max_non_variant_ratio is not None and not float(max_non_variant_ratio) >= 0.0:
         raise ValueError("max_non_variant_ratio: None or a number >= 0")
     names = [str(n) for n in (contigs if contigs is not None else fai_names(fai_text))]
     for n in names:
-        b = n.encode()
-        if not b or b"\0" in b or len(b) + 1 + 11 + 1 + 33 > sitefile.POSITION_WIDTH:
-            raise ValueError(f"{n!r}: a contig name of 1 to {sitefile.POSITION_WIDTH - 46} bytes without NUL is needed for the "
-                             f"{sitefile.POSITION_WIDTH}-byte position field")
+        _position_name(n)
     ctx = model.ctx
     dev = torch.device("cuda", ctx.device)
     table = _lib.ContigTable(fasta=fasta_path, names=names, device=ctx.device)
@@ -2519,13 +2474,7 @@ def mpileup_to_train_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, tr
     truth = (torch.from_numpy(t_keys).to(dev), torch.from_numpy(t_codes.view(np.int32)).to(dev))
     beds = None if extended_bed is None and confident_bed is None else _lib.BedTable(table, extended_bed, confident_bed, fai_text)
     st = _stream_stats(stats)
-    g = text = None
-    if isinstance(mpileup_path_or_bytes, (str, os.PathLike)):
-        g = open(mpileup_path_or_bytes, "rb")
-        size = os.fstat(g.fileno()).st_size
-        text = mmap.mmap(g.fileno(), 0, access=mmap.ACCESS_READ) if size else None
-    try:
-        src = (text if text is not None else b"") if g is not None else mpileup_path_or_bytes
+    with _text_of(mpileup_path_or_bytes) as src:
         counted = thr = ratios = None
         if max_non_variant_ratio is not None:
             t0 = time.perf_counter()
@@ -2544,8 +2493,8 @@ def mpileup_to_train_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, tr
 
         with ThreadPoolExecutor(max_workers=1) as pool:
             out = _staged_bins(out_dir, names, matrix_dtype, alt_info,
-                               lambda staging, state: _text_records_pass(model, ctx, src, table, chunk_bytes, min_af, indel_min_af, min_coverage,
-                                                                         st, alt_info, state, staging, pool, beds, train=labels),
+                               lambda staging, state: _records_pass(model, _KeyedRecords(ctx, table, beds, staging, alt_info, train=labels), src,
+                                                                    chunk_bytes, min_af, indel_min_af, min_coverage, st, state, pool),
                                st, staging_cls=staging_of)
         st["sites"] = st.get("sites", 0) + sum(out.values())
         result = {}
@@ -2562,11 +2511,3 @@ def mpileup_to_train_bins(model, mpileup_path_or_bytes, fasta_path, fai_text, tr
             result[name] = dict(sites=sites, variants=variants, non_variants=non_variants, kept=kept, ratio=ratio, truth=n_truth,
                                 recall=variants / n_truth if n_truth else float("nan"))
         return result
-    finally:
-        if text is not None:
-            try:
-                text.close()
-            except BufferError:                  # (an exception on its way up still holds views of the mapping)
-                pass
-        if g is not None:
-            g.close()

@@ -383,6 +383,15 @@ def big_insertions(n=120):
     return b"".join(b"+3" + bytes(let[(k // 8 ** j) % 8] for j in range(3)) for k in range(n))
 
 
+def outgrown_blob_text(contig=b"big"):
+    """300 lines, positions 50..249 with 120 distinct insertions each: 200 neighbouring sites whose alt_info (about 1 KB a site) does not
+    fit the blob budgeted for a first slot (64 bytes a site + 64 KB) -> (contig, seq, text)"""
+    seq = np.random.default_rng(43).choice(np.frombuffer(b"ACGT", np.uint8), 300).astype(np.uint8)
+    ins = big_insertions()
+    lines = [b"%s\t%d\tN\t10\t%s\tI\n" % (contig, p, bytes([seq[p - 1]]) * 10 + (ins if 50 <= p < 250 else b"")) for p in range(1, 301)]
+    return contig.decode(), seq, b"".join(lines)
+
+
 def three_causes_text(contig=b"tri"):
     """one text with three reasons to start a contig over: 200 neighbouring sites of 120 distinct insertions (positions 50..249: their
     alt_info outgrows a first slot's blob), the deep column at 1,000 (a count outside int16) and another name on two lines in three of

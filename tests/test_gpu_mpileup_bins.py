@@ -468,6 +468,24 @@ def test_a_deep_column_makes_every_file_int32(tmp_path, model):
     assert sorted(os.listdir(tmp_path / "b")) == ["deep.pd.bin", "s0.pd.bin", "s1.pd.bin"]
 
 
+def test_alt_text_outgrowing_its_slot_starts_the_text_over(tmp_path):
+    """the text of test_gpu_pileup_bins' test of the same restart (200 neighbouring sites of 120 distinct insertions): the whole text is
+    run again with larger blobs, and the file is contig_to_bin's and the oracle's, byte for byte.  A model of its own for either call: the
+    slots a model keeps from earlier calls may be large enough already"""
+    from nanosnp_amd.pipeline import contig_to_bin, mpileup_to_bins
+    name, seq, text = rc.outgrown_blob_text()
+    fasta, fai = _write_fasta(tmp_path, {name: seq})
+    pd, n = rc.oracle_pd(tmp_path, text, seq, "big")
+    assert n == 200 and sitefile.pd_to_bin(pd, tmp_path / "want.bin") == n
+    assert contig_to_bin(_model(), text, name, seq, str(tmp_path / "contig.bin")) == n
+    st = {}
+    out = mpileup_to_bins(_model(), text, fasta, fai, str(tmp_path / "b"), stats=st)
+    assert out == {"big": 200} and st["restarts"] == 1
+    got = (tmp_path / "b" / "big.pd.bin").read_bytes()
+    assert got == (tmp_path / "contig.bin").read_bytes() and got == (tmp_path / "want.bin").read_bytes()
+    assert os.listdir(tmp_path / "b") == ["big.pd.bin"]                   # no staging or .tmp name is left
+
+
 # ---- 7. round trip ---------------------------------------------------------------------------------------------------------------------
 def test_round_trip_equals_call_mpileup(tmp_path, genome, pileup_weights):
     from nanosnp_amd.pileup_model import LSTMNetwork

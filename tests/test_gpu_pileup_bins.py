@@ -341,15 +341,7 @@ def test_alt_text_outgrowing_its_slot_starts_the_contig_over(tmp_path):
     it (64 bytes a site + 64 KB); the contig is run again with larger slots and nothing is cut"""
     from oracle import oracle
     from nanosnp_amd.pipeline import contig_to_bin
-    rng = np.random.default_rng(43)
-    seq = rng.choice(np.frombuffer(b"ACGT", np.uint8), 300).astype(np.uint8)
-    let = b"ACGTNRYK"
-    ins = b"".join(b"+3" + bytes(let[(k // 8 ** j) % 8] for j in range(3)) for k in range(120))
-    lines = []
-    for p in range(1, 301):
-        c = bytes([seq[p - 1]]) * 10 + (ins if 50 <= p < 250 else b"")
-        lines.append(b"big\t%d\tN\t10\t%s\tI\n" % (p, c))
-    text = b"".join(lines)
+    _, seq, text = rc.outgrown_blob_text()
     (tmp_path / "b.mpileup").write_bytes(text)
     n = oracle.mpileup_to_pd(str(tmp_path / "b.mpileup"), seq.tobytes(), str(tmp_path / "b.pd"))
     assert n == 200 and sitefile.pd_to_bin((tmp_path / "b.pd").read_bytes(), tmp_path / "want.bin") == n
