@@ -558,6 +558,39 @@ int nsnp_pileup_loss_grad(nsnp_ctx* ctx, const float* const* params, const int32
                           int64_t N, const uint8_t* keep_mask, float keep_scale, float* const* grads, float* site_loss, uint8_t* pred,
                           void* stream);
 
+/* ---- training: the optimiser step (PileupModel/train.py:61-62, clip_grad_norm_ and optimizer.step(); optim.py:67-84, radam.py, lookahead.py) ----
+ * Generic over tensors: nothing here knows the PileupModel.  nsnp_optim_step, asynchronous on `stream`, two launches, no allocation, no host
+ * synchronisation, no floating-point atomics (the same call on the same bits gives the same bits):
+ *   params, grads, exp_avg, exp_avg_sq, slow   HOST arrays of n_tensors (1..NSNP_OPTIM_MAX_TENSORS) DEVICE pointers to fp32 tensors of counts[i] >= 1
+ *              floats each; any 4-byte alignment (views into one flat buffer are fine; 16-byte accesses are used only where all of a tensor's
+ *              pointers allow them, with the same bits either way).  grads is only read.  slow (and every slow[i]) may be NULL when args->sync
+ *              is 0.  Tensors must not overlap.
+ *   args       the scalars of this step, computed by the caller in float64 as the reference's Python does:
+ *                max_norm      > 0: gradients are scaled by c = min(1, max_norm / (norm + 1e-6)), norm the L2 norm over all tensors
+ *                              (torch.nn.utils.clip_grad_norm_); <= 0: no clipping
+ *                wd_mode       0 none; 1 g += weight_decay * p (torch Adam's L2 form); 2 p += decay * p in front of the update (radam.py:69-70,
+ *                              decay = -weight_decay * lr)
+ *                beta1, beta2  in [0, 1):  m = beta1 m + (1 - beta1) g,  v = beta2 v + (1 - beta2) g g
+ *                form          0: p -= a * m / (sqrt(v) * b + eps);  1: p -= a * m
+ *                              Adam:  form 0, a = lr / (1 - beta1^t), b = 1 / sqrt(1 - beta2^t)
+ *                              RAdam: b = 1, a = step_size * lr, form 0 when N_sma >= 5 and form 1 below (radam.py:55-67,73-77)
+ *                sync          0 none; 1 a Lookahead sync: slow += alpha * (p - slow), p = slow (alpha in [0, 1]); 2 the first sync: slow = p
+ *   scratch    device fp32 [nsnp_optim_scratch_floats(n_tensors, counts)]: the per-workgroup sums of g * g; needed when max_norm > 0 or
+ *              grad_norm_out is given, may be NULL otherwise (the first launch is skipped then)
+ *   grad_norm_out  NULL, or one device fp32: the unclipped norm
+ * NSNP_EINVAL, with nothing launched, for a null pointer, n_tensors outside 1..64, a count below 1, a pointer that is not 4-byte aligned, beta1 or
+ * beta2 outside [0, 1), alpha outside [0, 1], form / wd_mode / sync outside their lists.
+ * nsnp_optim_scratch_floats: the floats of scratch for these counts (>= 1), or NSNP_EINVAL; no device is touched. */
+#define NSNP_OPTIM_MAX_TENSORS 64
+typedef struct nsnp_optim_args {
+    double max_norm, weight_decay, decay, beta1, beta2, eps, a, b, alpha;
+    int wd_mode, form, sync;
+} nsnp_optim_args;
+int64_t nsnp_optim_scratch_floats(int n_tensors, const int64_t* counts);
+int nsnp_optim_step(nsnp_ctx* ctx, int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                    float* const* exp_avg_sq, float* const* slow, const int64_t* counts, const nsnp_optim_args* args, float* scratch,
+                    float* grad_norm_out, void* stream);
+
 /* ---- HaplotypeModel ------------------------------------------------------------------- */
 /* seq/bq/mq/hap: device int32 [N,D,L] planes as write_to_bins.py:44-61 stores them (padding
  * rows are -2); ref_row: device int32 [N,L].  out: device fp32 [N,105,L] -- float64 math as

@@ -86,6 +86,8 @@ _SIGNATURES = {
     "nsnp_pileup_train_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
     "nsnp_pileup_loss_grad": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
                                         C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nsnp_optim_scratch_floats": (C.c_int64, [C.c_int, C.c_void_p]),
+    "nsnp_optim_step": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 10),
     "nsnp_mpileup_tokenise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
     "nsnp_mpileup_tokenise_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 5 + [C.c_void_p] * 9),
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -303,6 +305,20 @@ def _stream_ptr(stream=None):
 
 def _dptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class OptimArgs(C.Structure):
+    """nsnp_optim_args of include/nanosnp.h: the scalars of one optimiser step, float64 as the caller computed them"""
+    _fields_ = [(k, C.c_double) for k in ("max_norm", "weight_decay", "decay", "beta1", "beta2", "eps", "a", "b", "alpha")] + \
+               [(k, C.c_int) for k in ("wd_mode", "form", "sync")]
+
+
+OPTIM_MAX_TENSORS = 64
+
+
+class OptimTensors:
+    """The tensors of Context.optim_step, checked once (Context.optim_tensors): the five pointer tables, the counts, the scratch size"""
+    __slots__ = ("n", "keep", "params", "grads", "exp_avg", "exp_avg_sq", "slow", "counts", "scratch_floats", "device", "grad_ptrs")
 
 
 class Context:
@@ -1124,6 +1140,63 @@ class Context:
                                              float(keep_scale), gp, _dptr(site_loss), _dptr(pred), _stream_ptr(stream)),
               self.handle, "nsnp_pileup_loss_grad")
         return site_loss, pred
+
+    def optim_scratch_floats(self, counts):
+        """floats of the partial-sum scratch of optim_step for tensors of these element counts"""
+        arr = (C.c_int64 * len(counts))(*[int(c) for c in counts])
+        n = int(self.lib.nsnp_optim_scratch_floats(len(counts), arr))
+        if n < 1:
+            raise NanoSNPError(f"optim_step: 1..{OPTIM_MAX_TENSORS} tensors of at least one element each")
+        return n
+
+    def optim_tensors(self, params, grads, exp_avg, exp_avg_sq, slow=None):
+        """the tensor lists of optim_step, checked once -> OptimTensors.  Every list: as many contiguous fp32 tensors on this context's device
+        as params, entry i in the shape of params[i]; views into a larger buffer are fine.  slow None: no Lookahead buffers (sync 0 only)."""
+        import torch
+        n = len(params)
+        if not 1 <= n <= OPTIM_MAX_TENSORS:
+            raise NanoSNPError(f"optim_step: 1..{OPTIM_MAX_TENSORS} tensors, got {n}")
+        lists = {"params": params, "grads": grads, "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
+        if slow is not None:
+            lists["slow"] = slow
+        for what, ts in lists.items():
+            if len(ts) != n:
+                raise NanoSNPError(f"optim_step: {len(ts)} {what} for {n} params")
+            for t, p in zip(ts, params):
+                if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device.index != self.device
+                        or not t.is_contiguous() or t.shape != p.shape or t.numel() < 1):
+                    raise NanoSNPError(f"optim_step: {what} must be non-empty contiguous fp32 tensors on cuda:{self.device} in the shapes of params")
+        ot = OptimTensors()
+        ot.n, ot.keep, ot.device = n, lists, params[0].device
+        for what in ("params", "grads", "exp_avg", "exp_avg_sq", "slow"):
+            setattr(ot, what, (C.c_void_p * n)(*[t.data_ptr() for t in lists[what]]) if what in lists else None)
+        ot.grad_ptrs = tuple(t.data_ptr() for t in grads)
+        ot.counts = (C.c_int64 * n)(*[t.numel() for t in params])
+        ot.scratch_floats = self.optim_scratch_floats([t.numel() for t in params])
+        return ot
+
+    def optim_step(self, tensors, args, scratch=None, grad_norm_out=None, stream=None):
+        """One fused optimiser step (nsnp_optim_step: gradient norm, clip, Adam / RAdam moments and update, Lookahead sync; two launches,
+        asynchronous).  tensors: an OptimTensors, or the tuple (params, grads, exp_avg, exp_avg_sq[, slow]) to check now; args: an OptimArgs
+        (the float64 scalars of this step); scratch: device fp32 of at least tensors.scratch_floats, made here when None and needed;
+        grad_norm_out: None or one device fp32 that receives the unclipped norm.  -> grad_norm_out."""
+        import torch
+        ot = tensors if isinstance(tensors, OptimTensors) else self.optim_tensors(*tensors)
+        if not isinstance(args, OptimArgs):
+            raise NanoSNPError("optim_step: args must be an OptimArgs")
+        if args.sync != 0 and ot.slow is None:
+            raise NanoSNPError("optim_step: a Lookahead sync needs the slow buffers")
+        if scratch is None and (args.max_norm > 0 or grad_norm_out is not None):
+            scratch = torch.empty(ot.scratch_floats, dtype=torch.float32, device=ot.device)
+        if scratch is not None and (scratch.dtype != torch.float32 or not scratch.is_cuda or scratch.device != ot.device
+                                    or not scratch.is_contiguous() or scratch.numel() < ot.scratch_floats):
+            raise NanoSNPError(f"optim_step: scratch fp32 [{ot.scratch_floats}] on the device")
+        if grad_norm_out is not None and (grad_norm_out.dtype != torch.float32 or not grad_norm_out.is_cuda or grad_norm_out.device != ot.device
+                                          or grad_norm_out.numel() != 1):
+            raise NanoSNPError("optim_step: grad_norm_out one fp32 on the device")
+        check(self.lib.nsnp_optim_step(self.handle, ot.n, ot.params, ot.grads, ot.exp_avg, ot.exp_avg_sq, ot.slow, ot.counts, C.byref(args),
+                                       _dptr(scratch), _dptr(grad_norm_out), _stream_ptr(stream)), self.handle, "nsnp_optim_step")
+        return grad_norm_out
 
     def pileup_gather_windows(self, counts, center_idx, stream=None):
         import torch

@@ -1,20 +1,32 @@
-"""Train the PileupModel on training window files (<chr>.td.bin): the reference's ``train()`` (PileupModel/train.py:27-90) on the device.
+"""Train the PileupModel on training window files (<chr>.td.bin): the reference's ``train()`` (PileupModel/train.py:27-90) and the epoch loop
+around it (train.py:222-247) on the device.
 
 ``PileupTrainer`` owns the 24 parameters as fp32 device tensors; ``loss_and_grad`` is one C-ABI call (nsnp_pileup_loss_grad: forward that
 keeps the gate activations, label-smoothed loss, backpropagation through time, weight gradients - hand-written HIP, fp32 MFMA) that
-overwrites the gradient buffers each parameter's ``.grad`` is bound to.  PyTorch does the plumbing only: device tensors, the random keep
-mask, gradient clipping and the optimiser.  fp32 only, one rank only.
+overwrites the gradient buffers each parameter's ``.grad`` is bound to.  ``DeviceOptimizer`` is the rest of a step as one more C-ABI call
+(nsnp_optim_step: gradient norm, clip, Adam / RAdam, Lookahead sync - two launches), with the reference's ``Optimizer`` bookkeeping
+(optim.py:10-39) around it; ``fit`` is the epoch loop with the learning-rate decay.  PyTorch does the plumbing only: device tensors and the
+random keep mask - and, when the caller passes a torch optimiser of their own, the clipping and that optimiser.  fp32 only, one rank only.
 
 Departures from the reference's loop:
   * the order is a seeded ``torch.randperm`` of each PASS of a file (fed to the kernel as centre indices, no window is copied), where the
     DataLoader shuffles a whole file;
   * the dropout mask between the two LSTM layers comes from a seeded torch generator on the device, not from the stream nn.LSTM draws from;
-  * the default optimiser is plain Adam (lr 1e-4); the reference wraps it in Lookahead, which torch does not have - pass your own;
+  * ``train_train_bins`` without an optimiser still steps plain Adam (lr 1e-4); ``fit`` defaults to the shipped configuration,
+    ``DeviceOptimizer(kind="LookaheadAdam", lr=1e-4)``;
+  * Adam's moments are updated as ``m = beta1 m + (1 - beta1) g`` and the denominator as ``sqrt(v) * (1 / sqrt(1 - beta2^t)) + eps``, where
+    torch writes a lerp and a division: the same numbers up to fp32 rounding (tests/golden/pileup_optim.npz is the reference's own run);
+  * a reference checkpoint's Lookahead slow buffers are keyed by ``id()`` and cannot be mapped to parameters: ``load_state_dict`` ignores them
+    and the slow buffers restart at the next sync, which is what the reference itself does after such a load;
   * the two indel heads get no gradient, as in the reference (model.py:109-110 leaves their losses out), and are carried along unchanged.
-Not here: ``balance_dataset``, the ``first_stage`` freeze, learning-rate decay, HaplotypeModel training, split precisions, sharding.
+Kept quirks: Lookahead's slow buffer is created at the FIRST sync (step k) as a copy of the fast weights, so that sync changes nothing and
+the first interpolation is at step 2k (lookahead.py:39-43); RAdam's weight decay is the decoupled ``p -= wd lr p`` (radam.py:69-70).
+Not here: ``balance_dataset``, the ``first_stage`` freeze, Novograd / Ranger / SGD / Adadelta, HaplotypeModel training, split precisions,
+sharding.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
@@ -108,11 +120,15 @@ class PileupTrainer:
             fwd.update({k: torch.from_numpy(v.copy()) for k, v in self.indel.items()})
         return enc, fwd
 
-    def save_checkpoint(self, path, epoch=0):
-        """the ``torch.save`` dict {encoder, forward_layer, epoch} LSTMNetwork.from_checkpoint reads back"""
+    def save_checkpoint(self, path, epoch=0, optimizer=None):
+        """the ``torch.save`` dict {encoder, forward_layer, epoch} LSTMNetwork.from_checkpoint reads back; with a DeviceOptimizer also
+        {optimizer: its state_dict(), epoch: its current_epoch, step: its global_step}, the entries of PileupModel/utils.py:67-77"""
         import torch
         enc, fwd = self.state_dicts()
-        torch.save({"encoder": enc, "forward_layer": fwd, "epoch": int(epoch)}, path)
+        ck = {"encoder": enc, "forward_layer": fwd, "epoch": int(epoch)}
+        if optimizer is not None:
+            ck.update(optimizer=optimizer.state_dict(), epoch=int(optimizer.current_epoch), step=int(optimizer.global_step))
+        torch.save(ck, path)
 
     def to_model(self, model=None, **kw):
         """a pileup_model.LSTMNetwork with these weights, through the existing upload path (packs the inference images: once per epoch, not
@@ -122,6 +138,166 @@ class PileupTrainer:
         m.encoder.load_state_dict(enc)
         m.forward_layer.load_state_dict(fwd)
         return m
+
+
+OPTIMIZER_KINDS = {"Adam": (False, False), "LookaheadAdam": (True, False), "Radam": (False, True), "LookaheadRadam": (True, True)}
+
+
+def step_scalars(radam, t, lr, beta1, beta2, weight_decay):
+    """the float64 scalars of step t (1-based) -> dict(a, b, form, wd_mode, decay) of include/nanosnp.h's nsnp_optim_args.
+    Adam: torch.optim.Adam's bias corrections; RAdam: N_sma and step_size in the expression order of PileupModel/radam.py:55-67."""
+    if not radam:
+        return dict(a=lr / (1 - beta1 ** t), b=1.0 / math.sqrt(1 - beta2 ** t), form=0, wd_mode=1 if weight_decay != 0 else 0, decay=0.0)
+    beta2_t = beta2 ** t
+    N_sma_max = 2 / (1 - beta2) - 1
+    N_sma = N_sma_max - 2 * t * beta2_t / (1 - beta2_t)
+    if N_sma >= 5:
+        step_size = math.sqrt((1 - beta2_t) * (N_sma - 4) / (N_sma_max - 4) * (N_sma - 2) / N_sma * N_sma_max / (N_sma_max - 2)) / (1 - beta1 ** t)
+    else:
+        step_size = 1.0 / (1 - beta1 ** t)
+    return dict(a=step_size * lr, b=1.0, form=0 if N_sma >= 5 else 1, wd_mode=2 if weight_decay != 0 else 0, decay=-weight_decay * lr)
+
+
+class DeviceOptimizer:
+    """The reference's ``Optimizer`` (PileupModel/optim.py:10-39) over one fused device step: clip_grad_norm_, Adam or RAdam and the Lookahead
+    wrapper (lookahead.py) are ONE call of nsnp_optim_step per batch.
+
+    trainer_or_params: a PileupTrainer, or a list of contiguous fp32 device tensors whose ``.grad`` is set before every step (at most 64).
+    kind: "LookaheadAdam" (the shipped configurations), "Adam", "LookaheadRadam", "Radam".  Owns exp_avg, exp_avg_sq and the slow buffers as
+    device tensors and the step counters; ``lr``, ``global_step`` (starts at 1), ``current_epoch`` and ``epoch()`` are optim.py's."""
+
+    def __init__(self, trainer_or_params, kind="LookaheadAdam", lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, alpha=0.5, k=6,
+                 ctx=None):
+        import torch
+        if kind not in OPTIMIZER_KINDS:
+            raise ValueError(f"kind: one of {sorted(OPTIMIZER_KINDS)}, got {kind!r}")
+        self.trainer = trainer_or_params if hasattr(trainer_or_params, "parameters") and hasattr(trainer_or_params, "ctx") else None
+        self.params = list(self.trainer.parameters() if self.trainer is not None else trainer_or_params)
+        if not self.params:
+            raise ValueError("no parameters")
+        self.ctx = ctx if ctx is not None else (self.trainer.ctx if self.trainer is not None else _lib.Context(self.params[0].device.index or 0))
+        self.kind = kind
+        self.lookahead, self.radam = OPTIMIZER_KINDS[kind]
+        beta1, beta2 = float(betas[0]), float(betas[1])
+        if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+            raise ValueError(f"betas in [0, 1), got {betas}")
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"Invalid slow update rate: {alpha}")
+        if int(k) < 1:
+            raise ValueError(f"Invalid lookahead steps: {k}")
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (beta1, beta2), float(eps), float(weight_decay)
+        self.alpha, self.k = float(alpha), int(k)
+        self.global_step, self.current_epoch = 1, 0
+        self.step_count = 0                                  # state['step'] of every parameter
+        self.lookahead_step = 0
+        self.slow_ready = False                              # the slow buffers hold weights (after the first sync)
+        data = [p.detach() for p in self.params]
+        self.exp_avg = [torch.zeros_like(p) for p in data]
+        self.exp_avg_sq = [torch.zeros_like(p) for p in data]
+        self.slow = [torch.zeros_like(p) for p in data] if self.lookahead else None
+        self._tensors = None
+        self._scratch = None
+        self._args = _lib.OptimArgs()
+
+    def _bind(self):
+        """the checked pointer tables; made again when a gradient buffer moved"""
+        if self.trainer is not None:
+            self.trainer._check_grads()
+        grads = [p.grad for p in self.params]
+        if any(g is None for g in grads):
+            raise _lib.NanoSNPError("DeviceOptimizer.step: a parameter has no .grad")
+        ot = self._tensors
+        if ot is None or ot.grad_ptrs != tuple(g.data_ptr() for g in grads):
+            import torch
+            ot = self.ctx.optim_tensors([p.detach() for p in self.params], grads, self.exp_avg, self.exp_avg_sq, self.slow)
+            self._tensors = ot
+            if self._scratch is None:
+                self._scratch = torch.empty(ot.scratch_floats, dtype=torch.float32, device=ot.device)
+        return ot
+
+    def step(self, max_grad_norm=None, stream=None):
+        """clip at max_grad_norm (None or <= 0: no clipping), one Adam / RAdam step, the Lookahead sync when it is due -> the gradients'
+        norm before clipping, a device scalar (nothing waits for it).  The gradient buffers are not written."""
+        import torch
+        ot = self._bind()
+        self.global_step += 1
+        self.step_count += 1
+        a = self._args
+        for key, val in step_scalars(self.radam, self.step_count, self.lr, self.betas[0], self.betas[1], self.weight_decay).items():
+            setattr(a, key, val)
+        a.max_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
+        a.weight_decay, a.beta1, a.beta2, a.eps, a.alpha = self.weight_decay, self.betas[0], self.betas[1], self.eps, self.alpha
+        a.sync = 0
+        if self.lookahead:
+            self.lookahead_step += 1
+            if self.lookahead_step % self.k == 0:
+                a.sync = 1 if self.slow_ready else 2
+                self.slow_ready = True
+        norm = torch.empty((), dtype=torch.float32, device=ot.device)
+        self.ctx.optim_step(ot, a, self._scratch, norm, stream=stream)
+        return norm
+
+    def zero_grad(self, set_to_none=False):
+        """nothing: nsnp_pileup_loss_grad overwrites the gradients (kept for the call shape of optim.py:27-28)"""
+
+    def epoch(self):
+        self.current_epoch += 1
+
+    def decay_lr(self, ratio):
+        self.lr *= float(ratio)
+
+    def state_dict(self):
+        """{state: {i: {step, exp_avg, exp_avg_sq}}, slow_state: {i: {slow_buffer}}, param_groups: [...]} keyed by parameter index, CPU
+        tensors: the layout of Lookahead.state_dict() (lookahead.py:60-72) with indices where it has id()s"""
+        n = len(self.params)
+        state = {i: {"step": self.step_count, "exp_avg": self.exp_avg[i].cpu().clone(), "exp_avg_sq": self.exp_avg_sq[i].cpu().clone()}
+                 for i in range(n)} if self.step_count > 0 else {}
+        slow = {i: {"slow_buffer": self.slow[i].cpu().clone()} for i in range(n)} if self.lookahead and self.slow_ready else {}
+        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "params": list(range(n))}
+        if self.lookahead:
+            group.update(lookahead_alpha=self.alpha, lookahead_k=self.k, lookahead_step=self.lookahead_step)
+        return {"state": state, "slow_state": slow, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict, global_step=None, current_epoch=None):
+        """a state_dict() of this class, or the ``optimizer`` entry of a checkpoint the reference's utils.save_model wrote (torch's layout:
+        state keyed by parameter index).  The reference's slow_state is keyed by id() and cannot be mapped: it is ignored and the slow
+        buffers restart at the next sync, as after the reference's own load.  lr, betas, eps, weight_decay and the Lookahead settings come
+        from param_groups[0].  global_step / current_epoch: the checkpoint's ``step`` / ``epoch`` entries, when given."""
+        import torch
+        n = len(self.params)
+        groups = state_dict["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != n:
+            raise _lib.NanoSNPError(f"load_state_dict: one parameter group of {n} parameters expected")
+        state = state_dict.get("state", {})
+        if state and sorted(state) != list(range(n)):
+            raise _lib.NanoSNPError(f"load_state_dict: state keyed by the parameter indices 0..{n - 1} expected")
+        steps = {int(float(state[i]["step"])) for i in state}
+        if len(steps) > 1:
+            raise _lib.NanoSNPError("load_state_dict: the parameters have different step counts")
+        for i in range(n):
+            for name, mine in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+                if state:
+                    src = state[i][name]
+                    if tuple(src.shape) != tuple(mine[i].shape):
+                        raise _lib.NanoSNPError(f"load_state_dict: {name} of parameter {i} has shape {tuple(src.shape)}")
+                    mine[i].copy_(src.to(torch.float32))
+                else:
+                    mine[i].zero_()
+        self.step_count = steps.pop() if steps else 0
+        g = groups[0]
+        self.lr, self.betas, self.eps, self.weight_decay = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]), float(g["weight_decay"])
+        if self.lookahead:
+            self.alpha, self.k = float(g.get("lookahead_alpha", self.alpha)), int(g.get("lookahead_k", self.k))
+            self.lookahead_step = int(g.get("lookahead_step", 0))
+            slow = state_dict.get("slow_state", {})
+            self.slow_ready = bool(slow) and set(slow) == set(range(n)) and all("slow_buffer" in slow[i] for i in range(n))
+            if self.slow_ready:
+                for i in range(n):
+                    self.slow[i].copy_(slow[i]["slow_buffer"].to(torch.float32))
+        if global_step is not None:
+            self.global_step = int(global_step)
+        if current_epoch is not None:
+            self.current_epoch = int(current_epoch)
 
 
 def _paths(training_paths):
@@ -147,8 +323,8 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     in the order of a seeded ``torch.randperm`` (CPU generator seeded with `seed`, one draw per pass in file order), batches of
     `batch_size` restart with every pass; the order reaches the kernel as centre indices.  Per batch: a Bernoulli keep mask [n,33,128] with
     keep probability 1 - dropout from a device generator seeded with `seed` (none at dropout 0), loss_and_grad,
-    clip_grad_norm_(parameters, max_grad_norm) (skipped when max_grad_norm is None), optimizer.step().  optimizer None: torch.optim.Adam(lr=1e-4,
-    betas=(0.9, 0.999), eps=1e-8).  mean_loss is the mean over batches of the batch loss (the quantity train.py:60 accumulates, per batch
+    clip_grad_norm_(parameters, max_grad_norm) (skipped when max_grad_norm is None), optimizer.step() - with a DeviceOptimizer both are its
+    one fused step(max_grad_norm), and torch's clip does not run.  optimizer None: torch.optim.Adam(lr=1e-4, betas=(0.9, 0.999), eps=1e-8).  mean_loss is the mean over batches of the batch loss (the quantity train.py:60 accumulates, per batch
     rather than per site); the accuracies are over sites, from the argmax the loss kernel writes."""
     import torch
     import torch.distributed as tdist
@@ -163,6 +339,7 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     ctx, dev = trainer.ctx, trainer.device
     if optimizer is None:
         optimizer = torch.optim.Adam(trainer.parameters(), lr=1e-4, betas=(0.9, 0.999), eps=1e-8)
+    fused = isinstance(optimizer, DeviceOptimizer)
     st = stats if stats is not None else {}
     for k in ("passes", "rows", "bytes_h2d"):
         st.setdefault(k, 0)
@@ -205,9 +382,12 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
                 if dropout > 0.0:
                     mask = (torch.rand((n, 33, 128), generator=mask_gen, device=dev) >= float(dropout)).to(torch.uint8)
                 loss, pred = trainer._loss_and_grad_cls(ds.x32[:m * 33], centers[o:o + n].contiguous(), cls[o:o + n], n, mask, dropout)
-                if max_grad_norm is not None:
-                    torch.nn.utils.clip_grad_norm_(trainer.parameters(), max_grad_norm)
-                optimizer.step()
+                if fused:
+                    optimizer.step(max_grad_norm)
+                else:
+                    if max_grad_norm is not None:
+                        torch.nn.utils.clip_grad_norm_(trainer.parameters(), max_grad_norm)
+                    optimizer.step()
                 batch_losses.append(loss)
                 correct += (pred == cls[o:o + n, :2]).sum(0)
                 sites += n
@@ -216,3 +396,41 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     mean_loss = float(torch.stack(batch_losses).double().mean()) if batch_losses else float("nan")
     return {"sites": sites, "batches": len(batch_losses), "mean_loss": mean_loss, "gt_accuracy": float(correct[0]) / div,
             "zy_accuracy": float(correct[1]) / div}
+
+
+def fit(trainer, training_paths, validating_paths=None, epochs=1, optimizer=None, batch_size=2000, dropout=0.3, max_grad_norm=20.0,
+        decay_ratio=0.98, begin_to_adjust_lr=10, seed=2022, save_prefix=None, start_epoch=0, pass_sites=65536, eval_batch_size=None):
+    """The epoch loop of PileupModel/train.py:222-247 -> one dict per epoch: train_train_bins' result plus {epoch, lr (the rate the epoch
+    ran with), global_step, eval (evaluate_train_bins' result or None), checkpoint (its path or None)}.
+
+    Per epoch in range(start_epoch, epochs): optimizer.epoch(); train_train_bins with seed + epoch, so that every epoch has an order and masks
+    of its own; evaluate.evaluate_train_bins on validating_paths when given (through trainer.to_model, one upload per epoch);
+    trainer.save_checkpoint(<save_prefix>.epoch<e>.chkpt, optimizer=optimizer) when save_prefix is given; optimizer.decay_lr(decay_ratio)
+    once epoch >= begin_to_adjust_lr.  optimizer None: DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-4), the shipped configuration.
+    To resume: trainer from the checkpoint, optimizer.load_state_dict(ck["optimizer"], ck["step"], ck["epoch"]), start_epoch=ck["epoch"]."""
+    from . import evaluate
+    if optimizer is None:
+        optimizer = DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-4)
+    fused = isinstance(optimizer, DeviceOptimizer)
+    out, model = [], None
+    for epoch in range(int(start_epoch), int(epochs)):
+        if fused:
+            optimizer.epoch()
+        lr = optimizer.lr if fused else optimizer.param_groups[0]["lr"]
+        res = train_train_bins(trainer, training_paths, optimizer=optimizer, batch_size=batch_size, dropout=dropout, max_grad_norm=max_grad_norm,
+                               seed=int(seed) + epoch, pass_sites=pass_sites)
+        res.update(epoch=epoch, lr=lr, global_step=optimizer.global_step if fused else None, eval=None, checkpoint=None)
+        if validating_paths is not None:
+            model = trainer.to_model(model)
+            res["eval"] = evaluate.evaluate_train_bins(model, validating_paths, batch_size=int(eval_batch_size or batch_size), pass_sites=pass_sites)
+        if save_prefix is not None:
+            res["checkpoint"] = f"{save_prefix}.epoch{epoch}.chkpt"
+            trainer.save_checkpoint(res["checkpoint"], epoch=epoch, optimizer=optimizer if fused else None)
+        if epoch >= int(begin_to_adjust_lr):
+            if fused:
+                optimizer.decay_lr(decay_ratio)
+            else:
+                for g in optimizer.param_groups:
+                    g["lr"] *= float(decay_ratio)
+        out.append(res)
+    return out

@@ -1,0 +1,158 @@
+"""The optimiser step of the reference's training loop (PileupModel/train.py:61-62: clip_grad_norm_, optimizer.step()), restated in float64
+numpy for the tests of nsnp_optim_step and of nanosnp_amd.train.DeviceOptimizer.  Test infrastructure, written from the published rules -
+
+    torch.nn.utils.clip_grad_norm_   norm = sqrt(sum g^2) over all tensors; g *= min(1, max_norm / (norm + 1e-6))
+    torch.optim.Adam                 g += wd p;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;
+                                     p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+    RAdam                            PileupModel/radam.py:43-79: the same moments; N_sma = N_max - 2 t b2^t / (1 - b2^t), N_max = 2 / (1 - b2) - 1;
+                                     p -= wd lr p;  N_sma >= 5: p -= step_size lr m / (sqrt(v) + eps), below: p -= lr / (1 - b1^t) m
+    Lookahead                        PileupModel/lookahead.py:34-58: every k-th step slow += alpha (p - slow), p = slow; the slow buffer is
+                                     created at the FIRST such step as a copy of p, so that step changes nothing
+
+This is not the reference run in float64: radam.py:27,31 casts gradient and parameter to fp32 whatever dtype they have.
+
+The fixture tests/golden/pileup_optim.npz (make_golden_optim.py) holds what the reference's own optimisers computed in fp32 on the tensors,
+gradients and cases listed here; load_fixture() reads it back."""
+from __future__ import annotations
+
+import math
+import os
+
+import numpy as np
+
+SHAPES = ((1,), (3,), (7,), (21,), (1023,), (1024,), (1025,), (33, 5))       # the counts that can break a range mapping
+SIZES = tuple(int(np.prod(s)) for s in SHAPES)
+TOTAL = sum(SIZES)
+STEPS = 14
+RECORD = (1, 5, 6, 7, 12, 13, 14)           # both RAdam branches (N_sma 4.996 at step 5, 5.994 at 6), the no-op first sync (6), the first real one (12)
+CASES = {
+    "la_adam_shipped": dict(kind="LookaheadAdam", lr=1e-4, weight_decay=0.0, alpha=0.5, k=6, max_norm=20.0),
+    "la_adam_wd": dict(kind="LookaheadAdam", lr=1e-2, weight_decay=1e-4, alpha=0.8, k=2, max_norm=2.0),
+    "la_radam": dict(kind="LookaheadRadam", lr=1e-3, weight_decay=1e-4, alpha=0.5, k=6, max_norm=20.0),
+    "adam_plain": dict(kind="Adam", lr=1e-4, weight_decay=0.0, alpha=0.5, k=6, max_norm=None),
+}
+KINDS = {"Adam": (False, False), "LookaheadAdam": (True, False), "Radam": (False, True), "LookaheadRadam": (True, True)}     # (lookahead, radam)
+FACTOR = 4.0                                 # what tests/test_gpu_train.py grants over the reference's own fp32 distance
+ULP = 2.0 ** -23                             # one rounding of a stored fp32 value, relative
+
+
+def bound(ref_abs_max, values):
+    """FACTOR x max(the reference's own distance from float64, one rounding of the largest stored magnitude)"""
+    return FACTOR * max(float(ref_abs_max), ULP * float(np.abs(values).max()))
+
+
+class Rules:
+    """one optimiser over a list of float64 arrays"""
+
+    def __init__(self, params, kind, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, alpha=0.5, k=6, lookahead=None):
+        self.lookahead, self.radam = KINDS[kind]
+        if lookahead is not None:
+            self.lookahead = bool(lookahead)
+        self.p = [np.array(a, np.float64) for a in params]
+        self.m = [np.zeros_like(a) for a in self.p]
+        self.v = [np.zeros_like(a) for a in self.p]
+        self.slow = None
+        self.lr, self.betas, self.eps, self.wd, self.alpha, self.k = float(lr), betas, float(eps), float(weight_decay), float(alpha), int(k)
+        self.t = 0
+
+    def step(self, grads, max_norm=None):
+        """-> the norm of the gradients before clipping"""
+        g = [np.array(a, np.float64) for a in grads]
+        norm = math.sqrt(sum(float((a * a).sum()) for a in g))
+        if max_norm is not None and max_norm > 0:
+            c = min(1.0, max_norm / (norm + 1e-6))
+            g = [a * c for a in g]
+        b1, b2 = self.betas
+        self.t += 1
+        t = self.t
+        if self.radam:
+            b2t = b2 ** t
+            n_max = 2.0 / (1.0 - b2) - 1.0
+            n_sma = n_max - 2.0 * t * b2t / (1.0 - b2t)
+            if n_sma >= 5:
+                step_size = math.sqrt((1 - b2t) * (n_sma - 4) / (n_max - 4) * (n_sma - 2) / n_sma * n_max / (n_max - 2)) / (1 - b1 ** t)
+            else:
+                step_size = 1.0 / (1 - b1 ** t)
+        for i in range(len(self.p)):
+            x = g[i]
+            if not self.radam and self.wd != 0:
+                x = x + self.wd * self.p[i]
+            self.m[i] = b1 * self.m[i] + (1 - b1) * x
+            self.v[i] = b2 * self.v[i] + (1 - b2) * x * x
+            if self.radam:
+                if self.wd != 0:
+                    self.p[i] = self.p[i] - self.wd * self.lr * self.p[i]
+                if n_sma >= 5:
+                    self.p[i] = self.p[i] - step_size * self.lr * self.m[i] / (np.sqrt(self.v[i]) + self.eps)
+                else:
+                    self.p[i] = self.p[i] - step_size * self.lr * self.m[i]
+            else:
+                denom = np.sqrt(self.v[i]) / math.sqrt(1 - b2 ** t) + self.eps
+                self.p[i] = self.p[i] - self.lr / (1 - b1 ** t) * self.m[i] / denom
+        if self.lookahead and t % self.k == 0:
+            if self.slow is None:
+                self.slow = [a.copy() for a in self.p]
+            for i in range(len(self.p)):
+                self.slow[i] = self.slow[i] + self.alpha * (self.p[i] - self.slow[i])
+                self.p[i] = self.slow[i].copy()
+        return norm
+
+
+def split(flat):
+    """a flat [TOTAL] array -> the eight tensors"""
+    out, o = [], 0
+    for s, n in zip(SHAPES, SIZES):
+        out.append(np.asarray(flat[o:o + n]).reshape(s))
+        o += n
+    return out
+
+
+def join(tensors):
+    return np.concatenate([np.asarray(a).reshape(-1) for a in tensors])
+
+
+def run(case, p0, grads, lookahead=None):
+    """the float64 trajectory of a case -> dict(p={step: flat}, m, v, slow (flat or None), norm [STEPS])"""
+    cfg = CASES[case]
+    r = Rules(split(p0), cfg["kind"], lr=cfg["lr"], weight_decay=cfg["weight_decay"], alpha=cfg["alpha"], k=cfg["k"], lookahead=lookahead)
+    out = dict(p={}, norm=np.zeros(STEPS))
+    for s in range(1, STEPS + 1):
+        out["norm"][s - 1] = r.step(split(grads[s - 1]), cfg["max_norm"])
+        if s in RECORD:
+            out["p"][s] = join(r.p)
+    out["m"], out["v"], out["slow"] = join(r.m), join(r.v), None if r.slow is None else join(r.slow)
+    return out
+
+
+# ---- the fixture file: fp32 arrays as four byte planes (the sign / exponent plane and, across steps, the high mantissa plane repeat: deflate
+# finds that only when the bytes of a float are apart) -------------------------------------------------------------------------------------
+def pack(a):
+    a = np.ascontiguousarray(a, np.float32)
+    return a.reshape(-1).view(np.uint8).reshape(-1, 4).T.copy()
+
+
+def unpack(planes, shape):
+    return np.ascontiguousarray(planes.T).view(np.float32).reshape(shape)
+
+
+def case_grads(base, scale):
+    """the gradients of a case: the shared base [STEPS, TOTAL] times the case's power-of-two scale per step, exact in fp32"""
+    return (base * scale[:, None]).astype(np.float32)
+
+
+def load_fixture(path=None):
+    """-> dict(p0 [TOTAL], base [STEPS, TOTAL], cases={name: dict(grads [STEPS, TOTAL], p {step: flat}, m, v, slow or None, norm [STEPS],
+    ref_abs_max dict(p, m, v, slow), ref_norm_rel)})"""
+    path = path or os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pileup_optim.npz")
+    z = np.load(path)
+    assert tuple(z["record"].tolist()) == RECORD and tuple(z["sizes"].tolist()) == SIZES
+    out = dict(p0=unpack(z["p0"], (TOTAL,)), base=unpack(z["grad_base"], (STEPS, TOTAL)), cases={})
+    for name in CASES:
+        ps = unpack(z[f"{name}_p"], (len(RECORD), TOTAL))
+        ram = z[f"{name}_ref_abs_max"]
+        out["cases"][name] = dict(
+            grads=case_grads(out["base"], z[f"{name}_grad_scale"]), p={s: ps[j] for j, s in enumerate(RECORD)},
+            m=unpack(z[f"{name}_m"], (TOTAL,)), v=unpack(z[f"{name}_v"], (TOTAL,)),
+            slow=unpack(z[f"{name}_slow"], (TOTAL,)) if f"{name}_slow" in z.files else None, norm=z[f"{name}_norm"],
+            ref_abs_max=dict(p=float(ram[0]), m=float(ram[1]), v=float(ram[2]), slow=float(ram[3])), ref_norm_rel=float(z[f"{name}_ref_norm_rel"]))
+    return out
