@@ -73,10 +73,11 @@ def truth_table(vcf_text, names):
 
 
 def one_hot(quads):
-    """[(gt21, zy, l1, l2)] -> int32 [n, 90]"""
+    """[(gt21, zy, l1, l2)] -> int32 [n, 90]: column c is 1 where c is one of gt21, 21 + zy, 24 + l1, 57 + l2.  (A truth VCF gives
+    gt21 < 21, zy < 3 and lengths < 33; the packed code has room for more, and a column beyond 89 does not exist.)"""
     y = np.zeros((len(quads), 90), np.int32)
     for i, (gt, zy, l1, l2) in enumerate(quads):
-        y[i, [gt, 21 + zy, 24 + l1, 57 + l2]] = 1
+        y[i, [c for c in (gt, 21 + zy, 24 + l1, 57 + l2) if c < 90]] = 1
     return y
 
 

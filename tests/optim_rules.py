@@ -9,6 +9,9 @@ numpy for the tests of nsnp_optim_step and of nanosnp_amd.train.DeviceOptimizer.
     Lookahead                        PileupModel/lookahead.py:34-58: every k-th step slow += alpha (p - slow), p = slow; the slow buffer is
                                      created at the FIRST such step as a copy of p, so that step changes nothing
 
+plan / owner / first_float_of restate the range map of nsnp_optim_step (which workgroup visits which floats), RANGE_SETS are the tensor
+sets of tests/test_gpu_optim_ranges.py.
+
 This is not the reference run in float64: radam.py:27,31 casts gradient and parameter to fp32 whatever dtype they have.
 
 The fixture tests/golden/pileup_optim.npz (make_golden_optim.py) holds what the reference's own optimisers computed in fp32 on the tensors,
@@ -34,6 +37,46 @@ CASES = {
 KINDS = {"Adam": (False, False), "LookaheadAdam": (True, False), "Radam": (False, True), "LookaheadRadam": (True, True)}     # (lookahead, radam)
 FACTOR = 4.0                                 # what tests/test_gpu_train.py grants over the reference's own fp32 distance
 ULP = 2.0 ** -23                             # one rounding of a stored fp32 value, relative
+
+
+# ---- the range map of nsnp_optim_step (optim_step.hip, "Range map"), restated --------------------------------------------------------------
+TILE, MAX_GRID = 1024, 2048
+SMALL_2 = (1, 1023, 1024, 1025, 2047, 2048, 2049, 3073)     # around a range of 2,048: see tests/test_gpu_optim_ranges.py
+SMALL_4 = (1, 1023, 1024, 1025, 3073, 4095, 4096, 4097, 6145)                # around a range of 4,096
+# the tensor sets of tests/test_gpu_optim_ranges.py: counts in table order, and what its docstring claims of them
+RANGE_SETS = {
+    "mult2": dict(counts=SMALL_2[:4] + (2041 * 1024 + 5,) + SMALL_2[4:], filler=4, mult=2, grid=1031),
+    "mult4": dict(counts=SMALL_4[:4] + (2047 * 2048 + 5,) + SMALL_4[4:], filler=4, mult=4, grid=1035),
+    "partials": dict(counts=(300 * 1024 + 5,), filler=0, mult=1, grid=301),
+}
+
+
+def plan(counts):
+    """-> (mult, first): mult the smallest power of two with sum(ceil(n / (1024 mult))) <= 2048, a range being 1,024 mult floats and a
+    workgroup serving one range; first[i] the first workgroup of tensor i, first[len(counts)] the grid"""
+    assert len(counts) >= 1 and all(int(n) >= 1 for n in counts)
+    mult = 1
+    while sum(-(-int(n) // (TILE * mult)) for n in counts) > MAX_GRID:
+        mult *= 2
+    first = [0]
+    for n in counts:
+        first.append(first[-1] + -(-int(n) // (TILE * mult)))
+    return mult, first
+
+
+def owner(counts, tensor, offset):
+    """the workgroup that visits float `offset` of tensor `tensor`, and the tile of its range the float lies in"""
+    mult, first = plan(counts)
+    assert 0 <= offset < counts[tensor]
+    return first[tensor] + offset // (TILE * mult), offset % (TILE * mult) // TILE
+
+
+def first_float_of(counts, workgroup):
+    """-> (tensor, offset) of the first float that workgroup visits"""
+    mult, first = plan(counts)
+    assert 0 <= workgroup < first[-1]
+    t = max(i for i in range(len(counts)) if first[i] <= workgroup)
+    return t, (workgroup - first[t]) * TILE * mult
 
 
 def bound(ref_abs_max, values):

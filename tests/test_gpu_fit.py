@@ -87,38 +87,46 @@ def _steps(tr, opt, x, cls, first, last):
         opt.step(MAX_NORM)
 
 
-def test_resume_is_bit_exact(rows, tmp_path):
-    """14 straight steps = 7 steps, save_checkpoint(optimizer=...), a fresh trainer from the file plus load_state_dict, 7 more steps.  The
-    checkpoint is cut between the first sync (step 6, which fills the slow buffers) and the second (step 12, which reads them)."""
+@pytest.mark.parametrize("kind, cut", [("LookaheadAdam", 7), ("LookaheadRadam", 5)])
+def test_resume_is_bit_exact(rows, tmp_path, kind, cut):
+    """14 straight steps = `cut` steps, save_checkpoint(optimizer=...), a fresh trainer from the file plus load_state_dict, the other steps.
+    LookaheadAdam, 7: the checkpoint is cut between the first sync (step 6, which fills the slow buffers) and the second (step 12, which
+    reads them).  LookaheadRadam, 5: it is written while N_sma < 5 and before any sync - the file holds no slow buffers - and the first
+    resumed step is both the first form = 0 step of RAdam and the first Lookahead sync."""
     import torch
     from nanosnp_amd import train
     _, x, label = rows
     xd = torch.from_numpy(x).cuda()
     cls = torch.from_numpy(er.decode_labels(label)[0].astype(np.int64)).cuda()
     a = _trainer()
-    oa = train.DeviceOptimizer(a, kind="LookaheadAdam", lr=LR, weight_decay=1e-4)
+    oa = train.DeviceOptimizer(a, kind=kind, lr=LR, weight_decay=1e-4)
     _steps(a, oa, xd, cls, 0, 14)
     b = _trainer()
-    ob = train.DeviceOptimizer(b, kind="LookaheadAdam", lr=LR, weight_decay=1e-4)
+    ob = train.DeviceOptimizer(b, kind=kind, lr=LR, weight_decay=1e-4)
     ob.epoch()
-    _steps(b, ob, xd, cls, 0, 7)
+    _steps(b, ob, xd, cls, 0, cut)
     path = str(tmp_path / "mid.chkpt")
     b.save_checkpoint(path, optimizer=ob)
     ck = torch.load(path, map_location="cpu", weights_only=False)
-    assert ck["epoch"] == 1 and ck["step"] == 8 and sorted(ck["optimizer"]) == ["param_groups", "slow_state", "state"]
-    assert sorted(ck["optimizer"]["state"]) == sorted(ck["optimizer"]["slow_state"]) == list(range(24))
+    assert ck["epoch"] == 1 and ck["step"] == cut + 1 and sorted(ck["optimizer"]) == ["param_groups", "slow_state", "state"]
+    assert sorted(ck["optimizer"]["state"]) == list(range(24)) and sorted(ck["optimizer"]["slow_state"]) == (list(range(24)) if cut >= 6 else [])
     assert sorted(ck["optimizer"]["state"][0]) == ["exp_avg", "exp_avg_sq", "step"] and not ck["optimizer"]["state"][0]["exp_avg"].is_cuda
+    if kind == "LookaheadRadam":
+        assert [train.step_scalars(True, t, LR, 0.9, 0.999, 1e-4)["form"] for t in (cut, cut + 1)] == [1, 0] and cut + 1 == ob.k
     c = train.PileupTrainer.from_checkpoint(path, chunk_sites=64)
-    oc = train.DeviceOptimizer(c, kind="LookaheadAdam", lr=3.0, weight_decay=0.5, alpha=0.1, k=3)      # (every setting comes from the file)
+    oc = train.DeviceOptimizer(c, kind=kind, lr=3.0, weight_decay=0.5, alpha=0.1, k=3)               # (every setting comes from the file)
     oc.load_state_dict(ck["optimizer"], ck["step"], ck["epoch"])
-    assert (oc.lr, oc.weight_decay, oc.alpha, oc.k, oc.global_step, oc.current_epoch, oc.step_count) == (LR, 1e-4, 0.5, 6, 8, 1, 7)
-    _steps(c, oc, xd, cls, 7, 14)
+    assert (oc.lr, oc.weight_decay, oc.alpha, oc.k, oc.global_step, oc.current_epoch, oc.step_count) == (LR, 1e-4, 0.5, 6, cut + 1, 1, cut)
+    assert oc.slow_ready == (cut >= 6) and oc.lookahead_step == cut
+    _steps(c, oc, xd, cls, cut, 14)
     torch.cuda.synchronize()
     for pa, pc in zip(_host(a), _host(c)):
         assert np.array_equal(pa, pc)
     for ta, tc in zip(oa.exp_avg + oa.exp_avg_sq + oa.slow, oc.exp_avg + oc.exp_avg_sq + oc.slow):
         assert torch.equal(ta, tc)
     assert oa.global_step == oc.global_step == 15
+    if kind != "LookaheadAdam":
+        return
     # a reference checkpoint's optimizer entry: torch's state plus a slow_state keyed by id() - the moments load, the slow buffers restart
     theirs = {"state": {i: {"step": torch.tensor(7.0), "exp_avg": st["exp_avg"], "exp_avg_sq": st["exp_avg_sq"]} for i, st in ck["optimizer"]["state"].items()},
               "slow_state": {140000000000000 + 64 * i: v for i, v in ck["optimizer"]["slow_state"].items()},

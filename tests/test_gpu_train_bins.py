@@ -148,20 +148,24 @@ def _truth_for(keys, t, pattern, rng):
     return tk, dict(zip(tk.tolist(), quads))
 
 
-def _run_entry(ctx, table, keys, centers, tk, quads, thr, seed, pinned=False, m_extra=5):
+def _run_entry(ctx, table, keys, centers, tk, quads, thr, seed, pinned=False, m_extra=5, extra_rows=0, codes=None):
+    """-> (kept centres, their label rows, meta, the whole label buffer).  extra_rows: rows of a pinned label buffer behind the N the entry
+    is told of; codes: the packed codes of tk where they are already an array (a large table)"""
     import torch
     dev = torch.device("cuda", 0)
     key_col = np.concatenate([keys, np.full(m_extra, _lib.KEY_FILLER, np.int64)])
-    codes = np.array([g | z << 8 | a << 16 | b << 24 for g, z, a, b in (quads[k] for k in tk.tolist())], np.uint32)
+    if codes is None:
+        codes = np.array([g | z << 8 | a << 16 | b << 24 for g, z, a, b in (quads[k] for k in tk.tolist())], np.uint32)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     kw = {}
     if pinned:
-        kw = dict(label=torch.full((max(len(centers), 1), 90), -7, dtype=torch.int32).pin_memory(), meta=torch.zeros(4, dtype=torch.int64).pin_memory())
+        kw = dict(label=torch.full((max(len(centers), 1) + extra_rows, 90), -7, dtype=torch.int32).pin_memory(),
+                  meta=torch.zeros(4, dtype=torch.int64).pin_memory())
     kept, label, meta = ctx.pileup_label_sites_keys(up(key_col), up(np.asarray(centers, np.int64)), table, up(tk), up(codes.view(np.int32)),
                                                     None if thr is None else up(np.array(thr, np.int64)), seed, **kw)
     torch.cuda.synchronize()
     m = meta.cpu().numpy()
-    return kept.cpu().numpy()[:m[0]], label.cpu().numpy()[:m[0]], m, label
+    return kept.cpu().numpy()[:m[0]], label.cpu().numpy()[:m[0]], m, kw.get("label", label)
 
 
 @pytest.mark.parametrize("n", N_SITES)

@@ -83,6 +83,49 @@ def test_step_scalars_of_the_binding():
     assert train.step_scalars(False, 3, lr, b1, b2, 0.0)["wd_mode"] == 0 and train.step_scalars(True, 3, lr, b1, b2, 0.0)["wd_mode"] == 0
 
 
+PLAN_TABLE = [
+    [1], [1024], [1025], list(orl.SIZES), [1] * 64,
+    [2048 * 1024 - 1], [2048 * 1024], [2048 * 1024 + 1],                        # 2,048 workgroups are the limit: mult 1, 1, 2
+    [2047 * 1024, 1], [2047 * 1024, 1, 1], [2047 * 1024 + 1, 1],                # the same limit reached by several tensors: 1, 2, 2
+    [4096 * 1024], [4096 * 1024 + 1], [2048 * 2048, 1],                         # and the next one: 2, 4, 4
+    [32 * 1024 + 1] * 64,                                                       # 33 tiles each, 2,112 at mult 1: 17 ranges each at mult 2
+    [32 * 1024] * 64, [1 << 31, 3],
+] + [list(s["counts"]) for s in orl.RANGE_SETS.values()]
+
+
+def test_range_map_restated():
+    """optim_rules.plan against the library's own opt_plan, through the only figure the library gives away (the grid), and the claims the
+    docstring of tests/test_gpu_optim_ranges.py makes of its tensor sets"""
+    from nanosnp_amd import _lib
+    lib = _lib.load()
+    for counts in PLAN_TABLE:
+        mult, first = orl.plan(counts)
+        assert len(first) == len(counts) + 1 and first[0] == 0 and all(b > a for a, b in zip(first, first[1:])), counts
+        assert first[-1] <= 2048 and mult & (mult - 1) == 0, counts
+        assert mult == 1 or sum(-(-n // (1024 * (mult // 2))) for n in counts) > 2048, counts             # the SMALLEST such power of two
+        assert lib.nsnp_optim_scratch_floats(len(counts), (C.c_int64 * len(counts))(*counts)) == first[-1], counts
+    want = {(2048 * 1024 - 1,): (1, 2048), (2048 * 1024,): (1, 2048), (2048 * 1024 + 1,): (2, 1025), (2047 * 1024, 1): (1, 2048),
+            (2047 * 1024, 1, 1): (2, 1026), (2047 * 1024 + 1, 1): (2, 1025), (4096 * 1024,): (2, 2048), (4096 * 1024 + 1,): (4, 1025),
+            (2048 * 2048, 1): (4, 1025), (32 * 1024 + 1,) * 64: (2, 64 * 17), (32 * 1024,) * 64: (1, 2048)}
+    for counts, (mult, grid) in want.items():
+        got = orl.plan(counts)
+        assert (got[0], got[1][-1]) == (mult, grid), counts
+    # the sets of the device test are what it says they are: an accidental change of sizes cannot turn it back into a mult = 1 test
+    for name, s in orl.RANGE_SETS.items():
+        mult, first = orl.plan(s["counts"])
+        assert (mult, first[-1]) == (s["mult"], s["grid"]), name
+        assert first[-1] > 257 and s["counts"][s["filler"]] == max(s["counts"]), name                    # a second trip over the partial sums
+    two, four = orl.RANGE_SETS["mult2"], orl.RANGE_SETS["mult4"]
+    assert sum(-(-n // 1024) for n in two["counts"]) == 2058 and sum(-(-n // 2048) for n in four["counts"]) == 2065
+    assert sorted(set(two["counts"]) - {max(two["counts"])}) == [1, 1023, 1024, 1025, 2047, 2048, 2049, 3073]
+    assert sorted(set(four["counts"]) - {max(four["counts"])}) == [1, 1023, 1024, 1025, 3073, 4095, 4096, 4097, 6145]
+    assert orl.RANGE_SETS["partials"]["counts"] == (300 * 1024 + 5,)
+    # the last range of each filler ends inside a tile that is not its first: lanes leave the tile loop at different k
+    assert (2041 * 1024 + 5) % 2048 == 1024 + 5 and (2047 * 2048 + 5) % 4096 == 2048 + 5
+    assert orl.owner(two["counts"], 4, 2048 * 7 + 1024) == (4 + 7, 1) and orl.first_float_of(two["counts"], 4 + 7) == (4, 2048 * 7)
+    assert orl.owner(four["counts"], 9, 6144) == (1034, 2) and orl.first_float_of(four["counts"], 1034) == (9, 4096)
+
+
 def test_symbols_struct_and_scratch_query():
     from nanosnp_amd import _lib
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nanosnp.h")).read(), flags=re.S)
