@@ -156,7 +156,7 @@ int nsnp_ctx_set_option(nsnp_ctx* ctx, const char* name, int64_t value);
  * k_hap_gemm), 7 the convolution GEMM + pooling launches of a CatModel pass (12 + 4), 8 a whole CatModel pass;
  * `launches` then counts passes.  Id 9: the heads launch of a HaplotypeModel pass (the softmax heads of nsnp_hap_forward or the scoring
  * heads of nsnp_hap_eval).  Ids 10-12: the forward, backward and weight-gradient launches of a chunk of nsnp_pileup_loss_grad, one event
- * pair per phase; `launches` counts chunks.  Synchronous. */
+ * pair per phase; `launches` counts chunks.  Ids 13-15: the same three phases of a chunk of nsnp_hap_loss_grad.  Synchronous. */
 int nsnp_ctx_enable_timing(nsnp_ctx* ctx, int enable);
 int nsnp_ctx_read_timing(nsnp_ctx* ctx, int kernel, double* total_ms, int64_t* launches);
 
@@ -669,6 +669,40 @@ int nsnp_hap_eval(nsnp_ctx* ctx, const float* xp, const float* xh, const uint8_t
 
 /* nsnp_pileup_batch_loss for rows of two heads: site_loss fp32 [N,2] (8-byte aligned) -> batch_sum double [ceil(N / batch_size), 2]. */
 int nsnp_hap_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream);
+
+/* ---- training the HaplotypeModel: the loss gradients of a batch (HaplotypeModel/train_dev.py:58-59, model(...) and loss.backward()) ------
+ * fp32 only and one device: with hap_precision 1 or 2 nsnp_hap_loss_grad returns NSNP_EINVAL.  The entries need no nsnp_hap_load_weights:
+ * the parameters are the caller's device tensors in plain state-dict layout, because they change every step; the packed images of the
+ * inference entries are not read and not refreshed (upload a trained state again to score or call with it).
+ *
+ * nsnp_hap_train_reserve allocates the workspace of the saved activations and gate gradients for chunks of max_sites (1..65,536) sites of a
+ * model of n_features (1..128) input features and n_gt, n_zy (each >= 1, at most 16 together) classes; hidden size 256, three layers, windows
+ * of 33 and 11 positions.  1,652,864 bytes per site (413,216 floats: gates, c and h of the 222 (layer, direction, step) triples, the masked
+ * layer inputs, the gradients) plus 2 MB per 128 (site, step) rows of the pileup window (the weight gradients' slices: 277 MB at 512
+ * sites); synchronous.  NSNP_ENOMEM: the previous reservation stays in force.  NSNP_EINVAL for sizes outside these ranges.  A batch larger
+ * than the reservation runs in chunks of that size, in order, adding into the same gradients.
+ *
+ * nsnp_hap_loss_grad, asynchronous on `stream`; every shape follows the dims of the reservation (a caller whose tensors have other dims
+ * reserves again first; the Python wrapper refuses them):
+ *   params     HOST array of 58 DEVICE pointers, the tensors, order and shapes of nsnp_hap_load_weights
+ *   xp, xh     device fp32 [N,F,33] and [N,F,11], as nsnp_hap_eval takes them
+ *   cls        device uint8 [N,2] = { genotype, zygosity }; a class outside its head counts as the head's last
+ *   keep_masks NULL (no dropout), or a HOST array of 4 device uint8 tensors of 0 / 1: behind pileup layer 0 and pileup layer 1 [N,33,512],
+ *              behind haplotype layer 0 and haplotype layer 1 [N,11,512], in the layer output's order [forward 256 | reverse 256].  The next
+ *              layer sees h * mask * keep_scale (keep_scale = 1 / (1 - p) of nn.LSTM(dropout=p)), the backward pass applies the same
+ *              factor.  NULL gives the bits of all-ones masks with scale 1.
+ *   grads      HOST array of 58 device pointers, same shapes: OVERWRITTEN with d(mean gt loss + mean zy loss) / d(param), the means over all
+ *              N sites.  bias_ih and bias_hh of a layer and direction receive the same values.
+ *   site_loss  NULL, or device fp32 [N,2]: the label-smoothed losses of nsnp_hap_eval
+ *   pred       NULL, or device uint8 [N,2]: the first maximum of the genotype / zygosity logits
+ * A head of one class has loss 0, pred 0 and gradient 0, as in nsnp_hap_eval.  N == 0 is a no-op (grads untouched).  NSNP_EINVAL for null
+ * arguments and without a reservation.  The network runs the reduced schedule of the inference entries (layer 2: 17 of 33 and 6 of 11 steps
+ * per direction, dense layer and heads at the centre), which is exact for the gradient too because the loss reads the centre only.  Every
+ * matrix product is fp32 MFMA; no floating-point atomics: the same call gives the same bits twice.  nsnp_ctx_read_timing ids 13, 14, 15: the
+ * forward, backward and weight-gradient phases of a chunk, one event pair each. */
+int nsnp_hap_train_reserve(nsnp_ctx* ctx, int64_t max_sites, int n_features, int n_gt, int n_zy);
+int nsnp_hap_loss_grad(nsnp_ctx* ctx, const float* const* params, const float* xp, const float* xh, const uint8_t* cls, int64_t N,
+                       const uint8_t* const* keep_masks, float keep_scale, float* const* grads, float* site_loss, uint8_t* pred, void* stream);
 
 /* ---- legacy haplotype caller (HaplotypeModel/predict.py -> model.CatModel; not run by run_caller.sh) ---- */
 /* host_tensors: the 132 floating-point tensors of CatModel(nc0=5,nc1=5,nc2=2,nclass=10,nh=256).state_dict()

@@ -84,6 +84,9 @@ _SIGNATURES = {
     "nsnp_pileup_eval_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
     "nsnp_pileup_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_train_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
+    "nsnp_hap_train_reserve": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "nsnp_hap_loss_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_loss_grad": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
                                         C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_optim_scratch_floats": (C.c_int64, [C.c_int, C.c_void_p]),
@@ -345,7 +348,8 @@ class Context:
 
     # ids of nsnp_ctx_read_timing; the last three are ONE event pair around a chain of launches of a pass (include/nanosnp.h)
     KERNELS = ("pileup_l0", "pileup_proj1", "pileup_l1", "pileup_head", "encode_columns", "hap_features",
-               "hap_lstm_chain", "cat_conv_chain", "cat_forward_pass", "hap_head", "train_forward", "train_backward", "train_wgrad")
+               "hap_lstm_chain", "cat_conv_chain", "cat_forward_pass", "hap_head", "train_forward", "train_backward", "train_wgrad",
+               "hap_train_forward", "hap_train_backward", "hap_train_wgrad")
 
     def enable_timing(self, enable=True):
         check(self.lib.nsnp_ctx_enable_timing(self.handle, int(bool(enable))), self.handle, "nsnp_ctx_enable_timing")
@@ -1139,6 +1143,75 @@ class Context:
         check(self.lib.nsnp_pileup_loss_grad(self.handle, pp, _dptr(counts), _dptr(center_idx), _dptr(cls), n, _dptr(keep_mask),
                                              float(keep_scale), gp, _dptr(site_loss), _dptr(pred), _stream_ptr(stream)),
               self.handle, "nsnp_pileup_loss_grad")
+        return site_loss, pred
+
+    @staticmethod
+    def hap_train_shapes(n_features=105, n_gt=10, n_zy=3):
+        """the shapes of the 58 tensors of haplotype_model.state_dict_keys() at these dims (hidden size 256, three layers)"""
+        enc = []
+        for l in range(3):
+            enc += [(1024, n_features if l == 0 else 512), (1024, 256), (1024,), (1024,)] * 2
+        enc += [(256, 512), (256,)]
+        return enc + enc + [(256, 512), (256,), (n_gt, 256), (n_gt,), (n_zy, 256), (n_zy,)]
+
+    def hap_train_reserve(self, max_sites, n_features=105, n_gt=10, n_zy=3):
+        """workspace of hap_loss_grad for chunks of max_sites sites of a model of these dims (1,652,864 bytes per site); synchronous"""
+        check(self.lib.nsnp_hap_train_reserve(self.handle, int(max_sites), int(n_features), int(n_gt), int(n_zy)), self.handle,
+              "nsnp_hap_train_reserve")
+        self._hap_train_dims = (int(n_features), int(n_gt), int(n_zy))
+
+    def _hap_train_tensors(self, tensors, shapes, what):
+        import torch
+        if len(tensors) != 58:
+            raise NanoSNPError(f"hap_loss_grad: expected 58 {what}, got {len(tensors)}")
+        for t, shape in zip(tensors, shapes):
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise NanoSNPError(f"hap_loss_grad: {what} must be contiguous device fp32 tensors in the state-dict shapes of the reserved dims, "
+                                   f"got {tuple(t.shape)} for {shape}")
+        return (C.c_void_p * 58)(*[t.data_ptr() for t in tensors])
+
+    def hap_loss_grad(self, params, xp, xh, cls, grads, keep_masks=None, keep_scale=1.0, n=None, site_loss=None, pred=None, stream=None):
+        """forward, label-smoothed loss and backward of a batch of the HaplotypeModel: grads (58 device fp32 tensors in the shapes of params)
+        are OVERWRITTEN with d(mean gt + mean zy) / d(param) -> (site_loss fp32 [n,2], pred uint8 [n,2]).  params: the 58 device tensors in
+        state-dict order; xp [N,F,33], xh [N,F,11] contiguous device fp32; cls: device uint8 [>= n, 2]; keep_masks: None or four device uint8
+        tensors [n,33,512], [n,33,512], [n,11,512], [n,11,512] (behind pileup layers 0 and 1, haplotype layers 0 and 1), the next layer sees
+        h * mask * keep_scale; n: the sites to run (default: all of xp).  Needs hap_train_reserve with the dims of these tensors; a larger
+        batch runs in chunks of the reservation."""
+        import torch
+        dims = getattr(self, "_hap_train_dims", None)
+        if dims is None:
+            raise NanoSNPError("hap_loss_grad: hap_train_reserve first")
+        F, n_gt, n_zy = dims
+        for t, l, what in ((xp, 33, "xp"), (xh, 11, "xh")):
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape[2] != l:
+                raise NanoSNPError(f"hap_loss_grad: {what} must be a contiguous device fp32 [N,F,{l}]")
+            if t.shape[1] != F:
+                raise NanoSNPError(f"hap_loss_grad: {what} has {t.shape[1]} features, the reservation is for {F}")
+        n_all = int(xp.shape[0])
+        n = n_all if n is None else int(n)
+        dev = xp.device
+        if n < 0 or n > n_all or xh.shape[0] < n:
+            raise NanoSNPError("hap_loss_grad: n sites within xp and xh")
+        if cls.dtype != torch.uint8 or cls.numel() < 2 * n or not cls.is_cuda or not cls.is_contiguous():
+            raise NanoSNPError("hap_loss_grad: cls uint8 [N,2] on the device, one row per site")
+        shapes = self.hap_train_shapes(F, n_gt, n_zy)
+        pp, gp = self._hap_train_tensors(params, shapes, "parameters"), self._hap_train_tensors(grads, shapes, "gradients")
+        mp = None
+        if keep_masks is not None:
+            if len(keep_masks) != 4:
+                raise NanoSNPError("hap_loss_grad: four keep masks (pileup layers 0 and 1, haplotype layers 0 and 1)")
+            for m, l in zip(keep_masks, (33, 33, 11, 11)):
+                if (m.dtype != torch.uint8 or not m.is_cuda or not m.is_contiguous() or m.dim() != 3 or m.shape[0] < n
+                        or tuple(m.shape[1:]) != (l, 512)):
+                    raise NanoSNPError(f"hap_loss_grad: keep mask uint8 [N,{l},512] on the device")
+            mp = (C.c_void_p * 4)(*[m.data_ptr() for m in keep_masks])
+        site_loss = site_loss if site_loss is not None else torch.empty((n, 2), dtype=torch.float32, device=dev)
+        pred = pred if pred is not None else torch.empty((n, 2), dtype=torch.uint8, device=dev)
+        if (site_loss.dtype != torch.float32 or site_loss.numel() < 2 * n or not site_loss.is_cuda or not site_loss.is_contiguous()
+                or pred.dtype != torch.uint8 or pred.numel() < 2 * n or not pred.is_cuda or not pred.is_contiguous()):
+            raise NanoSNPError("hap_loss_grad: site_loss fp32 [N,2] and pred uint8 [N,2] on the device")
+        check(self.lib.nsnp_hap_loss_grad(self.handle, pp, _dptr(xp), _dptr(xh), _dptr(cls), n, mp, float(keep_scale), gp, _dptr(site_loss),
+                                          _dptr(pred), _stream_ptr(stream)), self.handle, "nsnp_hap_loss_grad")
         return site_loss, pred
 
     def optim_scratch_floats(self, counts):

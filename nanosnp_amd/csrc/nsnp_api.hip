@@ -73,6 +73,7 @@ int  nsnp_hap_reserve(nsnp_ctx* ctx);
 void nsnp_cat_free(nsnp_ctx* ctx);   // cat_forward.hip
 void nsnp_tok_free(nsnp_ctx* ctx);   // mpileup_tokenise.hip
 void nsnp_train_free(nsnp_ctx* ctx); // pileup_train.hip
+void nsnp_hap_train_free(nsnp_ctx* ctx); // hap_train.hip
 
 // ---- per-kernel timing ----------------------------------------------------------------------------
 constexpr size_t TIMER_MAX_PAIRS = 8192;
@@ -281,6 +282,7 @@ extern "C" int nsnp_ctx_destroy(nsnp_ctx* ctx)
     if (ctx->pw.head6_b) (void)hipFree(ctx->pw.head6_b);
     nsnp_tok_free(ctx);
     nsnp_train_free(ctx);
+    nsnp_hap_train_free(ctx);
     (void)nsnp_comm_destroy(ctx);
     nsnp_hap_free(ctx);
     nsnp_cat_free(ctx);

@@ -83,6 +83,7 @@ struct CatWeightsDev;   // cat_forward.hip
 enum { NSNP_K_L0 = 0, NSNP_K_PROJ1, NSNP_K_L1, NSNP_K_HEAD, NSNP_K_ENCODE, NSNP_K_HAPFEAT, NSNP_K_HAPLSTM, NSNP_K_CATCONV, NSNP_K_CAT,
        NSNP_K_HAPHEAD,     // the heads launch of a HaplotypeModel pass: k_hap_heads or k_hap_head_eval
        NSNP_K_TRAIN_FWD, NSNP_K_TRAIN_BWD, NSNP_K_TRAIN_WGRAD,   // the three phases of a chunk of nsnp_pileup_loss_grad, ONE event pair each (pileup_train.hip)
+       NSNP_K_HAPTRAIN_FWD, NSNP_K_HAPTRAIN_BWD, NSNP_K_HAPTRAIN_WGRAD,   // the same three phases of a chunk of nsnp_hap_loss_grad (hap_train.hip)
        NSNP_K_COUNT };
 struct KernelTimer {
     std::vector<hipEvent_t> start[NSNP_K_COUNT], stop[NSNP_K_COUNT];
@@ -141,6 +142,7 @@ struct nsnp_ctx {
     void* rec_tmp; size_t rec_tmp_bytes;      // nsnp_pileup_alt_info scratch: scanned sizes + the staging blob (pileup_records.hip)
     void* evl_tmp; size_t evl_tmp_bytes;      // nsnp_pileup_label_classes scratch: scanned flags + the four classes per row (pileup_eval.hip)
     void* tr_ws; int64_t tr_sites;            // nsnp_pileup_train_reserve: saved activations and gate gradients of a chunk of tr_sites sites (pileup_train.hip)
+    void* ht_ws; int64_t ht_sites; int ht_F, ht_ngt, ht_nzy;   // nsnp_hap_train_reserve: the workspace of a chunk of ht_sites sites at these dims (hap_train.hip)
     void* lab_tmp; size_t lab_tmp_bytes;      // nsnp_pileup_label_sites_keys scratch: scanned flags + two words per site (pileup_labels.hip)
     void* tok_ws; size_t tok_ws_bytes;        // mpileup tokeniser scratch: 4,112 bytes per 8 KB tile of text (mpileup_tokenise.hip)
     void* ctg_ws; size_t ctg_ws_bytes;        // nsnp_mpileup_tokenise_contigs scratch: 8 bytes per line + 16 per 256 lines (mpileup_tokenise.hip)

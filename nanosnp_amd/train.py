@@ -21,8 +21,17 @@ Departures from the reference's loop:
   * the two indel heads get no gradient, as in the reference (model.py:109-110 leaves their losses out), and are carried along unchanged.
 Kept quirks: Lookahead's slow buffer is created at the FIRST sync (step k) as a copy of the fast weights, so that sync changes nothing and
 the first interpolation is at step 2k (lookahead.py:39-43); RAdam's weight decay is the decoupled ``p -= wd lr p`` (radam.py:69-70).
-Not here: ``balance_dataset``, the ``first_stage`` freeze, Novograd / Ranger / SGD / Adadelta, HaplotypeModel training, split precisions,
-sharding.
+Not here: ``balance_dataset``, the ``first_stage`` freeze, Novograd / Ranger / SGD / Adadelta, split precisions, sharding.
+
+The HaplotypeModel (HaplotypeModel/train_dev.py:25-80) has the same pieces for one epoch: ``HaplotypeTrainer`` owns the 58 parameters,
+``loss_and_grad`` is one call of nsnp_hap_loss_grad (two 3-layer BiLSTM encoders of hidden size 256, four keep masks), ``DeviceOptimizer``
+steps them unchanged, ``train_haplotype_bins`` is one epoch over labelled haplotype site files.  Its departures:
+  * no ``pn_value`` upsampling: TrainingDataset draws variants with replacement per refcall block from an unseeded generator; here every
+    row LabelField keeps trains once;
+  * the order is a seeded ``torch.randperm`` of the kept rows of each PASS, not of a file;
+  * the four keep masks come from a seeded torch generator on the device, not from the stream nn.LSTM draws from;
+  * there is no epoch loop for this model yet: ``fit`` stays pileup-only;
+  * Ranger, the other shipped optimiser type, is still out.
 """
 from __future__ import annotations
 
@@ -396,6 +405,241 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     mean_loss = float(torch.stack(batch_losses).double().mean()) if batch_losses else float("nan")
     return {"sites": sites, "batches": len(batch_losses), "mean_loss": mean_loss, "gt_accuracy": float(correct[0]) / div,
             "zy_accuracy": float(correct[1]) / div}
+
+
+
+class HaplotypeTrainer:
+    """The 58 parameters of the HaplotypeModel on the device, with gradients from nsnp_hap_loss_grad: the counterpart of PileupTrainer.
+
+    state_dict: the tensors of model_dev.LSTMNetwork.state_dict() (haplotype_model.state_dict_keys(); the loss modules hold none); config: the
+    reference's config (None: ont_haplotype.yaml's dims), validated by the rules of haplotype_model.LSTMNetwork.  ``params``:
+    ``{key: torch.nn.Parameter}`` in state-dict order; every ``.grad`` is the buffer the kernel overwrites, so DeviceOptimizer(trainer, ...) and
+    ``torch.optim.X(trainer.parameters())`` both step them.  ``chunk_sites``: the workspace reservation (1,652,864 bytes per site); a larger
+    batch runs in chunks of it."""
+
+    def __init__(self, state_dict, config=None, device=0, chunk_sites=512, ctx=None):
+        import torch
+        from . import haplotype_model
+        self.ctx = ctx if ctx is not None else _lib.Context(device)
+        self.device = torch.device("cuda", self.ctx.device)
+        self.config = config
+        self.dims = haplotype_model.LSTMNetwork(config, self.ctx.device, ctx=self.ctx).dims          # (its __init__ refuses what the kernels are not built for)
+        self.keys = haplotype_model.state_dict_keys(self.dims["lstm_layers"])
+        d = self.dims
+        missing = [k for k in self.keys if k not in state_dict]
+        if missing:
+            raise KeyError(f"missing keys {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+        self.params = {}
+        for name, shape in zip(self.keys, _lib.Context.hap_train_shapes(d["pileup_dim"], d["gt_num_class"], d["zy_num_class"])):
+            t = state_dict[name]
+            a = np.array(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32)
+            if a.shape != shape:
+                raise _lib.NanoSNPError(f"{name}: shape {a.shape}, the configuration gives {shape}")
+            p = torch.nn.Parameter(torch.from_numpy(a).to(self.device), requires_grad=True)
+            p.grad = torch.zeros_like(p)
+            self.params[name] = p
+        self._grads = [p.grad for p in self.params.values()]
+        self.chunk_sites = int(chunk_sites)
+        self.ctx.hap_train_reserve(self.chunk_sites, d["pileup_dim"], d["gt_num_class"], d["zy_num_class"])
+
+    @classmethod
+    def from_checkpoint(cls, path, config=None, device=0, **kw):
+        """a ``torch.save``d state dict, as HaplotypeModel/train_dev.py:276 writes it"""
+        import torch
+        return cls(torch.load(path, map_location="cpu", weights_only=False), config, device, **kw)
+
+    def parameters(self):
+        return list(self.params.values())
+
+    def _check_grads(self):
+        # an optimiser's zero_grad(set_to_none=True) unbinds a gradient: bind the kernel's buffer again
+        for p, g in zip(self.params.values(), self._grads):
+            if p.grad is not g:
+                p.grad = g
+
+    def loss_and_grad(self, pileup_x, haplotype_x, gt_target, zy_target, keep_masks=None, p=0.0, stream=None):
+        """pileup_x [N,F,33], haplotype_x [N,F,11]: device tensors as LSTMNetwork.forward takes them (cast to fp32); gt_target, zy_target:
+        integer device tensors [N]; keep_masks: None or four device uint8 tensors [N,33,512], [N,33,512], [N,11,512], [N,11,512] (behind
+        pileup layers 0 and 1, haplotype layers 0 and 1), used with scale 1 / (1 - p) -> (loss, pred): the fp32 scalar mean(gt) + mean(zy) of
+        the label-smoothed losses, summed over the sites in float64, and pred uint8 [N,2].  Every parameter's .grad holds
+        d loss / d parameter afterwards."""
+        import torch
+        xp, xh = pileup_x.to(torch.float32).contiguous(), haplotype_x.to(torch.float32).contiguous()
+        n = int(xp.shape[0])
+        cls = torch.stack([t.reshape(-1).to(device=xp.device, dtype=torch.uint8) for t in (gt_target, zy_target)], dim=1).contiguous()
+        if tuple(cls.shape) != (n, 2):
+            raise ValueError(f"expected two targets of {n} classes")
+        return self._loss_and_grad_cls(xp, xh, cls, n, keep_masks, p, stream)
+
+    def _loss_and_grad_cls(self, xp, xh, cls, n, keep_masks, p, stream=None):
+        import torch
+        if keep_masks is not None and not 0.0 <= float(p) < 1.0:
+            raise ValueError("dropout probability in [0, 1)")
+        self._check_grads()
+        scale = 1.0 / (1.0 - float(p)) if keep_masks is not None else 1.0
+        site_loss, pred = self.ctx.hap_loss_grad(self.parameters(), xp, xh, cls, self._grads, keep_masks, scale, n=n, stream=stream)
+        if n == 0:
+            return torch.full((), float("nan"), dtype=torch.float32, device=xp.device), pred
+        s = self.ctx.hap_batch_loss(site_loss, n, stream=stream)[0]         # (the two-column batch sum: float64, a fixed tree)
+        return ((s[0] + s[1]) / n).to(torch.float32), pred
+
+    def state_dict(self):
+        """the 58 CPU tensors, keyed as model_dev.LSTMNetwork.state_dict() keys them"""
+        return {k: p.detach().cpu().clone() for k, p in self.params.items()}
+
+    def save_checkpoint(self, path):
+        """``torch.save`` of exactly state_dict(): what train_dev.py:276 writes and haplotype_model.LSTMNetwork().load_state_dict reads"""
+        import torch
+        torch.save(self.state_dict(), path)
+
+    def to_model(self, model=None):
+        """a haplotype_model.LSTMNetwork with these weights, through the existing upload path (packs the inference images: once per epoch,
+        not per step).  model: an LSTMNetwork to refresh instead of a new one on this trainer's context."""
+        from . import haplotype_model
+        m = model if model is not None else haplotype_model.LSTMNetwork(self.config, self.ctx.device, ctx=self.ctx)
+        m.load_state_dict(self.state_dict())
+        return m
+
+
+def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_size=512, dropout=0.1, max_grad_norm=2.0, seed=2022,
+                         pass_sites=16384, stats=None):
+    """One epoch of ``train(...)`` of HaplotypeModel/train_dev.py:25-80 over labelled haplotype site files
+    (sitefile.write_haplotype_train_bin) -> {sites, batches, mean_loss, gt_accuracy, zy_accuracy, refcalls, variants, unscorable_labels}.
+
+    The rows that train are those nsnp_hap_label_classes keeps: LabelField's filter (dataset_dev.py:174-187), the set
+    evaluate_haplotype_bins scores.  A file is read in passes of `pass_sites` rows, synchronously on the calling thread: the eight planes
+    staged in pinned memory (int8 while every value fits), sent, every row reduced to features (ctx.hap_features), the label pass, the kept
+    rows gathered in the order of a seeded ``torch.randperm`` of the KEPT rows (pass_order on a CPU generator seeded with `seed`, one draw per
+    pass that keeps a row, in file order); batches of `batch_size` restart with every pass.  Per batch: four Bernoulli keep masks ([n,33,512]
+    twice, [n,11,512] twice, in that order) with keep probability 1 - dropout from a device generator seeded with `seed` (none at dropout 0),
+    loss_and_grad, then optimizer.step(max_grad_norm) of a DeviceOptimizer - or clip_grad_norm_ (skipped when max_grad_norm is None) and
+    step() of a torch optimiser.  optimizer None: DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-5), the shipped configuration
+    (ont_haplotype.yaml).  The label pass reads the class counts of the heads loaded on the context: the trainer's weights are uploaded once
+    in front of the first pass when the context holds none of these dims.  mean_loss is the mean over batches of the batch loss; the
+    accuracies are over sites.
+
+    Departures from the reference's loop: no ``pn_value`` upsampling (TrainingDataset draws variants with replacement
+    per refcall block from an unseeded generator); the order is per pass, not per file; the masks come from a torch generator, not from the
+    stream nn.LSTM draws from; there is no epoch loop for this model yet (``fit`` is the PileupModel's); Ranger is not implemented."""
+    import torch
+    import torch.distributed as tdist
+    from . import evaluate, hap_pipeline, host
+    if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+        raise NotImplementedError("train_haplotype_bins under a process group of more than one rank (training is not sharded)")
+    if not isinstance(reference, hap_pipeline.DeviceReference):
+        raise TypeError("reference: a hap_pipeline.DeviceReference")
+    B = int(batch_size)
+    if B < 1:
+        raise ValueError("batch_size >= 1")
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("dropout in [0, 1)")
+    ctx, dev = trainer.ctx, trainer.device
+    if optimizer is None:
+        optimizer = DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-5)
+    fused = isinstance(optimizer, DeviceOptimizer)
+    st = stats if stats is not None else {}
+    for k in ("passes", "rows", "bytes_h2d"):
+        st.setdefault(k, 0)
+    if getattr(ctx, "_hap_dims", None) != (trainer.dims["gt_num_class"], trainer.dims["zy_num_class"]):
+        trainer.to_model()
+    P = int(max(1, pass_sites))
+    PL, HL = hap_pipeline.PILEUP_PLANES, hap_pipeline.HAPLOTYPE_PLANES
+    files = []
+    try:
+        for p in _paths(bin_paths):                            # every header is checked before anything runs
+            src = hap_pipeline.HapBinSource(p)
+            files.append(dict(path=p, src=src, n=src.n, e_out=1))
+            y = src.idx.get("candidate_labels")
+            if y is None or y[0] != np.dtype(np.int32) or y[1] != (src.n, sitefile.HAP_LABEL_WIDTH):
+                raise sitefile.SiteFileError(f"{p}: not a labelled haplotype bin (no candidate_labels int32 [N,{sitefile.HAP_LABEL_WIDTH}] "
+                                             "beside the read planes)")
+            files[-1]["y"] = sitefile.read_arrays(p, mmap=True)["candidate_labels"]
+        order_gen = torch.Generator().manual_seed(int(seed))
+        mask_gen = torch.Generator(device=dev).manual_seed(int(seed))
+        batch_losses, correct = [], torch.zeros(2, dtype=torch.int64, device=dev)
+        totals = np.zeros(4, np.int64)                         # kept, unscorable, refcalls, variants
+        live = [f for f in files if f["n"]]
+        if live:
+            Pmax = min(P, max(f["n"] for f in live))
+            Dp, Dh, elem = max(f["src"].Dp for f in live), max(f["src"].Dh for f in live), max(f["src"].elem for f in live)
+            hs, ds = evaluate._HapPassSet(Pmax, Dp, Dh, elem), evaluate._HapPassSet(Pmax, Dp, Dh, elem, dev)
+            off33 = torch.arange(-16, 17, dtype=torch.int64, device=dev)[None, :]
+        for f in live:
+            src = f["src"]
+            for a in range(0, f["n"], P):
+                b = min(f["n"], a + P)
+                m = b - a
+                hp, dp = hs.planes, ds.planes
+                torch.cuda.current_stream(dev).synchronize()   # (the previous pass has left both sets)
+                while True:                                    # the eight planes, narrowed to int8 while that fits
+                    e_out, nbytes, overflow = f["e_out"], 0, False
+                    for name in PL + HL:
+                        cnt = m * (src.Dp * 33 if name.startswith("pileup") else src.Dh * 11)
+                        v = hp.planes[name].numpy()[:cnt * e_out].view(np.int8 if e_out == 1 else np.int32)
+                        if src.stage_plane(name, a, b, v):
+                            overflow = True                    # a value outside int8 (e.g. a mapping quality of 255)
+                            break
+                        nbytes += v.nbytes
+                    if not overflow:
+                        break
+                    f["e_out"] = src.elem                      # this pass again, and the rest of the file, as the file's own dtype
+                cand_f, hap_f = src.position_fields(a, b)
+                cand_f = cand_f.reshape(m, -1)
+                cp, cc = host.parse_ctg_pos(cand_f, reference.table)
+                if (cc < 0).any():
+                    reference.add_names([bytes(r).rstrip(b"\0").split(b":")[0].decode() for r in cand_f[cc < 0]])
+                    cp, cc = host.parse_ctg_pos(cand_f, reference.table)
+                hpos, hctg = host.parse_ctg_pos(hap_f.reshape(m, 11, -1), reference.table)
+                hp.cand_pos.numpy()[:m] = cp; hp.cand_ctg.numpy()[:m] = cc
+                hp.hap_pos.numpy()[:m] = hpos; hp.hap_ctg.numpy()[:m] = hctg
+                hs.y.numpy()[:m] = f["y"][a:b]
+                for name in PL + HL:
+                    cnt = m * (src.Dp * 33 if name.startswith("pileup") else src.Dh * 11) * e_out
+                    dp.planes[name][:cnt].copy_(hp.planes[name][:cnt], non_blocking=True)
+                dp.cand_pos[:m].copy_(hp.cand_pos[:m], non_blocking=True); dp.cand_ctg[:m].copy_(hp.cand_ctg[:m], non_blocking=True)
+                dp.hap_pos[:m].copy_(hp.hap_pos[:m], non_blocking=True); dp.hap_ctg[:m].copy_(hp.hap_ctg[:m], non_blocking=True)
+                ds.y[:m].copy_(hs.y[:m], non_blocking=True)
+                ref_p = reference.rows(dp.cand_ctg[:m, None].expand(m, 33), dp.cand_pos[:m, None] - 1 + off33)
+                ref_h = reference.rows(dp.hap_ctg[:m], dp.hap_pos[:m] - 1)
+                tdt = torch.int8 if e_out == 1 else torch.int32
+                pl = lambda name, D, L: dp.planes[name][:m * D * L * e_out].view(tdt).view(m, D, L)
+                xp = ctx.hap_features(*[pl(nm, src.Dp, 33) for nm in PL], ref_p)
+                xh = ctx.hap_features(*[pl(nm, src.Dh, 11) for nm in HL], ref_h)
+                ctx.hap_label_classes(ds.y[:m], cls=ds.cls, rows=ds.rows, meta=hs.meta)
+                torch.cuda.current_stream(dev).synchronize()
+                meta = hs.meta.numpy().copy()
+                totals += meta
+                kept = int(meta[0])
+                st["passes"] += 1; st["rows"] += m; st["bytes_h2d"] += nbytes + m * (12 * 12 + 12)
+                if not kept:
+                    continue
+                order = pass_order(order_gen, kept).to(dev)
+                idx = ds.rows[:kept].index_select(0, order)
+                xp, xh = torch.index_select(xp, 0, idx), torch.index_select(xh, 0, idx)
+                cls = ds.cls[:kept].index_select(0, order).contiguous()
+                for o in range(0, kept, B):
+                    n = min(B, kept - o)
+                    masks = None
+                    if dropout > 0.0:
+                        masks = [(torch.rand((n, L, 512), generator=mask_gen, device=dev) >= float(dropout)).to(torch.uint8) for L in (33, 33, 11, 11)]
+                    loss, pred = trainer._loss_and_grad_cls(xp[o:o + n], xh[o:o + n], cls[o:o + n], n, masks, dropout)
+                    if fused:
+                        optimizer.step(max_grad_norm)
+                    else:
+                        if max_grad_norm is not None:
+                            torch.nn.utils.clip_grad_norm_(trainer.parameters(), max_grad_norm)
+                        optimizer.step()
+                    batch_losses.append(loss)
+                    correct += (pred == cls[o:o + n]).sum(0)
+    finally:
+        for f in files:
+            f["src"].close()
+    sites = int(totals[0])
+    div = max(sites, 1)
+    correct = correct.cpu().numpy()
+    mean_loss = float(torch.stack(batch_losses).double().mean()) if batch_losses else float("nan")
+    return {"sites": sites, "batches": len(batch_losses), "mean_loss": mean_loss, "gt_accuracy": float(correct[0]) / div,
+            "zy_accuracy": float(correct[1]) / div, "refcalls": int(totals[2]), "variants": int(totals[3]), "unscorable_labels": int(totals[1])}
 
 
 def fit(trainer, training_paths, validating_paths=None, epochs=1, optimizer=None, batch_size=2000, dropout=0.3, max_grad_norm=20.0,
