@@ -14,25 +14,14 @@
 // walks positions 0 .. L / 2, the reverse L - 1 .. L / 2) and receives a gradient at its last step only.
 //
 // W_hh is 1024 x 256 per layer and direction: 1 MB, no register file and no LDS holds it.  So the recurrence is one launch pair per step
-// over all sites of the chunk: the product through the tiled GEMM below, then the cell as a launch of its own.  The two directions and,
+// over all sites of the chunk: the product through k_tr_gemm, then the cell as a launch of its own.  The two directions and,
 // while the short encoder still runs, the two encoders share every launch through blockIdx.z.
 //
-// Kernels
-//   k_ht_gemm      C(m, n) (+)= sum_k A(m, k) B(k, n) on v_mfma_f32_16x16x4_f32.  A workgroup of four waves owns a 64 x 64 tile of C, each wave
-//                  32 x 32 of it (2 x 2 MFMA tiles); K streams through LDS in tiles of 16, the next tile's global loads in flight under the
-//                  products of this one.  Every operand is addressed through two-level strides (TrDim), so that one kernel serves
-//                    the input projections of a layer          (A = W_ih, B = the input rows of every (site, step), bias b_ih + b_hh)  -> G
-//                    the step products                         (A = W_hh, B = h of the previous step; C += : G_t)
-//                    W_hh^T dgates_t and W_ih^T dgates         (A = W^T)
-//                    output_proj, dense (+ tanh), the heads and their transposes
-//                    every weight gradient                     (K = sites x steps, cut into slices of HT_KCH rows: slice blockIdx.y writes its
-//                                                               own partial image, k_tr_reduce adds the images in order)
-//                  blockIdx.z selects one of up to four problems of a launch.
+// Kernels (the product k_tr_gemm, k_tr_loss, k_tr_colsum, k_tr_mask, k_tr_dtanh, k_tr_reduce and their launch helpers: train_common.hpp;
+// a weight gradient's slices are HT_KCH rows)
 //   k_ht_cell_fwd  gates_t (projection + product) -> sigma(i), sigma(f), tanh(g), sigma(o) in place, c_t and h_t saved; t = 0: no c before it.
-//                  Exact activations (expf, tanhf), here and in the dense layer's epilogue.
+//                  Exact activations (expf, tanhf), here and in the dense layer's epilogue (flag 4 of the product).
 //   k_ht_cell_bwd  dgates_t from dh_t = dH_external + rec and the carried dc, as k_tr_lstm_bwd forms it; overwrites the activations.
-//   k_ht_loss      per site: the smoothed loss, the first maximum, dz = (softmax(z) - true_dist) / N; a head of one class: 0, 0, 0.
-//   k_ht_colsum    bias gradients: column sums per slice.   k_tr_mask, k_tr_dtanh, k_tr_reduce: train_common.hpp.
 // No floating-point atomic anywhere: the same call gives the same bits twice.
 #include "train_common.hpp"
 
@@ -42,7 +31,6 @@ constexpr int HH = 256, HG = 1024, H2 = 512;                  // hidden units, g
 constexpr int HT_KCH = 128;                                   // reduction rows per slice of a weight gradient: short sums in one accumulator, the slices
                                                               // added in order by k_tr_reduce (1,024 rows per accumulator cost accuracy: docs/rounds/r29.md)
 constexpr int64_t HT_MAX_SITES = (int64_t)1 << 16;
-constexpr int BM = 64, BN = 64, BK = 16, LDS_LD = 80;         // LDS_LD: the four k rows a wave reads at once start 16 banks apart
 
 // floats per site of the workspace, encoder of L positions and Tc layer-2 steps:
 //   G   gates of the 2 (2 L + Tc) (layer, direction, step) triples, 1024 each            pileup 169,984   haplotype 57,344
@@ -81,124 +69,6 @@ HtWs carve(float* base, int64_t cap)
     return w;
 }
 int64_t part_floats(int64_t cap) { return NSNP_CDIV(cap * 33, (int64_t)HT_KCH) * HG * H2; }
-
-// ---- the tiled product --------------------------------------------------------------------------
-struct HtGemm {
-    const float* A; const float* B; float* C; const float* bias; const float* bias2;
-    int M, N; int64_t K; int kchunk;
-    TrDim am, ak, bk, bn, cm, cn;
-    int64_t cz;                // floats between the images of two K slices
-    int flags;                 // 1: C += , 2: tanh
-    int a_kfast, b_kfast;      // the operand is contiguous along K: a wave's loads walk K first
-};
-struct HtBatch { HtGemm g[4]; };
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// One operand's share of a K tile for one thread: 4 of the 64 x 16 elements.  kfast: element j is (row (tid >> 4) + 16 j, k tid & 15);
-// otherwise (row tid & 63, k (tid >> 6) + 4 j).  Rows outside the matrix and k outside the slice are zeros and are never loaded.
-struct HtStage {
-    const float* p; TrDim dk; int kfast, kk0, row0; int64_t roff[4]; bool rok[4];
-    __device__ __forceinline__ void init(const float* base, const TrDim& drow, const TrDim& dk_, int kfast_, int first_row, int rows, int tid)
-    {
-        p = base; dk = dk_; kfast = kfast_;
-        kk0 = kfast ? (tid & 15) : (tid >> 6);
-        row0 = kfast ? (tid >> 4) : (tid & 63);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = first_row + row0 + (kfast ? 16 * j : 0);
-            rok[j] = r < rows;
-            roff[j] = rok[j] ? tr_off(drow, r) : 0;
-        }
-    }
-    __device__ __forceinline__ void load(int64_t kt, int64_t k1, float (&v)[4]) const
-    {
-        if (kfast) {
-            const int64_t k = kt + kk0;
-            const bool kok = k < k1;
-            const int64_t ko = kok ? tr_off(dk, k) : 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (kok && rok[j]) ? p[roff[j] + ko] : 0.f;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int64_t k = kt + kk0 + 4 * j;
-                v[j] = (k < k1 && rok[0]) ? p[roff[0] + tr_off(dk, k)] : 0.f;
-            }
-        }
-    }
-    __device__ __forceinline__ void store(float (*lds)[LDS_LD], const float (&v)[4]) const
-    {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (kfast) lds[kk0][row0 + 16 * j] = v[j];
-            else lds[kk0 + 4 * j][row0] = v[j];
-        }
-    }
-};
-
-// grid (tiles of the largest problem, K slices, problems).  MFMA operands: lane l gives A(m + (l & 15), k + (l >> 4)) and
-// B(k + (l >> 4), n + (l & 15)); its accumulator register r is C(m + 4 (l >> 4) + r, n + (l & 15)).
-__global__ __launch_bounds__(256) void k_ht_gemm(const HtBatch batch)
-{
-    __shared__ float As[BK][LDS_LD], Bs[BK][LDS_LD];
-    const HtGemm& g = batch.g[blockIdx.z];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, r16 = lane & 15;
-    const int tiles_m = NSNP_CDIV(g.M, BM), tiles_n = NSNP_CDIV(g.N, BN);
-    if ((int64_t)blockIdx.x >= (int64_t)tiles_m * tiles_n) return;                    // (the whole workgroup)
-    const int64_t k0 = (int64_t)blockIdx.y * g.kchunk, k1 = k0 + g.kchunk < g.K ? k0 + g.kchunk : g.K;
-    if (k0 >= k1) return;
-    const int m0 = (int)(blockIdx.x % tiles_m) * BM, n0 = (int)(blockIdx.x / tiles_m) * BN;
-    HtStage sa, sb;
-    sa.init(g.A, g.am, g.ak, g.a_kfast, m0, g.M, tid);
-    sb.init(g.B, g.bn, g.bk, g.b_kfast, n0, g.N, tid);
-    const int wm = (w & 1) * 32, wn = (w >> 1) * 32;
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float ra[4], rb[4];
-    sa.load(k0, k1, ra); sb.load(k0, k1, rb);
-    for (int64_t kt = k0; kt < k1; kt += BK) {
-        __syncthreads();                                       // every wave has finished with the previous tile
-        sa.store(As, ra); sb.store(Bs, rb);
-        __syncthreads();
-        if (kt + BK < k1) { sa.load(kt + BK, k1, ra); sb.load(kt + BK, k1, rb); }
-#pragma unroll
-        for (int s = 0; s < BK / 4; ++s) {
-            const int k = 4 * s + q;
-            const float a0 = As[k][wm + r16], a1 = As[k][wm + 16 + r16];
-            const float b0 = Bs[k][wn + r16], b1 = Bs[k][wn + 16 + r16];
-            acc[0][0] = mfma4(a0, b0, acc[0][0]); acc[0][1] = mfma4(a0, b1, acc[0][1]);
-            acc[1][0] = mfma4(a1, b0, acc[1][0]); acc[1][1] = mfma4(a1, b1, acc[1][1]);
-        }
-    }
-    float* __restrict__ cbase = g.C + (int64_t)blockIdx.y * g.cz;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn + 16 * j + r16;
-        if (n >= g.N) continue;
-        float* __restrict__ pc = cbase + tr_off(g.cn, n);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm + 16 * i + 4 * q + r;
-                if (m >= g.M) continue;
-                float v = acc[i][j][r];
-                if (g.bias) v += g.bias[m];
-                if (g.bias2) v += g.bias2[m];
-                if (g.flags & 2) v = tanhf(v);
-                float* c = pc + tr_off(g.cm, m);
-                if (g.flags & 1) v += *c;
-                *c = v;
-            }
-    }
-}
 
 // ---- the cells ------------------------------------------------------------------------------------
 // The activations of this file are libm's (expf, tanhf, an IEEE division), not the v_exp_f32 + v_rcp_f32 forms of train_common.hpp, whose
@@ -252,97 +122,6 @@ __global__ __launch_bounds__(256) void k_ht_cell_bwd(const HtCellBBatch batch)
     p.dc[site * H2 + u] = dct * af;
 }
 
-// ---- the small kernels ------------------------------------------------------------------------
-// one lane per site.  Z, DZ: [n][16], genotype 0 .. n_gt - 1, zygosity behind it.  The rules of nsnp_hap_eval's heads: a target outside its head
-// counts as the head's last class, a head of one class has loss 0, pred 0 and gradient 0, pred is the first maximum.
-__global__ __launch_bounds__(256) void k_ht_loss(const float* __restrict__ Z, const uint8_t* __restrict__ cls, int64_t n, int n_gt, int n_zy,
-                                                 float inv_n, float* __restrict__ DZ, float* __restrict__ site_loss, uint8_t* __restrict__ pred)
-{
-    const int64_t site = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (site >= n) return;
-    for (int h = 0; h < 2; ++h) {
-        const int C = h ? n_zy : n_gt;
-        const float* z = Z + site * 16 + (h ? n_gt : 0);
-        float* dz = DZ + site * 16 + (h ? n_gt : 0);
-        if (C == 1) {
-            dz[0] = 0.f;
-            if (site_loss) site_loss[site * 2 + h] = 0.f;
-            if (pred) pred[site * 2 + h] = 0;
-            continue;
-        }
-        float bv = z[0]; int bi = 0;
-        for (int c = 1; c < C; ++c) if (z[c] > bv) { bv = z[c]; bi = c; }           // the first maximum
-        float se = 0.f, sz = 0.f;
-        for (int c = 0; c < C; ++c) { se += expf(z[c] - bv); sz += z[c]; }
-        int t = cls[site * 2 + h];
-        if (t >= C) t = C - 1;
-        const float lse = bv + logf(se);
-        const float lpt = z[t] - lse, slp = sz - (float)C * lse;
-        const float off = 0.1f / (float)(C - 1);
-        if (site_loss) site_loss[site * 2 + h] = -(0.9f * lpt + off * (slp - lpt));
-        if (pred) pred[site * 2 + h] = (uint8_t)bi;
-        for (int c = 0; c < C; ++c) dz[c] = (expf(z[c] - lse) - (c == t ? 0.9f : off)) * inv_n;
-    }
-}
-
-// part[z][m] = sum of src[tr_off(rows, r) + m] over the rows r of slice z, in order; grid (slices, ceil(M / 256))
-__global__ __launch_bounds__(256) void k_ht_colsum(const float* __restrict__ src, const TrDim rows, int M, int64_t R, float* __restrict__ part)
-{
-    const int m = blockIdx.y * 256 + threadIdx.x;
-    if (m >= M) return;
-    const int64_t r0 = (int64_t)blockIdx.x * HT_KCH, r1 = r0 + HT_KCH < R ? r0 + HT_KCH : R;
-    float s = 0.f;
-    for (int64_t r = r0; r < r1; ++r) s += src[tr_off(rows, r) + m];
-    part[(int64_t)blockIdx.x * M + m] = s;
-}
-
-// ---- launch helpers ---------------------------------------------------------------------------
-void launch(hipStream_t s, const HtBatch& b, int count)
-{
-    int64_t tiles = 0, slices = 1;
-    for (int i = 0; i < count; ++i) {
-        const HtGemm& g = b.g[i];
-        const int64_t t = (int64_t)NSNP_CDIV(g.M, BM) * NSNP_CDIV(g.N, BN), z = NSNP_CDIV(g.K, (int64_t)g.kchunk);
-        if (t > tiles) tiles = t;
-        if (z > slices) slices = z;
-    }
-    if (count < 1 || tiles < 1) return;
-    hipLaunchKernelGGL(k_ht_gemm, dim3((unsigned)tiles, (unsigned)slices, (unsigned)count), dim3(256), 0, s, b);
-}
-
-// Y(m, sample) (+)= sum_k W(m, k) X(sample, k) (+ biases): K in one slice
-HtGemm rows_gemm(const float* W, TrDim wm, TrDim wk, int M, int K, const float* X, TrDim xk, TrDim xs, int64_t S, float* Y, TrDim ys,
-                 const float* b1, const float* b2, int flags)
-{
-    HtGemm g{};
-    g.A = W; g.B = X; g.C = Y; g.bias = b1; g.bias2 = b2;
-    g.M = M; g.N = (int)S; g.K = K; g.kchunk = K;
-    g.am = wm; g.ak = wk; g.bk = xk; g.bn = xs; g.cm = lin(1); g.cn = ys; g.cz = 0; g.flags = flags;
-    g.a_kfast = wk.T == 0 && wk.si == 1; g.b_kfast = xk.T == 0 && xk.si == 1;
-    return g;
-}
-void gemm1(hipStream_t s, const HtGemm& g) { HtBatch b{}; b.g[0] = g; launch(s, b, 1); }
-
-// dW[m][n] (+)= sum over rows r of DY(r, m) X(r, n): slices of HT_KCH rows, then the ordered sum
-void wgrad(hipStream_t s, float* part, const float* DY, TrDim dyr, int M, const float* X, TrDim xr, TrDim xn, int N, int64_t R, float* out, int add)
-{
-    HtGemm g{};
-    g.A = DY; g.B = X; g.C = part;
-    g.M = M; g.N = N; g.K = R; g.kchunk = HT_KCH;
-    g.am = lin(1); g.ak = dyr; g.bk = xr; g.bn = xn; g.cm = lin(N); g.cn = lin(1); g.cz = (int64_t)M * N; g.flags = 0;
-    g.a_kfast = 0; g.b_kfast = 0;
-    gemm1(s, g);
-    hipLaunchKernelGGL(k_tr_reduce, dim3(blocks((int64_t)M * N)), dim3(256), 0, s, (const float*)part, (int64_t)M * N,
-                       (int)NSNP_CDIV(R, (int64_t)HT_KCH), add, out, (float*)nullptr);
-}
-
-void bgrad(hipStream_t s, float* part, const float* src, TrDim rows, int M, int64_t R, float* out, float* out2, int add)
-{
-    const int Zn = (int)NSNP_CDIV(R, (int64_t)HT_KCH);
-    hipLaunchKernelGGL(k_ht_colsum, dim3((unsigned)Zn, (unsigned)NSNP_CDIV(M, 256)), dim3(256), 0, s, src, rows, M, R, part);
-    hipLaunchKernelGGL(k_tr_reduce, dim3(blocks(M)), dim3(256), 0, s, (const float*)part, (int64_t)M, Zn, add, out, out2);
-}
-
 // the walk of direction d of layer l: step t of T is position pos0 + t * dpos of the layer's input, row hrow0 + t * dhrow of H / C
 struct Walk { int T, rows, pos0, dpos, hrow0, dhrow; };
 Walk walk(const EncWs& e, int l, int d)
@@ -370,7 +149,7 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const float* xp, const floa
     {
         ScopedKernelTimer tm(ctx, NSNP_K_HAPTRAIN_FWD, s);
         for (int l = 0; l < 3; ++l) {
-            HtBatch b{}; int nb = 0;
+            TrBatch b{}; int nb = 0;
             for (int e = 0; e < 2; ++e)
                 for (int d = 0; d < 2; ++d) {      // G[l][d][site][step] = W_ih x(position of the step) + b_ih + b_hh
                     const EncWs& E = w.e[e]; const Walk k = walk(E, l, d);
@@ -381,7 +160,7 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const float* xp, const floa
             launch(s, b, nb);
             const int Tmax = l < 2 ? 33 : 17;
             for (int t = 0; t < Tmax; ++t) {
-                HtBatch gb{}; HtCellFBatch cb{}; int np = 0;
+                TrBatch gb{}; HtCellFBatch cb{}; int np = 0;
                 for (int e = 0; e < 2; ++e)
                     for (int d = 0; d < 2; ++d) {
                         const EncWs& E = w.e[e]; const Walk k = walk(E, l, d);
@@ -407,7 +186,7 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const float* xp, const floa
                 }
         }
         {   // output_proj of both encoders at the centre = the last step of both directions of layer 2
-            HtBatch b{};
+            TrBatch b{};
             for (int e = 0; e < 2; ++e) {
                 const EncWs& E = w.e[e];
                 b.g[e] = rows_gemm(P[26 * e + 24], lin(H2), lin(1), HH, H2, E.H[2] + (int64_t)(E.Tc - 1) * H2, lin(1), lin((int64_t)E.Tc * H2), n,
@@ -415,14 +194,14 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const float* xp, const floa
             }
             launch(s, b, 2);
         }
-        gemm1(s, rows_gemm(P[52], lin(H2), lin(1), HH, H2, w.Y, lin(1), lin(H2), n, w.MID, lin(HH), P[53], nullptr, 2));
+        gemm1(s, rows_gemm(P[52], lin(H2), lin(1), HH, H2, w.Y, lin(1), lin(H2), n, w.MID, lin(HH), P[53], nullptr, 4));
         {
-            HtBatch b{};
+            TrBatch b{};
             b.g[0] = rows_gemm(P[54], lin(HH), lin(1), n_gt, HH, w.MID, lin(1), lin(HH), n, w.Z, lin(16), P[55], nullptr, 0);
             b.g[1] = rows_gemm(P[56], lin(HH), lin(1), n_zy, HH, w.MID, lin(1), lin(HH), n, w.Z + n_gt, lin(16), P[57], nullptr, 0);
             launch(s, b, 2);
         }
-        hipLaunchKernelGGL(k_ht_loss, dim3(blocks(n)), dim3(256), 0, s, (const float*)w.Z, cls, n, n_gt, n_zy, inv_n, w.DZ, site_loss, pred);
+        hipLaunchKernelGGL(k_tr_loss, dim3(blocks(n)), dim3(256), 0, s, (const float*)w.Z, cls, n, n, n_gt, n_zy, 16, 2, inv_n, w.DZ, site_loss, pred);
     }
     {
         ScopedKernelTimer tm(ctx, NSNP_K_HAPTRAIN_BWD, s);
@@ -432,7 +211,7 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const float* xp, const floa
         hipLaunchKernelGGL(k_tr_dtanh, dim3(blocks(n * HH)), dim3(256), 0, s, w.DMID, (const float*)w.MID, n * HH);
         gemm1(s, rows_gemm(P[52], lin(1), lin(H2), H2, HH, w.DMID, lin(1), lin(HH), n, w.DY, lin(H2), nullptr, nullptr, 0));
         {
-            HtBatch b{};
+            TrBatch b{};
             for (int e = 0; e < 2; ++e)
                 b.g[e] = rows_gemm(P[26 * e + 24], lin(1), lin(H2), H2, HH, w.DY + e * HH, lin(1), lin(H2), n, w.e[e].DHC, lin(H2), nullptr, nullptr, 0);
             launch(s, b, 2);
@@ -440,7 +219,7 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const float* xp, const floa
         for (int l = 2; l >= 0; --l) {
             const int Tmax = l < 2 ? 33 : 17;
             for (int j = 0; j < Tmax; ++j) {       // the j-th step from the end of every walk that is that long
-                HtBatch gb{}; HtCellBBatch cb{}; int np = 0, ng = 0;
+                TrBatch gb{}; HtCellBBatch cb{}; int np = 0, ng = 0;
                 for (int e = 0; e < 2; ++e)
                     for (int d = 0; d < 2; ++d) {
                         const EncWs& E = w.e[e]; const Walk k = walk(E, l, d);
@@ -465,7 +244,7 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const float* xp, const floa
             // the gradient of the layer's input: sum over the directions of W_ih^T dgates at the step's position, then the mask's factor
             for (int e = 0; e < 2; ++e) (void)hipMemsetAsync(w.e[e].DX, 0, (size_t)(n * w.e[e].L * H2) * sizeof(float), s);
             for (int d = 0; d < 2; ++d) {          // (the directions meet at positions both walk: one after the other)
-                HtBatch b{};
+                TrBatch b{};
                 for (int e = 0; e < 2; ++e) {
                     const EncWs& E = w.e[e]; const Walk k = walk(E, l, d);
                     b.g[e] = rows_gemm(P[26 * e + 8 * l + 4 * d], lin(1), lin(H2), H2, HG, E.G[l][d], lin(1), lin(HG), n * k.T,
@@ -491,24 +270,24 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const float* xp, const floa
                     float* const* Gr = grads + 26 * e + 8 * l + 4 * d;
                     const float* g = E.G[l][d];
                     const int64_t sh = (int64_t)k.rows * H2;
-                    wgrad(s, part, g, lin(HG), HG, in_base(e, l) + k.pos0 * in_sp(l), two(k.T, in_so(e, l), k.dpos * in_sp(l)), lin(in_sk(e, l)),
+                    wgrad(s, part, HT_KCH, g, lin(HG), HG, in_base(e, l) + k.pos0 * in_sp(l), two(k.T, in_so(e, l), k.dpos * in_sp(l)), lin(in_sk(e, l)),
                           in_k(l), n * k.T, Gr[0], add);
                     // step t + 1 (t = 0 .. T - 2) meets the h of step t
-                    wgrad(s, part, g + HG, two(k.T - 1, (int64_t)k.T * HG, HG), HG, E.H[l] + (int64_t)k.hrow0 * H2 + d * HH,
+                    wgrad(s, part, HT_KCH, g + HG, two(k.T - 1, (int64_t)k.T * HG, HG), HG, E.H[l] + (int64_t)k.hrow0 * H2 + d * HH,
                           two(k.T - 1, sh, (int64_t)k.dhrow * H2), lin(1), HH, n * (k.T - 1), Gr[1], add);
-                    bgrad(s, part, g, lin(HG), HG, n * k.T, Gr[2], Gr[3], add);
+                    bgrad(s, part, HT_KCH, g, lin(HG), HG, n * k.T, Gr[2], Gr[3], add);
                 }
         for (int e = 0; e < 2; ++e) {
             const EncWs& E = w.e[e];
-            wgrad(s, part, w.DY + e * HH, lin(H2), HH, E.H[2] + (int64_t)(E.Tc - 1) * H2, lin((int64_t)E.Tc * H2), lin(1), H2, n, grads[26 * e + 24], add);
-            bgrad(s, part, w.DY + e * HH, lin(H2), HH, n, grads[26 * e + 25], nullptr, add);
+            wgrad(s, part, HT_KCH, w.DY + e * HH, lin(H2), HH, E.H[2] + (int64_t)(E.Tc - 1) * H2, lin((int64_t)E.Tc * H2), lin(1), H2, n, grads[26 * e + 24], add);
+            bgrad(s, part, HT_KCH, w.DY + e * HH, lin(H2), HH, n, grads[26 * e + 25], nullptr, add);
         }
-        wgrad(s, part, w.DMID, lin(HH), HH, w.Y, lin(H2), lin(1), H2, n, grads[52], add);
-        bgrad(s, part, w.DMID, lin(HH), HH, n, grads[53], nullptr, add);
-        wgrad(s, part, w.DZ, lin(16), n_gt, w.MID, lin(HH), lin(1), HH, n, grads[54], add);
-        bgrad(s, part, w.DZ, lin(16), n_gt, n, grads[55], nullptr, add);
-        wgrad(s, part, w.DZ + n_gt, lin(16), n_zy, w.MID, lin(HH), lin(1), HH, n, grads[56], add);
-        bgrad(s, part, w.DZ + n_gt, lin(16), n_zy, n, grads[57], nullptr, add);
+        wgrad(s, part, HT_KCH, w.DMID, lin(HH), HH, w.Y, lin(H2), lin(1), H2, n, grads[52], add);
+        bgrad(s, part, HT_KCH, w.DMID, lin(HH), HH, n, grads[53], nullptr, add);
+        wgrad(s, part, HT_KCH, w.DZ, lin(16), n_gt, w.MID, lin(HH), lin(1), HH, n, grads[54], add);
+        bgrad(s, part, HT_KCH, w.DZ, lin(16), n_gt, n, grads[55], nullptr, add);
+        wgrad(s, part, HT_KCH, w.DZ + n_gt, lin(16), n_zy, w.MID, lin(HH), lin(1), HH, n, grads[56], add);
+        bgrad(s, part, HT_KCH, w.DZ + n_gt, lin(16), n_zy, n, grads[57], nullptr, add);
     }
 }
 
@@ -528,17 +307,9 @@ extern "C" int nsnp_hap_train_reserve(nsnp_ctx* ctx, int64_t max_sites, int n_fe
         ctx->ht_F = n_features; ctx->ht_ngt = n_gt; ctx->ht_nzy = n_zy;
         return NSNP_OK;
     }
-    NSNP_HIP(ctx, hipSetDevice(ctx->device));
-    NSNP_HIP(ctx, hipDeviceSynchronize());
-    void* ws = nullptr;
-    const hipError_t e = hipMalloc(&ws, (size_t)(max_sites * F_SITE + part_floats(max_sites)) * sizeof(float));
-    if (e != hipSuccess) {                                   // the previous reservation stays in force
-        (void)hipGetLastError();
-        ctx->last_err = e;
-        return e == hipErrorOutOfMemory ? NSNP_ENOMEM : NSNP_EHIP;
-    }
-    if (ctx->ht_ws) (void)hipFree(ctx->ht_ws);
-    ctx->ht_ws = ws; ctx->ht_sites = max_sites; ctx->ht_F = n_features; ctx->ht_ngt = n_gt; ctx->ht_nzy = n_zy;
+    const int rc = reserve_ws(ctx, &ctx->ht_ws, (size_t)(max_sites * F_SITE + part_floats(max_sites)) * sizeof(float));
+    if (rc != NSNP_OK) return rc;
+    ctx->ht_sites = max_sites; ctx->ht_F = n_features; ctx->ht_ngt = n_gt; ctx->ht_nzy = n_zy;
     return NSNP_OK;
 }
 

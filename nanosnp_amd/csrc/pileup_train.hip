@@ -16,13 +16,6 @@
 //
 // Kernels
 //   k_tr_gather    counts int32 (contiguous or through center_idx) -> X0 fp32 [Np,33,18], zeros behind site n.
-//   k_tr_gemm      C(m, n) = sum_k A(m, k) B(k, n) on v_mfma_f32_16x16x4_f32, one 16 x 16 tile of C per wave, every operand addressed
-//                  through two-level strides (TrDim), so that one kernel serves
-//                    the input projections of both layers     (A = W_ih, B = the step's input rows, bias b_ih + b_hh)        -> G
-//                    output_proj, dense (+ tanh), the two heads
-//                    their transposes in the backward pass    (A = W^T, B = the gradient rows)
-//                    every weight gradient                    (K = sites x steps, cut into slices of TR_KCH rows: slice z of the grid
-//                                                              writes its own partial image, k_tr_reduce adds the images in order)
 //   k_tr_lstm_fwd  the recurrence of one layer: a workgroup of 4 waves per (16 sites, direction), W_hh as MFMA A fragments in 64 VGPRs
 //                  per lane, h in LDS.  Wave w owns gate tiles w, w + 4, w + 8, w + 12, so a lane's four accumulators of one register
 //                  index are i, f, g, o of ONE hidden unit 16 w + 4 q + r.  G arrives holding the input projections and leaves
@@ -32,19 +25,16 @@
 //                  gradients replace the activations in G (in place) and go to LDS; dh of the previous step = W_hh^T dgates is 64
 //                  MFMAs per wave whose accumulators land on the lanes that own those units, so only dgates crosses LDS.
 //   k_tr_mask      x1 = h0 * mask * keep_scale (forward) and dx1 *= mask * keep_scale (backward); NULL mask: factor 1.
-//   k_tr_loss      per site: lp = z - logsumexp(z), the smoothed loss, the first maximum, dz = (softmax(z) - true_dist) / N.
-//   k_tr_dtanh, k_tr_colsum (bias gradients: column sums per slice), k_tr_reduce (adds the slices' images in a fixed order).
+// Every product outside the recurrence (the input projections of both layers, output_proj, dense + tanh, the two heads, their
+// transposes and every weight gradient in slices of TR_KCH rows) goes through k_tr_gemm; it, k_tr_loss, k_tr_colsum, k_tr_mask,
+// k_tr_dtanh, k_tr_reduce and their launch helpers are train_common.hpp's, shared with hap_train.hip.
 // No floating-point atomic anywhere: the same call gives the same bits twice.
-#include "train_common.hpp"      // the activations, TrDim, k_tr_mask, k_tr_dtanh, k_tr_reduce: shared with hap_train.hip
+#include "train_common.hpp"
 
 namespace {
 
+constexpr int TR_KCH = 1024;                                  // reduction rows per slice of a weight gradient
 constexpr int64_t TR_MAX_SITES = (int64_t)1 << 20;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // floats per site of the workspace
 constexpr int64_t F_X0 = 33 * 18, F_G0 = 2 * 33 * 256, F_H0 = 33 * 128, F_G1 = 2 * 17 * 256, F_H1 = 17 * 128;
@@ -64,70 +54,6 @@ TrWs carve(float* base, int64_t cap)
     return w;
 }
 int64_t part_floats(int64_t cap) { return NSNP_CDIV(cap * 33, (int64_t)TR_KCH) * 256 * 128; }
-
-// ---- two-level strides (TrDim, tr_off: train_common.hpp) ----------------------------------------
-// the K dimension walks in steps of 4
-struct TrIter {
-    int64_t off, so, si; int i, T;
-    __device__ __forceinline__ void init(const TrDim& d, int64_t k)
-    {
-        T = d.T; so = d.so; si = d.si; off = tr_off(d, k);
-        i = T ? (int)((uint32_t)k % (uint32_t)T) : 0;
-    }
-    __device__ __forceinline__ void step4()
-    {
-        off += 4 * si;
-        if (T) { i += 4; if (i >= T) { i -= T; off += so - (int64_t)T * si; } }        // (T >= 4 wherever it is not 0)
-    }
-};
-
-struct TrGemm {
-    const float* A; const float* B; float* C; const float* bias; const float* bias2;
-    int M, N; int64_t K; int kchunk;
-    TrDim am, ak, bk, bn, cm, cn;
-    int64_t cz;                // floats between the images of two K slices
-    int flags;                 // 1: C += , 2: tanh
-};
-
-// one wave per 16 x 16 tile of C, K slice blockIdx.y.  MFMA operands: lane l gives A(m0 + (l & 15), k + (l >> 4)) and
-// B(k + (l >> 4), n0 + (l & 15)); its accumulator register r is C(m0 + 4 (l >> 4) + r, n0 + (l & 15)).  Everything outside M, N and the
-// slice's K range is a zero operand and is never loaded or stored.
-__global__ __launch_bounds__(256) void k_tr_gemm(const TrGemm g)
-{
-    const int lane = threadIdx.x & 63, q = lane >> 4, r16 = lane & 15;
-    const int tiles_m = NSNP_CDIV(g.M, 16), tiles_n = NSNP_CDIV(g.N, 16);
-    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= (int64_t)tiles_m * tiles_n) return;
-    const int m0 = (int)(tile % tiles_m) * 16, n0 = (int)(tile / tiles_m) * 16;
-    const int64_t k0 = (int64_t)blockIdx.y * g.kchunk, k1 = k0 + g.kchunk < g.K ? k0 + g.kchunk : g.K;
-    const bool m_ok = m0 + r16 < g.M, n_ok = n0 + r16 < g.N;
-    const float* __restrict__ pa = g.A + (m_ok ? tr_off(g.am, m0 + r16) : 0);
-    const float* __restrict__ pb = g.B + (n_ok ? tr_off(g.bn, n0 + r16) : 0);
-    TrIter ia, ib;
-    ia.init(g.ak, k0 + q); ib.init(g.bk, k0 + q);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t k = k0 + q; k - q < k1; k += 4) {
-        const bool k_ok = k < k1;
-        const float a = (m_ok && k_ok) ? pa[ia.off] : 0.f;
-        const float b = (n_ok && k_ok) ? pb[ib.off] : 0.f;
-        acc = mfma4(a, b, acc);
-        ia.step4(); ib.step4();
-    }
-    if (!n_ok) return;
-    float* __restrict__ pc = g.C + (int64_t)blockIdx.y * g.cz + tr_off(g.cn, n0 + r16);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int m = m0 + 4 * q + r;
-        if (m >= g.M) continue;
-        float v = acc[r];
-        if (g.bias) v += g.bias[m];
-        if (g.bias2) v += g.bias2[m];
-        if (g.flags & 2) v = tanh_f(v);
-        float* c = pc + tr_off(g.cm, m);
-        if (g.flags & 1) v += *c;
-        *c = v;
-    }
-}
 
 // ---- the recurrences --------------------------------------------------------------------------
 // grid (Np / 16, 2 directions), 256 threads.  G of direction d: [Np][T][256] by STEP (gate rows i f g o as nn.LSTM orders them); H and Cs:
@@ -241,7 +167,7 @@ __global__ __launch_bounds__(256) void k_tr_lstm_bwd(float* __restrict__ G, cons
     }
 }
 
-// ---- the small kernels ------------------------------------------------------------------------
+// ---- the gather (the other small kernels: train_common.hpp) -------------------------------------
 __global__ __launch_bounds__(256) void k_tr_gather(const int32_t* __restrict__ counts, const int64_t* __restrict__ center_idx, int64_t n,
                                                    int64_t total, float* __restrict__ X0)
 {
@@ -251,87 +177,6 @@ __global__ __launch_bounds__(256) void k_tr_gather(const int32_t* __restrict__ c
     float v = 0.f;
     if (site < n) v = (float)(center_idx ? counts[(center_idx[site] - PCENTER) * PC + r] : counts[i]);
     X0[i] = v;
-}
-
-// (k_tr_mask, k_tr_dtanh, k_tr_reduce: train_common.hpp)
-// one lane per site.  Z, DZ: [Np][24], genotype 0..20, zygosity 21..23
-__global__ __launch_bounds__(256) void k_tr_loss(const float* __restrict__ Z, const uint8_t* __restrict__ cls, int64_t n, int64_t np, float inv_n,
-                                                 float* __restrict__ DZ, float* __restrict__ site_loss, uint8_t* __restrict__ pred)
-{
-    const int64_t site = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (site >= np) return;
-    if (site >= n) {
-        for (int c = 0; c < 24; ++c) DZ[site * 24 + c] = 0.f;
-        return;
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int C = h ? 3 : 21;
-        const float* z = Z + site * 24 + (h ? 21 : 0);
-        float* dz = DZ + site * 24 + (h ? 21 : 0);
-        float bv = z[0]; int bi = 0;
-        for (int c = 1; c < C; ++c) if (z[c] > bv) { bv = z[c]; bi = c; }           // the first maximum
-        float se = 0.f, sz = 0.f;
-        for (int c = 0; c < C; ++c) { se += expf(z[c] - bv); sz += z[c]; }
-        int t = cls[site * 4 + h];
-        if (t >= C) t = C - 1;
-        // lp = z - logsumexp(z); loss = -(0.9 lp[t] + 0.1 / (C - 1) (sum(lp) - lp[t]))      optim.py:138-144
-        const float lse = bv + logf(se);
-        const float lpt = z[t] - lse, slp = sz - (float)C * lse;
-        const float off = 0.1f / (float)(C - 1);
-        if (site_loss) site_loss[site * 2 + h] = -(0.9f * lpt + off * (slp - lpt));
-        if (pred) pred[site * 2 + h] = (uint8_t)bi;
-        for (int c = 0; c < C; ++c) dz[c] = (expf(z[c] - lse) - (c == t ? 0.9f : off)) * inv_n;
-    }
-}
-
-// part[z][m] = sum of src[r * ld + m] over the rows r of slice z, in order; M <= 256
-__global__ __launch_bounds__(256) void k_tr_colsum(const float* __restrict__ src, int ld, int M, int64_t R, float* __restrict__ part)
-{
-    const int m = threadIdx.x;
-    if (m >= M) return;
-    const int64_t r0 = (int64_t)blockIdx.x * TR_KCH, r1 = r0 + TR_KCH < R ? r0 + TR_KCH : R;
-    float s = 0.f;
-    for (int64_t r = r0; r < r1; ++r) s += src[r * ld + m];
-    part[(int64_t)blockIdx.x * M + m] = s;
-}
-
-// ---- launch helpers ---------------------------------------------------------------------------
-void gemm(hipStream_t s, const TrGemm& g)
-{
-    const int64_t tiles = (int64_t)NSNP_CDIV(g.M, 16) * NSNP_CDIV(g.N, 16);
-    const unsigned Zn = (unsigned)NSNP_CDIV(g.K, (int64_t)g.kchunk);
-    hipLaunchKernelGGL(k_tr_gemm, dim3((unsigned)NSNP_CDIV(tiles, (int64_t)4), Zn), dim3(256), 0, s, g);
-}
-
-// Y(m, sample) = sum_k W(m, k) X(sample, k) (+ biases): K in one slice
-void gemm_rows(hipStream_t s, const float* W, TrDim wm, TrDim wk, int M, int K, const float* X, TrDim xs, int64_t S, float* Y, TrDim ys,
-               const float* b1, const float* b2, int flags)
-{
-    TrGemm g{};
-    g.A = W; g.B = X; g.C = Y; g.bias = b1; g.bias2 = b2;
-    g.M = M; g.N = (int)S; g.K = K; g.kchunk = K;
-    g.am = wm; g.ak = wk; g.bk = lin(1); g.bn = xs; g.cm = lin(1); g.cn = ys; g.cz = 0; g.flags = flags;
-    gemm(s, g);
-}
-
-// dW[m][n] (+)= sum over rows r of DY(r, m) X(r, n): slices of TR_KCH rows, then the ordered sum
-void wgrad(hipStream_t s, float* part, const float* DY, TrDim dyr, int M, const float* X, TrDim xr, int N, int64_t R, float* out, int add)
-{
-    TrGemm g{};
-    g.A = DY; g.B = X; g.C = part;
-    g.M = M; g.N = N; g.K = R; g.kchunk = TR_KCH;
-    g.am = lin(1); g.ak = dyr; g.bk = xr; g.bn = lin(1); g.cm = lin(N); g.cn = lin(1); g.cz = (int64_t)M * N; g.flags = 0;
-    gemm(s, g);
-    hipLaunchKernelGGL(k_tr_reduce, dim3(blocks((int64_t)M * N)), dim3(256), 0, s, (const float*)part, (int64_t)M * N,
-                       (int)NSNP_CDIV(R, (int64_t)TR_KCH), add, out, (float*)nullptr);
-}
-
-void bgrad(hipStream_t s, float* part, const float* src, int ld, int M, int64_t R, float* out, float* out2, int add)
-{
-    const int Zn = (int)NSNP_CDIV(R, (int64_t)TR_KCH);
-    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)Zn), dim3(256), 0, s, src, ld, M, R, part);
-    hipLaunchKernelGGL(k_tr_reduce, dim3(blocks(M)), dim3(256), 0, s, (const float*)part, (int64_t)M, Zn, add, out, out2);
 }
 
 // one chunk of n <= reservation sites; `add`: the gradients of earlier chunks are in grads already
@@ -346,35 +191,35 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const int32_t* counts, cons
         ScopedKernelTimer tm(ctx, NSNP_K_TRAIN_FWD, s);
         hipLaunchKernelGGL(k_tr_gather, dim3(blocks(np * F_X0)), dim3(256), 0, s, counts, center_idx, n, np * F_X0, w.X0);
         for (int d = 0; d < 2; ++d)             // layer 0 input projections: G0[d][site][step] = W_ih x(position of the step) + b_ih + b_hh
-            gemm_rows(s, P[4 * d], lin(18), lin(1), 256, 18, w.X0 + (d ? 32 * 18 : 0), two(33, 33 * 18, d ? -18 : 18), S0,
-                      w.G0 + d * S0 * 256, lin(256), P[4 * d + 2], P[4 * d + 3], 0);
+            gemm1(s, rows_gemm(P[4 * d], lin(18), lin(1), 256, 18, w.X0 + (d ? 32 * 18 : 0), lin(1), two(33, 33 * 18, d ? -18 : 18), S0,
+                      w.G0 + d * S0 * 256, lin(256), P[4 * d + 2], P[4 * d + 3], 0));
         hipLaunchKernelGGL(k_tr_lstm_fwd, dim3(groups, 2), dim3(256), 0, s, w.G0, P[1], P[5], w.H0, w.C0, 33, 33, 1);
         hipLaunchKernelGGL(k_tr_mask, dim3(blocks(np * F_H0)), dim3(256), 0, s, (const float*)w.H0, w.X1, mask, scale, n * F_H0, np * F_H0);
         for (int d = 0; d < 2; ++d)             // layer 1: steps 0..16 are positions 0..16 (forward) and 32..16 (reverse)
-            gemm_rows(s, P[8 + 4 * d], lin(128), lin(1), 256, 128, w.X1 + (d ? 32 * 128 : 0), two(17, 33 * 128, d ? -128 : 128), S1,
-                      w.G1 + d * S1 * 256, lin(256), P[8 + 4 * d + 2], P[8 + 4 * d + 3], 0);
+            gemm1(s, rows_gemm(P[8 + 4 * d], lin(128), lin(1), 256, 128, w.X1 + (d ? 32 * 128 : 0), lin(1), two(17, 33 * 128, d ? -128 : 128), S1,
+                      w.G1 + d * S1 * 256, lin(256), P[8 + 4 * d + 2], P[8 + 4 * d + 3], 0));
         hipLaunchKernelGGL(k_tr_lstm_fwd, dim3(groups, 2), dim3(256), 0, s, w.G1, P[9], P[13], w.H1, w.C1, 17, 17, 0);
         const float* h1c = w.H1 + 16 * 128;     // step 16 of both directions = position 16; one row per site, 17 * 128 apart
-        gemm_rows(s, P[16], lin(128), lin(1), 128, 128, h1c, lin(17 * 128), np, w.Y1, lin(128), P[17], nullptr, 0);
-        gemm_rows(s, P[18], lin(128), lin(1), 256, 128, w.Y1, lin(128), np, w.X2, lin(256), P[19], nullptr, 2);
-        gemm_rows(s, P[20], lin(256), lin(1), 21, 256, w.X2, lin(256), np, w.Z, lin(24), P[21], nullptr, 0);
-        gemm_rows(s, P[22], lin(256), lin(1), 3, 256, w.X2, lin(256), np, w.Z + 21, lin(24), P[23], nullptr, 0);
-        hipLaunchKernelGGL(k_tr_loss, dim3(blocks(np)), dim3(256), 0, s, (const float*)w.Z, cls, n, np, inv_n, w.DZ, site_loss, pred);
+        gemm1(s, rows_gemm(P[16], lin(128), lin(1), 128, 128, h1c, lin(1), lin(17 * 128), np, w.Y1, lin(128), P[17], nullptr, 0));
+        gemm1(s, rows_gemm(P[18], lin(128), lin(1), 256, 128, w.Y1, lin(1), lin(128), np, w.X2, lin(256), P[19], nullptr, 2));
+        gemm1(s, rows_gemm(P[20], lin(256), lin(1), 21, 256, w.X2, lin(1), lin(256), np, w.Z, lin(24), P[21], nullptr, 0));
+        gemm1(s, rows_gemm(P[22], lin(256), lin(1), 3, 256, w.X2, lin(1), lin(256), np, w.Z + 21, lin(24), P[23], nullptr, 0));
+        hipLaunchKernelGGL(k_tr_loss, dim3(blocks(np)), dim3(256), 0, s, (const float*)w.Z, cls, n, np, 21, 3, 24, 4, inv_n, w.DZ, site_loss, pred);
     }
     {
         ScopedKernelTimer tm(ctx, NSNP_K_TRAIN_BWD, s);
         // heads^T, tanh', dense^T, output_proj^T
-        gemm_rows(s, P[20], lin(1), lin(256), 256, 21, w.DZ, lin(24), np, w.DX2, lin(256), nullptr, nullptr, 0);
-        gemm_rows(s, P[22], lin(1), lin(256), 256, 3, w.DZ + 21, lin(24), np, w.DX2, lin(256), nullptr, nullptr, 1);
+        gemm1(s, rows_gemm(P[20], lin(1), lin(256), 256, 21, w.DZ, lin(1), lin(24), np, w.DX2, lin(256), nullptr, nullptr, 0));
+        gemm1(s, rows_gemm(P[22], lin(1), lin(256), 256, 3, w.DZ + 21, lin(1), lin(24), np, w.DX2, lin(256), nullptr, nullptr, 1));
         hipLaunchKernelGGL(k_tr_dtanh, dim3(blocks(np * 256)), dim3(256), 0, s, w.DX2, (const float*)w.X2, np * 256);
-        gemm_rows(s, P[18], lin(1), lin(128), 128, 256, w.DX2, lin(256), np, w.DY1, lin(128), nullptr, nullptr, 0);
-        gemm_rows(s, P[16], lin(1), lin(128), 128, 128, w.DY1, lin(128), np, w.DH1, lin(128), nullptr, nullptr, 0);
+        gemm1(s, rows_gemm(P[18], lin(1), lin(128), 128, 256, w.DX2, lin(1), lin(256), np, w.DY1, lin(128), nullptr, nullptr, 0));
+        gemm1(s, rows_gemm(P[16], lin(1), lin(128), 128, 128, w.DY1, lin(1), lin(128), np, w.DH1, lin(128), nullptr, nullptr, 0));
         hipLaunchKernelGGL(k_tr_lstm_bwd, dim3(groups, 2), dim3(256), 0, s, w.G1, P[9], P[13], (const float*)w.C1, (const float*)w.DH1, 17, 17, 0, 1);
         // dx1 = sum over the directions of W_ih^T dgates at the step's position; position 16 receives both
         (void)hipMemsetAsync(w.DX1, 0, (size_t)(np * F_H0) * sizeof(float), s);
         for (int d = 0; d < 2; ++d)
-            gemm_rows(s, P[8 + 4 * d], lin(1), lin(128), 128, 256, w.G1 + d * S1 * 256, lin(256), S1, w.DX1 + (d ? 32 * 128 : 0),
-                      two(17, 33 * 128, d ? -128 : 128), nullptr, nullptr, 1);
+            gemm1(s, rows_gemm(P[8 + 4 * d], lin(1), lin(128), 128, 256, w.G1 + d * S1 * 256, lin(1), lin(256), S1, w.DX1 + (d ? 32 * 128 : 0),
+                      two(17, 33 * 128, d ? -128 : 128), nullptr, nullptr, 1));
         if (mask) hipLaunchKernelGGL(k_tr_mask, dim3(blocks(np * F_H0)), dim3(256), 0, s, (const float*)w.DX1, w.DX1, mask, scale, n * F_H0, np * F_H0);
         hipLaunchKernelGGL(k_tr_lstm_bwd, dim3(groups, 2), dim3(256), 0, s, w.G0, P[1], P[5], (const float*)w.C0, (const float*)w.DX1, 33, 33, 1, 0);
     }
@@ -383,24 +228,24 @@ void run_chunk(nsnp_ctx* ctx, const float* const* P, const int32_t* counts, cons
         float* part = w.PART;
         for (int d = 0; d < 2; ++d) {
             const float* g0 = w.G0 + d * S0 * 256;
-            wgrad(s, part, g0, lin(256), 256, w.X0 + (d ? 32 * 18 : 0), two(33, 33 * 18, d ? -18 : 18), 18, S0, grads[4 * d], add);
+            wgrad(s, part, TR_KCH, g0, lin(256), 256, w.X0 + (d ? 32 * 18 : 0), two(33, 33 * 18, d ? -18 : 18), lin(1), 18, S0, grads[4 * d], add);
             // step t + 1 (t = 0..31) meets the h of step t: position t (forward), 32 - t (reverse)
-            wgrad(s, part, g0 + 256, two(32, 33 * 256, 256), 256, w.H0 + d * 64 + (d ? 32 * 128 : 0), two(32, 33 * 128, d ? -128 : 128), 64,
+            wgrad(s, part, TR_KCH, g0 + 256, two(32, 33 * 256, 256), 256, w.H0 + d * 64 + (d ? 32 * 128 : 0), two(32, 33 * 128, d ? -128 : 128), lin(1), 64,
                   np * 32, grads[4 * d + 1], add);
-            bgrad(s, part, g0, 256, 256, S0, grads[4 * d + 2], grads[4 * d + 3], add);
+            bgrad(s, part, TR_KCH, g0, lin(256), 256, S0, grads[4 * d + 2], grads[4 * d + 3], add);
             const float* g1 = w.G1 + d * S1 * 256;
-            wgrad(s, part, g1, lin(256), 256, w.X1 + (d ? 32 * 128 : 0), two(17, 33 * 128, d ? -128 : 128), 128, S1, grads[8 + 4 * d], add);
-            wgrad(s, part, g1 + 256, two(16, 17 * 256, 256), 256, w.H1 + d * 64, two(16, 17 * 128, 128), 64, np * 16, grads[8 + 4 * d + 1], add);
-            bgrad(s, part, g1, 256, 256, S1, grads[8 + 4 * d + 2], grads[8 + 4 * d + 3], add);
+            wgrad(s, part, TR_KCH, g1, lin(256), 256, w.X1 + (d ? 32 * 128 : 0), two(17, 33 * 128, d ? -128 : 128), lin(1), 128, S1, grads[8 + 4 * d], add);
+            wgrad(s, part, TR_KCH, g1 + 256, two(16, 17 * 256, 256), 256, w.H1 + d * 64, two(16, 17 * 128, 128), lin(1), 64, np * 16, grads[8 + 4 * d + 1], add);
+            bgrad(s, part, TR_KCH, g1, lin(256), 256, S1, grads[8 + 4 * d + 2], grads[8 + 4 * d + 3], add);
         }
-        wgrad(s, part, w.DY1, lin(128), 128, w.H1 + 16 * 128, lin(17 * 128), 128, np, grads[16], add);
-        bgrad(s, part, w.DY1, 128, 128, np, grads[17], nullptr, add);
-        wgrad(s, part, w.DX2, lin(256), 256, w.Y1, lin(128), 128, np, grads[18], add);
-        bgrad(s, part, w.DX2, 256, 256, np, grads[19], nullptr, add);
-        wgrad(s, part, w.DZ, lin(24), 21, w.X2, lin(256), 256, np, grads[20], add);
-        bgrad(s, part, w.DZ, 24, 21, np, grads[21], nullptr, add);
-        wgrad(s, part, w.DZ + 21, lin(24), 3, w.X2, lin(256), 256, np, grads[22], add);
-        bgrad(s, part, w.DZ + 21, 24, 3, np, grads[23], nullptr, add);
+        wgrad(s, part, TR_KCH, w.DY1, lin(128), 128, w.H1 + 16 * 128, lin(17 * 128), lin(1), 128, np, grads[16], add);
+        bgrad(s, part, TR_KCH, w.DY1, lin(128), 128, np, grads[17], nullptr, add);
+        wgrad(s, part, TR_KCH, w.DX2, lin(256), 256, w.Y1, lin(128), lin(1), 128, np, grads[18], add);
+        bgrad(s, part, TR_KCH, w.DX2, lin(256), 256, np, grads[19], nullptr, add);
+        wgrad(s, part, TR_KCH, w.DZ, lin(24), 21, w.X2, lin(256), lin(1), 256, np, grads[20], add);
+        bgrad(s, part, TR_KCH, w.DZ, lin(24), 21, np, grads[21], nullptr, add);
+        wgrad(s, part, TR_KCH, w.DZ + 21, lin(24), 3, w.X2, lin(256), lin(1), 256, np, grads[22], add);
+        bgrad(s, part, TR_KCH, w.DZ + 21, lin(24), 3, np, grads[23], nullptr, add);
     }
 }
 
@@ -416,18 +261,10 @@ extern "C" int nsnp_pileup_train_reserve(nsnp_ctx* ctx, int64_t max_sites)
 {
     if (!ctx || max_sites <= 0 || max_sites > TR_MAX_SITES) return NSNP_EINVAL;
     if (ctx->tr_ws && ctx->tr_sites == max_sites) return NSNP_OK;
-    NSNP_HIP(ctx, hipSetDevice(ctx->device));
-    NSNP_HIP(ctx, hipDeviceSynchronize());
     const int64_t cap = NSNP_CDIV(max_sites, (int64_t)16) * 16;
-    void* ws = nullptr;
-    const hipError_t e = hipMalloc(&ws, (size_t)(cap * F_SITE + part_floats(cap)) * sizeof(float));
-    if (e != hipSuccess) {                                   // the previous reservation stays in force
-        (void)hipGetLastError();
-        ctx->last_err = e;
-        return e == hipErrorOutOfMemory ? NSNP_ENOMEM : NSNP_EHIP;
-    }
-    if (ctx->tr_ws) (void)hipFree(ctx->tr_ws);
-    ctx->tr_ws = ws; ctx->tr_sites = max_sites;
+    const int rc = reserve_ws(ctx, &ctx->tr_ws, (size_t)(cap * F_SITE + part_floats(cap)) * sizeof(float));
+    if (rc != NSNP_OK) return rc;
+    ctx->tr_sites = max_sites;
     return NSNP_OK;
 }
 

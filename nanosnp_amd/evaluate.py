@@ -15,9 +15,33 @@ import os
 
 import numpy as np
 
-from . import _lib, host, sitefile
+from . import _lib, hap_pipeline, host, sitefile
 
 HEAD_NAMES = ("gt", "zy", "id1", "id2")
+
+
+def _paths(paths, suffix):
+    """a list of paths as given; a directory: its files whose names end with `suffix`, in os.listdir order; anything else: that one path"""
+    if isinstance(paths, (str, os.PathLike)):
+        d = str(paths)
+        return [os.path.join(d, f) for f in os.listdir(d) if f.endswith(suffix)] if os.path.isdir(d) else [d]
+    return [str(p) for p in paths]
+
+
+def _open_window_files(paths):
+    """the ``.td.bin`` files of a run, memory-mapped; every header is checked before anything runs"""
+    files = []
+    for p in paths:
+        idx = sitefile.array_index(p)
+        if ("position_matrix" not in idx or idx["position_matrix"][0] not in (np.dtype(np.int32), np.dtype(np.int16))
+                or idx["position_matrix"][1][1:] != (33, 18)):
+            raise sitefile.SiteFileError(f"{p}: not a window file (position_matrix int16 / int32 [N,33,18])")
+        n = int(idx["position_matrix"][1][0])
+        if "label" not in idx or idx["label"][0] != np.dtype(np.int32) or idx["label"][1] != (n, _lib.Context.LABEL_WIDTH):
+            raise sitefile.SiteFileError(f"{p}: not a training window file (no label int32 [N,{_lib.Context.LABEL_WIDTH}] beside the windows)")
+        a = sitefile.read_arrays(p, mmap=True)
+        files.append(dict(path=p, n=n, x=a["position_matrix"], y=a["label"], elem=idx["position_matrix"][0].itemsize))
+    return files
 
 
 class _PassSet:
@@ -72,22 +96,7 @@ def evaluate_train_bins(model, validating_paths, batch_size=1000, variants_only=
     st = stats if stats is not None else {}
     for k in ("passes", "rows", "bytes_h2d"):
         st.setdefault(k, 0)
-    if isinstance(validating_paths, (str, os.PathLike)):
-        d = str(validating_paths)
-        paths = [os.path.join(d, f) for f in os.listdir(d) if f.endswith(".bin")] if os.path.isdir(d) else [d]
-    else:
-        paths = [str(p) for p in validating_paths]
-    files = []
-    for p in paths:                                        # every header is checked before anything runs
-        idx = sitefile.array_index(p)
-        if ("position_matrix" not in idx or idx["position_matrix"][0] not in (np.dtype(np.int32), np.dtype(np.int16))
-                or idx["position_matrix"][1][1:] != (33, 18)):
-            raise sitefile.SiteFileError(f"{p}: not a window file (position_matrix int16 / int32 [N,33,18])")
-        n = int(idx["position_matrix"][1][0])
-        if "label" not in idx or idx["label"][0] != np.dtype(np.int32) or idx["label"][1] != (n, _lib.Context.LABEL_WIDTH):
-            raise sitefile.SiteFileError(f"{p}: not a training window file (no label int32 [N,{_lib.Context.LABEL_WIDTH}] beside the windows)")
-        a = sitefile.read_arrays(p, mmap=True)
-        files.append(dict(path=p, n=n, x=a["position_matrix"], y=a["label"], elem=idx["position_matrix"][0].itemsize))
+    files = _open_window_files(_paths(validating_paths, ".bin"))
     P = int(max(1, pass_sites))
     passes = [(fi, a, min(f["n"], a + P)) for fi, f in enumerate(files) for a in range(0, f["n"], P)]
     last_pass_of = {fi: k for k, (fi, _, _) in enumerate(passes)}
@@ -196,7 +205,6 @@ class _HapPassSet:
     """buffers of one pass in flight: hap_pipeline's set of read planes and position arrays with the pass's label rows beside them"""
     def __init__(self, P, Dp, Dh, elem, dev=None):
         import torch
-        from . import hap_pipeline
         self.planes = hap_pipeline._Set(P, Dp, Dh, elem, dev)
         kw = dict(pin_memory=True) if dev is None else dict(device=dev)
         self.y = torch.empty((P, sitefile.HAP_LABEL_WIDTH), dtype=torch.int32, **kw)
@@ -218,6 +226,80 @@ def _macro_prf(cm):
     recall, precision = tp / (tp + fn + 1e-6), tp / (tp + fp + 1e-6)
     f1 = 2 * (precision * recall) / (precision + recall + 1e-6)
     return float(recall.mean()), float(precision.mean()), float(f1.mean())
+
+
+def _open_hap_files(paths, narrow):
+    """the labelled haplotype bins of a run, open (the caller closes every f["src"]); every header is checked before anything runs.
+    e_out: the bytes per plane element a pass is staged with - 1 (int8) under `narrow` until a value does not fit"""
+    files = []
+    try:
+        for p in paths:
+            src = hap_pipeline.HapBinSource(p)
+            files.append(dict(path=p, src=src, n=src.n, e_out=1 if (narrow or src.elem == 1) else src.elem))
+            y = src.idx.get("candidate_labels")
+            if y is None or y[0] != np.dtype(np.int32) or y[1] != (src.n, sitefile.HAP_LABEL_WIDTH):
+                raise sitefile.SiteFileError(f"{p}: not a labelled haplotype bin (no candidate_labels int32 [N,{sitefile.HAP_LABEL_WIDTH}] "
+                                             "beside the read planes)")
+            files[-1]["y"] = sitefile.read_arrays(p, mmap=True)["candidate_labels"]
+    except BaseException:
+        for f in files:
+            f["src"].close()
+        raise
+    return files
+
+
+def _fill_hap_pass(f, a, b, hs, reference):
+    """rows [a, b) of file f into the pinned set hs: the eight planes, narrowed to int8 while that fits, the parsed positions (contigs the
+    reference's table does not know yet are added to it) and the label rows; -> bytes of planes staged"""
+    src, m, hp = f["src"], b - a, hs.planes
+    while True:
+        e_out, nbytes, overflow = f["e_out"], 0, False
+        for name in hap_pipeline.PILEUP_PLANES + hap_pipeline.HAPLOTYPE_PLANES:
+            cnt = m * (src.Dp * 33 if name.startswith("pileup") else src.Dh * 11)
+            v = hp.planes[name].numpy()[:cnt * e_out].view(np.int8 if e_out == 1 else np.int32)
+            if src.stage_plane(name, a, b, v):
+                overflow = True                            # a value outside int8 (e.g. a mapping quality of 255)
+                break
+            nbytes += v.nbytes
+        if not overflow:
+            break
+        f["e_out"] = src.elem                              # this pass again, and the rest of the file, as the file's own dtype
+    cand_f, hap_f = src.position_fields(a, b)
+    cand_f = cand_f.reshape(m, -1)
+    cp, cc = host.parse_ctg_pos(cand_f, reference.table)
+    if (cc < 0).any():
+        reference.add_names([bytes(r).rstrip(b"\0").split(b":")[0].decode() for r in cand_f[cc < 0]])
+        cp, cc = host.parse_ctg_pos(cand_f, reference.table)
+    hpos, hctg = host.parse_ctg_pos(hap_f.reshape(m, 11, -1), reference.table)
+    hp.cand_pos.numpy()[:m] = cp; hp.cand_ctg.numpy()[:m] = cc
+    hp.hap_pos.numpy()[:m] = hpos; hp.hap_ctg.numpy()[:m] = hctg
+    hs.y.numpy()[:m] = f["y"][a:b]
+    return nbytes
+
+
+def _send_hap_pass(f, m, hs, ds):
+    """the m filled rows of the pinned set hs to the device set ds, on the current stream"""
+    src, e_out, hp, dp = f["src"], f["e_out"], hs.planes, ds.planes
+    for name in hap_pipeline.PILEUP_PLANES + hap_pipeline.HAPLOTYPE_PLANES:
+        cnt = m * (src.Dp * 33 if name.startswith("pileup") else src.Dh * 11) * e_out
+        dp.planes[name][:cnt].copy_(hp.planes[name][:cnt], non_blocking=True)
+    dp.cand_pos[:m].copy_(hp.cand_pos[:m], non_blocking=True); dp.cand_ctg[:m].copy_(hp.cand_ctg[:m], non_blocking=True)
+    dp.hap_pos[:m].copy_(hp.hap_pos[:m], non_blocking=True); dp.hap_ctg[:m].copy_(hp.hap_ctg[:m], non_blocking=True)
+    ds.y[:m].copy_(hs.y[:m], non_blocking=True)
+
+
+def _hap_pass_features(ctx, f, m, ds, hs, reference, off33):
+    """every row of the pass on the device set ds reduced to features -> (xp, xh); its label pass into ds.cls, ds.rows and hs.meta"""
+    import torch
+    src, e_out, dp = f["src"], f["e_out"], ds.planes
+    ref_p = reference.rows(dp.cand_ctg[:m, None].expand(m, 33), dp.cand_pos[:m, None] - 1 + off33)      # as stream_segments fetches them
+    ref_h = reference.rows(dp.hap_ctg[:m], dp.hap_pos[:m] - 1)
+    tdt = torch.int8 if e_out == 1 else torch.int32
+    pl = lambda name, D, L: dp.planes[name][:m * D * L * e_out].view(tdt).view(m, D, L)
+    xp = ctx.hap_features(*[pl(nm, src.Dp, 33) for nm in hap_pipeline.PILEUP_PLANES], ref_p)
+    xh = ctx.hap_features(*[pl(nm, src.Dh, 11) for nm in hap_pipeline.HAPLOTYPE_PLANES], ref_h)
+    ctx.hap_label_classes(ds.y[:m], cls=ds.cls, rows=ds.rows, meta=hs.meta)
+    return xp, xh
 
 
 def evaluate_haplotype_bins(model, bin_paths, reference, batch_size=512, pass_sites=16384, narrow=True, keep_sites=False, stats=None):
@@ -248,7 +330,6 @@ def evaluate_haplotype_bins(model, bin_paths, reference, batch_size=512, pass_si
     and scored (nsnp_hap_eval).  Losses, predictions, classes and rows stay on the device until the run ends."""
     import torch
     import torch.distributed as tdist
-    from . import hap_pipeline
     if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
         raise NotImplementedError("evaluate_haplotype_bins under a process group of more than one rank (validation is not sharded)")
     if not getattr(model, "_loaded", False):
@@ -264,21 +345,8 @@ def evaluate_haplotype_bins(model, bin_paths, reference, batch_size=512, pass_si
     st = stats if stats is not None else {}
     for k in ("passes", "rows", "bytes_h2d", "passes_int8"):
         st.setdefault(k, 0)
-    if isinstance(bin_paths, (str, os.PathLike)):
-        d = str(bin_paths)
-        paths = [os.path.join(d, f) for f in os.listdir(d)] if os.path.isdir(d) else [d]
-    else:
-        paths = [str(p) for p in bin_paths]
-    files = []
+    files = _open_hap_files(_paths(bin_paths, ""), narrow)                 # (a directory: every file of it)
     try:
-        for p in paths:                                    # every header is checked before anything runs
-            src = hap_pipeline.HapBinSource(p)
-            files.append(dict(path=p, src=src, n=src.n, e_out=1 if (narrow or src.elem == 1) else src.elem))
-            y = src.idx.get("candidate_labels")
-            if y is None or y[0] != np.dtype(np.int32) or y[1] != (src.n, sitefile.HAP_LABEL_WIDTH):
-                raise sitefile.SiteFileError(f"{p}: not a labelled haplotype bin (no candidate_labels int32 [N,{sitefile.HAP_LABEL_WIDTH}] "
-                                             "beside the read planes)")
-            files[-1]["y"] = sitefile.read_arrays(p, mmap=True)["candidate_labels"]
         return _evaluate_haplotype(model, ctx, dev, files, reference, B, int(max(1, pass_sites)), keep_sites, st, n_gt, n_zy)
     finally:
         for f in files:
@@ -287,7 +355,6 @@ def evaluate_haplotype_bins(model, bin_paths, reference, batch_size=512, pass_si
 
 def _evaluate_haplotype(model, ctx, dev, files, reference, B, P, keep_sites, st, n_gt, n_zy):
     import torch
-    from . import hap_pipeline
     passes = [(fi, a, min(f["n"], a + P)) for fi, f in enumerate(files) for a in range(0, f["n"], P)]
     last_pass_of = {fi: k for k, (fi, _, _) in enumerate(passes)}
     counters = ctx.hap_eval_counters(dev)
@@ -312,65 +379,24 @@ def _evaluate_haplotype(model, ctx, dev, files, reference, B, P, keep_sites, st,
         labelled = [None] * len(passes)                    # the event behind the label pass of pass k (blocking: the host sleeps on it)
         fill = {}                                          # file -> kept sites so far
         off33 = torch.arange(-16, 17, dtype=torch.int64, device=dev)[None, :]
-        PL, HL = hap_pipeline.PILEUP_PLANES, hap_pipeline.HAPLOTYPE_PLANES
-
-        def stage_planes(f, a, b, hp):
-            """the eight planes of rows [a, b) into the pinned set, narrowed to int8 while that fits; -> bytes staged"""
-            src, m = f["src"], b - a
-            while True:
-                e_out, nbytes, overflow = f["e_out"], 0, False
-                for name in PL + HL:
-                    cnt = m * (src.Dp * 33 if name.startswith("pileup") else src.Dh * 11)
-                    v = hp.planes[name].numpy()[:cnt * e_out].view(np.int8 if e_out == 1 else np.int32)
-                    if src.stage_plane(name, a, b, v):
-                        overflow = True                    # a value outside int8 (e.g. a mapping quality of 255)
-                        break
-                    nbytes += v.nbytes
-                if not overflow:
-                    return nbytes
-                f["e_out"] = src.elem                      # this pass again, and the rest of the file, as the file's own dtype
 
         def issue(k):
             """stage pass k, send it, reduce every row to features, run its label pass"""
             fi, a, b = passes[k]
             f, m = files[fi], b - a
-            src = f["src"]
             hs, ds = hsets[k % 3], dsets[k % 3]
-            hp, dp = hs.planes, ds.planes
             if hs.h2d_done is not None:
                 hs.h2d_done.synchronize()                  # (pass k - 3 has left this pinned set)
-            nbytes = stage_planes(f, a, b, hp)
-            e_out = f["e_out"]
-            cand_f, hap_f = src.position_fields(a, b)
-            cand_f = cand_f.reshape(m, -1)
-            cp, cc = host.parse_ctg_pos(cand_f, reference.table)
-            if (cc < 0).any():
-                reference.add_names([bytes(r).rstrip(b"\0").split(b":")[0].decode() for r in cand_f[cc < 0]])
-                cp, cc = host.parse_ctg_pos(cand_f, reference.table)
-            hpos, hctg = host.parse_ctg_pos(hap_f.reshape(m, 11, -1), reference.table)
-            hp.cand_pos.numpy()[:m] = cp; hp.cand_ctg.numpy()[:m] = cc
-            hp.hap_pos.numpy()[:m] = hpos; hp.hap_ctg.numpy()[:m] = hctg
-            hs.y.numpy()[:m] = f["y"][a:b]
+            nbytes = _fill_hap_pass(f, a, b, hs, reference)
             if ds.free is not None:
                 copy_stream.wait_event(ds.free)            # (pass k - 3 has been scored out of this device set)
             with torch.cuda.stream(copy_stream):
-                for name in PL + HL:
-                    cnt = m * (src.Dp * 33 if name.startswith("pileup") else src.Dh * 11) * e_out
-                    dp.planes[name][:cnt].copy_(hp.planes[name][:cnt], non_blocking=True)
-                dp.cand_pos[:m].copy_(hp.cand_pos[:m], non_blocking=True); dp.cand_ctg[:m].copy_(hp.cand_ctg[:m], non_blocking=True)
-                dp.hap_pos[:m].copy_(hp.hap_pos[:m], non_blocking=True); dp.hap_ctg[:m].copy_(hp.hap_ctg[:m], non_blocking=True)
-                ds.y[:m].copy_(hs.y[:m], non_blocking=True)
+                _send_hap_pass(f, m, hs, ds)
                 hs.h2d_done = torch.cuda.Event(blocking=True); hs.h2d_done.record(copy_stream)
             main.wait_event(hs.h2d_done)
-            ref_p = reference.rows(dp.cand_ctg[:m, None].expand(m, 33), dp.cand_pos[:m, None] - 1 + off33)      # as stream_segments fetches them
-            ref_h = reference.rows(dp.hap_ctg[:m], dp.hap_pos[:m] - 1)
-            tdt = torch.int8 if e_out == 1 else torch.int32
-            pl = lambda name, D, L: dp.planes[name][:m * D * L * e_out].view(tdt).view(m, D, L)
-            ds.xp = ctx.hap_features(*[pl(nm, src.Dp, 33) for nm in PL], ref_p)
-            ds.xh = ctx.hap_features(*[pl(nm, src.Dh, 11) for nm in HL], ref_h)
-            ctx.hap_label_classes(ds.y[:m], cls=ds.cls, rows=ds.rows, meta=hs.meta)
+            ds.xp, ds.xh = _hap_pass_features(ctx, f, m, ds, hs, reference, off33)
             labelled[k] = torch.cuda.Event(blocking=True); labelled[k].record(main)
-            st["passes"] += 1; st["rows"] += m; st["bytes_h2d"] += nbytes + m * (12 * 12 + 12); st["passes_int8"] += int(e_out == 1)
+            st["passes"] += 1; st["rows"] += m; st["bytes_h2d"] += nbytes + m * (12 * 12 + 12); st["passes_int8"] += int(f["e_out"] == 1)
 
         def score(k):
             """the kept sites of pass k (its count is on the host by now) through forward, loss and counts"""

@@ -36,11 +36,10 @@ steps them unchanged, ``train_haplotype_bins`` is one epoch over labelled haplot
 from __future__ import annotations
 
 import math
-import os
 
 import numpy as np
 
-from . import _lib, sitefile
+from . import _lib
 from .pileup_model import ENCODER_KEYS, FORWARD_KEYS, INDEL_KEYS, LSTMNetwork
 
 PARAM_NAMES = ["encoder." + k for k in ENCODER_KEYS] + ["forward_layer." + k for k in FORWARD_KEYS]
@@ -309,13 +308,6 @@ class DeviceOptimizer:
             self.current_epoch = int(current_epoch)
 
 
-def _paths(training_paths):
-    if isinstance(training_paths, (str, os.PathLike)):
-        d = str(training_paths)
-        return [os.path.join(d, f) for f in os.listdir(d) if f.endswith(".bin")] if os.path.isdir(d) else [d]
-    return [str(p) for p in training_paths]
-
-
 def pass_order(generator, m):
     """the order of the m rows of one pass: a seeded torch.randperm on the CPU generator of the epoch"""
     import torch
@@ -337,7 +329,7 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     rather than per site); the accuracies are over sites, from the argmax the loss kernel writes."""
     import torch
     import torch.distributed as tdist
-    from .evaluate import _PassSet
+    from .evaluate import _PassSet, _open_window_files, _paths
     if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
         raise NotImplementedError("train_train_bins under a process group of more than one rank (training is not sharded)")
     B = int(batch_size)
@@ -352,17 +344,7 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     st = stats if stats is not None else {}
     for k in ("passes", "rows", "bytes_h2d"):
         st.setdefault(k, 0)
-    files = []
-    for p in _paths(training_paths):                           # every header is checked before anything runs
-        idx = sitefile.array_index(p)
-        if ("position_matrix" not in idx or idx["position_matrix"][0] not in (np.dtype(np.int32), np.dtype(np.int16))
-                or idx["position_matrix"][1][1:] != (33, 18)):
-            raise sitefile.SiteFileError(f"{p}: not a window file (position_matrix int16 / int32 [N,33,18])")
-        n = int(idx["position_matrix"][1][0])
-        if "label" not in idx or idx["label"][0] != np.dtype(np.int32) or idx["label"][1] != (n, _lib.Context.LABEL_WIDTH):
-            raise sitefile.SiteFileError(f"{p}: not a training window file (no label int32 [N,{_lib.Context.LABEL_WIDTH}] beside the windows)")
-        a = sitefile.read_arrays(p, mmap=True)
-        files.append(dict(path=p, n=n, x=a["position_matrix"], y=a["label"], elem=idx["position_matrix"][0].itemsize))
+    files = _open_window_files(_paths(training_paths, ".bin"))
     P = int(max(1, pass_sites))
     order_gen = torch.Generator().manual_seed(int(seed))
     mask_gen = torch.Generator(device=dev).manual_seed(int(seed))
@@ -523,7 +505,7 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
     stream nn.LSTM draws from; there is no epoch loop for this model yet (``fit`` is the PileupModel's); Ranger is not implemented."""
     import torch
     import torch.distributed as tdist
-    from . import evaluate, hap_pipeline, host
+    from . import evaluate, hap_pipeline
     if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
         raise NotImplementedError("train_haplotype_bins under a process group of more than one rank (training is not sharded)")
     if not isinstance(reference, hap_pipeline.DeviceReference):
@@ -543,17 +525,8 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
     if getattr(ctx, "_hap_dims", None) != (trainer.dims["gt_num_class"], trainer.dims["zy_num_class"]):
         trainer.to_model()
     P = int(max(1, pass_sites))
-    PL, HL = hap_pipeline.PILEUP_PLANES, hap_pipeline.HAPLOTYPE_PLANES
-    files = []
+    files = evaluate._open_hap_files(evaluate._paths(bin_paths, ".bin"), True)
     try:
-        for p in _paths(bin_paths):                            # every header is checked before anything runs
-            src = hap_pipeline.HapBinSource(p)
-            files.append(dict(path=p, src=src, n=src.n, e_out=1))
-            y = src.idx.get("candidate_labels")
-            if y is None or y[0] != np.dtype(np.int32) or y[1] != (src.n, sitefile.HAP_LABEL_WIDTH):
-                raise sitefile.SiteFileError(f"{p}: not a labelled haplotype bin (no candidate_labels int32 [N,{sitefile.HAP_LABEL_WIDTH}] "
-                                             "beside the read planes)")
-            files[-1]["y"] = sitefile.read_arrays(p, mmap=True)["candidate_labels"]
         order_gen = torch.Generator().manual_seed(int(seed))
         mask_gen = torch.Generator(device=dev).manual_seed(int(seed))
         batch_losses, correct = [], torch.zeros(2, dtype=torch.int64, device=dev)
@@ -565,47 +538,13 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
             hs, ds = evaluate._HapPassSet(Pmax, Dp, Dh, elem), evaluate._HapPassSet(Pmax, Dp, Dh, elem, dev)
             off33 = torch.arange(-16, 17, dtype=torch.int64, device=dev)[None, :]
         for f in live:
-            src = f["src"]
             for a in range(0, f["n"], P):
                 b = min(f["n"], a + P)
                 m = b - a
-                hp, dp = hs.planes, ds.planes
                 torch.cuda.current_stream(dev).synchronize()   # (the previous pass has left both sets)
-                while True:                                    # the eight planes, narrowed to int8 while that fits
-                    e_out, nbytes, overflow = f["e_out"], 0, False
-                    for name in PL + HL:
-                        cnt = m * (src.Dp * 33 if name.startswith("pileup") else src.Dh * 11)
-                        v = hp.planes[name].numpy()[:cnt * e_out].view(np.int8 if e_out == 1 else np.int32)
-                        if src.stage_plane(name, a, b, v):
-                            overflow = True                    # a value outside int8 (e.g. a mapping quality of 255)
-                            break
-                        nbytes += v.nbytes
-                    if not overflow:
-                        break
-                    f["e_out"] = src.elem                      # this pass again, and the rest of the file, as the file's own dtype
-                cand_f, hap_f = src.position_fields(a, b)
-                cand_f = cand_f.reshape(m, -1)
-                cp, cc = host.parse_ctg_pos(cand_f, reference.table)
-                if (cc < 0).any():
-                    reference.add_names([bytes(r).rstrip(b"\0").split(b":")[0].decode() for r in cand_f[cc < 0]])
-                    cp, cc = host.parse_ctg_pos(cand_f, reference.table)
-                hpos, hctg = host.parse_ctg_pos(hap_f.reshape(m, 11, -1), reference.table)
-                hp.cand_pos.numpy()[:m] = cp; hp.cand_ctg.numpy()[:m] = cc
-                hp.hap_pos.numpy()[:m] = hpos; hp.hap_ctg.numpy()[:m] = hctg
-                hs.y.numpy()[:m] = f["y"][a:b]
-                for name in PL + HL:
-                    cnt = m * (src.Dp * 33 if name.startswith("pileup") else src.Dh * 11) * e_out
-                    dp.planes[name][:cnt].copy_(hp.planes[name][:cnt], non_blocking=True)
-                dp.cand_pos[:m].copy_(hp.cand_pos[:m], non_blocking=True); dp.cand_ctg[:m].copy_(hp.cand_ctg[:m], non_blocking=True)
-                dp.hap_pos[:m].copy_(hp.hap_pos[:m], non_blocking=True); dp.hap_ctg[:m].copy_(hp.hap_ctg[:m], non_blocking=True)
-                ds.y[:m].copy_(hs.y[:m], non_blocking=True)
-                ref_p = reference.rows(dp.cand_ctg[:m, None].expand(m, 33), dp.cand_pos[:m, None] - 1 + off33)
-                ref_h = reference.rows(dp.hap_ctg[:m], dp.hap_pos[:m] - 1)
-                tdt = torch.int8 if e_out == 1 else torch.int32
-                pl = lambda name, D, L: dp.planes[name][:m * D * L * e_out].view(tdt).view(m, D, L)
-                xp = ctx.hap_features(*[pl(nm, src.Dp, 33) for nm in PL], ref_p)
-                xh = ctx.hap_features(*[pl(nm, src.Dh, 11) for nm in HL], ref_h)
-                ctx.hap_label_classes(ds.y[:m], cls=ds.cls, rows=ds.rows, meta=hs.meta)
+                nbytes = evaluate._fill_hap_pass(f, a, b, hs, reference)
+                evaluate._send_hap_pass(f, m, hs, ds)
+                xp, xh = evaluate._hap_pass_features(ctx, f, m, ds, hs, reference, off33)
                 torch.cuda.current_stream(dev).synchronize()
                 meta = hs.meta.numpy().copy()
                 totals += meta

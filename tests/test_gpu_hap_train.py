@@ -4,7 +4,7 @@ The parity rule is the project's own: for every one of the 58 tensors max |g_dev
 tests/golden/hap_grad.npz (the reference's own fp32 distance from the restatement; 4 is the factor the forward and the pileup gradients are
 granted); loss and site_loss within 1e-4; pred equal wherever the float64 margin exceeds hap_eval_rules.MARGIN.
 
-The kernel's site tile is 64 (k_ht_gemm: 64 x 64 tiles of C) and a weight-gradient slice is 128 (site, step) rows: N = 1 has 33, 11 and
+The kernel's site tile is 64 (k_tr_gemm: 64 x 64 tiles of C) and a weight-gradient slice is 128 (site, step) rows: N = 1 has 33, 11 and
 fewer rows and crosses none, N = 17 crosses a slice boundary for both encoders at layers 0 and 1 (561 and 187 rows) and for neither at
 layer 2's recurrent weights of the 11-step encoder (85 rows), N = 96 crosses it everywhere."""
 from __future__ import annotations

@@ -4,7 +4,7 @@ float64 restatement tests/grad_rules.py; the idiom and the helpers are those of 
 What the sizes select (TR_KCH = 1,024 reduction rows per slice of a weight gradient, k_tr_reduce adds the slices' images):
   N = 1040 / 1025   the dense layers' and heads' weight and bias gradients get a second slice (16 rows; at N = 1025 one real row and 15
                     padding sites); layer 0 gets 34 slices whose starts 1024 z cover every residue modulo 33 (1024 % 33 == 1), layer 1
-                    every residue modulo 17 (1024 % 17 == 4): TrIter::init and the wrap of step4() from every phase
+                    every residue modulo 17 (1024 % 17 == 4): a slice of k_tr_gemm starts at every phase of the two-level K stride
   N = 257           the device against the numbers the REFERENCE's own fp32 model code left in tests/golden/pileup_grad.npz
   chunks            a reservation of 40 (cap 48 != tr_sites), N = 100 in chunks of 40, 40, 20 - each with padding sites - through
                     center_idx + base and keep_mask + base * F_H0
