@@ -774,11 +774,17 @@ class Context:
 
     NAME_ENTRY = 44           # NSNP_NAME_ENTRY
 
-    def mpileup_line_names(self, text, name, cap_lines, cap_names=64, line_idx=None, names=None, meta=None, stream=None):
-        """Column 0 of every line of a device text against `name` (nsnp_mpileup_line_names) -> (line_idx int32 [cap_lines]: -1 where the
-        line's first token is `name`, else its entry in names; names uint8 [cap_names, 44]; meta int64 [4] = {lines that differ, status})"""
+    # ---- what the wrappers of the record entries share (one contig: pos + chr_seq + name; several: key + ContigTable) ----
+
+    @staticmethod
+    def _device_or_pinned(*outs):
+        for t, what in outs:
+            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
+                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
+
+    def _line_names_outputs(self, text, cap_lines, cap_names, line_idx, names, meta):
+        """line_idx, names and meta of mpileup_line_names / _contigs: those not given, then the checks"""
         import torch
-        name = name.encode() if isinstance(name, str) else bytes(name)
         dev = text.device
         if line_idx is None:
             line_idx = torch.empty(max(int(cap_lines), 1), dtype=torch.int32, device=dev)
@@ -787,6 +793,69 @@ class Context:
         if meta is None:
             meta = torch.zeros(4, dtype=torch.int64, device=dev)
         assert text.dtype == torch.uint8 and text.is_cuda and line_idx.dtype == torch.int32 and line_idx.is_cuda and names.is_cuda
+        return line_idx, names, meta
+
+    def _records_outputs(self, what, n, elem, dev, position_matrix, position, meta, site_key=False):
+        """The outputs of pileup_window_records / _keys: those not given, then the checks (site_key False: the entry has none)"""
+        import torch
+        dt = {2: torch.int16, 4: torch.int32}.get(elem)
+        if dt is None:
+            raise NanoSNPError("elem: 2 (int16) or 4 (int32)")
+        keyed = site_key is not False
+        if position_matrix is None:
+            position_matrix = torch.empty((max(n, 1), 33, 18), dtype=dt, device=dev)
+        if position is None:
+            position = torch.empty((max(n, 1), self.POSITION_WIDTH), dtype=torch.uint8, device=dev)
+        if keyed and site_key is None:
+            site_key = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._device_or_pinned((position_matrix, "position_matrix"), (position, "position"), *([(site_key, "site_key")] if keyed else []), (meta, "meta"))
+        if (position_matrix.dtype != dt or position_matrix.numel() < n * 594 or position.dtype != torch.uint8 or position.numel() < n * self.POSITION_WIDTH
+                or (keyed and (site_key.dtype != torch.int64 or site_key.numel() < n))):
+            raise NanoSNPError(f"{what}: output buffers too small or of the wrong type")
+        return position_matrix, position, site_key, meta
+
+    def _records_views(self, n, position_matrix, position):
+        return position_matrix.view(-1)[:n * 594].view(n, 33, 18), position.view(-1)[:n * self.POSITION_WIDTH].view(n, self.POSITION_WIDTH)
+
+    @staticmethod
+    def _line_names_arg(line_names, m, maker):
+        """(line_idx, names) of `maker` for the same lines, or (None, None): per-site names"""
+        import torch
+        line_idx, names = line_names if line_names is not None else (None, None)
+        if line_idx is not None and (line_idx.dtype != torch.int32 or line_idx.numel() < m or not line_idx.is_cuda or not names.is_cuda):
+            raise NanoSNPError(f"line_names: device int32 [M] and the name table of {maker}")
+        return line_idx, names
+
+    def _alt_info_run(self, what, launch, n, dev, cap, blob, offsets, meta, stream):
+        """The outputs of pileup_alt_info / _keys (those not given, then the checks), launch(blob, cap, offsets, meta), and the second run
+        with the size the first one reported when neither a cap nor a blob was given"""
+        import torch
+        retry = cap is None and blob is None
+        cap = int(blob.numel() if blob is not None else (64 * n + 4096 if cap is None else cap))
+        if blob is None:
+            blob = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if meta is None:
+            meta = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._device_or_pinned((blob, "blob"), (offsets, "offsets"), (meta, "meta"))
+        if blob.numel() < cap or offsets.numel() < n + 1:
+            raise NanoSNPError(f"{what}: output buffers too small")
+        launch(blob, cap, offsets, meta)
+        if retry:
+            (stream or torch.cuda.current_stream(dev)).synchronize()
+            need = int(meta[0])
+            if need > cap:
+                return self._alt_info_run(what, launch, n, dev, need, None, offsets, meta, stream)
+        return blob, offsets[:n + 1], meta
+
+    def mpileup_line_names(self, text, name, cap_lines, cap_names=64, line_idx=None, names=None, meta=None, stream=None):
+        """Column 0 of every line of a device text against `name` (nsnp_mpileup_line_names) -> (line_idx int32 [cap_lines]: -1 where the
+        line's first token is `name`, else its entry in names; names uint8 [cap_names, 44]; meta int64 [4] = {lines that differ, status})"""
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        line_idx, names, meta = self._line_names_outputs(text, cap_lines, cap_names, line_idx, names, meta)
         check(self.lib.nsnp_mpileup_line_names(self.handle, _dptr(text), int(text.numel()), name, len(name), int(line_idx.numel()), _dptr(line_idx),
                                                _dptr(names), int(names.shape[0]), meta.data_ptr(), _stream_ptr(stream)),
               self.handle, "nsnp_mpileup_line_names")
@@ -800,31 +869,15 @@ class Context:
         pinned tensors with room for N sites (the first N rows are written); meta is valid once the stream has passed the call."""
         import torch
         n, m = int(center_idx.shape[0]), int(counts.shape[0])
-        dev = counts.device
         assert counts.dtype == torch.int32 and center_idx.dtype == torch.int64 and pos.dtype == torch.int64 and chr_seq.dtype == torch.uint8
         name = name.encode() if isinstance(name, str) else bytes(name)
-        dt = {2: torch.int16, 4: torch.int32}.get(elem)
-        if dt is None:
-            raise NanoSNPError("elem: 2 (int16) or 4 (int32)")
-        if position_matrix is None:
-            position_matrix = torch.empty((max(n, 1), 33, 18), dtype=dt, device=dev)
-        if position is None:
-            position = torch.empty((max(n, 1), self.POSITION_WIDTH), dtype=torch.uint8, device=dev)
-        if meta is None:
-            meta = torch.zeros(4, dtype=torch.int64, device=dev)
-        for t, what in ((position_matrix, "position_matrix"), (position, "position"), (meta, "meta")):
-            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
-                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
-        if position_matrix.dtype != dt or position_matrix.numel() < n * 594 or position.dtype != torch.uint8 or position.numel() < n * self.POSITION_WIDTH:
-            raise NanoSNPError("window_records: output buffers too small or of the wrong type")
-        line_idx, names = line_names if line_names is not None else (None, None)      # (mpileup_line_names of the same lines: per-site names)
-        if line_idx is not None and (line_idx.dtype != torch.int32 or line_idx.numel() < m or not line_idx.is_cuda or not names.is_cuda):
-            raise NanoSNPError("line_names: device int32 [M] and the name table of mpileup_line_names")
+        position_matrix, position, _, meta = self._records_outputs("window_records", n, elem, counts.device, position_matrix, position, meta)
+        line_idx, names = self._line_names_arg(line_names, m, "mpileup_line_names")
         check(self.lib.nsnp_pileup_window_records2(self.handle, _dptr(counts), _dptr(center_idx), _dptr(pos), m, n, _dptr(chr_seq), int(chr_seq.numel()),
                                                    name, len(name), int(elem), _dptr(line_idx), _dptr(names), position_matrix.data_ptr(),
                                                    position.data_ptr(), meta.data_ptr(), _stream_ptr(stream)),
               self.handle, "nsnp_pileup_window_records2")
-        return position_matrix.view(-1)[:n * 594].view(n, 33, 18), position.view(-1)[:n * self.POSITION_WIDTH].view(n, self.POSITION_WIDTH), meta
+        return (*self._records_views(n, position_matrix, position), meta)
 
     def pileup_alt_info(self, bases, col_off, ref, pos, depth, center_idx, chr_seq, cap=None, blob=None, offsets=None, meta=None, stream=None):
         """The alt_info texts of the sites center_idx [N] (nsnp_pileup_alt_info) -> (blob uint8 [cap], offsets int64 [N + 1], meta int64 [4] =
@@ -833,49 +886,25 @@ class Context:
         guess was too small."""
         import torch
         n, m = int(center_idx.shape[0]), int(ref.shape[0])
-        dev = ref.device
         assert bases.dtype == torch.uint8 and col_off.dtype == torch.int64 and ref.dtype == torch.uint8 and pos.dtype == torch.int64
         assert depth.dtype == torch.int32 and center_idx.dtype == torch.int64 and chr_seq.dtype == torch.uint8
         if col_off.shape[0] != m + 1 or pos.shape[0] != m or depth.shape[0] != m:
             raise NanoSNPError("alt_info: col_off [M + 1], pos [M] and depth [M] must match ref [M]")
-        retry = cap is None and blob is None
-        cap = int(blob.numel() if blob is not None else (64 * n + 4096 if cap is None else cap))
-        if blob is None:
-            blob = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-        if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        if meta is None:
-            meta = torch.zeros(4, dtype=torch.int64, device=dev)
-        for t, what in ((blob, "blob"), (offsets, "offsets"), (meta, "meta")):
-            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
-                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
-        if blob.numel() < cap or offsets.numel() < n + 1:
-            raise NanoSNPError("alt_info: output buffers too small")
-        check(self.lib.nsnp_pileup_alt_info(self.handle, _dptr(bases), int(bases.numel()), _dptr(col_off), _dptr(ref), _dptr(pos), _dptr(depth), m,
-                                            _dptr(center_idx), n, _dptr(chr_seq), int(chr_seq.numel()), blob.data_ptr(), cap, offsets.data_ptr(),
-                                            meta.data_ptr(), _stream_ptr(stream)),
-              self.handle, "nsnp_pileup_alt_info")
-        if retry:
-            (stream or torch.cuda.current_stream(dev)).synchronize()
-            need = int(meta[0])
-            if need > cap:
-                return self.pileup_alt_info(bases, col_off, ref, pos, depth, center_idx, chr_seq, cap=need, offsets=offsets, meta=meta, stream=stream)
-        return blob, offsets[:n + 1], meta
+
+        def launch(blob, cap, offsets, meta):
+            check(self.lib.nsnp_pileup_alt_info(self.handle, _dptr(bases), int(bases.numel()), _dptr(col_off), _dptr(ref), _dptr(pos), _dptr(depth), m,
+                                                _dptr(center_idx), n, _dptr(chr_seq), int(chr_seq.numel()), blob.data_ptr(), cap, offsets.data_ptr(),
+                                                meta.data_ptr(), _stream_ptr(stream)),
+                  self.handle, "nsnp_pileup_alt_info")
+        return self._alt_info_run("alt_info", launch, n, ref.device, cap, blob, offsets, meta, stream)
 
     def mpileup_line_names_contigs(self, text, cid, table, cap_lines=None, cap_names=64, line_idx=None, names=None, meta=None, stream=None):
         """mpileup_line_names against a ContigTable (nsnp_mpileup_line_names_contigs): cid int32 per line as mpileup_tokenise_contigs wrote it
         for the same device text -> (line_idx int32 [cap_lines]: -1 where the line's first token is the table name of its contig or the line
         belongs to no wanted contig, else its entry in names; names uint8 [cap_names, 44]; meta int64 [4] = {lines that differ, status})"""
         import torch
-        dev = text.device
         cap_lines = int(cid.numel() if cap_lines is None else cap_lines)
-        if line_idx is None:
-            line_idx = torch.empty(max(cap_lines, 1), dtype=torch.int32, device=dev)
-        if names is None:
-            names = torch.empty((max(int(cap_names), 1), self.NAME_ENTRY), dtype=torch.uint8, device=dev)
-        if meta is None:
-            meta = torch.zeros(4, dtype=torch.int64, device=dev)
-        assert text.dtype == torch.uint8 and text.is_cuda and line_idx.dtype == torch.int32 and line_idx.is_cuda and names.is_cuda
+        line_idx, names, meta = self._line_names_outputs(text, cap_lines, cap_names, line_idx, names, meta)
         if cid.dtype != torch.int32 or not cid.is_cuda or not cid.is_contiguous() or cid.numel() < cap_lines or line_idx.numel() < cap_lines:
             raise NanoSNPError("line_names_contigs: cid and line_idx must be contiguous device int32 tensors of at least cap_lines entries")
         check(self.lib.nsnp_mpileup_line_names_contigs(self.handle, _dptr(text), int(text.numel()), _dptr(cid), _dptr(table.names_blob),
@@ -892,30 +921,12 @@ class Context:
         cap_names: the entries of names that count (default: all it holds).  The four outputs may be given: device or pinned tensors."""
         import torch
         n, m = int(center_idx.shape[0]), int(counts.shape[0])
-        dev = counts.device
         assert counts.dtype == torch.int32 and center_idx.dtype == torch.int64 and key.dtype == torch.int64
         if key.shape[0] != m or not key.is_contiguous():
             raise NanoSNPError("window_records_keys: key [M] must match counts [M,18]")
-        dt = {2: torch.int16, 4: torch.int32}.get(elem)
-        if dt is None:
-            raise NanoSNPError("elem: 2 (int16) or 4 (int32)")
-        if position_matrix is None:
-            position_matrix = torch.empty((max(n, 1), 33, 18), dtype=dt, device=dev)
-        if position is None:
-            position = torch.empty((max(n, 1), self.POSITION_WIDTH), dtype=torch.uint8, device=dev)
-        if site_key is None:
-            site_key = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-        if meta is None:
-            meta = torch.zeros(4, dtype=torch.int64, device=dev)
-        for t, what in ((position_matrix, "position_matrix"), (position, "position"), (site_key, "site_key"), (meta, "meta")):
-            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
-                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
-        if (position_matrix.dtype != dt or position_matrix.numel() < n * 594 or position.dtype != torch.uint8 or position.numel() < n * self.POSITION_WIDTH
-                or site_key.dtype != torch.int64 or site_key.numel() < n):
-            raise NanoSNPError("window_records_keys: output buffers too small or of the wrong type")
-        line_idx, names = line_names if line_names is not None else (None, None)
-        if line_idx is not None and (line_idx.dtype != torch.int32 or line_idx.numel() < m or not line_idx.is_cuda or not names.is_cuda):
-            raise NanoSNPError("line_names: device int32 [M] and the name table of mpileup_line_names_contigs")
+        position_matrix, position, site_key, meta = self._records_outputs("window_records_keys", n, elem, counts.device, position_matrix, position, meta,
+                                                                          site_key)
+        line_idx, names = self._line_names_arg(line_names, m, "mpileup_line_names_contigs")
         n_names = int(names.numel() // self.NAME_ENTRY) if names is not None else 0
         cap_names = n_names if cap_names is None else int(cap_names)
         if cap_names < 0 or cap_names > n_names:
@@ -925,42 +936,24 @@ class Context:
                                                        _dptr(line_idx), _dptr(names), cap_names, position_matrix.data_ptr(), position.data_ptr(),
                                                        site_key.data_ptr(), meta.data_ptr(), _stream_ptr(stream)),
               self.handle, "nsnp_pileup_window_records_keys")
-        return (position_matrix.view(-1)[:n * 594].view(n, 33, 18), position.view(-1)[:n * self.POSITION_WIDTH].view(n, self.POSITION_WIDTH),
-                site_key.view(-1)[:n], meta)
+        return (*self._records_views(n, position_matrix, position), site_key.view(-1)[:n], meta)
 
     def pileup_alt_info_keys(self, bases, col_off, ref, key, depth, center_idx, table, cap=None, blob=None, offsets=None, meta=None, stream=None):
         """pileup_alt_info for a chunk of several contigs (nsnp_pileup_alt_info_keys): key int64 [M] for pos, the ContigTable for chr_seq -> (blob
         uint8 [cap], offsets int64 [N + 1], meta int64 [4] = {bytes needed, status, 0, 0}); everything else as pileup_alt_info."""
         import torch
         n, m = int(center_idx.shape[0]), int(ref.shape[0])
-        dev = ref.device
         assert bases.dtype == torch.uint8 and col_off.dtype == torch.int64 and ref.dtype == torch.uint8 and key.dtype == torch.int64
         assert depth.dtype == torch.int32 and center_idx.dtype == torch.int64
         if col_off.shape[0] != m + 1 or key.shape[0] != m or depth.shape[0] != m:
             raise NanoSNPError("alt_info_keys: col_off [M + 1], key [M] and depth [M] must match ref [M]")
-        retry = cap is None and blob is None
-        cap = int(blob.numel() if blob is not None else (64 * n + 4096 if cap is None else cap))
-        if blob is None:
-            blob = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-        if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        if meta is None:
-            meta = torch.zeros(4, dtype=torch.int64, device=dev)
-        for t, what in ((blob, "blob"), (offsets, "offsets"), (meta, "meta")):
-            if not (t.is_cuda or t.is_pinned()) or not t.is_contiguous():
-                raise NanoSNPError(f"{what}: a contiguous tensor on the device or in pinned memory")
-        if blob.numel() < cap or offsets.numel() < n + 1:
-            raise NanoSNPError("alt_info_keys: output buffers too small")
-        check(self.lib.nsnp_pileup_alt_info_keys(self.handle, _dptr(bases), int(bases.numel()), _dptr(col_off), _dptr(ref), _dptr(key), _dptr(depth), m,
-                                                 _dptr(center_idx), n, _dptr(table.genome), _dptr(table.seq_off), len(table), blob.data_ptr(), cap,
-                                                 offsets.data_ptr(), meta.data_ptr(), _stream_ptr(stream)),
-              self.handle, "nsnp_pileup_alt_info_keys")
-        if retry:
-            (stream or torch.cuda.current_stream(dev)).synchronize()
-            need = int(meta[0])
-            if need > cap:
-                return self.pileup_alt_info_keys(bases, col_off, ref, key, depth, center_idx, table, cap=need, offsets=offsets, meta=meta, stream=stream)
-        return blob, offsets[:n + 1], meta
+
+        def launch(blob, cap, offsets, meta):
+            check(self.lib.nsnp_pileup_alt_info_keys(self.handle, _dptr(bases), int(bases.numel()), _dptr(col_off), _dptr(ref), _dptr(key), _dptr(depth), m,
+                                                     _dptr(center_idx), n, _dptr(table.genome), _dptr(table.seq_off), len(table), blob.data_ptr(), cap,
+                                                     offsets.data_ptr(), meta.data_ptr(), _stream_ptr(stream)),
+                  self.handle, "nsnp_pileup_alt_info_keys")
+        return self._alt_info_run("alt_info_keys", launch, n, ref.device, cap, blob, offsets, meta, stream)
 
     LABEL_WIDTH = 90
 

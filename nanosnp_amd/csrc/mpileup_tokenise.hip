@@ -571,12 +571,7 @@ static int tok_reserve(nsnp_ctx* ctx, int64_t n_tiles, hipStream_t s)
 {
     const size_t need = (size_t)n_tiles * (8 + 8 + 16 * TK_BLOCK) + 64 + 256;      // per tile: newlines, bytes, 16 bytes of masks per thread (the chained scan: 16 per tile)
     if (ctx->tok_ws_bytes >= need) return NSNP_OK;
-    NSNP_HIP(ctx, hipStreamSynchronize(s));
-    if (ctx->tok_ws) (void)hipFree(ctx->tok_ws);
-    ctx->tok_ws = nullptr; ctx->tok_ws_bytes = 0;
-    const size_t want = need + need / 4;
-    NSNP_HIP(ctx, hipMalloc(&ctx->tok_ws, want));
-    ctx->tok_ws_bytes = want;
+    if (int rc = nsnp_scratch_reserve(ctx, &ctx->tok_ws, &ctx->tok_ws_bytes, need, need / 4, s)) return rc;
     NSNP_HIP(ctx, hipMemsetAsync(ctx->tok_ws, 0, 64, s));            // the status words start at zero; every call leaves them so (k_tok_status)
     return NSNP_OK;
 }
@@ -822,14 +817,7 @@ __global__ void k_ctg_status(int64_t* __restrict__ ws_meta, int64_t cap_runs, in
 
 static int ctg_reserve(nsnp_ctx* ctx, size_t need, hipStream_t s)
 {
-    if (ctx->ctg_ws_bytes >= need) return NSNP_OK;
-    NSNP_HIP(ctx, hipStreamSynchronize(s));
-    if (ctx->ctg_ws) (void)hipFree(ctx->ctg_ws);
-    ctx->ctg_ws = nullptr; ctx->ctg_ws_bytes = 0;
-    const size_t want = need + need / 4;
-    NSNP_HIP(ctx, hipMalloc(&ctx->ctg_ws, want));
-    ctx->ctg_ws_bytes = want;
-    return NSNP_OK;
+    return nsnp_scratch_reserve(ctx, &ctx->ctg_ws, &ctx->ctg_ws_bytes, need, need / 4, s);
 }
 
 extern "C" int nsnp_mpileup_tokenise_contigs(nsnp_ctx* ctx, const uint8_t* text, int64_t text_len, const uint8_t* names_blob, const int64_t* name_off,

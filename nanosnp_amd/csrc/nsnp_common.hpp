@@ -169,6 +169,20 @@ struct ScopedKernelTimer {
         if (e_ != hipSuccess) { (ctx)->last_err = e_; return NSNP_EHIP; }          \
     } while (0)
 
+// A scratch buffer of the context (*p, *bytes) with room for `need` bytes: it grows only when a larger request than ever before arrives,
+// synchronously (the stream is drained, the old buffer freed, need + slack bytes allocated; size it with a warm-up call).  After a failed
+// allocation the buffer is null with 0 bytes, last_err is set and NSNP_EHIP returned.
+inline int nsnp_scratch_reserve(nsnp_ctx* ctx, void** p, size_t* bytes, size_t need, size_t slack, hipStream_t s)
+{
+    if (*bytes >= need) return NSNP_OK;
+    NSNP_HIP(ctx, hipStreamSynchronize(s));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *bytes = 0;
+    NSNP_HIP(ctx, hipMalloc(p, need + slack));
+    *bytes = need + slack;
+    return NSNP_OK;
+}
+
 // host-side packers (pack.cpp compiled as part of the .hip translation unit set)
 typedef float (*nsnp_wfun)(const void* user, int row, int k);
 void nsnp_pack_image(float* img, int n_tiles, int n_j4, nsnp_wfun f, const void* user);

@@ -970,14 +970,7 @@ extern "C" int nsnp_pileup_select_sites(nsnp_ctx* ctx, const int64_t* pos, const
     if (M == 0) { NSNP_HIP(ctx, hipMemsetAsync(n_sites, 0, sizeof(int64_t), s)); return NSNP_OK; }
     const int64_t n_blocks = NSNP_CDIV(M, SEL_TILE);
     const size_t need = (size_t)n_blocks * sizeof(int64_t);
-    if (ctx->sel_tmp_bytes < need) {
-        // grows only when a larger M than ever before arrives (synchronous; size it with a warm-up call)
-        NSNP_HIP(ctx, hipStreamSynchronize(s));
-        if (ctx->sel_tmp) (void)hipFree(ctx->sel_tmp);
-        ctx->sel_tmp = nullptr; ctx->sel_tmp_bytes = 0;
-        NSNP_HIP(ctx, hipMalloc((void**)&ctx->sel_tmp, need));
-        ctx->sel_tmp_bytes = need;
-    }
+    if (int rc = nsnp_scratch_reserve(ctx, (void**)&ctx->sel_tmp, &ctx->sel_tmp_bytes, need, 0, s)) return rc;      // (exactly `need`: no slack here)
     hipLaunchKernelGGL(k_select_count, dim3((unsigned)n_blocks), dim3(SEL_BLOCK), 0, s, pos, flags, M, ctx->sel_tmp);
     hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, s, ctx->sel_tmp, n_blocks, n_sites);
     hipLaunchKernelGGL(k_select_scatter, dim3((unsigned)n_blocks), dim3(SEL_BLOCK), 0, s, pos, flags, M,
@@ -1030,13 +1023,7 @@ static int select_sites_range(nsnp_ctx* ctx, const int64_t* pos, const uint8_t* 
     // the site count lives behind the block counts of the selection scratch (one word more than nsnp_pileup_select_sites needs)
     const int64_t n_blocks = NSNP_CDIV(M, SEL_TILE);
     const size_t need = (size_t)(n_blocks + 1) * sizeof(int64_t);
-    if (ctx->sel_tmp_bytes < need) {
-        NSNP_HIP(ctx, hipStreamSynchronize(s));
-        if (ctx->sel_tmp) (void)hipFree(ctx->sel_tmp);
-        ctx->sel_tmp = nullptr; ctx->sel_tmp_bytes = 0;
-        NSNP_HIP(ctx, hipMalloc((void**)&ctx->sel_tmp, need + need / 4));
-        ctx->sel_tmp_bytes = need + need / 4;
-    }
+    if (int rc = nsnp_scratch_reserve(ctx, (void**)&ctx->sel_tmp, &ctx->sel_tmp_bytes, need, need / 4, s)) return rc;
     int64_t* n_sites = ctx->sel_tmp + n_blocks;
     hipLaunchKernelGGL(k_select_count, dim3((unsigned)n_blocks), dim3(SEL_BLOCK), 0, s, pos, flags, M, ctx->sel_tmp);
     hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, s, ctx->sel_tmp, n_blocks, n_sites);
@@ -1288,14 +1275,7 @@ static int filter_columns_launch(nsnp_ctx* ctx, const int64_t* pos, const int64_
     }
     const int64_t n_blocks = NSNP_CDIV(M, FIL_TILE);
     const size_t need = (size_t)(2 * n_blocks + 2) * sizeof(int64_t);
-    if (ctx->fil_tmp_bytes < need) {
-        // grows only when a larger M than ever before arrives (synchronous; size it with a warm-up call)
-        NSNP_HIP(ctx, hipStreamSynchronize(s));
-        if (ctx->fil_tmp) (void)hipFree(ctx->fil_tmp);
-        ctx->fil_tmp = nullptr; ctx->fil_tmp_bytes = 0;
-        NSNP_HIP(ctx, hipMalloc((void**)&ctx->fil_tmp, need + need / 4));
-        ctx->fil_tmp_bytes = need + need / 4;
-    }
+    if (int rc = nsnp_scratch_reserve(ctx, (void**)&ctx->fil_tmp, &ctx->fil_tmp_bytes, need, need / 4, s)) return rc;
     hipLaunchKernelGGL(k_filter_count<Rule>, dim3((unsigned)n_blocks), dim3(FIL_BLOCK), 0, s, pos, col_off, r0, r1, M, n_blocks, ctx->fil_tmp);
     hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(1024), 0, s, ctx->fil_tmp, n_blocks, M, own_lo, own_hi, meta);
     hipLaunchKernelGGL(k_filter_scatter<Rule>, dim3((unsigned)n_blocks), dim3(FIL_BLOCK), 0, s, pos, col_off, bases, ref, r0, r1, M, n_blocks,

@@ -348,13 +348,7 @@ int label_scratch(nsnp_ctx* ctx, int64_t N, hipStream_t s, int64_t** scan, uint3
 {
     const size_t scan_bytes = (((size_t)N + 1) * sizeof(int64_t) + 15) & ~(size_t)15;
     const size_t need = scan_bytes + (size_t)N * sizeof(uint32_t) + 16;
-    if (ctx->evl_tmp_bytes < need) {
-        NSNP_HIP(ctx, hipStreamSynchronize(s));
-        if (ctx->evl_tmp) (void)hipFree(ctx->evl_tmp);
-        ctx->evl_tmp = nullptr; ctx->evl_tmp_bytes = 0;
-        NSNP_HIP(ctx, hipMalloc(&ctx->evl_tmp, need + need / 4));
-        ctx->evl_tmp_bytes = need + need / 4;
-    }
+    if (int rc = nsnp_scratch_reserve(ctx, &ctx->evl_tmp, &ctx->evl_tmp_bytes, need, need / 4, s)) return rc;
     *scan = (int64_t*)ctx->evl_tmp;
     *word = (uint32_t*)((uint8_t*)ctx->evl_tmp + scan_bytes);
     return NSNP_OK;

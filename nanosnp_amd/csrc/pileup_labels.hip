@@ -187,13 +187,7 @@ extern "C" int nsnp_pileup_label_sites_keys(nsnp_ctx* ctx, const int64_t* key, i
     const size_t scan_bytes = (((size_t)N + 1) * sizeof(int64_t) + 15) & ~(size_t)15;
     const size_t word_bytes = ((size_t)N * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t need = scan_bytes + 2 * word_bytes + 16;
-    if (ctx->lab_tmp_bytes < need) {
-        NSNP_HIP(ctx, hipStreamSynchronize(s));
-        if (ctx->lab_tmp) (void)hipFree(ctx->lab_tmp);
-        ctx->lab_tmp = nullptr; ctx->lab_tmp_bytes = 0;
-        NSNP_HIP(ctx, hipMalloc(&ctx->lab_tmp, need + need / 4));
-        ctx->lab_tmp_bytes = need + need / 4;
-    }
+    if (int rc = nsnp_scratch_reserve(ctx, &ctx->lab_tmp, &ctx->lab_tmp_bytes, need, need / 4, s)) return rc;
     int64_t* scan = (int64_t*)ctx->lab_tmp;
     uint32_t* info = (uint32_t*)((uint8_t*)ctx->lab_tmp + scan_bytes);
     uint32_t* kept_code = (uint32_t*)((uint8_t*)ctx->lab_tmp + scan_bytes + word_bytes);
