@@ -670,6 +670,30 @@ int nsnp_hap_eval(nsnp_ctx* ctx, const float* xp, const float* xh, const uint8_t
 /* nsnp_pileup_batch_loss for rows of two heads: site_loss fp32 [N,2] (8-byte aligned) -> batch_sum double [ceil(N / batch_size), 2]. */
 int nsnp_hap_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream);
 
+/* ---- training the HaplotypeModel: the sample list of a pass under pn_value upsampling (TrainingDataset.__init__, dataset_dev.py:190-230) --
+ * cls uint8 [kept,2]: the kept rows' classes as nsnp_hap_label_classes leaves them, device; byte 1 is 0 exactly for a refcall.
+ *   samples int64 [cap]  indices in [0, kept) into the kept list (map them through `rows`); the first M are written        (device)
+ *   meta    int64 [4]  = { M, refcalls, variants, blocks }; device or pinned host memory
+ * The refcalls, in order, are cut into blocks of 1,000; the last holds the remaining 1..1,000.  Block b of len_b refcalls contributes its
+ * refcalls in order and then q_b = (int64)((double)len_b * pn_value) variant draws - Python's int(len * pn_value): the float64 product,
+ * truncated (int(90 * 0.7) is 62, not 63).  Block b starts at b * (1000 + (int64)(1000.0 * pn_value)): closed form.  M = refcalls + sum q_b.
+ * Without a variant every q_b is 0 (the reference's except: branch); without a refcall the list is empty (the reference's quirk too).
+ * Draw j of block b picks variant ((uint64)r * variants) >> 32, r = word 0 of Philox4x32-10 at counter { j, b, draw, 0 } under the key
+ * { seed & 0xffffffff, seed >> 32 } (csrc/nsnp_philox.hpp).  Multiply-shift departs from uniform by less than variants / 2^32 in total.  The
+ * reference draws from an unseeded np.random, so only the distribution is its own; here the list is a pure function of the arguments, the same
+ * bits on every run whatever the grid.  `draw` is the caller's pass counter, so that passes differ.  The reference's shuffle inside a block is
+ * not made: the caller's permutation of the whole list stands for it and for the DataLoader's.
+ * NSNP_EINVAL with nothing written: cap < M, pn_value negative, not finite or above NSNP_HAP_PN_VALUE_MAX (a draw index is 32 bits),
+ * kept < 0 or >= 2^32, samples NULL with M > 0.
+ * Four launches (refcall flags, the one-workgroup exclusive scan of nsnp_hap_label_classes, the two lists, placement); no workgroup waits for
+ * another, nothing is added atomically.  Between the third and the fourth the entry WAITS for the stream once and reads the two counts: cap
+ * cannot be held against M without them.  With kept == 0 there is one launch and no wait.  Scratch: nsnp_pileup_label_classes' buffer, 20
+ * bytes per kept row (scan, lists, words), grown as there; it is overwritten, so run the entry behind the work that reads a label pass's
+ * scratch - on the same stream, or after it has finished. */
+#define NSNP_HAP_PN_VALUE_MAX 4194304.0
+int nsnp_hap_train_samples(nsnp_ctx* ctx, const uint8_t* cls, int64_t kept, double pn_value, uint64_t seed, uint32_t draw, int64_t* samples,
+                           int64_t cap, int64_t* meta, void* stream);
+
 /* ---- training the HaplotypeModel: the loss gradients of a batch (HaplotypeModel/train_dev.py:58-59, model(...) and loss.backward()) ------
  * fp32 only and one device: with hap_precision 1 or 2 nsnp_hap_loss_grad returns NSNP_EINVAL.  The entries need no nsnp_hap_load_weights:
  * the parameters are the caller's device tensors in plain state-dict layout, because they change every step; the packed images of the

@@ -101,6 +101,8 @@ _SIGNATURES = {
     "nsnp_hap_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
     "nsnp_hap_label_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nsnp_hap_train_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p]),
     "nsnp_hap_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
     "nsnp_hap_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_cat_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
@@ -1385,6 +1387,34 @@ class Context:
         check(self.lib.nsnp_hap_label_classes(self.handle, _dptr(label), n, _dptr(cls), _dptr(rows), meta.data_ptr(), _stream_ptr(stream)),
               self.handle, "nsnp_hap_label_classes")
         return cls, rows, meta
+
+    HAP_PN_VALUE_MAX = 4194304.0                # NSNP_HAP_PN_VALUE_MAX
+
+    def hap_train_samples(self, cls, kept, pn_value, seed, draw=0, samples=None, meta=None, stream=None):
+        """cls: device uint8 [>= kept, 2] as hap_label_classes leaves it -> (samples int64, meta int64 [4]): the training sample list of a pass
+        under pn_value upsampling (nsnp_hap_train_samples): the first meta[0] entries of samples are indices in [0, kept) into the kept
+        list; meta = {M, refcalls, variants, blocks}, on the device or in pinned memory.  seed: 64 bits, draw: 32 bits (the pass counter).
+        samples None: a new tensor with room for any split of `kept` rows; a given one smaller than M is refused with nothing written.
+        The entry waits for the stream once (for the two counts)."""
+        import torch
+        kept, pn_value, seed, draw = int(kept), float(pn_value), int(seed), int(draw)
+        if cls.dtype != torch.uint8 or not cls.is_cuda or not cls.is_contiguous() or kept < 0 or cls.numel() < 2 * kept:
+            raise NanoSNPError("hap_train_samples: cls must be a contiguous device uint8 [kept,2]")
+        if not (0.0 <= pn_value <= self.HAP_PN_VALUE_MAX):
+            raise NanoSNPError(f"hap_train_samples: pn_value in [0, {self.HAP_PN_VALUE_MAX:.0f}], got {pn_value}")
+        if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 32):
+            raise NanoSNPError("hap_train_samples: seed in [0, 2^64) and draw in [0, 2^32)")
+        dev = cls.device
+        if samples is None:
+            samples = torch.empty(max(kept + -(-kept // 1000) * int(1000.0 * pn_value), 1), dtype=torch.int64, device=dev)
+        meta = meta if meta is not None else torch.zeros(4, dtype=torch.int64, device=dev)
+        if samples.dtype != torch.int64 or not samples.is_cuda or not samples.is_contiguous():
+            raise NanoSNPError("hap_train_samples: samples int64 on the device")
+        if meta.dtype != torch.int64 or meta.numel() < 4 or not (meta.is_cuda or meta.is_pinned()) or not meta.is_contiguous():
+            raise NanoSNPError("hap_train_samples: meta int64 [4] on the device or in pinned memory")
+        check(self.lib.nsnp_hap_train_samples(self.handle, _dptr(cls), kept, pn_value, seed, draw, _dptr(samples), int(samples.numel()),
+                                              meta.data_ptr(), _stream_ptr(stream)), self.handle, "nsnp_hap_train_samples")
+        return samples, meta
 
     def hap_eval_counters(self, device=None):
         """a zeroed counter tensor for hap_eval: int64 [n_gt * n_gt + n_zy * n_zy]"""

@@ -19,7 +19,11 @@
 //   nsnp_hap_label_classes   k_hapl_flags (LabelField + the target rule, dataset_dev.py:174-187,320), k_evl_scan, k_hapl_compact
 //   nsnp_hap_batch_loss      k_evl_batch_loss over rows of two heads
 // Its heads kernel, k_hap_head_eval, lives beside the forward it ends (hap_forward.hip).
+//
+// The HaplotypeModel's training samples (TrainingDataset.__init__, HaplotypeModel/dataset_dev.py:190-230) start from that label pass's cls:
+//   nsnp_hap_train_samples   k_haps_flags, k_evl_scan, k_haps_lists, one host wait for the two counts, k_haps_place (nsnp_philox.hpp)
 #include "nsnp_common.hpp"
+#include "nsnp_philox.hpp"
 
 namespace {
 
@@ -287,6 +291,50 @@ __global__ __launch_bounds__(EVL_BLOCK) void k_hapl_compact(const int64_t* __res
     rows[o] = n;
 }
 
+// ---- HaplotypeModel training: the sample list of a pass under pn_value upsampling (TrainingDataset.__init__, dataset_dev.py:190-230) ----
+// Input: cls of the kept rows (byte 1 is 0 exactly for a refcall).  k_haps_flags marks the refcalls for k_evl_scan (keep = refcall; the word
+// carries EVL_M2 / EVL_M3, so the scan's meta is {refcalls, 0, refcalls, variants}).  A kept row is a refcall or a variant, so ONE scan ranks
+// both: row n is refcall number scan[n] or variant number n - scan[n].  k_haps_lists writes list = {refcalls in order, variants in order}.
+// k_haps_place: a lane per output entry.  Block b of HAPS_REFS refcalls starts at b * (HAPS_REFS + q_full) - closed form, no scan over blocks
+// - and holds its refcalls and then its draws; draw j of block b is Philox4x32-10 word 0 at counter {j, b, draw, 0} under the key
+// {seed low, seed high}, turned into a variant by multiply-shift (nsnp_philox.hpp).  Nothing is accumulated and no lane reads another's output.
+constexpr int64_t HAPS_REFS = 1000;                          // block_size of dataset_dev.py:204
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_haps_flags(const uint8_t* __restrict__ cls, int64_t N, int64_t* __restrict__ keep, uint32_t* __restrict__ word)
+{
+    const int64_t n = (int64_t)blockIdx.x * EVL_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const bool refcall = cls[n * 2 + 1] == 0;
+    keep[n] = refcall ? 1 : 0;
+    word[n] = refcall ? EVL_M2 : EVL_M3;
+}
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_haps_lists(const int64_t* __restrict__ scan, int64_t N, int64_t* __restrict__ list)
+{
+    const int64_t n = (int64_t)blockIdx.x * EVL_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const int64_t o = scan[n], n_ref = scan[N];
+    const int64_t at = scan[n + 1] != o ? o : n_ref + (n - o);           // (refcalls fill [0, n_ref), variants [n_ref, N): in [0, N) by construction)
+    if (at < 0 || at >= N) return;
+    list[at] = n;
+}
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_haps_place(const int64_t* __restrict__ list, int64_t n_ref, int64_t n_var, int64_t M, int64_t q_full,
+                                                          uint32_t key0, uint32_t key1, uint32_t draw, int64_t* __restrict__ samples,
+                                                          int64_t* __restrict__ meta)
+{
+    const int64_t i = (int64_t)blockIdx.x * EVL_BLOCK + threadIdx.x;
+    if (i == 0) { meta[0] = M; meta[1] = n_ref; meta[2] = n_var; meta[3] = NSNP_CDIV(n_ref, HAPS_REFS); }
+    if (i >= M) return;
+    const int64_t stride = HAPS_REFS + q_full;
+    const int64_t b = i / stride, w = i - b * stride;
+    const int64_t left = n_ref - b * HAPS_REFS, len = left < HAPS_REFS ? left : HAPS_REFS;
+    int64_t at;
+    if (w < len) at = b * HAPS_REFS + w;
+    else at = n_ref + (int64_t)nsnp_philox_index(nsnp_philox4x32_10((uint32_t)(w - len), (uint32_t)b, draw, 0u, key0, key1).v[0], (uint64_t)n_var);
+    samples[i] = list[at];
+}
+
 __global__ __launch_bounds__(EVL_BLOCK) void k_evl_compact(const int64_t* __restrict__ scan, const uint32_t* __restrict__ word, int64_t N,
                                                            uint32_t* __restrict__ cls, int64_t* __restrict__ center_idx)
 {
@@ -354,6 +402,20 @@ int label_scratch(nsnp_ctx* ctx, int64_t N, hipStream_t s, int64_t** scan, uint3
     return NSNP_OK;
 }
 
+// scratch of a sample list (the same buffer): the scan, the two lists (N entries together), the scan's four counts, one word per row
+int sample_scratch(nsnp_ctx* ctx, int64_t N, hipStream_t s, int64_t** scan, int64_t** list, int64_t** counts, uint32_t** word)
+{
+    const size_t scan_bytes = (((size_t)N + 1) * sizeof(int64_t) + 15) & ~(size_t)15;
+    const size_t list_bytes = ((size_t)N + 4) * sizeof(int64_t);
+    const size_t need = scan_bytes + list_bytes + (size_t)N * sizeof(uint32_t) + 16;
+    if (int rc = nsnp_scratch_reserve(ctx, &ctx->evl_tmp, &ctx->evl_tmp_bytes, need, need / 4, s)) return rc;
+    *scan = (int64_t*)ctx->evl_tmp;
+    *list = (int64_t*)((uint8_t*)ctx->evl_tmp + scan_bytes);
+    *counts = *list + N;
+    *word = (uint32_t*)((uint8_t*)ctx->evl_tmp + scan_bytes + list_bytes);
+    return NSNP_OK;
+}
+
 }  // namespace
 
 void nsnp_pileup_eval_heads_launch(nsnp_ctx* ctx, int64_t n, const uint8_t* cls, float* site_loss, uint8_t* pred, int64_t* counters,
@@ -409,4 +471,41 @@ extern "C" int nsnp_hap_label_classes(nsnp_ctx* ctx, const int32_t* label, int64
 extern "C" int nsnp_hap_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream)
 {
     return batch_loss<2>(ctx, site_loss, N, batch_size, batch_sum, stream);
+}
+
+// ---- HaplotypeModel training: the sample list of a pass (include/nanosnp.h) ---------------------------------------------------------------
+extern "C" int nsnp_hap_train_samples(nsnp_ctx* ctx, const uint8_t* cls, int64_t kept, double pn_value, uint64_t seed, uint32_t draw,
+                                      int64_t* samples, int64_t cap, int64_t* meta, void* stream)
+{
+    if (!ctx || !meta || kept < 0 || kept > 0xffffffffll || (kept > 0 && !cls)) return NSNP_EINVAL;
+    if (!(pn_value >= 0.0) || !(pn_value <= NSNP_HAP_PN_VALUE_MAX)) return NSNP_EINVAL;          // (NaN fails both; a draw index is 32 bits)
+    hipStream_t s = (hipStream_t)stream;
+    int64_t n_ref = 0, n_var = 0;
+    int64_t* list = nullptr;
+    if (kept > 0) {
+        int64_t *scan, *counts; uint32_t* word;
+        if (const int rc = sample_scratch(ctx, kept, s, &scan, &list, &counts, &word)) return rc;
+        const unsigned grid = (unsigned)NSNP_CDIV(kept, (int64_t)EVL_BLOCK);
+        hipLaunchKernelGGL(k_haps_flags, dim3(grid), dim3(EVL_BLOCK), 0, s, cls, kept, scan, word);
+        hipLaunchKernelGGL(k_evl_scan, dim3(1), dim3(1024), 0, s, scan, (const uint32_t*)word, kept, counts);
+        hipLaunchKernelGGL(k_haps_lists, dim3(grid), dim3(EVL_BLOCK), 0, s, (const int64_t*)scan, kept, list);
+        NSNP_HIP(ctx, hipGetLastError());
+        int64_t host[4];                                      // the one wait of the entry: `cap` cannot be held against M without the counts
+        NSNP_HIP(ctx, hipMemcpyAsync(host, counts, sizeof(host), hipMemcpyDeviceToHost, s));
+        NSNP_HIP(ctx, hipStreamSynchronize(s));
+        n_ref = host[2]; n_var = host[3];
+        if (n_ref < 0 || n_var < 0 || n_ref + n_var != kept) return NSNP_EINVAL;
+    }
+    // int(len * pn_value) in float64, truncated, as Python computes it (dataset_dev.py:214,224); no draws without a variant (the except: branch)
+    const int64_t blocks = NSNP_CDIV(n_ref, HAPS_REFS);
+    const int64_t q_full = n_var > 0 ? (int64_t)((double)HAPS_REFS * pn_value) : 0;
+    const int64_t q_tail = n_var > 0 && blocks > 0 ? (int64_t)((double)(n_ref - (blocks - 1) * HAPS_REFS) * pn_value) : 0;
+    const int64_t M = blocks > 0 ? n_ref + (blocks - 1) * q_full + q_tail : 0;
+    if (cap < M || (M > 0 && !samples)) return NSNP_EINVAL;
+    const int64_t grid = NSNP_CDIV(M > 0 ? M : 1, (int64_t)EVL_BLOCK);
+    if (grid > 0x7fffffffll) return NSNP_EINVAL;
+    hipLaunchKernelGGL(k_haps_place, dim3((unsigned)grid), dim3(EVL_BLOCK), 0, s, (const int64_t*)list, n_ref, n_var, M, q_full,
+                       (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, samples, meta);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
 }

@@ -23,14 +23,17 @@ Kept quirks: Lookahead's slow buffer is created at the FIRST sync (step k) as a 
 the first interpolation is at step 2k (lookahead.py:39-43); RAdam's weight decay is the decoupled ``p -= wd lr p`` (radam.py:69-70).
 Not here: ``balance_dataset``, the ``first_stage`` freeze, Novograd / Ranger / SGD / Adadelta, split precisions, sharding.
 
-The HaplotypeModel (HaplotypeModel/train_dev.py:25-80) has the same pieces for one epoch: ``HaplotypeTrainer`` owns the 58 parameters,
+The HaplotypeModel (HaplotypeModel/train_dev.py:25-80, 258-291) has the same pieces: ``HaplotypeTrainer`` owns the 58 parameters,
 ``loss_and_grad`` is one call of nsnp_hap_loss_grad (two 3-layer BiLSTM encoders of hidden size 256, four keep masks), ``DeviceOptimizer``
-steps them unchanged, ``train_haplotype_bins`` is one epoch over labelled haplotype site files.  Its departures:
-  * no ``pn_value`` upsampling: TrainingDataset draws variants with replacement per refcall block from an unseeded generator; here every
-    row LabelField keeps trains once;
-  * the order is a seeded ``torch.randperm`` of the kept rows of each PASS, not of a file;
+steps them unchanged, ``train_haplotype_bins`` is one epoch over labelled haplotype site files - with ``pn_value`` the variants are
+upsampled per block of 1,000 refcalls as TrainingDataset does it, by nsnp_hap_train_samples on the device - and ``fit_haplotype`` is the
+epoch loop with validation, the best checkpoint by genotype macro-F1, the decay and its stop.  Its departures:
+  * the variants of a block are drawn from the variants of the PASS, not of the file, by a seeded counter-based generator (Philox4x32-10)
+    where the reference draws from an unseeded np.random: the same distribution, another stream;
+  * the order is a seeded ``torch.randperm`` of the samples of each PASS, not of a file;
   * the four keep masks come from a seeded torch generator on the device, not from the stream nn.LSTM draws from;
-  * there is no epoch loop for this model yet: ``fit`` stays pileup-only;
+  * ``fit_haplotype`` also writes the fused optimiser's state beside every epoch's checkpoint, so a run can resume (the reference saves no
+    optimiser state and cannot);
   * Ranger, the other shipped optimiser type, is still out.
 """
 from __future__ import annotations
@@ -483,10 +486,23 @@ class HaplotypeTrainer:
         return m
 
 
+def pn_sample_count(n_ref, n_var, pn_value):
+    """M of nsnp_hap_train_samples from the counts the label pass reports: n_ref refcalls cut into blocks of 1,000, each followed by
+    int(len * pn_value) variant draws (Python's float product, truncated: dataset_dev.py:214,224); no draws without a variant"""
+    n_ref, n_var, pn_value = int(n_ref), int(n_var), float(pn_value)
+    if n_ref <= 0:
+        return 0
+    if n_var <= 0:
+        return n_ref
+    blocks = -(-n_ref // 1000)
+    return n_ref + (blocks - 1) * int(1000.0 * pn_value) + int(float(n_ref - (blocks - 1) * 1000) * pn_value)
+
+
 def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_size=512, dropout=0.1, max_grad_norm=2.0, seed=2022,
-                         pass_sites=16384, stats=None):
+                         pass_sites=16384, stats=None, pn_value=None):
     """One epoch of ``train(...)`` of HaplotypeModel/train_dev.py:25-80 over labelled haplotype site files
-    (sitefile.write_haplotype_train_bin) -> {sites, batches, mean_loss, gt_accuracy, zy_accuracy, refcalls, variants, unscorable_labels}.
+    (sitefile.write_haplotype_train_bin) -> {sites, batches, mean_loss, gt_accuracy, zy_accuracy, refcalls, variants, unscorable_labels,
+    samples_refcall, samples_variant}.
 
     The rows that train are those nsnp_hap_label_classes keeps: LabelField's filter (dataset_dev.py:174-187), the set
     evaluate_haplotype_bins scores.  A file is read in passes of `pass_sites` rows, synchronously on the calling thread: the eight planes
@@ -500,9 +516,18 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
     in front of the first pass when the context holds none of these dims.  mean_loss is the mean over batches of the batch loss; the
     accuracies are over sites.
 
-    Departures from the reference's loop: no ``pn_value`` upsampling (TrainingDataset draws variants with replacement
-    per refcall block from an unseeded generator); the order is per pass, not per file; the masks come from a torch generator, not from the
-    stream nn.LSTM draws from; there is no epoch loop for this model yet (``fit`` is the PileupModel's); Ranger is not implemented."""
+    pn_value None: every kept row trains once, as above.  A float (the shipped configuration trains with 0.7): TrainingDataset's upsampling
+    (dataset_dev.py:190-230) on the device.  After the label pass ctx.hap_train_samples(cls, kept, pn_value, seed, draw = the pass's number in
+    the epoch) lists the pass's refcalls in blocks of 1,000, each followed by int(len * pn_value) variants drawn with replacement;
+    pass_order of the list's length permutes it (this stands for the reference's shuffle inside a block and for its DataLoader's), and rows
+    and classes are gathered through the result.  A pass whose list is empty - no kept refcall - is skipped without drawing an order.
+    `sites` then counts samples (a variant drawn three times counts three times) and equals the sum of pn_sample_count over the passes;
+    samples_refcall / samples_variant split it (without pn_value they equal refcalls / variants).
+
+    Departures from the reference's loop: variants are drawn from the PASS's variants, not the file's
+    (pass_sites >= the rows of a file gives the reference's scope), by a seeded counter-based generator where the reference's np.random is
+    unseeded; the order is per pass, not per file; the masks come from a torch generator, not from the stream nn.LSTM draws from; the default
+    optimiser here leaves out the shipped weight_decay of 1e-4 (fit_haplotype's default has it); Ranger is not implemented."""
     import torch
     import torch.distributed as tdist
     from . import evaluate, hap_pipeline
@@ -515,6 +540,9 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
         raise ValueError("batch_size >= 1")
     if not 0.0 <= float(dropout) < 1.0:
         raise ValueError("dropout in [0, 1)")
+    pn = None if pn_value is None else float(pn_value)
+    if pn is not None and not 0.0 <= pn <= _lib.Context.HAP_PN_VALUE_MAX:
+        raise ValueError(f"pn_value: None or in [0, {_lib.Context.HAP_PN_VALUE_MAX:.0f}]")
     ctx, dev = trainer.ctx, trainer.device
     if optimizer is None:
         optimizer = DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-5)
@@ -531,6 +559,8 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
         mask_gen = torch.Generator(device=dev).manual_seed(int(seed))
         batch_losses, correct = [], torch.zeros(2, dtype=torch.int64, device=dev)
         totals = np.zeros(4, np.int64)                         # kept, unscorable, refcalls, variants
+        drawn = np.zeros(2, np.int64)                          # samples that are refcalls, samples that are variants
+        samples, sample_meta, pass_no = None, torch.zeros(4, dtype=torch.int64, device=dev), 0
         live = [f for f in files if f["n"]]
         if live:
             Pmax = min(P, max(f["n"] for f in live))
@@ -550,14 +580,28 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
                 totals += meta
                 kept = int(meta[0])
                 st["passes"] += 1; st["rows"] += m; st["bytes_h2d"] += nbytes + m * (12 * 12 + 12)
-                if not kept:
-                    continue
-                order = pass_order(order_gen, kept).to(dev)
+                draw, pass_no = pass_no, pass_no + 1
+                if pn is not None:
+                    # the pass's sample list - refcall blocks, each with its variant draws - and the seeded order over the whole list
+                    count = pn_sample_count(meta[2], meta[3], pn)
+                    if not count:
+                        continue
+                    if samples is None or samples.numel() < count:
+                        samples = torch.empty(count + count // 4, dtype=torch.int64, device=dev)
+                    ctx.hap_train_samples(ds.cls, kept, pn, int(seed) & (2 ** 64 - 1), draw=draw, samples=samples, meta=sample_meta)
+                    drawn += (int(meta[2]), count - int(meta[2]))
+                    order = samples[:count].index_select(0, pass_order(order_gen, count).to(dev))
+                else:
+                    if not kept:
+                        continue
+                    count = kept
+                    order = pass_order(order_gen, kept).to(dev)
+                    drawn += (int(meta[2]), int(meta[3]))
                 idx = ds.rows[:kept].index_select(0, order)
                 xp, xh = torch.index_select(xp, 0, idx), torch.index_select(xh, 0, idx)
                 cls = ds.cls[:kept].index_select(0, order).contiguous()
-                for o in range(0, kept, B):
-                    n = min(B, kept - o)
+                for o in range(0, count, B):
+                    n = min(B, count - o)
                     masks = None
                     if dropout > 0.0:
                         masks = [(torch.rand((n, L, 512), generator=mask_gen, device=dev) >= float(dropout)).to(torch.uint8) for L in (33, 33, 11, 11)]
@@ -573,12 +617,13 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
     finally:
         for f in files:
             f["src"].close()
-    sites = int(totals[0])
+    sites = int(totals[0]) if pn is None else int(drawn.sum())
     div = max(sites, 1)
     correct = correct.cpu().numpy()
     mean_loss = float(torch.stack(batch_losses).double().mean()) if batch_losses else float("nan")
     return {"sites": sites, "batches": len(batch_losses), "mean_loss": mean_loss, "gt_accuracy": float(correct[0]) / div,
-            "zy_accuracy": float(correct[1]) / div, "refcalls": int(totals[2]), "variants": int(totals[3]), "unscorable_labels": int(totals[1])}
+            "zy_accuracy": float(correct[1]) / div, "refcalls": int(totals[2]), "variants": int(totals[3]), "unscorable_labels": int(totals[1]),
+            "samples_refcall": int(drawn[0]), "samples_variant": int(drawn[1])}
 
 
 def fit(trainer, training_paths, validating_paths=None, epochs=1, optimizer=None, batch_size=2000, dropout=0.3, max_grad_norm=20.0,
@@ -616,4 +661,77 @@ def fit(trainer, training_paths, validating_paths=None, epochs=1, optimizer=None
                 for g in optimizer.param_groups:
                     g["lr"] *= float(decay_ratio)
         out.append(res)
+    return out
+
+
+def fit_haplotype(trainer, bin_paths, reference, validating_paths=None, epochs=30, optimizer=None, batch_size=512, dropout=0.1,
+                  max_grad_norm=2.0, pn_value=0.7, decay_ratio=0.98, begin_to_adjust_lr=3, min_lr=1e-7, finetune=False, seed=2021,
+                  save_prefix=None, start_epoch=0, pass_sites=16384):
+    """The epoch loop of HaplotypeModel/train_dev.py:258-291 -> one dict per epoch: train_haplotype_bins' result plus {epoch, lr (the rate the
+    epoch ran with), global_step, eval (evaluate_haplotype_bins' result or None), checkpoint, best_checkpoint (paths or None), stopped}.
+
+    Per epoch in range(start_epoch, epochs): optimizer.epoch(); train_haplotype_bins with seed + epoch and pn_value (None: no upsampling);
+    with validating_paths, evaluate.evaluate_haplotype_bins through trainer.to_model (one upload per epoch, which also serves the next
+    epoch's label pass).  With save_prefix: <save_prefix>.chkpt whenever eval["gt_f1"] >= the best so far (the best starts at 0; the
+    reference's >=, so the last of tied epochs stays), and <save_prefix>.epoch<e>.chkpt every epoch - both plain state dicts, what
+    train_dev.py:276,280 writes and haplotype_model.LSTMNetwork().load_state_dict reads.  From epoch >= begin_to_adjust_lr the rate decays by
+    decay_ratio; when the new rate is below min_lr the loop ends behind this epoch and its dict has stopped True (train_dev.py:284-290).
+
+    optimizer None: DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-5, weight_decay=1e-4), the shipped ont_haplotype.yaml; finetune
+    starts it at a tenth of that rate (optim.py:19-22).  finetune with an optimizer of the caller's is refused: that optimizer carries its
+    own rate.  Defaults are the shipped file's (epochs 30, batch 512, dropout 0.1, max_grad_norm 2, pn_value 0.7, decay 0.98 from epoch 3,
+    seed 2021).
+
+    Beyond the reference, which saves no optimiser state and cannot resume: beside every epoch's checkpoint a fused optimiser leaves
+    <save_prefix>.epoch<e>.optim = {optimizer: state_dict(), step, epoch, best_gt_f1}, written behind the epoch's decay, so it holds the
+    rate the next epoch runs with.  To resume behind epoch e: trainer from <save_prefix>.epoch<e>.chkpt,
+    optimizer.load_state_dict(ck["optimizer"], ck["step"], ck["epoch"]) with ck = torch.load of that .optim, start_epoch = e + 1; the best
+    F1 so far is read from the same file when it is there."""
+    import os
+    import torch
+    import torch.distributed as tdist
+    from . import evaluate
+    if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+        raise NotImplementedError("fit_haplotype under a process group of more than one rank (training is not sharded)")
+    if optimizer is None:
+        optimizer = DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-5 * (0.1 if finetune else 1.0), weight_decay=1e-4)
+    elif finetune:
+        raise ValueError("finetune scales the rate of the default optimizer; an optimizer of the caller's carries its own")
+    fused = isinstance(optimizer, DeviceOptimizer)
+    best = 0.0
+    if save_prefix is not None and int(start_epoch) > 0 and os.path.exists(f"{save_prefix}.epoch{int(start_epoch) - 1}.optim"):
+        best = float(torch.load(f"{save_prefix}.epoch{int(start_epoch) - 1}.optim").get("best_gt_f1", 0.0))
+    out, model = [], None
+    for epoch in range(int(start_epoch), int(epochs)):
+        if fused:
+            optimizer.epoch()
+        lr = optimizer.lr if fused else optimizer.param_groups[0]["lr"]
+        res = train_haplotype_bins(trainer, bin_paths, reference, optimizer=optimizer, batch_size=batch_size, dropout=dropout,
+                                   max_grad_norm=max_grad_norm, seed=int(seed) + epoch, pass_sites=pass_sites, pn_value=pn_value)
+        res.update(epoch=epoch, lr=lr, global_step=optimizer.global_step if fused else None, eval=None, checkpoint=None, best_checkpoint=None,
+                   stopped=False)
+        if validating_paths is not None:
+            model = trainer.to_model(model)
+            res["eval"] = evaluate.evaluate_haplotype_bins(model, validating_paths, reference, batch_size=batch_size, pass_sites=pass_sites)
+            if res["eval"]["gt_f1"] >= best:
+                best = float(res["eval"]["gt_f1"])
+                if save_prefix is not None:
+                    res["best_checkpoint"] = f"{save_prefix}.chkpt"
+                    trainer.save_checkpoint(res["best_checkpoint"])
+        if save_prefix is not None:
+            res["checkpoint"] = f"{save_prefix}.epoch{epoch}.chkpt"
+            trainer.save_checkpoint(res["checkpoint"])
+        if epoch >= int(begin_to_adjust_lr):
+            if fused:
+                optimizer.decay_lr(decay_ratio)
+            else:
+                for g in optimizer.param_groups:
+                    g["lr"] *= float(decay_ratio)
+            res["stopped"] = (optimizer.lr if fused else optimizer.param_groups[0]["lr"]) < float(min_lr)
+        if save_prefix is not None and fused:
+            torch.save({"optimizer": optimizer.state_dict(), "step": optimizer.global_step, "epoch": optimizer.current_epoch, "best_gt_f1": best},
+                       f"{save_prefix}.epoch{epoch}.optim")
+        out.append(res)
+        if res["stopped"]:
+            break
     return out
