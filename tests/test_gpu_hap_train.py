@@ -2,7 +2,8 @@
 
 The parity rule is the project's own: for every one of the 58 tensors max |g_dev - g_f64| / max |g_f64| <= 4 x ref_rel_max of
 tests/golden/hap_grad.npz (the reference's own fp32 distance from the restatement; 4 is the factor the forward and the pileup gradients are
-granted); loss and site_loss within 1e-4; pred equal wherever the float64 margin exceeds hap_eval_rules.MARGIN.
+granted); loss and site_loss within 1e-4; pred equal wherever the float64 margin exceeds hap_eval_rules.MARGIN, and at most MARGIN_SHARE of
+the sites nearer than that.
 
 The kernel's site tile is 64 (k_tr_gemm: 64 x 64 tiles of C) and a weight-gradient slice is 128 (site, step) rows: N = 1 has 33, 11 and
 fewer rows and crosses none, N = 17 crosses a slice boundary for both encoders at layers 0 and 1 (561 and 187 rows) and for neither at
@@ -58,18 +59,22 @@ def main_harness():
     return Harness(weights(), 512)
 
 
-def check_parity(got, want, n_gt=10, label=""):
+def check_parity(got, want, n_gt=10, label="", bounds=None):
+    """bounds: None (bound() for every tensor) or one bound per tensor"""
     grads, site_loss, pred = got
     dist = np.array([gr.rel_dist(a, b) for a, b in zip(grads, want["grads"])])
-    print(f"{label}: per-tensor distance {dist.min():.2e} .. {dist.max():.2e} (tensor {int(dist.argmax())}), bound {bound():.2e}")
+    lim = np.full(dist.shape, bound()) if bounds is None else np.asarray(bounds, np.float64)
+    assert lim.shape == dist.shape
+    print(f"{label}: per-tensor distance {dist.min():.2e} .. {dist.max():.2e} (tensor {int(dist.argmax())}), bound {lim.min():.2e} .. {lim.max():.2e}")
     print("  " + " ".join(f"{d:.1e}" for d in dist))
     n = site_loss.shape[0]
     sl_err = float(np.abs(site_loss - want["site_loss"]).max())
     loss = float(site_loss.astype(np.float64).sum(0).sum() / n)
     print(f"  site_loss within {sl_err:.2e}, loss {loss:.6f} against {want['loss']:.6f}")
-    assert np.isfinite(dist).all() and dist.max() <= bound(), (label, int(dist.argmax()), float(dist.max()))
+    assert np.isfinite(dist).all() and (dist <= lim).all(), (label, int((dist / lim).argmax()), float((dist / lim).max()))
     assert sl_err <= 1e-4 and abs(loss - want["loss"]) <= 1e-4
     far = hr.margins(want["logits"], n_gt) >= hr.MARGIN
+    assert (~far).any(1).mean() <= hr.MARGIN_SHARE                        # a pred that may fall either way is the exception
     assert ((pred == want["pred"]) | ~far).all()
     for a, b in gr.BIAS_PAIRS:
         assert np.array_equal(grads[a], grads[b])
