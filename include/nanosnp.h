@@ -591,6 +591,38 @@ int nsnp_optim_step(nsnp_ctx* ctx, int n_tensors, float* const* params, const fl
                     float* const* exp_avg_sq, float* const* slow, const int64_t* counts, const nsnp_optim_args* args, float* scratch,
                     float* grad_norm_out, void* stream);
 
+/* The other optimiser types of the reference's build_optimizer (PileupModel/optim.py:42-104): Novograd (novograd.py:197-221; amsgrad and
+ * grad_averaging off, as optim.py builds it), torch.optim.SGD (dampening 0) and torch.optim.Adadelta, each behind the same clip and in front of
+ * the same Lookahead sync.  The contract of nsnp_optim_step: asynchronous on `stream`, two launches, no allocation, no host synchronisation, no
+ * floating-point atomics, grads only read, any 4-byte alignment with the same bits.
+ *   state_a, state_b   HOST arrays of DEVICE pointers like params, used or ignored (NULL allowed) by kind:
+ *                        NSNP_OPTIM_NOVOGRAD   state_a exp_avg;  state_b ignored.  The second moment is ONE fp32 per tensor: layer_in[n_tensors]
+ *                                              (device, read) and layer_out[n_tensors] (device, written; a different array: swap the two behind
+ *                                              every step, start from zeros).  n_t = the squared norm of tensor t's clipped gradient;
+ *                                              v_t = (v_t == 0) ? n_t : beta2 v_t + (1 - beta2) n_t at every step;  x = g c / (sqrt(v_t) + eps);
+ *                                              x += weight_decay p;  m = beta1 m + x;  p -= lr m.  scratch is always needed.
+ *                        NSNP_OPTIM_SGD        state_a momentum_buffer, ignored when momentum == 0;  state_b ignored.  x = g c + weight_decay p;
+ *                                              buf = momentum buf + x (from zeros: torch's first step);  x = nesterov ? x + momentum buf : buf;
+ *                                              p -= lr x.
+ *                        NSNP_OPTIM_ADADELTA   state_a square_avg, state_b acc_delta.  x = g c + weight_decay p;  sq = rho sq + (1 - rho) x x;
+ *                                              delta = sqrt(acc + eps) / sqrt(sq + eps) x;  acc = rho acc + (1 - rho) delta delta;  p -= lr delta.
+ *                      layer_in / layer_out are ignored by the other two kinds.  max_norm, sync, alpha, slow, scratch, grad_norm_out: as above
+ *                      (nsnp_optim_scratch_floats sizes scratch for both entries).
+ * NSNP_EINVAL, with nothing launched, for a null or not 4-byte aligned pointer that the kind uses, n_tensors outside 1..64, a count below 1, an
+ * unknown kind, beta1 / beta2 / rho / momentum outside [0, 1) (whatever the kind: leave the unused ones 0), alpha outside [0, 1], nesterov
+ * outside 0 / 1 or set with momentum == 0 (as torch refuses it), sync outside its list, Novograd without scratch or without both layer arrays,
+ * layer_in == layer_out. */
+#define NSNP_OPTIM_NOVOGRAD 0
+#define NSNP_OPTIM_SGD 1
+#define NSNP_OPTIM_ADADELTA 2
+typedef struct nsnp_optim_kind_args {
+    double lr, beta1, beta2, eps, weight_decay, momentum, rho, alpha, max_norm;
+    int kind, nesterov, sync;
+} nsnp_optim_kind_args;
+int nsnp_optim_step_kind(nsnp_ctx* ctx, int n_tensors, float* const* params, const float* const* grads, float* const* state_a,
+                         float* const* state_b, float* const* slow, const int64_t* counts, const nsnp_optim_kind_args* args,
+                         const float* layer_in, float* layer_out, float* scratch, float* grad_norm_out, void* stream);
+
 /* ---- HaplotypeModel ------------------------------------------------------------------- */
 /* seq/bq/mq/hap: device int32 [N,D,L] planes as write_to_bins.py:44-61 stores them (padding
  * rows are -2); ref_row: device int32 [N,L].  out: device fp32 [N,105,L] -- float64 math as

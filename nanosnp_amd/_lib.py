@@ -91,6 +91,7 @@ _SIGNATURES = {
                                         C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_optim_scratch_floats": (C.c_int64, [C.c_int, C.c_void_p]),
     "nsnp_optim_step": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 10),
+    "nsnp_optim_step_kind": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 12),
     "nsnp_mpileup_tokenise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
     "nsnp_mpileup_tokenise_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 5 + [C.c_void_p] * 9),
     "nsnp_hap_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -318,6 +319,13 @@ class OptimArgs(C.Structure):
                [(k, C.c_int) for k in ("wd_mode", "form", "sync")]
 
 
+class OptimKindArgs(C.Structure):
+    """nsnp_optim_kind_args of include/nanosnp.h: the scalars of one Novograd / SGD / Adadelta step (nsnp_optim_step_kind)"""
+    _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay", "momentum", "rho", "alpha", "max_norm")] + \
+               [(k, C.c_int) for k in ("kind", "nesterov", "sync")]
+
+
+OPTIM_NOVOGRAD, OPTIM_SGD, OPTIM_ADADELTA = 0, 1, 2          # NSNP_OPTIM_* of include/nanosnp.h
 OPTIM_MAX_TENSORS = 64
 
 
@@ -1219,14 +1227,16 @@ class Context:
 
     def optim_tensors(self, params, grads, exp_avg, exp_avg_sq, slow=None):
         """the tensor lists of optim_step, checked once -> OptimTensors.  Every list: as many contiguous fp32 tensors on this context's device
-        as params, entry i in the shape of params[i]; views into a larger buffer are fine.  slow None: no Lookahead buffers (sync 0 only)."""
+        as params, entry i in the shape of params[i]; views into a larger buffer are fine.  slow None: no Lookahead buffers (sync 0 only).
+        exp_avg / exp_avg_sq are the two state tables of optim_kind_step as well, either None where its kind has no such state."""
         import torch
         n = len(params)
         if not 1 <= n <= OPTIM_MAX_TENSORS:
             raise NanoSNPError(f"optim_step: 1..{OPTIM_MAX_TENSORS} tensors, got {n}")
-        lists = {"params": params, "grads": grads, "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
-        if slow is not None:
-            lists["slow"] = slow
+        lists = {"params": params, "grads": grads}
+        for what, ts in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("slow", slow)):
+            if ts is not None:
+                lists[what] = ts
         for what, ts in lists.items():
             if len(ts) != n:
                 raise NanoSNPError(f"optim_step: {len(ts)} {what} for {n} params")
@@ -1252,6 +1262,8 @@ class Context:
         ot = tensors if isinstance(tensors, OptimTensors) else self.optim_tensors(*tensors)
         if not isinstance(args, OptimArgs):
             raise NanoSNPError("optim_step: args must be an OptimArgs")
+        if ot.exp_avg is None or ot.exp_avg_sq is None:
+            raise NanoSNPError("optim_step: exp_avg and exp_avg_sq are both needed")
         if args.sync != 0 and ot.slow is None:
             raise NanoSNPError("optim_step: a Lookahead sync needs the slow buffers")
         if scratch is None and (args.max_norm > 0 or grad_norm_out is not None):
@@ -1264,6 +1276,38 @@ class Context:
             raise NanoSNPError("optim_step: grad_norm_out one fp32 on the device")
         check(self.lib.nsnp_optim_step(self.handle, ot.n, ot.params, ot.grads, ot.exp_avg, ot.exp_avg_sq, ot.slow, ot.counts, C.byref(args),
                                        _dptr(scratch), _dptr(grad_norm_out), _stream_ptr(stream)), self.handle, "nsnp_optim_step")
+        return grad_norm_out
+
+    def optim_kind_step(self, tensors, args, layer_in=None, layer_out=None, scratch=None, grad_norm_out=None, stream=None):
+        """One fused Novograd / SGD / Adadelta step (nsnp_optim_step_kind; two launches, asynchronous).  tensors: an OptimTensors whose
+        exp_avg / exp_avg_sq tables are the kind's state_a / state_b (None where the kind has none), or the tuple to check now; args: an
+        OptimKindArgs; layer_in / layer_out: Novograd's per-tensor second moments, two different device fp32 [n] (read / written);
+        scratch and grad_norm_out as for optim_step.  -> grad_norm_out."""
+        import torch
+        ot = tensors if isinstance(tensors, OptimTensors) else self.optim_tensors(*tensors)
+        if not isinstance(args, OptimKindArgs):
+            raise NanoSNPError("optim_kind_step: args must be an OptimKindArgs")
+        novo = args.kind == OPTIM_NOVOGRAD
+        need_a = args.kind != OPTIM_SGD or args.momentum != 0
+        if (need_a and ot.exp_avg is None) or (args.kind == OPTIM_ADADELTA and ot.exp_avg_sq is None):
+            raise NanoSNPError("optim_kind_step: a state table of this kind is missing")
+        if args.sync != 0 and ot.slow is None:
+            raise NanoSNPError("optim_kind_step: a Lookahead sync needs the slow buffers")
+        if scratch is None and (novo or args.max_norm > 0 or grad_norm_out is not None):
+            scratch = torch.empty(ot.scratch_floats, dtype=torch.float32, device=ot.device)
+        if scratch is not None and (scratch.dtype != torch.float32 or not scratch.is_cuda or scratch.device != ot.device
+                                    or not scratch.is_contiguous() or scratch.numel() < ot.scratch_floats):
+            raise NanoSNPError(f"optim_kind_step: scratch fp32 [{ot.scratch_floats}] on the device")
+        if grad_norm_out is not None and (grad_norm_out.dtype != torch.float32 or not grad_norm_out.is_cuda or grad_norm_out.device != ot.device
+                                          or grad_norm_out.numel() != 1):
+            raise NanoSNPError("optim_kind_step: grad_norm_out one fp32 on the device")
+        for t in (layer_in, layer_out):
+            if (t is None and novo) or (t is not None and (t.dtype != torch.float32 or not t.is_cuda or t.device != ot.device
+                                                           or not t.is_contiguous() or t.numel() < ot.n)):
+                raise NanoSNPError(f"optim_kind_step: layer_in / layer_out fp32 [{ot.n}] on the device")
+        check(self.lib.nsnp_optim_step_kind(self.handle, ot.n, ot.params, ot.grads, ot.exp_avg, ot.exp_avg_sq, ot.slow, ot.counts, C.byref(args),
+                                            _dptr(layer_in), _dptr(layer_out), _dptr(scratch), _dptr(grad_norm_out), _stream_ptr(stream)),
+              self.handle, "nsnp_optim_step_kind")
         return grad_norm_out
 
     def pileup_gather_windows(self, counts, center_idx, stream=None):

@@ -33,6 +33,29 @@
 // No floating-point atomics anywhere: the same call on the same bits gives the same bits.  The division is the IEEE sequence (no
 // fast-math); sqrt(v) compiles to v_sqrt_f32 with the denormal scaling around it (1 ulp, which reaches p scaled by lr: far below its
 // rounding).
+//
+// nsnp_optim_step_kind: Novograd (PileupModel/novograd.py:197-221, and behind Lookahead lookahead.py:111-113), torch.optim.SGD (dampening 0)
+// and torch.optim.Adadelta (optim.py:51-66, 85-96) on the same range map, the same k_opt_sqsum and the same two launches.
+//   k_opt_update_kind<KIND>   the total and c as k_opt_update has them.  Novograd's second moment is ONE scalar per tensor, the squared norm
+//                  of that tensor's clipped gradient, so no float of tensor t can move before all of t's gradients were seen - and they were:
+//                  ranges never cross tensors, so partials first[t] .. first[t + 1] - 1 are tensor t's own.  In the pass that adds all
+//                  partials a lane adds those of them that lie in that segment a second time, into a float64 of their own (lane l: partials
+//                  l, l + 256, ... in rising order), and the segment sum seg_t goes through the same float64 wave and workgroup tree:
+//                      n_t  = (float)(((double)c * (double)c) * seg_t)          (no second pass over the gradients)
+//                      v_t' = (v_t == 0) ? n_t : beta2 * v_t + (1 - beta2) * n_t     v_t = layer_in[t]; the test holds at EVERY step
+//                      d    = sqrt(v_t') + eps
+//                  Every workgroup of tensor t computes v_t' itself, from the same words in the same order: the same bits.  The first
+//                  workgroup of t, lane 0, stores it to layer_out[t]; the caller swaps layer_in and layer_out behind every step.  No
+//                  workgroup reads a word that another workgroup writes in the same launch (partials and layer_in are read only, layer_out,
+//                  p and the states are written by their one owner): this is why there is no third launch and nothing to wait for.
+//                  Then per float, fp32, no contraction, x = g * c (the gradient buffer is only read, where novograd.py:214 divides it in place):
+//                      Novograd   x = x / d;  x = x + wd * p (wd != 0);  m = beta1 * m + x;  p = p - lr * m            (no bias correction)
+//                      SGD        x = x + wd * p (wd != 0);  momentum != 0: buf = mu * buf + x,  x = nesterov ? x + mu * buf : buf;
+//                                 p = p - lr * x                           (a zero-filled buf gives torch's first-step buf = x exactly)
+//                      Adadelta   x = x + wd * p (wd != 0);  sq = rho * sq + ((1 - rho) * x) * x;  std = sqrt(sq + eps);
+//                                 delta = (sqrt(acc + eps) / std) * x;  acc = rho * acc + ((1 - rho) * delta) * delta;  p = p - lr * delta
+//                  and the Lookahead sync 1 / 2 of k_opt_update behind any of them.  Novograd has no per-element second moment: it reads p, g, m
+//                  and writes p, m.
 #include "nsnp_common.hpp"
 
 namespace {
@@ -171,6 +194,92 @@ __global__ __launch_bounds__(OPT_BLOCK) void k_opt_update(const OptTable tb, con
     }
 }
 
+struct OptKindScalars {
+    float lr, beta1, beta2, omb2, eps, wd, mu, rho, omrho, alpha, max_norm;
+    int nesterov, sync, clip, n_partials;
+};
+
+// tb.m / tb.v are the two state tables of a kind: Novograd exp_avg / unused, SGD momentum_buffer (momentum != 0) / unused, Adadelta square_avg / acc_delta
+template <int KIND>
+__global__ __launch_bounds__(OPT_BLOCK) void k_opt_update_kind(const OptTable tb, const OptKindScalars sc, const float* __restrict__ partial,
+                                                               const float* __restrict__ layer_in, float* __restrict__ layer_out,
+                                                               float* __restrict__ grad_norm_out)
+{
+    __shared__ double shd[4];
+    const int blk = blockIdx.x, t = opt_tensor_of(tb, blk);
+    float c = 1.0f, d = 1.0f;
+    if (sc.n_partials > 0) {
+        const int s0 = tb.first[t], s1 = tb.first[t + 1];
+        double tot = 0.0, seg = 0.0;
+        for (int i = threadIdx.x; i < sc.n_partials; i += OPT_BLOCK) {
+            const double x = (double)partial[i];
+            tot += x;
+            if (KIND == NSNP_OPTIM_NOVOGRAD && i >= s0 && i < s1) seg += x;
+        }
+        tot = opt_block_sum(tot, shd);
+        const float norm = (float)__dsqrt_rn(tot);
+        if (sc.clip) c = fminf(1.0f, sc.max_norm / (norm + 1e-6f));
+        if (grad_norm_out && blk == 0 && threadIdx.x == 0) *grad_norm_out = norm;
+        if (KIND == NSNP_OPTIM_NOVOGRAD) {
+            seg = opt_block_sum(seg, shd);
+            const float nt = (float)(((double)c * (double)c) * seg);
+            const float v0 = layer_in[t];
+            const float v1 = (v0 == 0.0f) ? nt : sc.beta2 * v0 + sc.omb2 * nt;
+            d = __fsqrt_rn(v1) + sc.eps;
+            if (blk == s0 && threadIdx.x == 0) layer_out[t] = v1;
+        }
+    }
+    float* __restrict__ p = tb.p[t];
+    const float* __restrict__ g = tb.g[t];
+    float* __restrict__ sa = tb.m[t];
+    float* __restrict__ sb = tb.v[t];
+    float* __restrict__ slow = tb.slow[t];
+    const int64_t n = tb.n[t];
+    const bool use_a = KIND != NSNP_OPTIM_SGD || sc.mu != 0.0f, use_b = KIND == NSNP_OPTIM_ADADELTA;
+    const bool vec = opt_al16(p) && opt_al16(g) && (!use_a || opt_al16(sa)) && (!use_b || opt_al16(sb)) && (sc.sync == 0 || opt_al16(slow));
+    const int64_t r0 = (int64_t)(blk - tb.first[t]) * tb.mult * OPT_TILE;
+    for (int k = 0; k < tb.mult; ++k) {
+        const int64_t i = r0 + (int64_t)k * OPT_TILE + 4 * threadIdx.x;
+        if (i >= n) break;
+        f32x4 pp = opt_load4(p, i, n, vec), aa = {0.0f, 0.0f, 0.0f, 0.0f}, bb = aa, ss;
+        const f32x4 gg = opt_load4(g, i, n, vec);
+        if (use_a) aa = opt_load4(sa, i, n, vec);
+        if (use_b) bb = opt_load4(sb, i, n, vec);
+        if (sc.sync == 1) ss = opt_load4(slow, i, n, vec);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float x = gg[e] * c, w = pp[e];
+            if (KIND == NSNP_OPTIM_NOVOGRAD) {
+                x = x / d;
+                if (sc.wd != 0.0f) x = x + sc.wd * w;
+                aa[e] = sc.beta1 * aa[e] + x;
+                w = w - sc.lr * aa[e];
+            } else if (KIND == NSNP_OPTIM_SGD) {
+                if (sc.wd != 0.0f) x = x + sc.wd * w;
+                if (use_a) {
+                    aa[e] = sc.mu * aa[e] + x;
+                    x = sc.nesterov ? x + sc.mu * aa[e] : aa[e];
+                }
+                w = w - sc.lr * x;
+            } else {
+                if (sc.wd != 0.0f) x = x + sc.wd * w;
+                aa[e] = sc.rho * aa[e] + (sc.omrho * x) * x;
+                const float sd = __fsqrt_rn(aa[e] + sc.eps);
+                const float delta = (__fsqrt_rn(bb[e] + sc.eps) / sd) * x;
+                bb[e] = sc.rho * bb[e] + (sc.omrho * delta) * delta;
+                w = w - sc.lr * delta;
+            }
+            if (sc.sync == 1) { ss[e] = ss[e] + sc.alpha * (w - ss[e]); w = ss[e]; }
+            pp[e] = w;
+        }
+        opt_store4(p, i, n, vec, pp);
+        if (use_a) opt_store4(sa, i, n, vec, aa);
+        if (use_b) opt_store4(sb, i, n, vec, bb);
+        if (sc.sync == 1) opt_store4(slow, i, n, vec, ss);
+        if (sc.sync == 2) opt_store4(slow, i, n, vec, pp);
+    }
+}
+
 // the range map of a set of counts: mult and first[]; false for a count below 1 or a grid beyond 2^31
 bool opt_plan(int n_tensors, const int64_t* counts, int* mult, int* first)
 {
@@ -234,6 +343,61 @@ extern "C" int nsnp_optim_step(nsnp_ctx* ctx, int n_tensors, float* const* param
     hipStream_t s = (hipStream_t)stream;
     if (need_norm) hipLaunchKernelGGL(k_opt_sqsum, dim3((unsigned)grid), dim3(OPT_BLOCK), 0, s, tb, scratch);
     hipLaunchKernelGGL(k_opt_update, dim3((unsigned)grid), dim3(OPT_BLOCK), 0, s, tb, sc, (const float*)scratch, grad_norm_out);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+extern "C" int nsnp_optim_step_kind(nsnp_ctx* ctx, int n_tensors, float* const* params, const float* const* grads, float* const* state_a,
+                                    float* const* state_b, float* const* slow, const int64_t* counts, const nsnp_optim_kind_args* args,
+                                    const float* layer_in, float* layer_out, float* scratch, float* grad_norm_out, void* stream)
+{
+    if (!ctx || !params || !grads || !counts || !args) return NSNP_EINVAL;
+    if (n_tensors < 1 || n_tensors > OPT_MAX) return NSNP_EINVAL;
+    const nsnp_optim_kind_args& A = *args;
+    if (A.kind != NSNP_OPTIM_NOVOGRAD && A.kind != NSNP_OPTIM_SGD && A.kind != NSNP_OPTIM_ADADELTA) return NSNP_EINVAL;
+    const auto unit = [](double x) { return x >= 0.0 && x < 1.0; };          // (false for a NaN)
+    if (!unit(A.beta1) || !unit(A.beta2) || !unit(A.rho) || !unit(A.momentum) || !(A.alpha >= 0.0 && A.alpha <= 1.0)) return NSNP_EINVAL;
+    if (A.nesterov != 0 && A.nesterov != 1) return NSNP_EINVAL;
+    if (A.nesterov && A.momentum == 0.0) return NSNP_EINVAL;                  // torch: "Nesterov momentum requires a momentum"
+    if (A.sync < 0 || A.sync > 2 || (A.sync != 0 && !slow)) return NSNP_EINVAL;
+    const bool novo = A.kind == NSNP_OPTIM_NOVOGRAD;
+    const bool use_a = A.kind != NSNP_OPTIM_SGD || A.momentum != 0.0, use_b = A.kind == NSNP_OPTIM_ADADELTA;
+    if ((use_a && !state_a) || (use_b && !state_b)) return NSNP_EINVAL;
+    const bool clip = A.max_norm > 0.0, need_norm = novo || clip || grad_norm_out;
+    if (need_norm && !scratch) return NSNP_EINVAL;
+    if (novo && (!layer_in || !layer_out || layer_in == layer_out)) return NSNP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(layer_in) | reinterpret_cast<uintptr_t>(layer_out) | reinterpret_cast<uintptr_t>(scratch) |
+         reinterpret_cast<uintptr_t>(grad_norm_out)) & 3) return NSNP_EINVAL;
+    OptTable tb;
+    memset(&tb, 0, sizeof tb);
+    for (int i = 0; i < n_tensors; ++i) {
+        if (!params[i] || !grads[i] || (use_a && !state_a[i]) || (use_b && !state_b[i]) || (A.sync != 0 && !slow[i])) return NSNP_EINVAL;
+        if ((reinterpret_cast<uintptr_t>(params[i]) | reinterpret_cast<uintptr_t>(grads[i]) | (use_a ? reinterpret_cast<uintptr_t>(state_a[i]) : 0) |
+             (use_b ? reinterpret_cast<uintptr_t>(state_b[i]) : 0) | (A.sync != 0 ? reinterpret_cast<uintptr_t>(slow[i]) : 0)) & 3) return NSNP_EINVAL;
+        tb.p[i] = params[i]; tb.g[i] = grads[i];
+        tb.m[i] = use_a ? state_a[i] : nullptr;
+        tb.v[i] = use_b ? state_b[i] : nullptr;
+        tb.slow[i] = A.sync != 0 ? slow[i] : nullptr;
+        tb.n[i] = counts[i];
+    }
+    if (!opt_plan(n_tensors, counts, &tb.mult, tb.first)) return NSNP_EINVAL;
+    tb.n_tensors = n_tensors;
+    const int grid = tb.first[n_tensors];
+    OptKindScalars sc;
+    sc.lr = (float)A.lr; sc.beta1 = (float)A.beta1; sc.beta2 = (float)A.beta2; sc.omb2 = (float)(1.0 - A.beta2);
+    sc.eps = (float)A.eps; sc.wd = (float)A.weight_decay; sc.mu = (float)A.momentum;
+    sc.rho = (float)A.rho; sc.omrho = (float)(1.0 - A.rho); sc.alpha = (float)A.alpha; sc.max_norm = (float)A.max_norm;
+    sc.nesterov = A.nesterov; sc.sync = A.sync; sc.clip = clip ? 1 : 0;
+    sc.n_partials = need_norm ? grid : 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (need_norm) hipLaunchKernelGGL(k_opt_sqsum, dim3((unsigned)grid), dim3(OPT_BLOCK), 0, s, tb, scratch);
+    const dim3 gd((unsigned)grid), bd(OPT_BLOCK);
+    if (novo)
+        hipLaunchKernelGGL(k_opt_update_kind<NSNP_OPTIM_NOVOGRAD>, gd, bd, 0, s, tb, sc, (const float*)scratch, layer_in, layer_out, grad_norm_out);
+    else if (A.kind == NSNP_OPTIM_SGD)
+        hipLaunchKernelGGL(k_opt_update_kind<NSNP_OPTIM_SGD>, gd, bd, 0, s, tb, sc, (const float*)scratch, layer_in, layer_out, grad_norm_out);
+    else
+        hipLaunchKernelGGL(k_opt_update_kind<NSNP_OPTIM_ADADELTA>, gd, bd, 0, s, tb, sc, (const float*)scratch, layer_in, layer_out, grad_norm_out);
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
 }

@@ -4,7 +4,8 @@ around it (train.py:222-247) on the device.
 ``PileupTrainer`` owns the 24 parameters as fp32 device tensors; ``loss_and_grad`` is one C-ABI call (nsnp_pileup_loss_grad: forward that
 keeps the gate activations, label-smoothed loss, backpropagation through time, weight gradients - hand-written HIP, fp32 MFMA) that
 overwrites the gradient buffers each parameter's ``.grad`` is bound to.  ``DeviceOptimizer`` is the rest of a step as one more C-ABI call
-(nsnp_optim_step: gradient norm, clip, Adam / RAdam, Lookahead sync - two launches), with the reference's ``Optimizer`` bookkeeping
+(nsnp_optim_step: gradient norm, clip, Adam / RAdam, Lookahead sync - two launches; nsnp_optim_step_kind, the same for Novograd, SGD and
+Adadelta, every type of the reference's build_optimizer but Ranger), with the reference's ``Optimizer`` bookkeeping
 (optim.py:10-39) around it; ``fit`` is the epoch loop with the learning-rate decay.  PyTorch does the plumbing only: device tensors and the
 random keep mask - and, when the caller passes a torch optimiser of their own, the clipping and that optimiser.  fp32 only, one rank only.
 
@@ -20,8 +21,12 @@ Departures from the reference's loop:
     and the slow buffers restart at the next sync, which is what the reference itself does after such a load;
   * the two indel heads get no gradient, as in the reference (model.py:109-110 leaves their losses out), and are carried along unchanged.
 Kept quirks: Lookahead's slow buffer is created at the FIRST sync (step k) as a copy of the fast weights, so that sync changes nothing and
-the first interpolation is at step 2k (lookahead.py:39-43); RAdam's weight decay is the decoupled ``p -= wd lr p`` (radam.py:69-70).
-Not here: ``balance_dataset``, the ``first_stage`` freeze, Novograd / Ranger / SGD / Adadelta, split precisions, sharding.
+the first interpolation is at step 2k (lookahead.py:39-43); RAdam's weight decay is the decoupled ``p -= wd lr p`` (radam.py:69-70);
+Novograd's second moment is one scalar per tensor that is COPIED from the gradient's squared norm whenever it is 0, not only at the first
+step, has no bias correction, and its weight decay is added behind the division (novograd.py:201-221).  Novograd's departures: the
+gradients are not divided in place (they are only read), and a tensor's squared norm is the float64 sum of the per-range fp32 sums the clip
+already made, times the squared clip coefficient, where the reference squares and adds the clipped gradients in fp32.
+Not here: ``balance_dataset``, the ``first_stage`` freeze, Ranger (its source is not in the reference tree), split precisions, sharding.
 
 The HaplotypeModel (HaplotypeModel/train_dev.py:25-80, 258-291) has the same pieces: ``HaplotypeTrainer`` owns the 58 parameters,
 ``loss_and_grad`` is one call of nsnp_hap_loss_grad (two 3-layer BiLSTM encoders of hidden size 256, four keep masks), ``DeviceOptimizer``
@@ -169,26 +174,50 @@ def step_scalars(radam, t, lr, beta1, beta2, weight_decay):
     return dict(a=step_size * lr, b=1.0, form=0 if N_sma >= 5 else 1, wd_mode=2 if weight_decay != 0 else 0, decay=-weight_decay * lr)
 
 
+# the kinds of nsnp_optim_step_kind, under the names of PileupModel/optim.py:42-104: (lookahead, rule, the per-element states in torch's names)
+RULE_KINDS = {"Novograd": (False, _lib.OPTIM_NOVOGRAD, ("exp_avg",)), "LookaheadNovograd": (True, _lib.OPTIM_NOVOGRAD, ("exp_avg",)),
+              "sgd": (False, _lib.OPTIM_SGD, ("momentum_buffer",)), "adadelta": (False, _lib.OPTIM_ADADELTA, ("square_avg", "acc_delta"))}
+
+
 class DeviceOptimizer:
-    """The reference's ``Optimizer`` (PileupModel/optim.py:10-39) over one fused device step: clip_grad_norm_, Adam or RAdam and the Lookahead
-    wrapper (lookahead.py) are ONE call of nsnp_optim_step per batch.
+    """The reference's ``Optimizer`` (PileupModel/optim.py:10-39) over one fused device step: clip_grad_norm_, the optimiser's rule and the
+    Lookahead wrapper (lookahead.py) are ONE call of nsnp_optim_step (Adam, RAdam) or nsnp_optim_step_kind (Novograd, SGD, Adadelta) per batch.
 
     trainer_or_params: a PileupTrainer, or a list of contiguous fp32 device tensors whose ``.grad`` is set before every step (at most 64).
-    kind: "LookaheadAdam" (the shipped configurations), "Adam", "LookaheadRadam", "Radam".  Owns exp_avg, exp_avg_sq and the slow buffers as
-    device tensors and the step counters; ``lr``, ``global_step`` (starts at 1), ``current_epoch`` and ``epoch()`` are optim.py's."""
+    kind: "LookaheadAdam" (the shipped configurations), "Adam", "LookaheadRadam", "Radam", "Novograd", "LookaheadNovograd", "sgd", "adadelta"
+    - optim.py's names; betas (0.9, 0.999) and eps 1e-8 are what it gives every type but Adadelta, whose rho and eps default to torch's 0.9 and
+    1e-6 (eps None: the kind's default); momentum / nesterov are SGD's.  Owns the state of its kind as device tensors and nothing else -
+    exp_avg and exp_avg_sq (Adam, RAdam); exp_avg and ``layer_v``, one second moment per TENSOR (Novograd); momentum_buffer (SGD with a
+    momentum); square_avg and acc_delta (Adadelta) - the slow buffers of a Lookahead kind and the step counters; ``lr``, ``global_step``
+    (starts at 1), ``current_epoch`` and ``epoch()`` are optim.py's."""
 
-    def __init__(self, trainer_or_params, kind="LookaheadAdam", lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, alpha=0.5, k=6,
-                 ctx=None):
+    def __init__(self, trainer_or_params, kind="LookaheadAdam", lr=1e-4, betas=(0.9, 0.999), eps=None, weight_decay=0.0, alpha=0.5, k=6,
+                 ctx=None, momentum=0.0, nesterov=False, rho=0.9):
         import torch
-        if kind not in OPTIMIZER_KINDS:
-            raise ValueError(f"kind: one of {sorted(OPTIMIZER_KINDS)}, got {kind!r}")
+        if kind not in OPTIMIZER_KINDS and kind not in RULE_KINDS:
+            raise ValueError(f"kind: one of {sorted(OPTIMIZER_KINDS) + sorted(RULE_KINDS)}, got {kind!r}")
+        if not 0.0 <= float(momentum) < 1.0:
+            raise ValueError(f"momentum in [0, 1), got {momentum}")
+        if not 0.0 <= float(rho) < 1.0:
+            raise ValueError(f"rho in [0, 1), got {rho}")
+        if nesterov and float(momentum) == 0.0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if eps is None:
+            eps = 1e-6 if kind == "adadelta" else 1e-8
         self.trainer = trainer_or_params if hasattr(trainer_or_params, "parameters") and hasattr(trainer_or_params, "ctx") else None
         self.params = list(self.trainer.parameters() if self.trainer is not None else trainer_or_params)
         if not self.params:
             raise ValueError("no parameters")
         self.ctx = ctx if ctx is not None else (self.trainer.ctx if self.trainer is not None else _lib.Context(self.params[0].device.index or 0))
         self.kind = kind
-        self.lookahead, self.radam = OPTIMIZER_KINDS[kind]
+        if kind in OPTIMIZER_KINDS:
+            (self.lookahead, self.radam), self.rule, self.state_names = OPTIMIZER_KINDS[kind], None, ("exp_avg", "exp_avg_sq")
+        else:
+            self.radam = False
+            self.lookahead, self.rule, self.state_names = RULE_KINDS[kind]
+            if self.rule == _lib.OPTIM_SGD and float(momentum) == 0.0:
+                self.state_names = ()
+        self.momentum, self.nesterov, self.rho = float(momentum), bool(nesterov), float(rho)
         beta1, beta2 = float(betas[0]), float(betas[1])
         if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
             raise ValueError(f"betas in [0, 1), got {betas}")
@@ -203,12 +232,26 @@ class DeviceOptimizer:
         self.lookahead_step = 0
         self.slow_ready = False                              # the slow buffers hold weights (after the first sync)
         data = [p.detach() for p in self.params]
-        self.exp_avg = [torch.zeros_like(p) for p in data]
-        self.exp_avg_sq = [torch.zeros_like(p) for p in data]
+        # every per-element state of the kind under torch's name, and nothing the kind does not use
+        for name in ("exp_avg", "exp_avg_sq", "momentum_buffer", "square_avg", "acc_delta"):
+            setattr(self, name, [torch.zeros_like(p) for p in data] if name in self.state_names else None)
         self.slow = [torch.zeros_like(p) for p in data] if self.lookahead else None
+        # Novograd's second moments, one per tensor: the kernel reads _layer[0] and writes _layer[1], step() swaps them
+        self._layer = [torch.zeros(len(data), dtype=torch.float32, device=data[0].device) for _ in range(2)] \
+            if self.rule == _lib.OPTIM_NOVOGRAD else None
         self._tensors = None
         self._scratch = None
-        self._args = _lib.OptimArgs()
+        self._args = _lib.OptimArgs() if self.rule is None else _lib.OptimKindArgs()
+
+    @property
+    def layer_v(self):
+        """Novograd: the second moment of every tensor after the last step, device fp32 [number of tensors]; None for the other kinds"""
+        return self._layer[0] if self._layer is not None else None
+
+    def _states(self):
+        """the (up to two) state tables in the order of the C entry's exp_avg / exp_avg_sq (state_a / state_b) arguments"""
+        tables = [getattr(self, name) for name in self.state_names]
+        return tables + [None] * (2 - len(tables))
 
     def _bind(self):
         """the checked pointer tables; made again when a gradient buffer moved"""
@@ -220,22 +263,25 @@ class DeviceOptimizer:
         ot = self._tensors
         if ot is None or ot.grad_ptrs != tuple(g.data_ptr() for g in grads):
             import torch
-            ot = self.ctx.optim_tensors([p.detach() for p in self.params], grads, self.exp_avg, self.exp_avg_sq, self.slow)
+            ot = self.ctx.optim_tensors([p.detach() for p in self.params], grads, *self._states(), self.slow)
             self._tensors = ot
             if self._scratch is None:
                 self._scratch = torch.empty(ot.scratch_floats, dtype=torch.float32, device=ot.device)
         return ot
 
     def step(self, max_grad_norm=None, stream=None):
-        """clip at max_grad_norm (None or <= 0: no clipping), one Adam / RAdam step, the Lookahead sync when it is due -> the gradients'
-        norm before clipping, a device scalar (nothing waits for it).  The gradient buffers are not written."""
+        """clip at max_grad_norm (None or <= 0: no clipping), one step of the kind's rule, the Lookahead sync when it is due -> the
+        gradients' norm before clipping, a device scalar (nothing waits for it).  The gradient buffers are not written."""
         import torch
         ot = self._bind()
         self.global_step += 1
         self.step_count += 1
         a = self._args
-        for key, val in step_scalars(self.radam, self.step_count, self.lr, self.betas[0], self.betas[1], self.weight_decay).items():
-            setattr(a, key, val)
+        if self.rule is None:
+            for key, val in step_scalars(self.radam, self.step_count, self.lr, self.betas[0], self.betas[1], self.weight_decay).items():
+                setattr(a, key, val)
+        else:
+            a.kind, a.lr, a.momentum, a.nesterov, a.rho = self.rule, self.lr, self.momentum, int(self.nesterov), self.rho
         a.max_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
         a.weight_decay, a.beta1, a.beta2, a.eps, a.alpha = self.weight_decay, self.betas[0], self.betas[1], self.eps, self.alpha
         a.sync = 0
@@ -245,7 +291,13 @@ class DeviceOptimizer:
                 a.sync = 1 if self.slow_ready else 2
                 self.slow_ready = True
         norm = torch.empty((), dtype=torch.float32, device=ot.device)
-        self.ctx.optim_step(ot, a, self._scratch, norm, stream=stream)
+        if self.rule is None:
+            self.ctx.optim_step(ot, a, self._scratch, norm, stream=stream)
+        elif self._layer is None:
+            self.ctx.optim_kind_step(ot, a, None, None, self._scratch, norm, stream=stream)
+        else:
+            self.ctx.optim_kind_step(ot, a, self._layer[0], self._layer[1], self._scratch, norm, stream=stream)
+            self._layer.reverse()                            # what this step wrote is what the next one reads
         return norm
 
     def zero_grad(self, set_to_none=False):
@@ -259,12 +311,30 @@ class DeviceOptimizer:
 
     def state_dict(self):
         """{state: {i: {step, exp_avg, exp_avg_sq}}, slow_state: {i: {slow_buffer}}, param_groups: [...]} keyed by parameter index, CPU
-        tensors: the layout of Lookahead.state_dict() (lookahead.py:60-72) with indices where it has id()s"""
+        tensors: the layout of Lookahead.state_dict() (lookahead.py:60-72) with indices where it has id()s.  The state entries and the group
+        are those of the kind's torch optimiser: Novograd {step, exp_avg, exp_avg_sq: a 0-d tensor} (novograd.py:182-187), SGD
+        {momentum_buffer} (no entry without a momentum), Adadelta {step, square_avg, acc_delta}."""
         n = len(self.params)
-        state = {i: {"step": self.step_count, "exp_avg": self.exp_avg[i].cpu().clone(), "exp_avg_sq": self.exp_avg_sq[i].cpu().clone()}
-                 for i in range(n)} if self.step_count > 0 else {}
+        with_step = self.rule != _lib.OPTIM_SGD
+        state = {}
+        if self.step_count > 0 and self.state_names:
+            v = self._layer[0].cpu() if self._layer is not None else None
+            for i in range(n):
+                state[i] = {"step": self.step_count} if with_step else {}
+                state[i].update({name: getattr(self, name)[i].cpu().clone() for name in self.state_names})
+                if v is not None:
+                    state[i]["exp_avg_sq"] = v[i].clone()
         slow = {i: {"slow_buffer": self.slow[i].cpu().clone()} for i in range(n)} if self.lookahead and self.slow_ready else {}
-        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "params": list(range(n))}
+        if self.rule is None:
+            group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "params": list(range(n))}
+        elif self.rule == _lib.OPTIM_NOVOGRAD:
+            group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "grad_averaging": False,
+                     "amsgrad": False, "params": list(range(n))}
+        elif self.rule == _lib.OPTIM_SGD:
+            group = {"lr": self.lr, "momentum": self.momentum, "dampening": 0, "weight_decay": self.weight_decay, "nesterov": self.nesterov,
+                     "params": list(range(n))}
+        else:
+            group = {"lr": self.lr, "rho": self.rho, "eps": self.eps, "weight_decay": self.weight_decay, "params": list(range(n))}
         if self.lookahead:
             group.update(lookahead_alpha=self.alpha, lookahead_k=self.k, lookahead_step=self.lookahead_step)
         return {"state": state, "slow_state": slow, "param_groups": [group]}
@@ -272,8 +342,10 @@ class DeviceOptimizer:
     def load_state_dict(self, state_dict, global_step=None, current_epoch=None):
         """a state_dict() of this class, or the ``optimizer`` entry of a checkpoint the reference's utils.save_model wrote (torch's layout:
         state keyed by parameter index).  The reference's slow_state is keyed by id() and cannot be mapped: it is ignored and the slow
-        buffers restart at the next sync, as after the reference's own load.  lr, betas, eps, weight_decay and the Lookahead settings come
-        from param_groups[0].  global_step / current_epoch: the checkpoint's ``step`` / ``epoch`` entries, when given."""
+        buffers restart at the next sync, as after the reference's own load.  lr, weight_decay, the kind's own settings (betas, eps, momentum,
+        nesterov, rho) and the Lookahead settings come from param_groups[0].  The state entries are the kind's (state_dict()): Novograd's
+        exp_avg_sq is a 0-d tensor per parameter, SGD's momentum_buffer comes without a step.  global_step / current_epoch: the checkpoint's
+        ``step`` / ``epoch`` entries, when given."""
         import torch
         n = len(self.params)
         groups = state_dict["param_groups"]
@@ -282,11 +354,14 @@ class DeviceOptimizer:
         state = state_dict.get("state", {})
         if state and sorted(state) != list(range(n)):
             raise _lib.NanoSNPError(f"load_state_dict: state keyed by the parameter indices 0..{n - 1} expected")
-        steps = {int(float(state[i]["step"])) for i in state}
+        steps = {int(float(state[i]["step"])) for i in state if "step" in state[i]}
         if len(steps) > 1:
             raise _lib.NanoSNPError("load_state_dict: the parameters have different step counts")
+        if self.rule == _lib.OPTIM_SGD and (float(groups[0].get("momentum", self.momentum)) != 0.0) != bool(self.state_names):
+            raise _lib.NanoSNPError("load_state_dict: an SGD state with a momentum needs an optimizer built with one, one without an optimizer without")
         for i in range(n):
-            for name, mine in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+            for name in self.state_names:
+                mine = getattr(self, name)
                 if state:
                     src = state[i][name]
                     if tuple(src.shape) != tuple(mine[i].shape):
@@ -294,9 +369,21 @@ class DeviceOptimizer:
                     mine[i].copy_(src.to(torch.float32))
                 else:
                     mine[i].zero_()
-        self.step_count = steps.pop() if steps else 0
+        if self._layer is not None:                          # Novograd's exp_avg_sq: a 0-d tensor per parameter
+            v = [float(state[i]["exp_avg_sq"]) for i in range(n)] if state else [0.0] * n
+            self._layer[0].copy_(torch.tensor(v, dtype=torch.float64).to(torch.float32))
+        # (torch's SGD keeps no step: any count above 0 says that the buffers hold a state)
+        self.step_count = steps.pop() if steps else (1 if state else 0)
         g = groups[0]
-        self.lr, self.betas, self.eps, self.weight_decay = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]), float(g["weight_decay"])
+        self.lr, self.weight_decay = float(g["lr"]), float(g["weight_decay"])
+        if "betas" in g:
+            self.betas = (float(g["betas"][0]), float(g["betas"][1]))
+        if "eps" in g:
+            self.eps = float(g["eps"])
+        if self.rule == _lib.OPTIM_SGD:
+            self.momentum, self.nesterov = float(g.get("momentum", self.momentum)), bool(g.get("nesterov", self.nesterov))
+        if self.rule == _lib.OPTIM_ADADELTA:
+            self.rho = float(g.get("rho", self.rho))
         if self.lookahead:
             self.alpha, self.k = float(g.get("lookahead_alpha", self.alpha)), int(g.get("lookahead_k", self.k))
             self.lookahead_step = int(g.get("lookahead_step", 0))
