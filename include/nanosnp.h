@@ -530,6 +530,43 @@ int nsnp_pileup_eval_windows(nsnp_ctx* ctx, const int32_t* counts, const int64_t
  * workgroup per batch, a fixed tree - the same bits whatever the launch and the run.  The caller divides by the batch's size. */
 int nsnp_pileup_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream);
 
+/* ---- training the PileupModel: the sample list of a pass under balance_dataset upsampling (PileupModel/dataset.py:32-66, use_balance) ------
+ * cls uint8 [N,4]: the rows' classes { gt, zy, id1, id2 } as nsnp_pileup_label_classes leaves them, device.
+ *   samples int64 [cap]  row indices in [0, N); the first M are written, nothing behind them                                 (device)
+ *   sizes   int64 [63]   rows per category, or NULL                                                                          (device)
+ *   meta    int64 [8]  = { M, K, U, max, rows in no category, status (0, or 1 when U == 0), 0, 0 }; device or pinned host memory
+ * The rule.  The category of a row is c = 3 gt + zy (gt 0..20, zy 0..2), the categories stand in ascending c (the insertion order of the
+ * reference's dict).  A row with gt >= 21 or zy >= 3 is in no category (the reference's np.where matches nothing for it): it is counted and
+ * never sampled.  size[c] = the rows of c, max = the largest size, K = the categories with size > 0, U = those with 0 < size < max - the
+ * reference's non_zero_categories, which does NOT count the categories that already stand at max: that quirk is kept.  Every nonempty
+ * category owns max slots: slot r < size[c] holds the category's r-th row in row order, slot r >= size[c] a row drawn with replacement from
+ * the category's own rows, once per slot.  The balanced list has L = K max slots, and M = L / U (integer division: int(L / U) of
+ * dataset.py:65 for every L < 2^38 and U <= 62) samples are drawn with replacement from the slots.  The reference's shuffle in front of that
+ * draw does not change its distribution and is not made.
+ * U == 0 - N == 0, one category, or every nonempty category at the same size - is where the reference divides by zero.  Here it is an
+ * ordinary event (the last pass of a file may hold one row): status 1, M = 0, no sample written, sizes and meta written; the caller trains
+ * such a pass on its rows as they are.
+ * The bound.  M <= 2 N always: E >= 1 categories stand at max, so max <= N / E, U = K - E, and K / (E (K - E)) <= K / (K - 1) <= 2 for
+ * K >= 2.  A buffer of 2 N entries always suffices.
+ * The draws (csrc/nsnp_philox.hpp; key { seed & 0xffffffff, seed >> 32 }; index(r, n) = ((uint64)r * n) >> 32).  Sample m takes the words v
+ * of Philox4x32-10 at counter { m & 0xffffffff, m >> 32, draw, 0 }: its category is the k-th nonempty one, k = index(v[0], K), its slot
+ * r = index(v[1], max) - a uniform slot of K max is a uniform category times a uniform slot within it, as every category owns max slots.
+ * An upsampled slot (c, t = r - size[c]) holds the category's row number index(w[0], size[c]), w at counter { t, c, draw, 1 }: two samples
+ * that hit the same slot get the same row, as in the reference.  The reference's np.random is unseeded, so only the distribution is its
+ * own; here the list is a pure function of (cls, seed, draw), the same bits on every run whatever the grid.  `draw` is the caller's pass
+ * counter.  The scope is the N rows of the call - a pass - where the reference's is a file.
+ * NSNP_EINVAL with nothing written: cap < M, N < 0 or N >= 2^32, samples NULL with M > 0.
+ * Four launches: the rows of every block of 256 per category (32-bit integer adds in LDS, whose order cannot reach the sums); ONE workgroup
+ * that scans the blocks' counts per category, serially per lane over a run of blocks, and makes the plan (sizes, offsets, max, K, U, M,
+ * the table of nonempty categories); every block ranks its rows inside their categories by ballots, stably, and writes the sorted list;
+ * placement, a lane per sample, which also writes sizes and meta.  No workgroup waits for another and no float is involved.  Between the
+ * third and the fourth the entry WAITS for the stream once and reads M: cap cannot be held against M without it.  With N == 0 there are two
+ * launches and no wait (status 1).  Scratch: nsnp_pileup_label_classes' buffer, 1,600 bytes + 256 per block of 256 rows + 4 per row (the
+ * plan, the counts, the list), grown as there; it is overwritten, so run the entry behind the work that reads a label pass's scratch - on
+ * the same stream, or after it has finished. */
+int nsnp_pileup_balance_samples(nsnp_ctx* ctx, const uint8_t* cls, int64_t N, uint64_t seed, uint32_t draw, int64_t* samples, int64_t cap,
+                                int64_t* sizes, int64_t* meta, void* stream);
+
 /* ---- training the PileupModel: the loss gradients of a batch (PileupModel/train.py:56-59, model(...) and loss.backward()) ---------------
  * fp32 only and one device: with pileup_precision 1 or 2 nsnp_pileup_loss_grad returns NSNP_EINVAL.  The entries need no
  * nsnp_pileup_load_weights: the parameters are the caller's device tensors in plain state-dict layout, because they change every step; the

@@ -104,6 +104,8 @@ _SIGNATURES = {
     "nsnp_hap_label_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_hap_train_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int64,
                                          C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_balance_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "nsnp_hap_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
     "nsnp_hap_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_cat_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
@@ -1045,6 +1047,40 @@ class Context:
         check(self.lib.nsnp_pileup_label_classes(self.handle, _dptr(label), n, int(bool(variants_only)), _dptr(cls), _dptr(center_idx),
                                                  meta.data_ptr(), _stream_ptr(stream)), self.handle, "nsnp_pileup_label_classes")
         return cls, center_idx, meta
+
+    def pileup_balance_samples(self, cls, n, seed, draw=0, samples=None, sizes=None, meta=None, stream=None):
+        """cls: device uint8 [>= n, 4] as pileup_label_classes leaves it -> (samples int64, sizes int64 [63] or None, meta int64 [8]): the
+        training sample list of a pass under balance_dataset upsampling (nsnp_pileup_balance_samples): the first meta[0] entries of samples
+        are row indices in [0, n); sizes = the rows per (genotype, zygosity) category 3 gt + zy; meta = {M, K, U, max, rows in no category,
+        status, 0, 0}, on the device or in pinned memory.  status 1 (U == 0: no category below the largest): M = 0 and no sample is
+        written.  seed: 64 bits, draw: 32 bits (the pass counter).  samples None: a new tensor of 2 n entries, which always suffices; a
+        given one smaller than M is refused with nothing written.  sizes None: a new tensor; False: not wanted (NULL).  The entry waits for
+        the stream once (for M)."""
+        import torch
+        n, seed, draw = int(n), int(seed), int(draw)
+        if cls.dtype != torch.uint8 or not cls.is_cuda or not cls.is_contiguous() or n < 0 or cls.numel() < 4 * n:
+            raise NanoSNPError("pileup_balance_samples: cls must be a contiguous device uint8 [n,4]")
+        if n >= 1 << 32:
+            raise NanoSNPError("pileup_balance_samples: n below 2^32")
+        if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 32):
+            raise NanoSNPError("pileup_balance_samples: seed in [0, 2^64) and draw in [0, 2^32)")
+        dev = cls.device
+        if samples is None:
+            samples = torch.empty(max(2 * n, 1), dtype=torch.int64, device=dev)
+        if sizes is None:
+            sizes = torch.zeros(63, dtype=torch.int64, device=dev)
+        elif sizes is False:
+            sizes = None
+        meta = meta if meta is not None else torch.zeros(8, dtype=torch.int64, device=dev)
+        if samples.dtype != torch.int64 or not samples.is_cuda or not samples.is_contiguous():
+            raise NanoSNPError("pileup_balance_samples: samples int64 on the device")
+        if sizes is not None and (sizes.dtype != torch.int64 or sizes.numel() < 63 or not sizes.is_cuda or not sizes.is_contiguous()):
+            raise NanoSNPError("pileup_balance_samples: sizes int64 [63] on the device")
+        if meta.dtype != torch.int64 or meta.numel() < 8 or not (meta.is_cuda or meta.is_pinned()) or not meta.is_contiguous():
+            raise NanoSNPError("pileup_balance_samples: meta int64 [8] on the device or in pinned memory")
+        check(self.lib.nsnp_pileup_balance_samples(self.handle, _dptr(cls), n, seed, draw, _dptr(samples), int(samples.numel()), _dptr(sizes),
+                                                   meta.data_ptr(), _stream_ptr(stream)), self.handle, "nsnp_pileup_balance_samples")
+        return samples, sizes, meta
 
     @staticmethod
     def _eval_inputs(counts, center_idx, what):

@@ -22,6 +22,9 @@
 //
 // The HaplotypeModel's training samples (TrainingDataset.__init__, HaplotypeModel/dataset_dev.py:190-230) start from that label pass's cls:
 //   nsnp_hap_train_samples   k_haps_flags, k_evl_scan, k_haps_lists, one host wait for the two counts, k_haps_place (nsnp_philox.hpp)
+//
+// The PileupModel's balanced training samples (balance_dataset, PileupModel/dataset.py:32-66) start from nsnp_pileup_label_classes' cls:
+//   nsnp_pileup_balance_samples   k_bal_count, k_bal_scan, k_bal_lists (a counting sort with 64 bins), one host wait for M, k_bal_place
 #include "nsnp_common.hpp"
 #include "nsnp_philox.hpp"
 
@@ -335,6 +338,138 @@ __global__ __launch_bounds__(EVL_BLOCK) void k_haps_place(const int64_t* __restr
     samples[i] = list[at];
 }
 
+// ---- PileupModel training: the sample list of a pass under balance_dataset upsampling (PileupModel/dataset.py:32-66) ----------------------
+// Input: cls [N,4] of a label pass; the category of a row is c = 3 gt + zy (0..62), bin 63 takes the rows in no category (gt >= 21 or
+// zy >= 3).  A one-pass counting sort with 64 bins ranks every row inside its category, stably, in row order:
+//   k_bal_count   a workgroup per block of EVL_BLOCK rows: the block's rows per bin                                   -> cnt[block][64]
+//   k_bal_scan    ONE workgroup of 1024 lanes = 16 segments x 64 bins.  A lane sums its bin over its segment's run of ceil(blocks / 16)
+//                 consecutive blocks serially, the 16 segment sums of a bin meet in LDS, the lane then rewrites its run as running offsets:
+//                 cnt becomes base[block][bin], exact for any number of blocks, no workgroup waits for another.  Segment 0 (one wave, a lane
+//                 per bin) makes the plan: size, the exclusive scan off over the bins, max / K / U / M and nz[k], the k-th nonempty category.
+//   k_bal_lists   a workgroup per block again: the peers of a lane - the lanes of its wave in the same bin - are the AND over the six bits of
+//                 c of the ballot of that bit or its complement; rank = the peers below it; the waves of a block meet in a [4][64] table in
+//                 LDS written by each peer group's first lane.  list[off[c] + base[block][c] + rank] = row: every position is a function of
+//                 the rows alone.
+//   k_bal_place   a lane per sample m: Philox words v at counter {m low, m high, draw, 0}; category nz[index(v[0], K)], slot r =
+//                 index(v[1], max); slot r < size is the category's r-th row, slot r >= size the row index(w[0], size) with w at counter
+//                 {r - size, c, draw, 1}.  Lane 0.. of the first workgroup also copy the plan's meta and sizes out: nothing reaches the
+//                 caller's memory before the entry has held cap against M.
+// The only atomics are k_bal_count's 32-bit integer adds in LDS, whose sums do not depend on their order.
+constexpr int BAL_BINS = 64, BAL_NONE = 63;
+constexpr int BAL_WAVES = EVL_BLOCK / 64;
+constexpr int BAL_SEGS = 16;                                 // segments of k_bal_scan: 16 x 64 bins = 1024 lanes
+constexpr int BAL_SIZE = 0, BAL_OFF = 64, BAL_NZ = 128, BAL_META = 192, BAL_PLAN = 200;      // the plan: int64 words
+
+__device__ __forceinline__ int bal_bin(const uint8_t* __restrict__ cls, int64_t n)
+{
+    const int gt = cls[n * 4], zy = cls[n * 4 + 1];
+    return gt < 21 && zy < 3 ? 3 * gt + zy : BAL_NONE;
+}
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_bal_count(const uint8_t* __restrict__ cls, int64_t N, uint32_t* __restrict__ cnt)
+{
+    __shared__ unsigned int h[BAL_BINS];
+    const int tid = threadIdx.x;
+    if (tid < BAL_BINS) h[tid] = 0;
+    __syncthreads();
+    const int64_t n = (int64_t)blockIdx.x * EVL_BLOCK + tid;
+    if (n < N) atomicAdd(&h[bal_bin(cls, n)], 1u);
+    __syncthreads();
+    if (tid < BAL_BINS) cnt[(int64_t)blockIdx.x * BAL_BINS + tid] = h[tid];
+}
+
+__global__ __launch_bounds__(BAL_SEGS * BAL_BINS) void k_bal_scan(uint32_t* __restrict__ cnt, int64_t n_blocks, int64_t* __restrict__ plan)
+{
+    __shared__ long long part[BAL_SEGS][BAL_BINS];
+    const int c = threadIdx.x & 63, seg = threadIdx.x >> 6;
+    const int64_t per = NSNP_CDIV(n_blocks, (int64_t)BAL_SEGS);
+    const int64_t b0 = seg * per < n_blocks ? seg * per : n_blocks, b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+    long long s = 0;
+    for (int64_t b = b0; b < b1; ++b) s += cnt[b * BAL_BINS + c];
+    part[seg][c] = s;
+    __syncthreads();
+    long long run = 0, size = 0;
+    for (int g = 0; g < BAL_SEGS; ++g) {
+        const long long v = part[g][c];
+        run += g < seg ? v : 0;
+        size += v;
+    }
+    for (int64_t b = b0; b < b1; ++b) { const uint32_t v = cnt[b * BAL_BINS + c]; cnt[b * BAL_BINS + c] = (uint32_t)run; run += v; }
+    if (seg != 0) return;
+    // the plan, by one wave with a lane per bin
+    long long mx = c < BAL_NONE ? size : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const long long v = __shfl_xor(mx, o); mx = v > mx ? v : mx; }
+    const bool nonempty = c < BAL_NONE && size > 0;
+    const unsigned long long ne = __ballot(nonempty), under = __ballot(nonempty && size < mx);
+    const int K = __popcll(ne), U = __popcll(under);
+    long long inc = size;                                    // (bin 63 is the last lane: off[63] = the rows in a category)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const long long v = __shfl_up(inc, o); inc += c >= o ? v : 0; }
+    const long long none = __shfl(size, BAL_NONE);
+    plan[BAL_SIZE + c] = size;
+    plan[BAL_OFF + c] = inc - size;
+    if (nonempty) plan[BAL_NZ + __popcll(ne & ((1ull << c) - 1ull))] = c;
+    if (c >= K) plan[BAL_NZ + c] = 0;                        // (behind the K entries; never followed)
+    if (c < 8) {
+        const long long L = (long long)K * mx;               // below 2^38: K <= 63, max < 2^32
+        const long long M = U ? L / U : 0;                   // int(L / U) of dataset.py:65
+        plan[BAL_META + c] = c == 0 ? M : c == 1 ? K : c == 2 ? U : c == 3 ? mx : c == 4 ? none : c == 5 ? (U ? 0 : 1) : 0;
+    }
+}
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_bal_lists(const uint8_t* __restrict__ cls, int64_t N, const uint32_t* __restrict__ base,
+                                                         const int64_t* __restrict__ plan, uint32_t* __restrict__ list)
+{
+    __shared__ unsigned int wtab[BAL_WAVES][BAL_BINS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    wtab[wave][lane] = 0;
+    const int64_t n = (int64_t)blockIdx.x * EVL_BLOCK + tid;
+    const bool live = n < N;
+    const int c = live ? bal_bin(cls, n) : BAL_NONE;
+    unsigned long long peers = __ballot(live);
+#pragma unroll
+    for (int bit = 0; bit < 6; ++bit) {
+        const bool set = (c >> bit) & 1;
+        const unsigned long long b = __ballot(set);
+        peers &= set ? b : ~b;
+    }
+    const int rank = __popcll(peers & ((1ull << lane) - 1ull));
+    __syncthreads();
+    if (live && rank == 0) wtab[wave][c] = (unsigned int)__popcll(peers);
+    __syncthreads();
+    if (!live || c == BAL_NONE) return;
+    int64_t at = plan[BAL_OFF + c] + base[(int64_t)blockIdx.x * BAL_BINS + c] + rank;
+    for (int w = 0; w < wave; ++w) at += wtab[w][c];
+    if (at < 0 || at >= N) return;                           // (at lies in [0, N) by construction)
+    list[at] = (uint32_t)n;
+}
+
+__global__ __launch_bounds__(EVL_BLOCK) void k_bal_place(const uint32_t* __restrict__ list, const int64_t* __restrict__ plan, int64_t N, int64_t M,
+                                                         uint32_t key0, uint32_t key1, uint32_t draw, int64_t* __restrict__ samples,
+                                                         int64_t* __restrict__ sizes, int64_t* __restrict__ meta)
+{
+    const int64_t m = (int64_t)blockIdx.x * EVL_BLOCK + threadIdx.x;
+    if (m < 8) meta[m] = plan[BAL_META + m];
+    if (sizes && m < BAL_NONE) sizes[m] = plan[BAL_SIZE + m];
+    if (m >= M) return;
+    const int64_t K = plan[BAL_META + 1], mx = plan[BAL_META + 3];
+    if (K < 1 || K > BAL_NONE || mx < 1 || N < 1) return;
+    const nsnp_philox4 v = nsnp_philox4x32_10((uint32_t)m, (uint32_t)((uint64_t)m >> 32), draw, 0u, key0, key1);
+    int64_t k = (int64_t)nsnp_philox_index(v.v[0], (uint64_t)K);
+    k = k < K ? k : K - 1;
+    int64_t c = plan[BAL_NZ + k];
+    c = c < 0 ? 0 : (c < BAL_NONE ? c : BAL_NONE - 1);
+    const int64_t size = plan[BAL_SIZE + c];
+    if (size < 1) return;                                    // (a nonempty category by construction)
+    int64_t r = (int64_t)nsnp_philox_index(v.v[1], (uint64_t)mx);
+    if (r >= size) r = (int64_t)nsnp_philox_index(nsnp_philox4x32_10((uint32_t)(r - size), (uint32_t)c, draw, 1u, key0, key1).v[0], (uint64_t)size);
+    r = r < size ? r : size - 1;
+    int64_t at = plan[BAL_OFF + c] + r;
+    at = at < 0 ? 0 : (at < N ? at : N - 1);
+    samples[m] = (int64_t)list[at];
+}
+
 __global__ __launch_bounds__(EVL_BLOCK) void k_evl_compact(const int64_t* __restrict__ scan, const uint32_t* __restrict__ word, int64_t N,
                                                            uint32_t* __restrict__ cls, int64_t* __restrict__ center_idx)
 {
@@ -413,6 +548,19 @@ int sample_scratch(nsnp_ctx* ctx, int64_t N, hipStream_t s, int64_t** scan, int6
     *list = (int64_t*)((uint8_t*)ctx->evl_tmp + scan_bytes);
     *counts = *list + N;
     *word = (uint32_t*)((uint8_t*)ctx->evl_tmp + scan_bytes + list_bytes);
+    return NSNP_OK;
+}
+
+// scratch of a balanced sample list (the same buffer): the plan, cnt / base [blocks][64], the list (N rows, 32 bits each: N < 2^32)
+int balance_scratch(nsnp_ctx* ctx, int64_t N, hipStream_t s, int64_t** plan, uint32_t** cnt, uint32_t** list)
+{
+    const size_t plan_bytes = (size_t)BAL_PLAN * sizeof(int64_t);
+    const size_t cnt_bytes = (size_t)NSNP_CDIV(N, (int64_t)EVL_BLOCK) * BAL_BINS * sizeof(uint32_t);
+    const size_t need = plan_bytes + cnt_bytes + (size_t)N * sizeof(uint32_t) + 16;
+    if (int rc = nsnp_scratch_reserve(ctx, &ctx->evl_tmp, &ctx->evl_tmp_bytes, need, need / 4, s)) return rc;
+    *plan = (int64_t*)ctx->evl_tmp;
+    *cnt = (uint32_t*)((uint8_t*)ctx->evl_tmp + plan_bytes);
+    *list = (uint32_t*)((uint8_t*)ctx->evl_tmp + plan_bytes + cnt_bytes);
     return NSNP_OK;
 }
 
@@ -506,6 +654,36 @@ extern "C" int nsnp_hap_train_samples(nsnp_ctx* ctx, const uint8_t* cls, int64_t
     if (grid > 0x7fffffffll) return NSNP_EINVAL;
     hipLaunchKernelGGL(k_haps_place, dim3((unsigned)grid), dim3(EVL_BLOCK), 0, s, (const int64_t*)list, n_ref, n_var, M, q_full,
                        (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, samples, meta);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+// ---- PileupModel training: the balanced sample list of a pass (include/nanosnp.h) ----------------------------------------------------------
+extern "C" int nsnp_pileup_balance_samples(nsnp_ctx* ctx, const uint8_t* cls, int64_t N, uint64_t seed, uint32_t draw, int64_t* samples,
+                                           int64_t cap, int64_t* sizes, int64_t* meta, void* stream)
+{
+    if (!ctx || !meta || N < 0 || N > 0xffffffffll || (N > 0 && !cls)) return NSNP_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t* plan; uint32_t *cnt, *list;
+    if (const int rc = balance_scratch(ctx, N, s, &plan, &cnt, &list)) return rc;
+    const int64_t n_blocks = NSNP_CDIV(N, (int64_t)EVL_BLOCK);
+    if (N > 0) hipLaunchKernelGGL(k_bal_count, dim3((unsigned)n_blocks), dim3(EVL_BLOCK), 0, s, cls, N, cnt);
+    hipLaunchKernelGGL(k_bal_scan, dim3(1), dim3(BAL_SEGS * BAL_BINS), 0, s, cnt, n_blocks, plan);
+    int64_t M = 0;
+    if (N > 0) {
+        hipLaunchKernelGGL(k_bal_lists, dim3((unsigned)n_blocks), dim3(EVL_BLOCK), 0, s, cls, N, (const uint32_t*)cnt, (const int64_t*)plan, list);
+        NSNP_HIP(ctx, hipGetLastError());
+        int64_t host[8];                                      // the one wait of the entry: `cap` cannot be held against M without the counts
+        NSNP_HIP(ctx, hipMemcpyAsync(host, plan + BAL_META, sizeof(host), hipMemcpyDeviceToHost, s));
+        NSNP_HIP(ctx, hipStreamSynchronize(s));
+        M = host[0];
+        if (M < 0 || M > 2 * N) return NSNP_EINVAL;           // (M <= 2 N by the rule)
+    }
+    if (cap < M || (M > 0 && !samples)) return NSNP_EINVAL;
+    const int64_t grid = NSNP_CDIV(M > 0 ? M : 1, (int64_t)EVL_BLOCK);
+    if (grid > 0x7fffffffll) return NSNP_EINVAL;              // (as nsnp_hap_train_samples; M <= 2 N < 2^33 gives at most 2^25 workgroups)
+    hipLaunchKernelGGL(k_bal_place, dim3((unsigned)grid), dim3(EVL_BLOCK), 0, s, (const uint32_t*)list, (const int64_t*)plan, N, M,
+                       (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, samples, sizes, meta);
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
 }

@@ -19,14 +19,19 @@ Departures from the reference's loop:
     torch writes a lerp and a division: the same numbers up to fp32 rounding (tests/golden/pileup_optim.npz is the reference's own run);
   * a reference checkpoint's Lookahead slow buffers are keyed by ``id()`` and cannot be mapped to parameters: ``load_state_dict`` ignores them
     and the slow buffers restart at the next sync, which is what the reference itself does after such a load;
-  * the two indel heads get no gradient, as in the reference (model.py:109-110 leaves their losses out), and are carried along unchanged.
+  * the two indel heads get no gradient, as in the reference (model.py:109-110 leaves their losses out), and are carried along unchanged;
+  * ``use_balance`` (``balance_dataset``, dataset.py:32-66: every (genotype, zygosity) category upsampled to the largest, then K max / U
+    samples drawn from that list) balances the rows of a PASS, not of a file (pass_sites >= a file's rows gives the reference's scope),
+    with a seeded counter-based generator (Philox4x32-10, nsnp_pileup_balance_samples on the device) where the reference's np.random is
+    unseeded: the same distribution, another stream; and a pass with no category below the largest (U == 0: one row, one category, equal
+    sizes), where the reference divides by zero, trains on its rows as they are.
 Kept quirks: Lookahead's slow buffer is created at the FIRST sync (step k) as a copy of the fast weights, so that sync changes nothing and
 the first interpolation is at step 2k (lookahead.py:39-43); RAdam's weight decay is the decoupled ``p -= wd lr p`` (radam.py:69-70);
 Novograd's second moment is one scalar per tensor that is COPIED from the gradient's squared norm whenever it is 0, not only at the first
 step, has no bias correction, and its weight decay is added behind the division (novograd.py:201-221).  Novograd's departures: the
 gradients are not divided in place (they are only read), and a tensor's squared norm is the float64 sum of the per-range fp32 sums the clip
 already made, times the squared clip coefficient, where the reference squares and adds the clipped gradients in fp32.
-Not here: ``balance_dataset``, the ``first_stage`` freeze, Ranger (its source is not in the reference tree), split precisions, sharding.
+Not here: the ``first_stage`` freeze, Ranger (its source is not in the reference tree), split precisions, sharding.
 
 The HaplotypeModel (HaplotypeModel/train_dev.py:25-80, 258-291) has the same pieces: ``HaplotypeTrainer`` owns the 58 parameters,
 ``loss_and_grad`` is one call of nsnp_hap_loss_grad (two 3-layer BiLSTM encoders of hidden size 256, four keep masks), ``DeviceOptimizer``
@@ -404,10 +409,25 @@ def pass_order(generator, m):
     return torch.randperm(m, generator=generator)
 
 
+def balance_sample_count(sizes):
+    """(M, K, U, max) of nsnp_pileup_balance_samples from the rows per (genotype, zygosity) category (63 counts, 3 gt + zy): max = the
+    largest, K = the nonempty categories, U = those below max (balance_dataset's non_zero_categories, dataset.py:50-57: the categories at
+    max are not counted), M = K max // U samples (int(len(total_indexes) / non_zero_categories), dataset.py:65).  M is None when U == 0,
+    where the reference divides by zero.  M <= 2 sum(sizes)."""
+    sizes = [int(s) for s in sizes]
+    if any(s < 0 for s in sizes):
+        raise ValueError("sizes: counts >= 0")
+    mx = max(sizes, default=0)
+    K = sum(1 for s in sizes if s > 0)
+    U = sum(1 for s in sizes if 0 < s < mx)
+    return (K * mx // U if U else None), K, U, mx
+
+
 def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, dropout=0.3, max_grad_norm=20.0, seed=2022, pass_sites=65536,
-                     stats=None):
+                     stats=None, use_balance=False):
     """One epoch of ``train(epoch, config, model, training_paths, batch_size, optimizer, ...)`` of PileupModel/train.py:27-90 over
-    ``.td.bin`` files -> {sites, batches, mean_loss, gt_accuracy, zy_accuracy}.
+    ``.td.bin`` files -> {sites, batches, mean_loss, gt_accuracy, zy_accuracy}; with use_balance also {rows, samples_drawn,
+    passes_unbalanced}.
 
     Every row trains (training has no for_evaluate filter).  A file is read in passes of `pass_sites` rows: staged in pinned memory, sent,
     widened to int32 on the device, its label rows decoded by nsnp_pileup_label_classes(variants_only=0).  The rows of a pass are visited
@@ -416,7 +436,15 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     keep probability 1 - dropout from a device generator seeded with `seed` (none at dropout 0), loss_and_grad,
     clip_grad_norm_(parameters, max_grad_norm) (skipped when max_grad_norm is None), optimizer.step() - with a DeviceOptimizer both are its
     one fused step(max_grad_norm), and torch's clip does not run.  optimizer None: torch.optim.Adam(lr=1e-4, betas=(0.9, 0.999), eps=1e-8).  mean_loss is the mean over batches of the batch loss (the quantity train.py:60 accumulates, per batch
-    rather than per site); the accuracies are over sites, from the argmax the loss kernel writes."""
+    rather than per site); the accuracies are over sites, from the argmax the loss kernel writes.
+
+    use_balance (TrainDataset(datapath, use_balance=True), dataset.py:84-90): behind the label pass ctx.pileup_balance_samples(cls, m, seed,
+    draw = the pass's number in the epoch) lists M = K max // U rows of the pass, drawn with replacement from the list in which every
+    (genotype, zygosity) category is upsampled to the largest (balance_sample_count; a buffer of 2 pass_sites entries, allocated once, always
+    suffices); pass_order(M) permutes the LIST - which also stands for the reference's shuffle - and centres and classes are gathered
+    through samples[order].  A pass with no category below the largest (status 1: one row, one category, equal sizes - where the reference
+    divides by zero) trains on its rows as without use_balance.  `sites` counts what trained (a row drawn three times counts three times),
+    `rows` the file rows read, `samples_drawn` the sum of M over the balanced passes, `passes_unbalanced` the passes with status 1."""
     import torch
     import torch.distributed as tdist
     from .evaluate import _PassSet, _open_window_files, _paths
@@ -441,6 +469,10 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     hs, ds = _PassSet(P), _PassSet(P, dev)
     batch_losses, correct = [], torch.zeros(2, dtype=torch.int64, device=dev)
     sites = 0
+    if use_balance:
+        samples = torch.empty(2 * P, dtype=torch.int64, device=dev)
+        bal_meta = torch.zeros(8, dtype=torch.int64).pin_memory()
+        rows_read, drawn, unbalanced, pass_no = 0, 0, 0, 0
     for f in files:
         for a in range(0, f["n"], P):
             b = min(f["n"], a + P)
@@ -454,11 +486,24 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
             ds.x32[:m * 33].view(-1).copy_(ds.x[:nb].view(torch.int16 if f["elem"] == 2 else torch.int32))
             ctx.pileup_label_classes(ds.y[:m], False, cls=ds.cls, center_idx=ds.centers, meta=hs.meta)
             st["passes"] += 1; st["rows"] += m; st["bytes_h2d"] += nb + m * 360
-            order = pass_order(order_gen, m).to(dev)
+            count, balanced = m, False                         # what trains: the rows of the pass, or its balanced list
+            if use_balance:
+                # (the entry waits for the stream once, in front of the launch that writes bal_meta: wait for that launch too)
+                ctx.pileup_balance_samples(ds.cls, m, int(seed) & (2 ** 64 - 1), draw=pass_no, samples=samples, sizes=False, meta=bal_meta)
+                torch.cuda.current_stream(dev).synchronize()
+                rows_read, pass_no = rows_read + m, pass_no + 1
+                if int(bal_meta[5]) == 0:
+                    count, balanced = int(bal_meta[0]), True
+                    drawn += count
+                else:
+                    unbalanced += 1
+            order = pass_order(order_gen, count).to(dev)
+            if balanced:
+                order = samples[:count].index_select(0, order)
             centers = ds.centers[:m].index_select(0, order)
             cls = ds.cls[:m].index_select(0, order).contiguous()
-            for o in range(0, m, B):
-                n = min(B, m - o)
+            for o in range(0, count, B):
+                n = min(B, count - o)
                 mask = None
                 if dropout > 0.0:
                     mask = (torch.rand((n, 33, 128), generator=mask_gen, device=dev) >= float(dropout)).to(torch.uint8)
@@ -475,8 +520,11 @@ def train_train_bins(trainer, training_paths, optimizer=None, batch_size=2000, d
     div = max(sites, 1)
     correct = correct.cpu().numpy()
     mean_loss = float(torch.stack(batch_losses).double().mean()) if batch_losses else float("nan")
-    return {"sites": sites, "batches": len(batch_losses), "mean_loss": mean_loss, "gt_accuracy": float(correct[0]) / div,
-            "zy_accuracy": float(correct[1]) / div}
+    res = {"sites": sites, "batches": len(batch_losses), "mean_loss": mean_loss, "gt_accuracy": float(correct[0]) / div,
+           "zy_accuracy": float(correct[1]) / div}
+    if use_balance:
+        res.update(rows=rows_read, samples_drawn=drawn, passes_unbalanced=unbalanced)
+    return res
 
 
 
@@ -714,14 +762,16 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
 
 
 def fit(trainer, training_paths, validating_paths=None, epochs=1, optimizer=None, batch_size=2000, dropout=0.3, max_grad_norm=20.0,
-        decay_ratio=0.98, begin_to_adjust_lr=10, seed=2022, save_prefix=None, start_epoch=0, pass_sites=65536, eval_batch_size=None):
+        decay_ratio=0.98, begin_to_adjust_lr=10, seed=2022, save_prefix=None, start_epoch=0, pass_sites=65536, eval_batch_size=None,
+        use_balance=False):
     """The epoch loop of PileupModel/train.py:222-247 -> one dict per epoch: train_train_bins' result plus {epoch, lr (the rate the epoch
     ran with), global_step, eval (evaluate_train_bins' result or None), checkpoint (its path or None)}.
 
     Per epoch in range(start_epoch, epochs): optimizer.epoch(); train_train_bins with seed + epoch, so that every epoch has an order and masks
     of its own; evaluate.evaluate_train_bins on validating_paths when given (through trainer.to_model, one upload per epoch);
     trainer.save_checkpoint(<save_prefix>.epoch<e>.chkpt, optimizer=optimizer) when save_prefix is given; optimizer.decay_lr(decay_ratio)
-    once epoch >= begin_to_adjust_lr.  optimizer None: DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-4), the shipped configuration.
+    once epoch >= begin_to_adjust_lr.  use_balance: train_train_bins' balance_dataset upsampling (config.training.use_balance); the lists
+    differ from epoch to epoch through seed + epoch.  optimizer None: DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-4), the shipped configuration.
     To resume: trainer from the checkpoint, optimizer.load_state_dict(ck["optimizer"], ck["step"], ck["epoch"]), start_epoch=ck["epoch"]."""
     from . import evaluate
     if optimizer is None:
@@ -733,7 +783,7 @@ def fit(trainer, training_paths, validating_paths=None, epochs=1, optimizer=None
             optimizer.epoch()
         lr = optimizer.lr if fused else optimizer.param_groups[0]["lr"]
         res = train_train_bins(trainer, training_paths, optimizer=optimizer, batch_size=batch_size, dropout=dropout, max_grad_norm=max_grad_norm,
-                               seed=int(seed) + epoch, pass_sites=pass_sites)
+                               seed=int(seed) + epoch, pass_sites=pass_sites, use_balance=use_balance)
         res.update(epoch=epoch, lr=lr, global_step=optimizer.global_step if fused else None, eval=None, checkpoint=None)
         if validating_paths is not None:
             model = trainer.to_model(model)
