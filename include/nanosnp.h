@@ -526,6 +526,19 @@ int nsnp_pileup_forward_logits(nsnp_ctx* ctx, const int32_t* counts, const int64
 int nsnp_pileup_eval_windows(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
                              uint8_t* pred, int64_t* counters, float* logits, void* stream);
 
+/* The two entries above with the arithmetic as an argument: precision 0 (exact fp32), 1 (f16x3), 2 (bf16x3), or -1 for the context's
+ * pileup_precision.  The entries above are fp32 only and return NSNP_EINVAL while the context option is 1 or 2; these neither read (unless
+ * -1) nor set the option.  precision 0 runs the implementation of the entries above: the same bytes.  Under 1 and 2 a scoring pass runs the
+ * layer kernels nsnp_pileup_forward_windows runs in that arithmetic under the context's options and differs from it in the heads launch
+ * only: the accumulators of the genotype and zygosity rows are the bits that forward takes its softmax from, and the tail (loss, first
+ * argmax, counters) is the fp32 entry's, operation for operation.  No float is added atomically; a second run gives the same bytes.
+ * NSNP_EINVAL for NULL pointers or a precision outside -1..2, NSNP_ENOWEIGHTS without the indel heads, nothing written either way;
+ * N == 0 is a no-op.  (A first bf16x3 pass on a context whose workspace was reserved for another arithmetic re-reserves it, synchronously.) */
+int nsnp_pileup_forward_logits2(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, int64_t N, int precision, float* logits,
+                                void* stream);
+int nsnp_pileup_eval_windows2(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const uint8_t* cls, int64_t N, int precision,
+                              float* site_loss, uint8_t* pred, int64_t* counters, float* logits, void* stream);
+
 /* batch_sum[b,h] = the float64 sum of site_loss[n,h] over the rows n of batch b (rows b * batch_size ..), double [ceil(N / batch_size), 4]: one
  * workgroup per batch, a fixed tree - the same bits whatever the launch and the run.  The caller divides by the batch's size. */
 int nsnp_pileup_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream);

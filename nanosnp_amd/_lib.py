@@ -7,6 +7,7 @@ gfx950 device and fails loudly otherwise.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -82,6 +83,8 @@ _SIGNATURES = {
     "nsnp_pileup_label_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_forward_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_eval_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "nsnp_pileup_forward_logits2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_eval_windows2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 5),
     "nsnp_pileup_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_pileup_train_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
     "nsnp_hap_train_reserve": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int]),
@@ -1095,21 +1098,47 @@ class Context:
             raise NanoSNPError(f"{what}: center_idx must be a contiguous device int64 tensor")
         return int(center_idx.shape[0])
 
-    def pileup_forward_logits(self, counts, center_idx=None, logits=None, stream=None):
-        """all four heads as raw logits, fp32 [N,90] (rows 0-20 gt, 21-23 zy, 24-56 indel1, 57-89 indel2); center_idx None: counts is [N,33,18]"""
+    @staticmethod
+    def eval_precision_arg(precision):
+        """the `precision` keyword of the scoring calls -> None (the fp32-only entry, which refuses while pileup_precision is 1 or 2) or the
+        argument of the numbered entries: 0 fp32, 1 f16x3, 2 bf16x3, "context" -> -1 (the context's pileup_precision)"""
+        if precision is None:
+            return None
+        if isinstance(precision, str):
+            if precision == "context":
+                return -1
+        elif not isinstance(precision, bool):
+            try:
+                if operator.index(precision) in (0, 1, 2):
+                    return operator.index(precision)
+            except TypeError:                                # (a float, a list, an array: no arithmetic either)
+                pass
+        raise NanoSNPError(f'precision: None, 0 (fp32), 1 (f16x3), 2 (bf16x3) or "context", not {precision!r}')
+
+    def pileup_forward_logits(self, counts, center_idx=None, logits=None, stream=None, precision=None):
+        """all four heads as raw logits, fp32 [N,90] (rows 0-20 gt, 21-23 zy, 24-56 indel1, 57-89 indel2); center_idx None: counts is [N,33,18].
+        precision: see eval_precision_arg (None: nsnp_pileup_forward_logits, else nsnp_pileup_forward_logits2 in that arithmetic)"""
         import torch
         n = self._eval_inputs(counts, center_idx, "forward_logits")
         logits = logits if logits is not None else torch.empty((n, self.LABEL_WIDTH), dtype=torch.float32, device=counts.device)
         if logits.dtype != torch.float32 or logits.numel() < n * self.LABEL_WIDTH or not logits.is_cuda or not logits.is_contiguous():
             raise NanoSNPError("forward_logits: logits fp32 [N,90] on the device")
-        check(self.lib.nsnp_pileup_forward_logits(self.handle, _dptr(counts), _dptr(center_idx), n, _dptr(logits), _stream_ptr(stream)),
-              self.handle, "nsnp_pileup_forward_logits")
+        prec = self.eval_precision_arg(precision)
+        if prec is None:
+            check(self.lib.nsnp_pileup_forward_logits(self.handle, _dptr(counts), _dptr(center_idx), n, _dptr(logits), _stream_ptr(stream)),
+                  self.handle, "nsnp_pileup_forward_logits")
+        else:
+            check(self.lib.nsnp_pileup_forward_logits2(self.handle, _dptr(counts), _dptr(center_idx), n, prec, _dptr(logits), _stream_ptr(stream)),
+                  self.handle, "nsnp_pileup_forward_logits2")
         return logits
 
-    def pileup_eval_windows(self, counts, center_idx, cls, counters, n=None, site_loss=None, pred=None, want_logits=False, stream=None):
+    def pileup_eval_windows(self, counts, center_idx, cls, counters, n=None, site_loss=None, pred=None, want_logits=False, stream=None,
+                            precision=None):
         """forward + label-smoothed loss + argmax + confusion counts -> (site_loss fp32 [n,4], pred uint8 [n,4], logits fp32 [n,90] or None).
-        cls: device uint8 [>= n, 4]; counters: device int64 [EVAL_COUNTERS], added to; n: the sites to run (default: all of center_idx / counts)"""
+        cls: device uint8 [>= n, 4]; counters: device int64 [EVAL_COUNTERS], added to; n: the sites to run (default: all of center_idx / counts).
+        precision: see eval_precision_arg (None: nsnp_pileup_eval_windows, else nsnp_pileup_eval_windows2 in that arithmetic)"""
         import torch
+        prec = self.eval_precision_arg(precision)
         n_all = self._eval_inputs(counts, center_idx, "eval_windows")
         n = n_all if n is None else int(n)
         dev = counts.device
@@ -1123,8 +1152,13 @@ class Context:
                 or pred.dtype != torch.uint8 or pred.numel() < 4 * n or not pred.is_cuda or not pred.is_contiguous()):
             raise NanoSNPError("eval_windows: site_loss fp32 [N,4] and pred uint8 [N,4] on the device")
         logits = torch.empty((n, self.LABEL_WIDTH), dtype=torch.float32, device=dev) if want_logits else None
-        check(self.lib.nsnp_pileup_eval_windows(self.handle, _dptr(counts), _dptr(center_idx), _dptr(cls), n, _dptr(site_loss), _dptr(pred),
-                                                _dptr(counters), _dptr(logits), _stream_ptr(stream)), self.handle, "nsnp_pileup_eval_windows")
+        if prec is None:
+            check(self.lib.nsnp_pileup_eval_windows(self.handle, _dptr(counts), _dptr(center_idx), _dptr(cls), n, _dptr(site_loss), _dptr(pred),
+                                                    _dptr(counters), _dptr(logits), _stream_ptr(stream)), self.handle, "nsnp_pileup_eval_windows")
+        else:
+            check(self.lib.nsnp_pileup_eval_windows2(self.handle, _dptr(counts), _dptr(center_idx), _dptr(cls), n, prec, _dptr(site_loss),
+                                                     _dptr(pred), _dptr(counters), _dptr(logits), _stream_ptr(stream)),
+                  self.handle, "nsnp_pileup_eval_windows2")
         return site_loss, pred, logits
 
     def pileup_batch_loss(self, site_loss, batch_size, n=None, stream=None):

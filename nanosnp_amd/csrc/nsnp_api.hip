@@ -280,6 +280,9 @@ extern "C" int nsnp_ctx_destroy(nsnp_ctx* ctx)
     if (ctx->evl_tmp) (void)hipFree(ctx->evl_tmp);
     if (ctx->pw.head6_w) (void)hipFree(ctx->pw.head6_w);
     if (ctx->pw.head6_b) (void)hipFree(ctx->pw.head6_b);
+    if (ctx->pw16.head6_w) (void)hipFree(ctx->pw16.head6_w);
+    if (ctx->pwb3.head6_w) (void)hipFree(ctx->pwb3.head6_w);
+    if (ctx->pwb3.head6_b) (void)hipFree(ctx->pwb3.head6_b);
     nsnp_tok_free(ctx);
     nsnp_train_free(ctx);
     nsnp_hap_train_free(ctx);
@@ -302,7 +305,13 @@ extern "C" int nsnp_ctx_reserve(nsnp_ctx* ctx, int64_t max_sites)
     if (!ctx || max_sites <= 0) return NSNP_EINVAL;
     // H0: 512 B per site and step on the fp32 / f16x3 paths, 768 B (three bf16 planes) on the bf16x3 path: the larger layout is
     // allocated only for a context that has selected pileup_precision 2 (the option re-reserves when it is set: below)
-    const int h0_floats = ctx->precision == 2 ? 192 : 128;
+    return nsnp_ctx_reserve_h0(ctx, max_sites, ctx->precision == 2 ? 192 : 128);
+}
+
+// (an explicit arithmetic of nsnp_pileup_forward_logits2 / nsnp_pileup_eval_windows2 needs the layout of ITS H0, not the option's)
+int nsnp_ctx_reserve_h0(nsnp_ctx* ctx, int64_t max_sites, int h0_floats)
+{
+    if (!ctx || max_sites <= 0 || (h0_floats != 128 && h0_floats != 192)) return NSNP_EINVAL;
     if (ctx->ws_h0 && ctx->chunk_sites == max_sites && ctx->ws_h0_floats >= h0_floats) return NSNP_OK;
     NSNP_HIP(ctx, hipSetDevice(ctx->device));
     NSNP_HIP(ctx, hipDeviceSynchronize());
@@ -339,13 +348,18 @@ extern "C" int nsnp_pileup_load_indel_heads(nsnp_ctx* ctx, const float* const* h
     for (int i = 0; i < 4; ++i) if (!host_tensors[i]) return NSNP_EINVAL;
     if (!ctx->pw.loaded) return NSNP_ENOWEIGHTS;
     NSNP_HIP(ctx, hipSetDevice(ctx->device));
-    return nsnp_pileup_pack_indel_heads(ctx, host_tensors);
+    // three images behind ONE flag: the fp32 packer raises it, a failure of a later image takes it back
+    int rc = nsnp_pileup_pack_indel_heads(ctx, host_tensors);
+    if (!rc) rc = nsnp_pileup_pack_indel_heads_f16(ctx, host_tensors);
+    if (!rc) rc = nsnp_pileup_pack_indel_heads_bf16(ctx, host_tensors);
+    if (rc) ctx->pw.indel_loaded = false;
+    return rc;
 }
 
 extern "C" int nsnp_pileup_forward_logits(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, int64_t N, float* logits, void* stream)
 {
     if (!ctx || N < 0 || (N > 0 && (!counts || !logits))) return NSNP_EINVAL;
-    if (ctx->precision != 0) return NSNP_EINVAL;           // fp32 only: the split-precision modes have no such heads kernel
+    if (ctx->precision != 0) return NSNP_EINVAL;           // fp32 only, and kept so: the arithmetic is an argument of the numbered successors below
     return nsnp_pileup_eval_impl(ctx, counts, center_idx, nullptr, N, nullptr, nullptr, nullptr, logits, (hipStream_t)stream);
 }
 
@@ -355,6 +369,31 @@ extern "C" int nsnp_pileup_eval_windows(nsnp_ctx* ctx, const int32_t* counts, co
     if (!ctx || N < 0 || (N > 0 && (!counts || !cls || !site_loss || !pred || !counters))) return NSNP_EINVAL;
     if (ctx->precision != 0) return NSNP_EINVAL;
     return nsnp_pileup_eval_impl(ctx, counts, center_idx, cls, N, site_loss, pred, counters, logits, (hipStream_t)stream);
+}
+
+// the numbered successors: the arithmetic is an argument (0 fp32, 1 f16x3, 2 bf16x3, -1 the context's pileup_precision), so a scoring pass
+// neither reads nor sets the option; 0 is nsnp_pileup_eval_impl, the implementation of the entries above
+static int pileup_eval_any(nsnp_ctx* ctx, int precision, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N,
+                           float* site_loss, uint8_t* pred, int64_t* counters, float* logits, hipStream_t s)
+{
+    if (precision == -1) precision = ctx->precision;
+    if (precision == 1) return nsnp_pileup_eval_f16x3(ctx, x, center_idx, cls, N, site_loss, pred, counters, logits, s);
+    if (precision == 2) return nsnp_pileup_eval_bf16x3(ctx, x, center_idx, cls, N, site_loss, pred, counters, logits, s);
+    return nsnp_pileup_eval_impl(ctx, x, center_idx, cls, N, site_loss, pred, counters, logits, s);
+}
+
+extern "C" int nsnp_pileup_forward_logits2(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, int64_t N, int precision,
+                                           float* logits, void* stream)
+{
+    if (!ctx || N < 0 || precision < -1 || precision > 2 || (N > 0 && (!counts || !logits))) return NSNP_EINVAL;
+    return pileup_eval_any(ctx, precision, counts, center_idx, nullptr, N, nullptr, nullptr, nullptr, logits, (hipStream_t)stream);
+}
+
+extern "C" int nsnp_pileup_eval_windows2(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const uint8_t* cls, int64_t N,
+                                         int precision, float* site_loss, uint8_t* pred, int64_t* counters, float* logits, void* stream)
+{
+    if (!ctx || N < 0 || precision < -1 || precision > 2 || (N > 0 && (!counts || !cls || !site_loss || !pred || !counters))) return NSNP_EINVAL;
+    return pileup_eval_any(ctx, precision, counts, center_idx, cls, N, site_loss, pred, counters, logits, (hipStream_t)stream);
 }
 
 // one dispatch for the three arithmetic modes; post / post_written as in nsnp_common.hpp

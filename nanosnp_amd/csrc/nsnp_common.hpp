@@ -64,6 +64,9 @@ struct PileupWeightsF16 {
     void* l0_whh_rs[2];                                      // register-stationary layer-0 kernel (K order of its exchange rows)
     void* proj_w; void* dense_w; void* head_w;
     void* arena; size_t arena_bytes; bool loaded;
+    // all 90 head rows as [6 tiles][8 K blocks][hi, lo][lane] of 8 fp16 (96 KB) for k_pileup_head_eval_h: an allocation of its own, made by
+    // nsnp_pileup_load_indel_heads; valid while pw.indel_loaded.  Its biases are pw.head6_b (the accumulator order of this kernel family)
+    void* head6_w;
 };
 
 // bf16 three-plane images of the same weights for the bf16x3 path (pileup_forward_bf16x3.hip): [tile][K block][plane][lane] of 8 bf16
@@ -72,6 +75,9 @@ struct PileupWeightsB3 {
     void* proj_w; void* dense_w; void* head_w;
     float* proj_b; float* dense_b; float* head_b;             // fp32, natural row order
     void* arena; size_t arena_bytes; bool loaded;
+    // all 90 head rows as [6 tiles][8 K blocks][3 planes][lane] of 8 bf16 (144 KB) and their biases [6 tiles][q][g] for k_pileup_head_eval_b3:
+    // an allocation of its own, made by nsnp_pileup_load_indel_heads; valid while pw.indel_loaded
+    void* head6_w; float* head6_b;
 };
 
 struct HapWeightsDev;   // hap_forward.hip
@@ -211,3 +217,14 @@ int nsnp_pileup_pack_weights_f16(nsnp_ctx* ctx, const float* const* w);
 int nsnp_pileup_forward_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, float* gt, float* zy,
                                const PostOut* post, hipStream_t s);
 int nsnp_pileup_pack_weights_bf16(nsnp_ctx* ctx, const float* const* w);
+// scoring in the split arithmetics (nsnp_pileup_forward_logits2 / nsnp_pileup_eval_windows2): the layer launches of the forward above under
+// the context's options, ending in the six-tile heads kernel of the same file.  Arguments as nsnp_pileup_eval_impl.
+int nsnp_pileup_eval_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
+                           uint8_t* pred, int64_t* counters, float* logits, hipStream_t s);
+int nsnp_pileup_eval_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
+                            uint8_t* pred, int64_t* counters, float* logits, hipStream_t s);
+// the fp16 hi/lo and bf16 three-plane images of all 90 head rows, behind nsnp_pileup_pack_indel_heads (w: the four indel tensors)
+int nsnp_pileup_pack_indel_heads_f16(nsnp_ctx* ctx, const float* const* w);
+int nsnp_pileup_pack_indel_heads_bf16(nsnp_ctx* ctx, const float* const* w);
+// the workspace of nsnp_ctx_reserve with at least h0_floats (128 or 192) floats per site and step of H0, whatever the context's pileup_precision
+int nsnp_ctx_reserve_h0(nsnp_ctx* ctx, int64_t max_sites, int h0_floats);

@@ -2101,7 +2101,7 @@ int nsnp_pileup_pack_weights(nsnp_ctx* ctx, const float* const* w)
     pw.proj_w = dev(h_proj); pw.proj_b = dev(h_pb); pw.dense_w = dev(h_dense); pw.dense_b = dev(h_db);
     pw.head_w = dev(h_head); pw.head_b = dev(h_hb);
     pw.loaded = true;
-    pw.indel_loaded = false;        // (the six-tile image repeats the genotype / zygosity rows of the weights it was packed behind)
+    pw.indel_loaded = false;        // (the six-tile images of all three arithmetics repeat the genotype / zygosity rows of the weights they were packed behind)
     return NSNP_OK;
 }
 

@@ -17,12 +17,15 @@
 //   k_pileup_l0_b3    layer-0 BiLSTM recurrence, 33 steps; 4 waves x 4 gate tiles, weights (3 planes) in 144 VGPRs, h through LDS
 //   k_pileup_l1_b3    layer-1 input projection + recurrence, 17 steps per direction; 8 waves x 2 gate tiles, 144 VGPRs of weights
 //   k_pileup_head_b3  output_proj at t = 16, tanh(dense), heads, softmax, argmax / max (predict.py:54-57)
+//   k_pileup_head_eval_b3  the same up to the head product, then all 90 head rows as raw logits and the loss / argmax / confusion
+//                     counts of a scoring pass (nsnp_pileup_eval_windows2; PileupModel/train.py:93-150)
 // Intermediates: H0 [16-site group][t][dir][plane 3][K block 2][quarter 4][site 16][8] bf16 (768 B per site and step, written
 // already split and in the LDS operand order, so layer 0 flushes and layer 1 stages it with linear 16-byte copies), H1c
 // [site][dir][64 units] fp32.
 #include "nsnp_common.hpp"
 #include "nsnp_lstm_cell.hpp"
 #include "nsnp_bf16.hpp"
+#include "nsnp_eval_tail.hpp"
 #include <type_traits>
 
 namespace {
@@ -790,6 +793,116 @@ __global__ __launch_bounds__(64 * HB3_WAVES) void k_pileup_head_b3(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// scoring heads: k_pileup_head_b3 up to its last product (restated: the same H1c, splits, staged images, K order and MFMA chains),
+// then the head product over the six tiles of the 90-row image instead of two.  The image is 144 KB and the stage 96 KB, so it comes in
+// two pieces (tiles 0..3, tiles 4..5); every accumulator runs kb = 0..7 with the six products of stage_gemm_b3<2, 8, 2>, so tiles 0 and 1
+// hold the bits k_pileup_head_b3 takes its softmax from.  The 90 logits of a wave's 16 sites then meet in LDS (the stage, free behind a
+// barrier: 8 waves x 16 sites x 103 floats = 51.5 KB) and the tail is k_pileup_head_eval's (nsnp_eval_tail.hpp).
+// LDS: the 96 KB stage + 10.5 KB of 32-bit confusion counters that leave once per workgroup.
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int HB3_EVAL_LDS_BYTES = HB3_STAGE_B8 * 16 + nsnp_eval::COUNTERS * 4;
+static_assert(HB3_WAVES * nsnp_eval::Z_WAVE * 4 <= HB3_STAGE_B8 * 16, "the logit exchange fits the stage");
+
+__global__ __launch_bounds__(64 * HB3_WAVES) void k_pileup_head_eval_b3(
+    const float* __restrict__ H1c, int64_t N,
+    const __bf16* __restrict__ proj_w, const float* __restrict__ proj_b,
+    const __bf16* __restrict__ dense_w, const float* __restrict__ dense_b,
+    const __bf16* __restrict__ head6_w, const float* __restrict__ head6_b,
+    const uint8_t* __restrict__ cls, float* __restrict__ site_loss, uint8_t* __restrict__ pred,
+    unsigned long long* __restrict__ counters, float* __restrict__ logits)
+{
+    extern __shared__ b8 lds_b3[];
+    b8* const wst = lds_b3;
+    unsigned int* const cnt = reinterpret_cast<unsigned int*>(lds_b3 + HB3_STAGE_B8);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = lane >> 4;
+    const int64_t site0 = ((int64_t)blockIdx.x * HB3_WAVES + wave) * 16;
+    const int64_t site = site0 + (lane & 15);
+    const int64_t sc = site < N ? site : N - 1;
+    for (int i = tid; i < nsnp_eval::COUNTERS; i += 64 * HB3_WAVES) cnt[i] = 0;        // (first read behind the barriers below)
+    // ---- k_pileup_head_b3 to the letter up to the head product ----
+    auto stage = [&](const __bf16* src, int n_b8) {
+        __syncthreads();                                   // everyone is done with the previous image
+        const b8* s8 = reinterpret_cast<const b8*>(src);
+        for (int i = tid; i < n_b8; i += 64 * HB3_WAVES) wst[i] = s8[i];
+        __syncthreads();
+    };
+    // B fragments of output_proj: K position 32 kb + 8 q + j = feature [fwd 64 | bwd 64] in natural order
+    b8 bh[4][3];
+    {
+        const f32x4* __restrict__ hin = reinterpret_cast<const f32x4*>(H1c + sc * 128 + 8 * q);
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            const f32x4 v0 = hin[kb * 8], v1 = hin[kb * 8 + 1];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                __bf16 a, b, d; split3(j < 4 ? v0[j & 3] : v1[j & 3], a, b, d);
+                bh[kb][0][j] = a; bh[kb][1][j] = b; bh[kb][2][j] = d;
+            }
+        }
+    }
+    // output_proj 128 -> 128
+    f32x4 ap[8];
+    {
+        const f32x4* pb = reinterpret_cast<const f32x4*>(proj_b);      // [tile][q] rows 16 tile + 4 q + g
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ap[i] = pb[i * 4 + q];
+        stage(proj_w, 8 * 4 * 3 * 64);
+        stage_gemm_b3<8, 4, 4>(wst, lane, bh, ap);
+    }
+    // dense 128 -> 256 + tanh: K position (kb, q, j) <-> proj feature 16 (2 kb + (j >> 2)) + 4 q + (j & 3): the lane's own registers
+    b8 dh[4][3];
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            __bf16 a, b, d; split3(ap[2 * kb + (j >> 2)][j & 3], a, b, d);
+            dh[kb][0][j] = a; dh[kb][1][j] = b; dh[kb][2][j] = d;
+        }
+    f32x4 ad[16];
+    {
+        const f32x4* db = reinterpret_cast<const f32x4*>(dense_b);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) ad[i] = db[i * 4 + q];
+        stage(dense_w, 8 * 4 * 3 * 64);
+        stage_gemm_b3<8, 4, 4>(wst, lane, dh, ad);
+        stage(dense_w + (size_t)8 * 4 * 3 * 64 * 8, 8 * 4 * 3 * 64);
+        stage_gemm_b3<8, 4, 4>(wst, lane, dh, ad + 8);
+    }
+    b8 eh[8][3];
+#pragma unroll
+    for (int kb = 0; kb < 8; ++kb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float z = ad[2 * kb + (j >> 2)][j & 3];
+            const float th = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((2.0f * nsnp_cell::LOG2E) * z)), 1.0f);
+            __bf16 a, b, d; split3(th, a, b, d);
+            eh[kb][0][j] = a; eh[kb][1][j] = b; eh[kb][2][j] = d;
+        }
+    f32x4 ah[6];
+    {
+        const f32x4* hb = reinterpret_cast<const f32x4*>(head6_b);     // [tile][q] rows 16 tile + 4 q + g
+#pragma unroll
+        for (int t = 0; t < 6; ++t) ah[t] = hb[t * 4 + q];
+        constexpr int PAIR_B8 = 2 * 8 * 3 * 64;                        // two tiles: the whole image of k_pileup_head_b3
+        stage(head6_w, 2 * PAIR_B8);
+        stage_gemm_b3<2, 8, 2>(wst, lane, eh, ah);
+        stage_gemm_b3<2, 8, 2>(wst + PAIR_B8, lane, eh, ah + 2);
+        stage(head6_w + (size_t)2 * PAIR_B8 * 8, PAIR_B8);
+        stage_gemm_b3<2, 8, 2>(wst, lane, eh, ah + 4);
+    }
+    __syncthreads();                                       // everyone is done with the weights: the stage becomes the logit exchange
+    float* const zw = reinterpret_cast<float*>(wst) + wave * nsnp_eval::Z_WAVE;
+    nsnp_eval::put_logits(zw, lane, ah);
+    __syncthreads();
+    nsnp_eval::wave_tail(zw, lane, site0, N, cls, site_loss, pred, cnt, logits);
+    if (cls) {
+        __syncthreads();
+        nsnp_eval::flush_counters(cnt, counters, tid, 64 * HB3_WAVES);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -861,6 +974,39 @@ int nsnp_pileup_pack_weights_bf16(nsnp_ctx* ctx, const float* const* w)
     return NSNP_OK;
 }
 
+// nsnp_pileup_load_indel_heads, bf16 three-plane image of all 90 head rows.  Rows 0..23 (tile 0, and the lanes of tile 1 whose row is
+// below 24) are read back from the two-tile image nsnp_pileup_pack_weights_bf16 uploaded - the very bits k_pileup_head_b3 multiplies;
+// rows 24..89 are split from the indel tensors w = {indel1 W, b, indel2 W, b} like every other weight, rows 90..95 are 0.
+int nsnp_pileup_pack_indel_heads_bf16(nsnp_ctx* ctx, const float* const* w)
+{
+    PileupWeightsB3& pw = ctx->pwb3;
+    if (!pw.loaded) return NSNP_ENOWEIGHTS;
+    constexpr size_t n_tile = (size_t)8 * 3 * 64 * 8;       // bf16 per tile
+    std::vector<uint16_t> img(6 * n_tile), old_w(2 * n_tile);
+    float bias[96], old_b[32];
+    NSNP_HIP(ctx, hipDeviceSynchronize());
+    NSNP_HIP(ctx, hipMemcpy(old_w.data(), pw.head_w, old_w.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    NSNP_HIP(ctx, hipMemcpy(old_b, pw.head_b, sizeof old_b, hipMemcpyDeviceToHost));
+    auto acc_feat = [](int kb, int q, int j) { return 16 * (2 * kb + (j >> 2)) + 4 * q + (j & 3); };
+    pack_b3(img.data(), 6, 8, [&](int row, int kb, int q, int j) {
+        const int f = acc_feat(kb, q, j);
+        if (row >= 24 && row < 57) return w[0][(row - 24) * 256 + f];
+        if (row >= 57 && row < 90) return w[2][(row - 57) * 256 + f];
+        return 0.f;
+    });
+    for (int tile = 0; tile < 2; ++tile) for (int kp = 0; kp < 8 * 3; ++kp) for (int lane = 0; lane < 64; ++lane)
+        if (16 * tile + (lane & 15) < 24) {
+            const size_t e = (((size_t)tile * 24 + kp) * 64 + lane) * 8;
+            memcpy(&img[e], &old_w[e], 8 * sizeof(uint16_t));
+        }
+    for (int r = 0; r < 96; ++r) bias[r] = r < 24 ? old_b[r] : (r < 57 ? w[1][r - 24] : (r < 90 ? w[3][r - 57] : 0.f));
+    if (!pw.head6_w) NSNP_HIP(ctx, hipMalloc(&pw.head6_w, img.size() * sizeof(uint16_t)));
+    if (!pw.head6_b) NSNP_HIP(ctx, hipMalloc((void**)&pw.head6_b, sizeof bias));
+    NSNP_HIP(ctx, hipMemcpy(pw.head6_w, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    NSNP_HIP(ctx, hipMemcpy(pw.head6_b, bias, sizeof bias, hipMemcpyHostToDevice));
+    return NSNP_OK;
+}
+
 static int set_lds_attr_b3(nsnp_ctx* ctx)
 {
     if (ctx->attr_set_b3) return NSNP_OK;
@@ -869,19 +1015,22 @@ static int set_lds_attr_b3(nsnp_ctx* ctx)
     SET(k_pileup_l1_b3<1>, b3_l1_lds_bytes(1)); SET(k_pileup_l1_b3<2>, b3_l1_lds_bytes(2)); SET(k_pileup_l1_b3<4>, b3_l1_lds_bytes(4));
     SET(k_pileup_l0_b3p, b3_l0_lds_bytes(2));
     SET(k_pileup_head_b3, HB3_STAGE_B8 * 16);
+    SET(k_pileup_head_eval_b3, HB3_EVAL_LDS_BYTES);
 #undef SET
     ctx->attr_set_b3 = true;
     return NSNP_OK;
 }
 
-int nsnp_pileup_forward_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, float* gt, float* zy,
-                               const PostOut* post, hipStream_t s)
+// The chunk loop and layers 0 and 1 of a bf16x3 pass, ending in the caller's heads launch heads(base, n) on the chunk's H1c: the ONE place
+// these launches are made - the probability forward and the scoring forward below differ in their heads kernel only.
+template <typename HeadsFn>
+static int forward_bf16x3_t(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, hipStream_t s, HeadsFn heads)
 {
-    if (!ctx->pwb3.loaded || !ctx->pw.loaded) return NSNP_ENOWEIGHTS;
     if (N == 0) return NSNP_OK;
     int rc = set_lds_attr_b3(ctx);
     if (rc) return rc;
-    if (!ctx->ws_h0 || ctx->ws_h0_floats < 192) { rc = nsnp_ctx_reserve(ctx, ctx->chunk_sites); if (rc) return rc; }
+    // (the 768-byte layout of H0 whatever the context's pileup_precision: an explicit arithmetic does not depend on the option)
+    if (!ctx->ws_h0 || ctx->ws_h0_floats < 192) { rc = nsnp_ctx_reserve_h0(ctx, ctx->chunk_sites, 192); if (rc) return rc; }
     const PileupWeightsB3& pw = ctx->pwb3;
     const PileupWeightsDev& p32 = ctx->pw;            // the fp32 path's layer-1 bias image (accumulator layout, gate rows scaled alike)
     __bf16* H0 = reinterpret_cast<__bf16*>(ctx->ws_h0);            // 768 B per site and step (nsnp_ctx_reserve sizes for it)
@@ -916,7 +1065,19 @@ int nsnp_pileup_forward_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* c
 #undef LAUNCH_L1
         }
         ScopedKernelTimer tm_head(ctx, NSNP_K_HEAD, s);
-        const bool po = post && post->gt_arg;
+        heads(base, n);
+    }
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
+int nsnp_pileup_forward_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, float* gt, float* zy,
+                               const PostOut* post, hipStream_t s)
+{
+    if (!ctx->pwb3.loaded || !ctx->pw.loaded) return NSNP_ENOWEIGHTS;
+    const PileupWeightsB3& pw = ctx->pwb3;
+    const bool po = post && post->gt_arg;
+    return forward_bf16x3_t(ctx, x, center_idx, N, s, [&](int64_t base, int64_t n) {
 #ifndef NSNP_B3_NOHEAD                                  /* (removal timing build) */
         hipLaunchKernelGGL(k_pileup_head_b3, dim3((unsigned)NSNP_CDIV(n, 16 * HB3_WAVES)), dim3(64 * HB3_WAVES), HB3_STAGE_B8 * 16, s,
                            ctx->ws_h1c, n, (const __bf16*)pw.proj_w, pw.proj_b, (const __bf16*)pw.dense_w, pw.dense_b,
@@ -924,7 +1085,20 @@ int nsnp_pileup_forward_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* c
                            po ? post->gt_arg + base : nullptr, po ? post->zy_arg + base : nullptr,
                            po ? post->gt_max + base : nullptr, po ? post->zy_max + base : nullptr);
 #endif
-    }
-    NSNP_HIP(ctx, hipGetLastError());
-    return NSNP_OK;
+    });
+}
+
+// nsnp_pileup_forward_logits2 / nsnp_pileup_eval_windows2 at precision 2.  cls NULL: logits only (site_loss, pred, counters unused)
+int nsnp_pileup_eval_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
+                            uint8_t* pred, int64_t* counters, float* logits, hipStream_t s)
+{
+    if (!ctx->pwb3.loaded || !ctx->pw.loaded || !ctx->pw.indel_loaded) return NSNP_ENOWEIGHTS;
+    const PileupWeightsB3& pw = ctx->pwb3;
+    return forward_bf16x3_t(ctx, x, center_idx, N, s, [&](int64_t base, int64_t n) {
+        hipLaunchKernelGGL(k_pileup_head_eval_b3, dim3((unsigned)NSNP_CDIV(n, 16 * HB3_WAVES)), dim3(64 * HB3_WAVES), HB3_EVAL_LDS_BYTES, s,
+                           ctx->ws_h1c, n, (const __bf16*)pw.proj_w, pw.proj_b, (const __bf16*)pw.dense_w, pw.dense_b,
+                           (const __bf16*)pw.head6_w, pw.head6_b, cls ? cls + base * 4 : nullptr, cls ? site_loss + base * 4 : nullptr,
+                           cls ? pred + base * 4 : nullptr, reinterpret_cast<unsigned long long*>(counters),
+                           logits ? logits + base * NSNP_LABEL_WIDTH : nullptr);
+    });
 }

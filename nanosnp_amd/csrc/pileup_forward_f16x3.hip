@@ -13,11 +13,13 @@
 //   K1r  k_pileup_l0_rs   layer 0, weights in VGPRs, h exchanged through LDS            default
 //   K23r k_pileup_l1_rs   layer 1 projection + recurrence, weights in VGPRs           default
 //   K4   k_pileup_head_h  output_proj, dense + tanh, heads, softmax                   default
+//   K4e  k_pileup_head_eval_h  K4 up to the head product, then all 90 head rows as logits, loss / argmax / counts   scoring (eval_windows2)
 //   K1   k_pileup_l0_h    layer 0 with LDS weight images, h in registers (the accumulator layout of tile i - lane = site +
 //                         16*q holds unit 4*i+q - is packed straight into the next step's B fragments)   l0_register_stationary 0
 //   K23  k_pileup_l1f_h   fused layer 1 with LDS images + a streamed ring             l1_register_stationary 0
 //   K2 / K3               unfused layer-1 projection and recurrence                    fused_l1 0
 #include "nsnp_common.hpp"
+#include "nsnp_eval_tail.hpp"
 #include <type_traits>
 
 #ifndef NSNP_F16_PIN
@@ -1145,6 +1147,99 @@ __global__ __launch_bounds__(64 * HEAD_WAVES) void k_pileup_head_h(
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// K4e: scoring heads.  k_pileup_head_h up to its last product (restated: the same H1c, splits, staged images, K order and MFMA
+// chains), then the head product over the six tiles of the 90-row image instead of two.  The image is 96 KB and the stage 64 KB, so it
+// comes in two pieces (tiles 0..3, tiles 4..5); every accumulator runs kb = 0..7 with the three products of wave_gemm_h<2, 8, .., 2>, so
+// tiles 0 and 1 hold the bits k_pileup_head_h takes its softmax from.  The 90 logits of a wave's 16 sites then meet in LDS (the stage,
+// free behind a barrier: 51.5 KB) and the tail is k_pileup_head_eval's (nsnp_eval_tail.hpp).
+// LDS: the 64 KB stage + 10.5 KB of 32-bit confusion counters that leave once per workgroup.
+// ---------------------------------------------------------------------------------------------
+constexpr int HEAD_EVAL_LDS_BYTES = HEAD_STAGE_H8 * 16 + nsnp_eval::COUNTERS * 4;
+static_assert(HEAD_WAVES * nsnp_eval::Z_WAVE * 4 <= HEAD_STAGE_H8 * 16, "the logit exchange fits the stage");
+
+__global__ __launch_bounds__(64 * HEAD_WAVES) void k_pileup_head_eval_h(
+    const _Float16* __restrict__ H1c, int64_t N,
+    const _Float16* __restrict__ proj_w, const float* __restrict__ proj_b,
+    const _Float16* __restrict__ dense_w, const float* __restrict__ dense_b,
+    const _Float16* __restrict__ head6_w, const float* __restrict__ head6_b,
+    const uint8_t* __restrict__ cls, float* __restrict__ site_loss, uint8_t* __restrict__ pred,
+    unsigned long long* __restrict__ counters, float* __restrict__ logits)
+{
+    extern __shared__ h8 lds_he[];
+    h8* const wst = lds_he;
+    unsigned int* const cnt = reinterpret_cast<unsigned int*>(lds_he + HEAD_STAGE_H8);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t site0 = ((int64_t)blockIdx.x * HEAD_WAVES + wave) * 16;
+    const int64_t site = site0 + (lane & 15);
+    const int64_t sc = site < N ? site : N - 1;
+    for (int i = tid; i < nsnp_eval::COUNTERS; i += 64 * HEAD_WAVES) cnt[i] = 0;       // (first read behind the barriers below)
+    const int q = lane >> 4;
+    // ---- k_pileup_head_h to the letter up to the head product ----
+    auto stage = [&](const _Float16* src, int n_h8) {
+        __syncthreads();                                   // everyone is done with the previous image
+        copy_to_lds_h(wst, src, n_h8, tid, 64 * HEAD_WAVES);
+        __syncthreads();
+    };
+    const h8* __restrict__ hin = reinterpret_cast<const h8*>(H1c + (sc * 2 * 4 + q) * 32);
+    h8 bh[4], bl[4];
+#pragma unroll
+    for (int dp = 0; dp < 2; ++dp)
+#pragma unroll
+        for (int half = 0; half < 2; ++half) { bh[dp * 2 + half] = hin[dp * 16 + half]; bl[dp * 2 + half] = hin[dp * 16 + 2 + half]; }
+    // output_proj 128 -> 128
+    f32x4 ap[8];
+    {
+        const f32x4* pb = reinterpret_cast<const f32x4*>(proj_b);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ap[i] = pb[i * 64 + lane];
+        stage(proj_w, 8 * 4 * 2 * 64);
+        wave_gemm_h<8, 4, 0, 4, 0, 4>(wst, lane, bh, bl, ap);
+    }
+    // dense 128 -> 256 + tanh: K position (kb, q, j) <-> proj feature 16*(2kb + (j>>2)) + 4q + (j&3)
+    h8 dh[4], dl[4];
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { _Float16 hi, lo; split1(ap[2 * kb + (j >> 2)][j & 3], hi, lo); dh[kb][j] = hi; dl[kb][j] = lo; }
+    f32x4 ad[16];
+    {
+        const f32x4* db = reinterpret_cast<const f32x4*>(dense_b);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) ad[i] = db[i * 64 + lane];
+        stage(dense_w, 8 * 4 * 2 * 64);
+        wave_gemm_h<8, 4, 0, 4, 0, 4>(wst, lane, dh, dl, ad);
+        stage(dense_w + (size_t)8 * 4 * 2 * 64 * 8, 8 * 4 * 2 * 64);
+        wave_gemm_h<8, 4, 0, 4, 0, 4>(wst, lane, dh, dl, ad + 8);
+    }
+    h8 eh[8], el[8];
+#pragma unroll
+    for (int kb = 0; kb < 8; ++kb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { _Float16 hi, lo; split1(tanh_f(ad[2 * kb + (j >> 2)][j & 3]), hi, lo); eh[kb][j] = hi; el[kb][j] = lo; }
+    f32x4 ah[6];
+    {
+        const f32x4* hb = reinterpret_cast<const f32x4*>(head6_b);     // [tile][lane], the accumulator image of the fp32 family
+#pragma unroll
+        for (int t = 0; t < 6; ++t) ah[t] = hb[t * 64 + lane];
+        constexpr int PAIR_H8 = 2 * 8 * 2 * 64;                        // two tiles: the whole image of k_pileup_head_h
+        stage(head6_w, 2 * PAIR_H8);
+        wave_gemm_h<2, 8, 0, 8, 0, 2>(wst, lane, eh, el, ah);
+        wave_gemm_h<2, 8, 0, 8, 2, 2>(wst, lane, eh, el, ah + 2);
+        stage(head6_w + (size_t)2 * PAIR_H8 * 8, PAIR_H8);
+        wave_gemm_h<2, 8, 0, 8, 0, 2>(wst, lane, eh, el, ah + 4);
+    }
+    __syncthreads();                                       // everyone is done with the weights: the stage becomes the logit exchange
+    float* const zw = reinterpret_cast<float*>(wst) + wave * nsnp_eval::Z_WAVE;
+    nsnp_eval::put_logits(zw, lane, ah);
+    __syncthreads();
+    nsnp_eval::wave_tail(zw, lane, site0, N, cls, site_loss, pred, cnt, logits);
+    if (cls) {
+        __syncthreads();
+        nsnp_eval::flush_counters(cnt, counters, tid, 64 * HEAD_WAVES);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1274,6 +1369,34 @@ int nsnp_pileup_pack_weights_f16(nsnp_ctx* ctx, const float* const* w)
     return NSNP_OK;
 }
 
+// nsnp_pileup_load_indel_heads, fp16 hi/lo image of all 90 head rows.  Rows 0..23 (tile 0, and the lanes of tile 1 whose row is below 24)
+// are read back from the two-tile image nsnp_pileup_pack_weights_f16 uploaded - the very bits k_pileup_head_h multiplies; rows 24..89 are
+// split from the indel tensors w = {indel1 W, b, indel2 W, b} like every other weight, rows 90..95 are 0.  The biases are pw.head6_b.
+int nsnp_pileup_pack_indel_heads_f16(nsnp_ctx* ctx, const float* const* w)
+{
+    PileupWeightsF16& pw = ctx->pw16;
+    if (!pw.loaded) return NSNP_ENOWEIGHTS;
+    constexpr size_t n_tile = (size_t)8 * 2 * 64 * 8;       // fp16 per tile
+    std::vector<_Float16> img(6 * n_tile), old_w(2 * n_tile);
+    NSNP_HIP(ctx, hipDeviceSynchronize());
+    NSNP_HIP(ctx, hipMemcpy(old_w.data(), pw.head_w, old_w.size() * sizeof(_Float16), hipMemcpyDeviceToHost));
+    auto acc_feat = [](int kb, int q, int j) { return 16 * (2 * kb + (j >> 2)) + 4 * q + (j & 3); };
+    pack_h(img.data(), 6, 8, [&](int row, int kb, int q, int j) {
+        const int f = acc_feat(kb, q, j);
+        if (row >= 24 && row < 57) return w[0][(row - 24) * 256 + f];
+        if (row >= 57 && row < 90) return w[2][(row - 57) * 256 + f];
+        return 0.f;
+    });
+    for (int tile = 0; tile < 2; ++tile) for (int kp = 0; kp < 8 * 2; ++kp) for (int lane = 0; lane < 64; ++lane)
+        if (16 * tile + (lane & 15) < 24) {
+            const size_t e = (((size_t)tile * 16 + kp) * 64 + lane) * 8;
+            memcpy(&img[e], &old_w[e], 8 * sizeof(_Float16));
+        }
+    if (!pw.head6_w) NSNP_HIP(ctx, hipMalloc(&pw.head6_w, img.size() * sizeof(_Float16)));
+    NSNP_HIP(ctx, hipMemcpy(pw.head6_w, img.data(), img.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    return NSNP_OK;
+}
+
 static int set_lds_attr_f16(nsnp_ctx* ctx)
 {
     if (ctx->attr_set_f16) return NSNP_OK;
@@ -1282,16 +1405,19 @@ static int set_lds_attr_f16(nsnp_ctx* ctx)
     SET(k_pileup_proj1_h, P1H_LDS_BYTES);
     SET(k_pileup_l1_rs<4>, r1_lds_bytes(4)); SET(k_pileup_l1_rs<2>, r1_lds_bytes(2));
     SET(k_pileup_l1f_h<4>, L1F_LDS_BYTES); SET(k_pileup_l1f_h<8>, L1F_LDS_BYTES); SET(k_pileup_l1f_h<12>, L1F_LDS_BYTES);
+    SET(k_pileup_head_eval_h, HEAD_EVAL_LDS_BYTES);
     SET(k_pileup_l1_h<8>, L1H_LDS_BYTES); SET(k_pileup_l1_h<4>, L1H_LDS_BYTES); SET(k_pileup_l1_h<2>, L1H_LDS_BYTES); SET(k_pileup_l1_h<1>, L1H_LDS_BYTES);
 #undef SET
     ctx->attr_set_f16 = true;
     return NSNP_OK;
 }
 
-int nsnp_pileup_forward_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx,
-                              int64_t N, float* gt, float* zy, hipStream_t s)
+// The chunk loop and layers 0 and 1 of an f16x3 pass under the context's options, ending in the caller's heads launch heads(base, n) on
+// the chunk's H1c: the ONE place these launches are made - the probability forward and the scoring forward below differ in their heads
+// kernel only.  (H0 and H1c have the bytes per site of the fp32 layout, so any reserved workspace serves.)
+template <typename HeadsFn>
+static int forward_f16x3_t(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, hipStream_t s, HeadsFn heads)
 {
-    if (!ctx->pw16.loaded || !ctx->pw.loaded) return NSNP_ENOWEIGHTS;
     if (N == 0) return NSNP_OK;
     int rc = set_lds_attr_f16(ctx);
     if (rc) return rc;
@@ -1378,10 +1504,39 @@ int nsnp_pileup_forward_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* ce
         }
         }
         ScopedKernelTimer tm_head(ctx, NSNP_K_HEAD, s);
-        hipLaunchKernelGGL(k_pileup_head_h, dim3((unsigned)NSNP_CDIV(n, 16 * HEAD_WAVES)), dim3(64 * HEAD_WAVES), 0, s, H1c, n,
-                           (const _Float16*)pw.proj_w, p32.proj_b, (const _Float16*)pw.dense_w, p32.dense_b,
-                           (const _Float16*)pw.head_w, p32.head_b, gt + base * NSNP_GT_CLASSES, zy + base * NSNP_ZY_CLASSES);
+        heads(base, n);
     }
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
+}
+
+int nsnp_pileup_forward_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx,
+                              int64_t N, float* gt, float* zy, hipStream_t s)
+{
+    if (!ctx->pw16.loaded || !ctx->pw.loaded) return NSNP_ENOWEIGHTS;
+    const PileupWeightsF16& pw = ctx->pw16;
+    const PileupWeightsDev& p32 = ctx->pw;
+    return forward_f16x3_t(ctx, x, center_idx, N, s, [&](int64_t base, int64_t n) {
+        hipLaunchKernelGGL(k_pileup_head_h, dim3((unsigned)NSNP_CDIV(n, 16 * HEAD_WAVES)), dim3(64 * HEAD_WAVES), 0, s,
+                           reinterpret_cast<const _Float16*>(ctx->ws_h1c), n,
+                           (const _Float16*)pw.proj_w, p32.proj_b, (const _Float16*)pw.dense_w, p32.dense_b,
+                           (const _Float16*)pw.head_w, p32.head_b, gt + base * NSNP_GT_CLASSES, zy + base * NSNP_ZY_CLASSES);
+    });
+}
+
+// nsnp_pileup_forward_logits2 / nsnp_pileup_eval_windows2 at precision 1.  cls NULL: logits only (site_loss, pred, counters unused)
+int nsnp_pileup_eval_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
+                           uint8_t* pred, int64_t* counters, float* logits, hipStream_t s)
+{
+    if (!ctx->pw16.loaded || !ctx->pw.loaded || !ctx->pw.indel_loaded) return NSNP_ENOWEIGHTS;
+    const PileupWeightsF16& pw = ctx->pw16;
+    const PileupWeightsDev& p32 = ctx->pw;
+    return forward_f16x3_t(ctx, x, center_idx, N, s, [&](int64_t base, int64_t n) {
+        hipLaunchKernelGGL(k_pileup_head_eval_h, dim3((unsigned)NSNP_CDIV(n, 16 * HEAD_WAVES)), dim3(64 * HEAD_WAVES), HEAD_EVAL_LDS_BYTES, s,
+                           reinterpret_cast<const _Float16*>(ctx->ws_h1c), n,
+                           (const _Float16*)pw.proj_w, p32.proj_b, (const _Float16*)pw.dense_w, p32.dense_b,
+                           (const _Float16*)pw.head6_w, p32.head6_b, cls ? cls + base * 4 : nullptr, cls ? site_loss + base * 4 : nullptr,
+                           cls ? pred + base * 4 : nullptr, reinterpret_cast<unsigned long long*>(counters),
+                           logits ? logits + base * NSNP_LABEL_WIDTH : nullptr);
+    });
 }

@@ -4,7 +4,8 @@
 ``TrainDataset(for_evaluate=True)`` does (dataset.py:98-104), runs the forward with all four heads and the label-smoothed loss
 (model.py:97-112, optim.py:137-144) and returns what eval() accumulates: the loss, the accuracies and the confusion matrices of genotype
 and zygosity - plus those of the two indel heads, which eval() computes logits for and then ignores.  Training is nanosnp_amd.train's:
-this is inference with labels attached.  fp32 only.
+this is inference with labels attached.  The arithmetic is the ``precision`` argument (fp32, f16x3 or bf16x3); ``compare_precisions``
+scores the same files under several and reports what differs.
 
 ``evaluate_haplotype_bins`` is the HaplotypeModel's counterpart, ``eval()`` of HaplotypeModel/evaluate_dev.py:16-86 over labelled haplotype
 site files (sitefile.write_haplotype_train_bin), under every ``hap_precision``.
@@ -61,7 +62,8 @@ class _PassSet:
             self.free = None
 
 
-def evaluate_train_bins(model, validating_paths, batch_size=1000, variants_only=True, pass_sites=65536, keep_sites=False, stats=None):
+def evaluate_train_bins(model, validating_paths, batch_size=1000, variants_only=True, pass_sites=65536, keep_sites=False, stats=None,
+                        precision=None):
     """``eval(epoch, config, model, validating_paths, batch_size, ...)`` of PileupModel/train.py:93-150 over ``.td.bin`` files -> dict
 
         sites                 kept sites (variants_only: rows whose zygosity class is > 0, dataset.py:99; else every row)
@@ -73,7 +75,10 @@ def evaluate_train_bins(model, validating_paths, batch_size=1000, variants_only=
         gt_confusion [21,21], zy_confusion [3,3], id1_confusion [33,33], id2_confusion [33,33]     int64 [target][predicted] (train.py:101-102)
         malformed_labels      rows (of all rows read) that are not one-hot in some family
         files                 with keep_sites: per file {path, rows int64 [k], cls uint8 [k,4], pred uint8 [k,4], site_loss fp32 [k,4]}
+        precision             with a `precision` argument: that argument, 0 / 1 / 2 or "context"
 
+    precision: None scores in fp32 through the fp32-only entry (refused while the context's pileup_precision is 1 or 2); 0 (fp32), 1 (f16x3),
+    2 (bf16x3) or "context" (the context's pileup_precision) name the arithmetic of the forward - an argument, no option is set.
     validating_paths: a list of paths or a directory (its ``*.bin`` files in os.listdir order).  Batches restart with every file, as the
     reference's DataLoader per file does.  Host loop: a file is read in passes of `pass_sites` rows through three pinned sets, sent on the
     package's copy stream (int16 windows widened on the device) with the label rows beside them; the label pass of pass k + 1
@@ -92,6 +97,7 @@ def evaluate_train_bins(model, validating_paths, batch_size=1000, variants_only=
     if B < 1:
         raise ValueError("batch_size >= 1")
     ctx = model.ctx
+    prec = ctx.eval_precision_arg(precision)              # (refused here, before anything is read; the calls below take the keyword itself)
     dev = torch.device("cuda", ctx.device)
     st = stats if stats is not None else {}
     for k in ("passes", "rows", "bytes_h2d"):
@@ -157,7 +163,7 @@ def evaluate_train_bins(model, validating_paths, batch_size=1000, variants_only=
             o, r = fill[fi], per_file[fi]
             if kept:
                 ctx.pileup_eval_windows(ds.x32[:m * 33], ds.centers[:kept], ds.cls, counters, n=kept, site_loss=r["loss"][o:o + kept],
-                                        pred=r["pred"][o:o + kept])
+                                        pred=r["pred"][o:o + kept], precision=precision)
                 r["cls"][o:o + kept].copy_(ds.cls[:kept])
                 r["rows"][o:o + kept].copy_(torch.div(ds.centers[:kept] - 16, 33, rounding_mode="floor") + a)
             fill[fi] = o + kept
@@ -197,7 +203,42 @@ def evaluate_train_bins(model, validating_paths, batch_size=1000, variants_only=
     res["zy_accuracy"] = float(np.trace(res["zy_confusion"])) / div
     if keep_sites:
         res["files"] = out_files
+    if prec is not None:
+        res["precision"] = "context" if prec == -1 else prec
     return res
+
+
+def precision_differences(base, other):
+    """two evaluate_train_bins(keep_sites=True) results over the same files -> what differs between them:
+        differing_sites       kept sites whose genotype, zygosity or either indel prediction differs
+        max_site_loss_diff    the largest |site_loss| difference over sites and heads
+        avg_loss_diff         other's avg_loss minus base's"""
+    if len(base["files"]) != len(other["files"]):
+        raise ValueError("results over different files")
+    differing, worst = 0, 0.0
+    for fb, fo in zip(base["files"], other["files"]):
+        if fb["path"] != fo["path"] or not np.array_equal(fb["rows"], fo["rows"]):
+            raise ValueError(f"results over different sites ({fb['path']}, {fo['path']})")
+        differing += int((fb["pred"] != fo["pred"]).any(axis=1).sum())
+        if fb["site_loss"].size:
+            worst = max(worst, float(np.abs(fo["site_loss"].astype(np.float64) - fb["site_loss"].astype(np.float64)).max()))
+    return {"differing_sites": differing, "max_site_loss_diff": worst, "avg_loss_diff": float(other["avg_loss"] - base["avg_loss"])}
+
+
+def compare_precisions(model, validating_paths, precisions=(0, 2, 1), **kw):
+    """what the arithmetic does to a checkpoint's calls on labelled data: one ``evaluate_train_bins(keep_sites=True, precision=p)`` per entry
+    of `precisions` (each named once) -> {p: {"result": that result, **precision_differences(result of precisions[0], result)}}, in the order
+    given.  Nothing is set on the context and so nothing is restored: the arithmetic is an argument."""
+    kw = dict(kw, keep_sites=True)
+    out, base = {}, None
+    names = [None if p is None else _lib.Context.eval_precision_arg(p) for p in precisions]
+    if None in names or len(set(names)) != len(names):
+        raise ValueError('precisions: 0, 1, 2 or "context", each once')
+    for p in precisions:
+        res = evaluate_train_bins(model, validating_paths, precision=p, **kw)
+        base = res if base is None else base
+        out[res["precision"]] = dict(result=res, **precision_differences(base, res))
+    return out
 
 
 # ---- HaplotypeModel: HaplotypeModel/evaluate_dev.py:16-86 ----------------------------------------------------------------------------

@@ -133,11 +133,12 @@ class LSTMNetwork:
         x = inputs if inputs.dtype == torch.int32 else inputs.to(torch.int32)
         return self.ctx.pileup_forward(x.contiguous(), stream=stream)
 
-    def forward(self, inputs, gt_target, zy_target, id1_target, id2_target, stream=None):
+    def forward(self, inputs, gt_target, zy_target, id1_target, id2_target, stream=None, precision=None):
         """``LSTMNetwork.forward`` (PileupModel/model.py:97-112), argument for argument: inputs as predict takes them, the four targets
         integer cuda tensors [N] -> (loss, gt_logits [N,21], zy_logits [N,3], id1_logits [N,33], id2_logits [N,33]).  loss = mean(gt) +
         mean(zy) of the label-smoothed losses (optim.py:137-144) as an fp32 scalar tensor: the indel losses are not in it, as
-        model.py:109-110.  fp32 only; needs the indel heads (a forward_layer state dict that had them, or load_indel_heads)."""
+        model.py:109-110.  Needs the indel heads (a forward_layer state dict that had them, or load_indel_heads).  precision: None is
+        fp32 only (refused while pileup_precision is 1 or 2); 0 / 1 / 2 / "context" name the arithmetic (Context.eval_precision_arg)."""
         import torch
         if not self._loaded or not self._indel_loaded:
             raise _lib.NanoSNPError("weights not loaded" if not self._loaded else "indel heads not loaded (the forward_layer state dict had none)")
@@ -151,7 +152,8 @@ class LSTMNetwork:
         if tuple(cls.shape) != (n, 4):
             raise ValueError(f"expected four targets of {n} classes")
         counters = torch.zeros(self.ctx.EVAL_COUNTERS, dtype=torch.int64, device=x.device)
-        site_loss, _, z = self.ctx.pileup_eval_windows(x, None, cls.contiguous(), counters, want_logits=True, stream=stream)
+        site_loss, _, z = self.ctx.pileup_eval_windows(x, None, cls.contiguous(), counters, want_logits=True, stream=stream,
+                                                         precision=precision)
         if n == 0:
             loss = torch.full((), float("nan"), dtype=torch.float32, device=x.device)          # (torch.mean of nothing)
         else:

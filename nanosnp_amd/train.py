@@ -763,12 +763,14 @@ def train_haplotype_bins(trainer, bin_paths, reference, optimizer=None, batch_si
 
 def fit(trainer, training_paths, validating_paths=None, epochs=1, optimizer=None, batch_size=2000, dropout=0.3, max_grad_norm=20.0,
         decay_ratio=0.98, begin_to_adjust_lr=10, seed=2022, save_prefix=None, start_epoch=0, pass_sites=65536, eval_batch_size=None,
-        use_balance=False):
+        use_balance=False, validate_precision=None):
     """The epoch loop of PileupModel/train.py:222-247 -> one dict per epoch: train_train_bins' result plus {epoch, lr (the rate the epoch
     ran with), global_step, eval (evaluate_train_bins' result or None), checkpoint (its path or None)}.
 
     Per epoch in range(start_epoch, epochs): optimizer.epoch(); train_train_bins with seed + epoch, so that every epoch has an order and masks
     of its own; evaluate.evaluate_train_bins on validating_paths when given (through trainer.to_model, one upload per epoch);
+    validate_precision is its `precision` (None: fp32; 0 / 1 / 2 / "context": the arithmetic the checkpoint will be deployed in - training
+    itself stays fp32 and does not depend on it);
     trainer.save_checkpoint(<save_prefix>.epoch<e>.chkpt, optimizer=optimizer) when save_prefix is given; optimizer.decay_lr(decay_ratio)
     once epoch >= begin_to_adjust_lr.  use_balance: train_train_bins' balance_dataset upsampling (config.training.use_balance); the lists
     differ from epoch to epoch through seed + epoch.  optimizer None: DeviceOptimizer(trainer, kind="LookaheadAdam", lr=1e-4), the shipped configuration.
@@ -787,7 +789,8 @@ def fit(trainer, training_paths, validating_paths=None, epochs=1, optimizer=None
         res.update(epoch=epoch, lr=lr, global_step=optimizer.global_step if fused else None, eval=None, checkpoint=None)
         if validating_paths is not None:
             model = trainer.to_model(model)
-            res["eval"] = evaluate.evaluate_train_bins(model, validating_paths, batch_size=int(eval_batch_size or batch_size), pass_sites=pass_sites)
+            res["eval"] = evaluate.evaluate_train_bins(model, validating_paths, batch_size=int(eval_batch_size or batch_size), pass_sites=pass_sites,
+                                                       precision=validate_precision)
         if save_prefix is not None:
             res["checkpoint"] = f"{save_prefix}.epoch{epoch}.chkpt"
             trainer.save_checkpoint(res["checkpoint"], epoch=epoch, optimizer=optimizer if fused else None)
