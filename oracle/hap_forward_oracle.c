@@ -41,9 +41,10 @@ static void encoder(const dirw_t* dw, const float* proj_w, const float* proj_b,
     free(cur); free(nxt);
 }
 
-void orc_hap_forward(const float* const* w, const float* xp, const float* xh, int64_t N,
-                     int F, int H, int n_layers, int Lp, int Lh, int n_gt, int n_zy,
-                     float* gt_prob, float* zy_prob, int nthreads)
+/* softmax != 0: the two heads' probabilities (predict); 0: what the heads give in front of the softmax (forward, model_dev.py:120-131) */
+static void hap_forward_(const float* const* w, const float* xp, const float* xh, int64_t N,
+                         int F, int H, int n_layers, int Lp, int Lh, int n_gt, int n_zy,
+                         float* gt_prob, float* zy_prob, int nthreads, int softmax)
 {
     const int per_enc = n_layers * 2 * 4 + 2;
     dirw_t* dw[2];
@@ -71,12 +72,28 @@ void orc_hap_forward(const float* const* w, const float* xp, const float* xh, in
         for (int j = 0; j < H; ++j) inner[j] = tanhf(inner[j]);
         orc_linear(inner, H, fw[2], fw[3], n_gt, gt_prob + n * n_gt);
         orc_linear(inner, H, fw[4], fw[5], n_zy, zy_prob + n * n_zy);
-        orc_softmax(gt_prob + n * n_gt, n_gt);
-        orc_softmax(zy_prob + n * n_zy, n_zy);
+        if (softmax) {
+            orc_softmax(gt_prob + n * n_gt, n_gt);
+            orc_softmax(zy_prob + n * n_zy, n_zy);
+        }
         free(cat); free(inner);
     }
     for (int e = 0; e < 2; ++e) {
         for (int i = 0; i < n_layers * 2; ++i) { free(dw[e][i].wih_t); free(dw[e][i].whh_t); }
         free(dw[e]);
     }
+}
+
+void orc_hap_forward(const float* const* w, const float* xp, const float* xh, int64_t N,
+                     int F, int H, int n_layers, int Lp, int Lh, int n_gt, int n_zy,
+                     float* gt_prob, float* zy_prob, int nthreads)
+{
+    hap_forward_(w, xp, xh, N, F, H, n_layers, Lp, Lh, n_gt, n_zy, gt_prob, zy_prob, nthreads, 1);
+}
+
+void orc_hap_forward_logits(const float* const* w, const float* xp, const float* xh, int64_t N,
+                            int F, int H, int n_layers, int Lp, int Lh, int n_gt, int n_zy,
+                            float* gt_logit, float* zy_logit, int nthreads)
+{
+    hap_forward_(w, xp, xh, N, F, H, n_layers, Lp, Lh, n_gt, n_zy, gt_logit, zy_logit, nthreads, 0);
 }

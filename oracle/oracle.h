@@ -149,6 +149,10 @@ void orc_hap_forward(const float* const* w, const float* xp /*[N,105,33]*/,
                      const float* xh /*[N,105,11]*/, int64_t N, int F, int H, int n_layers,
                      int Lp, int Lh, int n_gt, int n_zy,
                      float* gt_prob, float* zy_prob, int nthreads);
+/* the same forward in front of the two softmaxes: the logits nsnp_hap_eval scores */
+void orc_hap_forward_logits(const float* const* w, const float* xp, const float* xh, int64_t N, int F, int H,
+                            int n_layers, int Lp, int Lh, int n_gt, int n_zy,
+                            float* gt_logit, float* zy_logit, int nthreads);
 
 /* ---- legacy CatModel forward (C1/C2): HaplotypeModel/model.py:332-358, crnn.py:84-190 -- */
 /* weights: the 132 floating-point tensors of CatModel.state_dict() in order (see cat_forward_oracle.c);

@@ -53,6 +53,8 @@ def _load():
     lib.orc_hap_arrange.argtypes = [p, p, p, p, C.c_int, C.c_int, C.c_int, C.c_int, p, p, p, p, p]
     lib.orc_hap_forward.restype = None
     lib.orc_hap_forward.argtypes = [p, p, p, C.c_int64] + [C.c_int] * 7 + [p, p, C.c_int]
+    lib.orc_hap_forward_logits.restype = None
+    lib.orc_hap_forward_logits.argtypes = [p, p, p, C.c_int64] + [C.c_int] * 7 + [p, p, C.c_int]
     lib.orc_cat_forward.restype = None
     lib.orc_cat_forward.argtypes = [p, p, p, C.c_int64, p, C.c_int]
     lib.orc_cat_groups.restype = None
@@ -177,6 +179,18 @@ def hap_forward(weights, xp, xh, H=256, n_layers=3, n_gt=10, n_zy=3, nthreads=1)
     gt = np.empty((N, n_gt), np.float32); zy = np.empty((N, n_zy), np.float32)
     lib().orc_hap_forward(arr, _p(xp), _p(xh), N, F, H, n_layers, Lp, Lh, n_gt, n_zy,
                           _p(gt), _p(zy), nthreads)
+    return gt, zy
+
+
+def hap_forward_logits(weights, xp, xh, H=256, n_layers=3, n_gt=10, n_zy=3, nthreads=1):
+    """hap_forward in front of the two softmaxes: (genotype logits [N,n_gt], zygosity logits [N,n_zy])"""
+    ws, arr = _wptrs(weights)
+    xp = _c(xp, np.float32); xh = _c(xh, np.float32)
+    N, F, Lp = xp.shape
+    Lh = xh.shape[2]
+    gt = np.empty((N, n_gt), np.float32); zy = np.empty((N, n_zy), np.float32)
+    lib().orc_hap_forward_logits(arr, _p(xp), _p(xh), N, F, H, n_layers, Lp, Lh, n_gt, n_zy,
+                                 _p(gt), _p(zy), nthreads)
     return gt, zy
 
 
