@@ -820,6 +820,40 @@ int nsnp_cat_load_weights(nsnp_ctx* ctx, const float* const* host_tensors, int n
  * (g2 / g3 are ignored by CatModel.predict: model.py:332-358) -> gt_prob device fp32 [N,10] (softmax). */
 int nsnp_cat_forward(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N, float* gt_prob, void* stream);
 
+/* Test tap: runs the launches of nsnp_cat_forward (same context options, same kernels, same workspace) up to and including those of
+ * `stage`, then ONE un-tiling launch that writes that stage's image to `out` as plain fp32 in natural order - only the used channels
+ * and features, the unit_of_pos storage order of an LSTM's h undone, an f16x3 (hi, lo) pair decoded as hi + lo - and returns.
+ * One pass only: 0 < N <= 4096.  out_floats must be the stage's size exactly.  NSNP_EINVAL otherwise, nothing launched.
+ *   stage                         image                                   out
+ *   NSNP_CAT_ST_PIXELS            torch.cat((g0, g1), 1) as channels      [N,10,40,11]
+ *   NSNP_CAT_ST_BLOCK_Y + 2 i     ResBlock i: relu(bn1(conv1 x))          [N,C,H,W], C = 32,64,128,128,256,256, H = 40,20,10,10,3,3
+ *   NSNP_CAT_ST_BLOCK_OUT + 2 i   ResBlock i: relu(bn2(conv2 y) + sc(x))  the same
+ *   NSNP_CAT_ST_POOL + k          the max-pool after block 0, 1, 3        [N,32,20,11], [N,64,10,11], [N,128,3,11]
+ *   NSNP_CAT_ST_SEQ0              the last pool = the LSTM's input        [11,N,256]
+ *   NSNP_CAT_ST_PCT_FEATURES      calculate_percentage                    [11,N,20]
+ *   NSNP_CAT_ST_PCT_H + l         h of percentage layer l = 0, 1          [11,N,512] = [h_fwd ; h_bwd]
+ *                    + 2          the third layer runs six steps per direction: row s = [h_fwd(column s) ; h_bwd(column 10 - s)]   [6,N,512]
+ *   NSNP_CAT_ST_PCT_LINEAR        haplotype_percentage.out_layer at column 5   [N,256]
+ *   NSNP_CAT_ST_RNN0_H            h of haplotype_base.rnn.0               [11,N,512]
+ *   NSNP_CAT_ST_RNN0_EMB          its embedding                           [11,N,256]
+ *   NSNP_CAT_ST_RNN1_H            h of haplotype_base.rnn.1, six steps as above (row 5 = column 5)   [6,N,512]
+ *   NSNP_CAT_ST_CAT               the 512-vector in front of out_layer    [N,512]
+ * Later stages overwrite the buffers of earlier ones, which is why a stage is read by a run that stops there. */
+#define NSNP_CAT_ST_PIXELS        0
+#define NSNP_CAT_ST_BLOCK_Y       1
+#define NSNP_CAT_ST_BLOCK_OUT     2
+#define NSNP_CAT_ST_POOL          13
+#define NSNP_CAT_ST_SEQ0          16
+#define NSNP_CAT_ST_PCT_FEATURES  17
+#define NSNP_CAT_ST_PCT_H         18
+#define NSNP_CAT_ST_PCT_LINEAR    21
+#define NSNP_CAT_ST_RNN0_H        22
+#define NSNP_CAT_ST_RNN0_EMB      23
+#define NSNP_CAT_ST_RNN1_H        24
+#define NSNP_CAT_ST_CAT           25
+#define NSNP_CAT_N_STAGES         26
+int nsnp_cat_forward_stage(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N, int stage, float* out, int64_t out_floats, void* stream);
+
 /* Builds one group tensor [N,40,length,5] fp32 from the per-tag matrices the HDF5 bins hold
  * (dataset.py:862-915): read / base-quality / mapping-quality [N,depth,length] int32 per tag; the first 20
  * rows of tag 1 then of tag 2; planes (base, baseq, mapq, mask = base != -2, phase = 1 | 2).

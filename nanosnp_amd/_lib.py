@@ -113,6 +113,7 @@ _SIGNATURES = {
     "nsnp_hap_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_cat_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
     "nsnp_cat_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nsnp_cat_forward_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "nsnp_comm_unique_id": (C.c_int, [C.c_void_p]),
     "nsnp_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "nsnp_comm_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
@@ -1455,6 +1456,39 @@ class Context:
         check(self.lib.nsnp_cat_forward(self.handle, _dptr(g0), _dptr(g1), n, _dptr(gt), _stream_ptr(stream)),
               self.handle, "nsnp_cat_forward")
         return gt
+
+    @staticmethod
+    def cat_stage_shape(stage, n):
+        """name or number of a stage of nsnp_cat_forward_stage (include/nanosnp.h) -> (number, shape of its image for n sites)"""
+        ch, hs = (32, 64, 128, 128, 256, 256), (40, 20, 10, 10, 3, 3)
+        table = {"pixels": (0, (n, 10, 40, 11)), "seq0": (16, (11, n, 256)), "pct_features": (17, (11, n, 20)),
+                 "pct_h0": (18, (11, n, 512)), "pct_h1": (19, (11, n, 512)), "pct_h2": (20, (6, n, 512)), "pct_linear": (21, (n, 256)),
+                 "rnn0_h": (22, (11, n, 512)), "rnn0_emb": (23, (11, n, 256)), "rnn1_h": (24, (6, n, 512)), "cat": (25, (n, 512)),
+                 "pool0": (13, (n, 32, 20, 11)), "pool1": (14, (n, 64, 10, 11)), "pool3": (15, (n, 128, 3, 11))}
+        for i in range(6):
+            table[f"block{i}_y"] = (1 + 2 * i, (n, ch[i], hs[i], 11)); table[f"block{i}_out"] = (2 + 2 * i, (n, ch[i], hs[i], 11))
+        if isinstance(stage, str):
+            if stage not in table:
+                raise NanoSNPError(f"cat_forward_stage: unknown stage {stage!r}")
+            return table[stage]
+        for num, shape in table.values():
+            if num == int(stage):
+                return num, shape
+        raise NanoSNPError(f"cat_forward_stage: unknown stage {stage!r}")
+
+    def cat_forward_stage(self, g0, g1, stage, stream=None):
+        """Test tap: the launches of cat_forward up to and including `stage` (a name of cat_stage_shape or its number), then that
+        stage's image as a plain float32 tensor in natural order.  One pass: 0 < N <= 4096."""
+        import torch
+        if tuple(g0.shape[1:]) != (40, 11, 5) or g0.shape != g1.shape:
+            raise NanoSNPError(f"cat_forward_stage: g0/g1 must be [N,40,11,5], got {tuple(g0.shape)} / {tuple(g1.shape)}")
+        g0 = g0.contiguous().float(); g1 = g1.contiguous().float()
+        n = g0.shape[0]
+        num, shape = self.cat_stage_shape(stage, n)
+        out = torch.empty(shape, dtype=torch.float32, device=g0.device)
+        check(self.lib.nsnp_cat_forward_stage(self.handle, _dptr(g0), _dptr(g1), n, num, _dptr(out), out.numel(), _stream_ptr(stream)),
+              self.handle, "nsnp_cat_forward_stage")
+        return out
 
     def cat_groups(self, tag1, tag2, stream=None):
         """tag1 / tag2: (read, baseq, mapq) int32 cuda [N,depth,L] per tag -> [N,40,L,5] float32 (dataset.py:862-915)."""

@@ -181,6 +181,44 @@ __global__ __launch_bounds__(256) void k_cat_head(const float* __restrict__ cat,
     }
 }
 
+// Test tap (nsnp_cat_forward_stage): one image of the forward, un-tiled to plain fp32 in natural order.
+//   UNTILE_MAP : pixel image [pixel tile][cc][128][16], pixel (n, y, x)                  -> [d0 = N][F = C][d2 = H * W]
+//   UNTILE_ROWS: [t][tile][chunks][128][16] in natural feature order (t_stride, tile_stride floats) -> [d0 = T][d2 = N][F]
+//   UNTILE_H   : LSTM h [t][site tile][dir][16][128][16], unit_of_pos order inside a chunk -> [d0][d2 = N][512] = [h_fwd ; h_bwd];
+//                six > 0: row s holds the forward h of column s and the backward h of column six - s (the steps that ran)
+enum { UNTILE_MAP = 0, UNTILE_ROWS = 1, UNTILE_H = 2 };
+struct UntileArgs { const float* img; float* out; int kind, cc, F, six; long long d0, d2, t_stride, tile_stride; };
+
+template <bool F16>
+__global__ void k_cat_untile(const UntileArgs a)
+{
+    const int64_t total = (int64_t)a.d0 * a.F * a.d2;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const float* row; int c;
+        if (a.kind == UNTILE_MAP) {
+            const int64_t n = e / ((int64_t)a.F * a.d2);
+            const int64_t r = e - n * a.F * a.d2;
+            const int f = (int)(r / a.d2);
+            const int64_t pix = n * a.d2 + (r - (int64_t)f * a.d2);
+            row = a.img + ((size_t)(pix >> 7) * a.cc + (f >> 4)) * TILE_F + (size_t)(pix & 127) * BK; c = f & 15;
+        } else {
+            const int f = (int)(e % a.F);
+            const int64_t r = e / a.F;
+            const int64_t n = r % a.d2, t = r / a.d2;
+            if (a.kind == UNTILE_ROWS) {
+                row = a.img + (size_t)t * a.t_stride + (size_t)(n >> 7) * a.tile_stride + (size_t)(f >> 4) * TILE_F + (size_t)(n & 127) * BK;
+                c = f & 15;
+            } else {
+                const int d = f >> 8, u = f & 255, u16 = u & 15;
+                const int64_t ts = a.six > 0 && d ? a.six - t : t;
+                row = a.img + (size_t)ts * a.t_stride + (size_t)(n >> 7) * a.tile_stride + ((size_t)d * 16 + (u >> 4)) * TILE_F + (size_t)(n & 127) * BK;
+                c = (u16 & 1) * 8 + 4 * (u16 >> 3) + ((u16 >> 1) & 3);                      // unit_of_pos(c) == u16
+            }
+        }
+        a.out[e] = get_elem<F16>(row, c);
+    }
+}
+
 // dataset.PredictDataset.__getitem__ (dataset.py:862-915): per-tag read / base-quality / mapping-quality matrices
 // [N][D][L] int32 -> one group tensor [N][40][L][5] float: rows 0..19 tag 1, 20..39 tag 2 (first 20 rows of each),
 // planes (base, baseq, mapq, mask = base != -2, phase = 1 | 2)
@@ -781,10 +819,12 @@ int grid_for(int64_t total) { int64_t b = NSNP_CDIV(total, (int64_t)256); return
 
 namespace {
 
+struct CatTap { int stage; float* out; };       // nsnp_cat_forward_stage: stop after this stage's launches, its image un-tiled to out
+
 template <int AR>            // 0 exact fp32, 1 f16x3 (activation images hold fp16 pairs), 2 bf16x3 (activations stay fp32, weights as three bf16 planes)
-int cat_forward_impl(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N, float* gt_prob, void* stream)
+int cat_forward_impl(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N, float* gt_prob, void* stream, const CatTap* tap = nullptr)
 {
-    if (!ctx || N < 0 || (N > 0 && (!g0 || !g1 || !gt_prob))) return NSNP_EINVAL;
+    if (!ctx || N < 0 || (N > 0 && (!g0 || !g1 || (!gt_prob && !tap)))) return NSNP_EINVAL;
     if (!ctx->cw) return NSNP_ENOWEIGHTS;
     if (N == 0) return NSNP_OK;
     const CatWeightsDev& cw = *ctx->cw;
@@ -804,6 +844,14 @@ int cat_forward_impl(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N,
     float* hb[2] = {seq[1] + seq_f, seq[1] + seq_f + hb_f};
     float* cst = hb[1] + hb_f;
     float* cat = cst + c_f;
+    // the test tap (null on the path of nsnp_cat_forward): true when `stage` is the one asked for - its image has gone to tap->out
+    auto tapped = [&](int stage, int kind, const float* img, int64_t d0, int F, int64_t d2, int cc, int64_t t_stride, int64_t tile_stride, int six) {
+        if (!tap || tap->stage != stage) return false;
+        const UntileArgs u{img, tap->out, kind, cc, F, six, d0, d2, t_stride, tile_stride};
+        hipLaunchKernelGGL(k_cat_untile<F16>, dim3(grid_for(d0 * F * d2)), dim3(256), 0, s, u);
+        return true;
+    };
+#define CAT_TAP(...) do { if (tapped(__VA_ARGS__)) { NSNP_HIP(ctx, hipGetLastError()); return NSNP_OK; } } while (0)
 
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t n = N - n0 < chunk ? N - n0 : chunk;
@@ -815,16 +863,22 @@ int cat_forward_impl(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N,
 
         // ---- percentage branch: 3-layer BiLSTM on [11][n][20], Linear at column 5 -> cat chunks 0..15 ----
         hipLaunchKernelGGL(k_cat_percentage<F16>, dim3(grid_for((int64_t)CAT_L * n_tiles * TS * 4)), dim3(256), 0, s, a0, a1, n, n_tiles, xp);
+        CAT_TAP(NSNP_CAT_ST_PCT_FEATURES, UNTILE_ROWS, xp, CAT_L, 20, n, 0, (int64_t)n_tiles * 2 * TILE_F, 2 * TILE_F, 0);
         run_bilstm<AR>(ctx, s, cw.pct[0], wm, xp, 2, hb[0], cst, n_tiles, CAT_L, CAT_L);
+        CAT_TAP(NSNP_CAT_ST_PCT_H, UNTILE_H, hb[0], CAT_L, 2 * CAT_NH, n, 0, (int64_t)step_h, 32 * TILE_F, 0);
         run_bilstm<AR>(ctx, s, cw.pct[1], wm, hb[0], 32, hb[1], cst, n_tiles, CAT_L, CAT_L);
+        CAT_TAP(NSNP_CAT_ST_PCT_H + 1, UNTILE_H, hb[1], CAT_L, 2 * CAT_NH, n, 0, (int64_t)step_h, 32 * TILE_F, 0);
         run_bilstm<AR>(ctx, s, cw.pct[2], wm, hb[1], 32, hb[0], cst, n_tiles, CAT_L, CAT_CENTER + 1);
+        CAT_TAP(NSNP_CAT_ST_PCT_H + 2, UNTILE_H, hb[0], CAT_CENTER + 1, 2 * CAT_NH, n, 0, (int64_t)step_h, 32 * TILE_F, CAT_L - 1);
         run_linear_h<AR>(ctx, s, wm(cw.pct_w), cw.pct_b, hb[0] + (size_t)CAT_CENTER * step_h, n_tiles, cat, 32 * TILE_F);
+        CAT_TAP(NSNP_CAT_ST_PCT_LINEAR, UNTILE_ROWS, cat, 1, CAT_NH, n, 0, 0, 32 * TILE_F, 0);
 
         // ---- ResCRNN branch ----
         int Hc = CAT_ROWS;
         int64_t n_pix = n * Hc * CAT_L;
         int64_t n_ptiles = NSNP_CDIV(n_pix, (int64_t)TS);
         hipLaunchKernelGGL(k_cat_pack_pixels<F16>, dim3(grid_for(n_ptiles * TS * 16)), dim3(256), 0, s, a0, a1, n_pix, n_ptiles * TS, map[0]);
+        CAT_TAP(NSNP_CAT_ST_PIXELS, UNTILE_MAP, map[0], n, CAT_CH[0], Hc * CAT_L, 1, 0, 0, 0);
         int cur = 0;                                              // map[cur] holds the block input
         ScopedKernelTimer tm_conv(ctx, NSNP_K_CATCONV, s);         // the 12 conv GEMM launches (+ 4 pools) of this pass
         for (int i = 0; i < 6; ++i) {
@@ -843,6 +897,7 @@ int cat_forward_impl(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N,
                 const unsigned gx = pix2 ? (unsigned)((n_ptiles + 1) / 2) : (unsigned)n_ptiles;
                 if (pix2) hipLaunchKernelGGL((k_cat_conv<AR == 2 ? 0 : AR, 2>), dim3(gx, rt, 1), dim3(256), 0, s, c);   // (pix2 implies AR != 2)
                 else hipLaunchKernelGGL((k_cat_conv<AR, 1>), dim3(gx, rt, 1), dim3(256), 0, s, c);
+                CAT_TAP(NSNP_CAT_ST_BLOCK_Y + 2 * i, UNTILE_MAP, Y, n, b.cout, Hc * CAT_L, b.cc_out, 0, 0, 0);
                 c.w = wm(b.w2); c.bias = b.b2; c.x = Y; c.sc = X; c.cc_in = b.cc_out; c.cc_sc = b.cc_in; c.nk_img = 9 * b.cc_out + b.cc_in;
                 c.out = O;
                 if (pix2) hipLaunchKernelGGL((k_cat_conv<AR == 2 ? 0 : AR, 2>), dim3(gx, rt, 1), dim3(256), 0, s, c);   // (pix2 implies AR != 2)
@@ -855,6 +910,7 @@ int cat_forward_impl(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N,
             a.w = wm(b.w1); a.bias = b.b1; a.in0 = X; a.nk0 = 9 * b.cc_in; a.cc0_shift = shift_of(b.cc_in);
             a.nk1 = 0; a.nk_img = a.nk0; a.out = Y; a.out_tile_stride = b.cc_out * TILE_F;
             launch_hap_gemm<MODE_LINEAR_RELU, AR, true>(ctx, s, L, (int)((unsigned)n_ptiles), rt, 1);
+            CAT_TAP(NSNP_CAT_ST_BLOCK_Y + 2 * i, UNTILE_MAP, Y, n, b.cout, Hc * CAT_L, b.cc_out, 0, 0, 0);
             // out = relu(bn2(conv2(y)) + shortcut(x))
             a.w = wm(b.w2); a.bias = b.b2; a.in0 = Y; a.nk0 = 9 * b.cc_out; a.cc0_shift = shift_of(b.cc_out);
             a.in1 = X; a.nk1 = b.cc_in; a.in1_tile_stride = b.cc_in * TILE_F; a.nk_img = a.nk0 + a.nk1;
@@ -862,6 +918,7 @@ int cat_forward_impl(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N,
             launch_hap_gemm<MODE_LINEAR_RELU, AR, true>(ctx, s, L, (int)((unsigned)n_ptiles), rt, 1);
             }
             cur = (cur + 2) % 3;
+            CAT_TAP(NSNP_CAT_ST_BLOCK_OUT + 2 * i, UNTILE_MAP, map[cur], n, b.cout, Hc * CAT_L, b.cc_out, 0, 0, 0);
             if (CAT_POOL[i]) {
                 const int kh = CAT_POOL[i], Ho = (Hc - kh) / kh + 1;
                 const bool last = i == 5;
@@ -871,23 +928,64 @@ int cat_forward_impl(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N,
                                    map[cur], b.cc_out, n, Hc, CAT_L, kh, Ho, last ? 1 : 0, n_tiles, dst);
                 Hc = Ho; n_pix = n * Hc * CAT_L; n_ptiles = n_out_tiles;
                 cur = (cur + 1) % 3;
+                if (last) CAT_TAP(NSNP_CAT_ST_SEQ0, UNTILE_ROWS, seq[0], CAT_L, CAT_NH, n, 0, (int64_t)n_tiles * 16 * TILE_F, 16 * TILE_F, 0);
+                else CAT_TAP(NSNP_CAT_ST_POOL + (i == 3 ? 2 : i), UNTILE_MAP, map[cur], n, b.cout, Hc * CAT_L, b.cc_out, 0, 0, 0);
             }
         }
         tm_conv.stop();
         if (Hc != 1) return NSNP_ESHAPE;                          // crnn.py:183 asserts the same
         // BidirectionalLSTM 0: all 11 columns, embedding on every column (crnn.py:12-20)
         run_bilstm<AR>(ctx, s, cw.rnn[0], wm, seq[0], 16, hb[0], cst, n_tiles, CAT_L, CAT_L);
+        CAT_TAP(NSNP_CAT_ST_RNN0_H, UNTILE_H, hb[0], CAT_L, 2 * CAT_NH, n, 0, (int64_t)step_h, 32 * TILE_F, 0);
         run_linear_h<AR>(ctx, s, wm(cw.emb_w[0]), cw.emb_b[0], hb[0], CAT_L * n_tiles, seq[1], 16 * TILE_F);
+        CAT_TAP(NSNP_CAT_ST_RNN0_EMB, UNTILE_ROWS, seq[1], CAT_L, CAT_NH, n, 0, (int64_t)n_tiles * 16 * TILE_F, 16 * TILE_F, 0);
         // BidirectionalLSTM 1: only column 5 is used downstream
         run_bilstm<AR>(ctx, s, cw.rnn[1], wm, seq[1], 16, hb[1], cst, n_tiles, CAT_L, CAT_CENTER + 1);
+        CAT_TAP(NSNP_CAT_ST_RNN1_H, UNTILE_H, hb[1], CAT_CENTER + 1, 2 * CAT_NH, n, 0, (int64_t)step_h, 32 * TILE_F, CAT_L - 1);
         run_linear_h<AR>(ctx, s, wm(cw.emb_w[1]), cw.emb_b[1], hb[1] + (size_t)CAT_CENTER * step_h, n_tiles, cat + 16 * TILE_F, 32 * TILE_F);
+        CAT_TAP(NSNP_CAT_ST_CAT, UNTILE_ROWS, cat, 1, 2 * CAT_NH, n, 0, 0, 32 * TILE_F, 0);
         hipLaunchKernelGGL(k_cat_head<F16>, dim3((unsigned)NSNP_CDIV(n, 4)), dim3(256), 0, s, cat, n, cw.out_w, cw.out_b, gt_prob + n0 * CAT_CLASSES);
     }
     NSNP_HIP(ctx, hipGetLastError());
     return NSNP_OK;
+#undef CAT_TAP
+}
+
+// floats of a stage's un-tiled image for N sites (include/nanosnp.h), 0 for an unknown stage
+int64_t cat_stage_floats(int stage, int64_t N)
+{
+    if (stage == NSNP_CAT_ST_PIXELS) return N * CAT_CH[0] * CAT_ROWS * CAT_L;
+    if (stage >= NSNP_CAT_ST_BLOCK_Y && stage < NSNP_CAT_ST_POOL) {
+        const int i = (stage - NSNP_CAT_ST_BLOCK_Y) / 2;
+        int H = CAT_ROWS;
+        for (int k = 0; k < i; ++k) if (CAT_POOL[k]) H /= CAT_POOL[k];
+        return N * CAT_CH[i + 1] * H * CAT_L;
+    }
+    if (stage == NSNP_CAT_ST_POOL) return N * 32 * 20 * CAT_L;
+    if (stage == NSNP_CAT_ST_POOL + 1) return N * 64 * 10 * CAT_L;
+    if (stage == NSNP_CAT_ST_POOL + 2) return N * 128 * 3 * CAT_L;
+    if (stage == NSNP_CAT_ST_SEQ0 || stage == NSNP_CAT_ST_RNN0_EMB) return CAT_L * N * CAT_NH;
+    if (stage == NSNP_CAT_ST_PCT_FEATURES) return CAT_L * N * 20;
+    if (stage == NSNP_CAT_ST_PCT_H || stage == NSNP_CAT_ST_PCT_H + 1 || stage == NSNP_CAT_ST_RNN0_H) return CAT_L * N * 2 * CAT_NH;
+    if (stage == NSNP_CAT_ST_PCT_H + 2 || stage == NSNP_CAT_ST_RNN1_H) return (CAT_CENTER + 1) * N * 2 * CAT_NH;
+    if (stage == NSNP_CAT_ST_PCT_LINEAR) return N * CAT_NH;
+    if (stage == NSNP_CAT_ST_CAT) return N * 2 * CAT_NH;
+    return 0;
 }
 
 }  // namespace
+
+extern "C" int nsnp_cat_forward_stage(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N, int stage, float* out, int64_t out_floats,
+                                      void* stream)
+{
+    if (!ctx || !g0 || !g1 || !out || N <= 0 || N > CAT_PASS) return NSNP_EINVAL;
+    const int64_t want = cat_stage_floats(stage, N);
+    if (want == 0 || out_floats != want) return NSNP_EINVAL;
+    const CatTap tap{stage, out};
+    if (ctx->cat_precision == 1) return cat_forward_impl<1>(ctx, g0, g1, N, nullptr, stream, &tap);
+    if (ctx->cat_precision == 2) return cat_forward_impl<2>(ctx, g0, g1, N, nullptr, stream, &tap);
+    return cat_forward_impl<0>(ctx, g0, g1, N, nullptr, stream, &tap);
+}
 
 extern "C" int nsnp_cat_forward(nsnp_ctx* ctx, const float* g0, const float* g1, int64_t N, float* gt_prob, void* stream)
 {
