@@ -711,6 +711,47 @@ int nsnp_hap_arrange_reads2(nsnp_ctx* ctx, const int32_t* seq, const int32_t* bq
                             const int32_t* hap, const int32_t* n_reads, int64_t N, int R, int L, int D_out, int tie_order,
                             int32_t* oseq, int32_t* obq, int32_t* omq, int32_t* ohap, int32_t* depth, void* stream);
 
+/* ---- stage-4 read matrices from decoded alignment records (create_pileup_haplotype.py:39-60,89-134) -------------------------------------
+ * The records of ONE contig as a struct of arrays on the device, in file (coordinate) order:
+ *   start     int64 [R]      1-based leftmost reference position, non-decreasing
+ *   mapq      uint8 [R]      hp  int32 [R]  the HP tag, -1 = no tag (counts as 3)
+ *   cigar     uint32 [sum n_ops]  BAM's encoding len << 4 | op, ops 0..8 = MIDNSHP=X;  cigar_off int64 [R+1]
+ *   seq, qual uint8 [sum query_len]  one ASCII base / one quality per base, soft clips included;  seq_off int64 [R+1]
+ * cols int64 [P]: the wanted 1-based columns, strictly increasing.  A record covers [a, b], b = a + (sum of M, D, N, =, X lengths) - 1.
+ * The callers validate the arrays on the host (readmatrix.AlignmentRecords); the kernels never read a base outside a record's own
+ * seq range whatever the CIGAR says (such a cell counts as a foreign base).
+ *
+ * scratch: nsnp_hap_read_scratch_bytes(R, P) bytes of device memory, 16-byte aligned, the caller's (0 = R or P out of range).
+ *
+ * nsnp_hap_read_depths: depth[c] int32 [P] = records with a <= cols[c] <= b (deletions and reference skips count, as pysam's
+ * PileupColumn.n does); rows (optional, device int64 [1]) = records that cover at least one column.  Integer atomics into a
+ * difference array and a prefix sum: no result depends on an order.
+ *
+ * nsnp_hap_read_matrices: the four int32 matrices [rows, P] (caller-allocated with cap_rows rows; every cell of the first `rows` rows
+ * is written once, zeros included).  Rows are the covering records in record order; row_record[row] int64 = the record.  Cells:
+ *   op holding the column   seq                    hap   baseq          mapq
+ *   M, =, X                 A,C,G,T -> 1..4 (any case)  tag   qual[query offset]  mapq
+ *   D                       -1                     tag   0              mapq
+ *   N, or outside [a, b]    0                      0     0              0
+ * meta int64 [4] (device) = { rows, status, record, column }: status NSNP_READS_OK, or the first offence in the order the host
+ * function meets them (by column, then record): NSNP_READS_TOO_DEEP a column deeper than max_coverage (record -1),
+ * NSNP_READS_BAD_HP a covering record whose tag is outside 1..3, NSNP_READS_FOREIGN_BASE a base outside ACGTacgt at a wanted
+ * column.  column is the 1-based position.  With a status other than OK the matrices are complete but mean nothing to the
+ * reference, which returns nothing then.  The call never aborts on data.
+ * The call waits for the stream once, to compare the row count with cap_rows before the outputs are written: NSNP_EINVAL when
+ * cap_rows is below it (nothing written), and for null or negative arguments.  NSNP_ESHAPE for R or P above 2^31 - 16. */
+#define NSNP_READS_OK 0
+#define NSNP_READS_TOO_DEEP 1
+#define NSNP_READS_BAD_HP 2
+#define NSNP_READS_FOREIGN_BASE 3
+size_t nsnp_hap_read_scratch_bytes(int64_t R, int64_t P);
+int nsnp_hap_read_depths(nsnp_ctx* ctx, const int64_t* start, const uint32_t* cigar, const int64_t* cigar_off, int64_t R,
+                         const int64_t* cols, int64_t P, int32_t* depth, int64_t* rows, void* scratch, void* stream);
+int nsnp_hap_read_matrices(nsnp_ctx* ctx, const int64_t* start, const uint8_t* mapq, const int32_t* hp, const uint32_t* cigar,
+                           const int64_t* cigar_off, const uint8_t* seq, const uint8_t* qual, const int64_t* seq_off, int64_t R,
+                           const int64_t* cols, int64_t P, int64_t max_coverage, int32_t* oseq, int32_t* ohap, int32_t* obq,
+                           int32_t* omq, int64_t cap_rows, int64_t* row_record, int64_t* meta, void* scratch, void* stream);
+
 /* host_tensors: the 58 fp32 tensors of model_dev.LSTMNetwork.state_dict() in order
  * (pileup_encoder 26, haplotype_encoder 26, forward_layer 6), HOST pointers.
  * hidden must be a multiple of 64; F = 105 input features; 3 layers as ont_haplotype.yaml. */

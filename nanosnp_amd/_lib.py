@@ -101,6 +101,10 @@ _SIGNATURES = {
     "nsnp_hap_features_i8": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nsnp_hap_arrange_reads": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "nsnp_hap_arrange_reads2": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "nsnp_hap_read_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "nsnp_hap_read_depths": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    "nsnp_hap_read_matrices": (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4 +
+                               [C.c_int64] + [C.c_void_p] * 4),
     "nsnp_hap_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int] + [C.c_int] * 5),
     "nsnp_hap_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
@@ -1426,6 +1430,56 @@ class Context:
                                                _dptr(depth), _stream_ptr(stream)),
               self.handle, "nsnp_hap_arrange_reads2")
         return outs[0], outs[1], outs[2], outs[3], depth
+
+    # ---- stage-4 read matrices from alignment records (hap_reads.hip) ----
+    def _read_scratch(self, rec, cols):
+        import torch
+        need = self.lib.nsnp_hap_read_scratch_bytes(rec.n, cols.shape[0])
+        if need == 0:
+            raise NanoSNPError("hap_read_*: more than 2^31 - 16 records or columns")
+        return torch.empty(need, dtype=torch.uint8, device=cols.device)
+
+    @staticmethod
+    def _read_cols(rec, cols):
+        import torch
+        if cols.dtype != torch.int64 or cols.dim() != 1 or not cols.is_contiguous() or cols.device != rec.start.device:
+            raise NanoSNPError("hap_read_*: cols must be a contiguous int64 vector on the records' device")
+
+    def hap_read_depths(self, rec, cols, want_rows=False, stream=None):
+        """rec: readmatrix.AlignmentRecords.to_device(); cols: int64 cuda [P], strictly increasing 1-based positions.
+        -> depth int32 [P] (records whose reference span holds the column), with want_rows also int64 [1]: the records that cover
+        at least one column."""
+        import torch
+        self._read_cols(rec, cols)
+        P = cols.shape[0]
+        depth = torch.empty(P, dtype=torch.int32, device=cols.device)
+        rows = torch.empty(1, dtype=torch.int64, device=cols.device) if want_rows else None
+        scratch = self._read_scratch(rec, cols)
+        check(self.lib.nsnp_hap_read_depths(self.handle, _dptr(rec.start), _dptr(rec.cigar), _dptr(rec.cigar_off), rec.n, _dptr(cols), P,
+                                            _dptr(depth), _dptr(rows), _dptr(scratch), _stream_ptr(stream)),
+              self.handle, "nsnp_hap_read_depths")
+        scratch.record_stream(stream if stream is not None else torch.cuda.current_stream())
+        return (depth, rows) if want_rows else depth
+
+    def hap_read_matrices(self, rec, cols, max_coverage, cap_rows, stream=None):
+        """-> (seq, hap, baseq, mapq) int32 cuda [cap_rows, P], row_record int64 [cap_rows], meta int64 [4] = {rows, status, record,
+        column} (include/nanosnp.h).  cap_rows must be at least the row count (hap_read_depths(..., want_rows=True)); the first
+        `rows` rows are written, each cell once."""
+        import torch
+        self._read_cols(rec, cols)
+        P, cap = cols.shape[0], int(cap_rows)
+        dev = cols.device
+        outs = [torch.empty((cap, P), dtype=torch.int32, device=dev) for _ in range(4)]
+        row_record = torch.empty(cap, dtype=torch.int64, device=dev)
+        meta = torch.empty(4, dtype=torch.int64, device=dev)
+        scratch = self._read_scratch(rec, cols)
+        check(self.lib.nsnp_hap_read_matrices(self.handle, _dptr(rec.start), _dptr(rec.mapq), _dptr(rec.hp), _dptr(rec.cigar),
+                                              _dptr(rec.cigar_off), _dptr(rec.seq), _dptr(rec.qual), _dptr(rec.seq_off), rec.n, _dptr(cols),
+                                              P, min(max(int(max_coverage), -1), 2 ** 31 - 1), *[_dptr(o) for o in outs], cap, _dptr(row_record), _dptr(meta),
+                                              _dptr(scratch), _stream_ptr(stream)),
+              self.handle, "nsnp_hap_read_matrices")
+        scratch.record_stream(stream if stream is not None else torch.cuda.current_stream())
+        return outs[0], outs[1], outs[2], outs[3], row_record, meta
 
     def hap_load_weights(self, tensors, n_features=105, hidden=256, n_layers=3, n_gt=10, n_zy=3):
         import numpy as np
