@@ -539,6 +539,23 @@ int nsnp_pileup_forward_logits2(nsnp_ctx* ctx, const int32_t* counts, const int6
 int nsnp_pileup_eval_windows2(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, const uint8_t* cls, int64_t N, int precision,
                               float* site_loss, uint8_t* pred, int64_t* counters, float* logits, void* stream);
 
+/* Test tap: runs the layer launches of the PileupModel forward in arithmetic `precision` (0, 1, 2, or -1 for the context's
+ * pileup_precision) under the context's current options - the same kernels on the same workspace as nsnp_pileup_forward /
+ * nsnp_pileup_forward_logits2 - then, in place of the heads launch, ONE un-tiling launch that writes the named image to `out` as plain
+ * fp32 in natural order, and returns.  counts / center_idx as nsnp_pileup_forward_logits (center_idx NULL: counts is [N,33,18]).
+ *   stage                 image                                                         out
+ *   NSNP_PILEUP_ST_H0     h of layer 0 at all 33 positions, feature = dir * 64 + unit   [N,33,128]  (torch's bidirectional output)
+ *   NSNP_PILEUP_ST_H1C    h of layer 1 at position 16, [h_fwd ; h_bwd]                  [N,128]
+ * The storage of each arithmetic is decoded: the unit order of the fp32 rows ([site][t][dir][q][16], unit 4 i + q at entry i of row q),
+ * an f16x3 (hi, lo) pair as hi + lo, the three bf16 planes of the bf16x3 H0 (16-site groups) as their exact sum.  Only sites < N are
+ * written.  One pass: 0 < N <= the reserved chunk (nsnp_ctx_reserve, 32768 by default); out_floats must be the image's size exactly.
+ * NSNP_EINVAL otherwise (also for a NULL pointer, an unknown stage or precision), nothing launched. */
+#define NSNP_PILEUP_ST_H0   0
+#define NSNP_PILEUP_ST_H1C  1
+#define NSNP_PILEUP_N_STAGES 2
+int nsnp_pileup_forward_stage(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, int64_t N, int precision, int stage,
+                              float* out, int64_t out_floats, void* stream);
+
 /* batch_sum[b,h] = the float64 sum of site_loss[n,h] over the rows n of batch b (rows b * batch_size ..), double [ceil(N / batch_size), 4]: one
  * workgroup per batch, a fixed tree - the same bits whatever the launch and the run.  The caller divides by the batch's size. */
 int nsnp_pileup_batch_loss(nsnp_ctx* ctx, const float* site_loss, int64_t N, int64_t batch_size, double* batch_sum, void* stream);

@@ -117,6 +117,7 @@ _SIGNATURES = {
     "nsnp_hap_batch_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nsnp_cat_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
     "nsnp_cat_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nsnp_pileup_forward_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "nsnp_cat_forward_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "nsnp_comm_unique_id": (C.c_int, [C.c_void_p]),
     "nsnp_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
@@ -1136,6 +1137,34 @@ class Context:
             check(self.lib.nsnp_pileup_forward_logits2(self.handle, _dptr(counts), _dptr(center_idx), n, prec, _dptr(logits), _stream_ptr(stream)),
                   self.handle, "nsnp_pileup_forward_logits2")
         return logits
+
+    @staticmethod
+    def pileup_stage_shape(stage, n):
+        """name or number of a stage of nsnp_pileup_forward_stage (include/nanosnp.h) -> (number, shape of its image for n sites)"""
+        table = {"h0": (0, (n, 33, 128)), "h1c": (1, (n, 128))}
+        if isinstance(stage, str):
+            if stage not in table:
+                raise NanoSNPError(f"pileup_forward_stage: unknown stage {stage!r}")
+            return table[stage]
+        for num, shape in table.values():
+            if not isinstance(stage, bool) and num == operator.index(stage):
+                return num, shape
+        raise NanoSNPError(f"pileup_forward_stage: unknown stage {stage!r}")
+
+    def pileup_forward_stage(self, counts, stage, center_idx=None, precision="context", stream=None):
+        """Test tap: the layer launches of the forward in arithmetic `precision` (0, 1, 2 or "context") under the current options, then
+        the image `stage` ("h0": layer 0's h [N,33,128], "h1c": layer 1's h at position 16 [N,128]; or its number) as a plain float32
+        tensor, feature = dir * 64 + unit.  One pass: 0 < N <= the reserved chunk."""
+        import torch
+        n = self._eval_inputs(counts, center_idx, "forward_stage")
+        prec = self.eval_precision_arg(precision)
+        if prec is None:
+            raise NanoSNPError('pileup_forward_stage: precision 0, 1, 2 or "context"')
+        num, shape = self.pileup_stage_shape(stage, n)
+        out = torch.empty(shape, dtype=torch.float32, device=counts.device)
+        check(self.lib.nsnp_pileup_forward_stage(self.handle, _dptr(counts), _dptr(center_idx), n, prec, num, _dptr(out), out.numel(),
+                                                 _stream_ptr(stream)), self.handle, "nsnp_pileup_forward_stage")
+        return out
 
     def pileup_eval_windows(self, counts, center_idx, cls, counters, n=None, site_loss=None, pred=None, want_logits=False, stream=None,
                             precision=None):

@@ -396,6 +396,20 @@ extern "C" int nsnp_pileup_eval_windows2(nsnp_ctx* ctx, const int32_t* counts, c
     return pileup_eval_any(ctx, precision, counts, center_idx, cls, N, site_loss, pred, counters, logits, (hipStream_t)stream);
 }
 
+// the test tap of include/nanosnp.h: the argument rules here, the pass of each arithmetic beside its forward (nsnp_pileup_stage_*)
+extern "C" int nsnp_pileup_forward_stage(nsnp_ctx* ctx, const int32_t* counts, const int64_t* center_idx, int64_t N, int precision, int stage,
+                                         float* out, int64_t out_floats, void* stream)
+{
+    if (!ctx || !counts || !out || precision < -1 || precision > 2) return NSNP_EINVAL;
+    if (stage != NSNP_PILEUP_ST_H0 && stage != NSNP_PILEUP_ST_H1C) return NSNP_EINVAL;
+    if (N <= 0 || N > ctx->chunk_sites || out_floats != N * (stage == NSNP_PILEUP_ST_H0 ? PW : 1) * 128) return NSNP_EINVAL;
+    if (precision == -1) precision = ctx->precision;
+    const PileupTap tap{stage, out};
+    if (precision == 1) return nsnp_pileup_stage_f16x3(ctx, counts, center_idx, N, tap, (hipStream_t)stream);
+    if (precision == 2) return nsnp_pileup_stage_bf16x3(ctx, counts, center_idx, N, tap, (hipStream_t)stream);
+    return nsnp_pileup_stage_impl(ctx, counts, center_idx, N, tap, (hipStream_t)stream);
+}
+
 // one dispatch for the three arithmetic modes; post / post_written as in nsnp_common.hpp
 static int pileup_forward_any(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, float* gt, float* zy,
                               const PostOut* post, bool* post_written, hipStream_t s)

@@ -223,6 +223,14 @@ int nsnp_pileup_eval_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* cente
                            uint8_t* pred, int64_t* counters, float* logits, hipStream_t s);
 int nsnp_pileup_eval_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
                             uint8_t* pred, int64_t* counters, float* logits, hipStream_t s);
+// nsnp_pileup_forward_stage (test tap): one pass of N <= chunk_sites sites through the layer launches of the forward of each arithmetic
+// under the context's options, nsnp_pileup_untile_launch (pileup_forward.hip: ws_h0 or ws_h1c of that arithmetic -> tap.out as plain
+// fp32) standing where the heads launch stands
+struct PileupTap { int stage; float* out; };
+void nsnp_pileup_untile_launch(nsnp_ctx* ctx, int precision, const PileupTap& tap, int64_t n, hipStream_t s);
+int nsnp_pileup_stage_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, const PileupTap& tap, hipStream_t s);
+int nsnp_pileup_stage_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, const PileupTap& tap, hipStream_t s);
+int nsnp_pileup_stage_bf16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, const PileupTap& tap, hipStream_t s);
 // the fp16 hi/lo and bf16 three-plane images of all 90 head rows, behind nsnp_pileup_pack_indel_heads (w: the four indel tensors)
 int nsnp_pileup_pack_indel_heads_f16(nsnp_ctx* ctx, const float* const* w);
 int nsnp_pileup_pack_indel_heads_bf16(nsnp_ctx* ctx, const float* const* w);

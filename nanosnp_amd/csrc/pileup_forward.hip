@@ -2316,6 +2316,64 @@ int nsnp_pileup_eval_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center
     return NSNP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Test tap (nsnp_pileup_forward_stage): H0 or H1c of one pass, un-tiled to plain fp32 in natural order - [N,33,128] / [N,128],
+// feature dir * 64 + unit.  One thread per output float; the storage of the three arithmetics:
+//   fp32     [site][t][dir][q][16]: entry i of row q is unit 4 i + q (K1 above, h_store_col)
+//   f16x3    [site][t][dir][q][16 hi | 16 lo] fp16, the same unit order (pileup_forward_f16x3.hip), decoded as hi + lo
+//   bf16x3   H0: [16-site group][t][dir][plane 3][K block 2][quarter 4][site 16][8] bf16, unit 16 w + 4 u + q' at K position
+//            16 w + 4 q' + u (pileup_forward_bf16x3.hip), decoded as the sum of the planes (exact: they are split3 of an fp32);
+//            H1c: fp32 [site][dir][unit]
+// steps = 33 (H0) or 1 (H1c).  Reads sites < N only, which every layer kernel has written.
+// ---------------------------------------------------------------------------------------------
+__global__ void k_pileup_untile(const void* __restrict__ img, int prec, int steps, int64_t n_out, float* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_out) return;
+    const int f = (int)(i & 127), dir = f >> 6, unit = f & 63;
+    const int64_t row = i >> 7, site = row / steps;
+    const int t = (int)(row - site * steps);
+    const int q = unit & 3, m = unit >> 2;
+    float v;
+    if (prec == 0) {
+        v = static_cast<const float*>(img)[((site * steps + t) * 2 + dir) * 64 + q * 16 + m];
+    } else if (prec == 1) {
+        const _Float16* p = static_cast<const _Float16*>(img) + (((site * steps + t) * 2 + dir) * 4 + q) * 32;
+        v = (float)p[m] + (float)p[16 + m];
+    } else if (steps == 1) {
+        v = static_cast<const float*>(img)[(site * 2 + dir) * 64 + unit];
+    } else {
+        const int pos = 16 * (unit >> 4) + 4 * q + (m & 3);                       // K position of the unit in a layer-0 row
+        const __bf16* p = static_cast<const __bf16*>(img) + (((site >> 4) * steps + t) * 2 + dir) * 3072
+                          + (pos >> 5) * 512 + ((pos >> 3) & 3) * 128 + (int)(site & 15) * 8 + (pos & 7);
+        v = (float)((double)(float)p[0] + (double)(float)p[1024] + (double)(float)p[2048]);
+    }
+    out[i] = v;
+}
+
+void nsnp_pileup_untile_launch(nsnp_ctx* ctx, int precision, const PileupTap& tap, int64_t n, hipStream_t s)
+{
+    const bool h0 = tap.stage == NSNP_PILEUP_ST_H0;
+    const int64_t n_out = n * (h0 ? PW : 1) * 128;
+    hipLaunchKernelGGL(k_pileup_untile, dim3((unsigned)NSNP_CDIV(n_out, (int64_t)256)), dim3(256), 0, s,
+                       h0 ? (const void*)ctx->ws_h0 : (const void*)ctx->ws_h1c, precision, h0 ? PW : 1, n_out, tap.out);
+}
+
+// the fp32 pass of nsnp_pileup_forward_stage: the prologue and the layer launches of nsnp_pileup_forward_impl, the un-tiling launch
+// where its heads launch stands
+int nsnp_pileup_stage_impl(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, const PileupTap& tap, hipStream_t s)
+{
+    if (!ctx->pw.loaded) return NSNP_ENOWEIGHTS;
+    int rc = set_lds_attr_once(ctx);
+    if (rc) return rc;
+    if (!ctx->ws_h0) { rc = nsnp_ctx_reserve(ctx, ctx->chunk_sites); if (rc) return rc; }
+    rc = launch_layers(ctx, x, center_idx, N, s);
+    if (rc) return rc;
+    nsnp_pileup_untile_launch(ctx, 0, tap, N, s);
+    NSNP_HIP(ctx, hipGetLastError());
+    return NSNP_OK;
+}
+
 NSNP_DEVCLK_READER(nsnp_devclk_read_pileup)
 
 extern "C" int nsnp_pileup_postprocess(nsnp_ctx* ctx, const float* gt_prob, const float* zy_prob,

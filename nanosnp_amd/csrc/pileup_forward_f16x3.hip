@@ -1524,6 +1524,13 @@ int nsnp_pileup_forward_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* ce
     });
 }
 
+// nsnp_pileup_forward_stage at precision 1 (N <= chunk_sites: one pass): the un-tiling launch stands where the heads launch stands
+int nsnp_pileup_stage_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, int64_t N, const PileupTap& tap, hipStream_t s)
+{
+    if (!ctx->pw16.loaded || !ctx->pw.loaded) return NSNP_ENOWEIGHTS;
+    return forward_f16x3_t(ctx, x, center_idx, N, s, [&](int64_t, int64_t n) { nsnp_pileup_untile_launch(ctx, 1, tap, n, s); });
+}
+
 // nsnp_pileup_forward_logits2 / nsnp_pileup_eval_windows2 at precision 1.  cls NULL: logits only (site_loss, pred, counters unused)
 int nsnp_pileup_eval_f16x3(nsnp_ctx* ctx, const int32_t* x, const int64_t* center_idx, const uint8_t* cls, int64_t N, float* site_loss,
                            uint8_t* pred, int64_t* counters, float* logits, hipStream_t s)
