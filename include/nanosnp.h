@@ -769,6 +769,44 @@ int nsnp_hap_read_matrices(nsnp_ctx* ctx, const int64_t* start, const uint8_t* m
                            const int64_t* cols, int64_t P, int64_t max_coverage, int32_t* oseq, int32_t* ohap, int32_t* obq,
                            int32_t* omq, int64_t cap_rows, int64_t* row_record, int64_t* meta, void* scratch, void* stream);
 
+/* ---- stage-4 site groups from the pileup call rows (select_hetesnp_homosnp.py:82-104,180-230) ------------------------------------------
+ * Which sites go to the HaplotypeModel, decided from the [N,13] float64 call rows (nsnp_pileup_call_rows: column 0 a position or a key,
+ * 1 / 2 the genotype / zygosity argmax, 3 / 4 their maxima) and the reference byte of every row (any case), without the pileup.vcf in
+ * between: what merge.select_groups(..., reference_bug=False) finds in the text the row writer (nsnp_vcf_format_batches, batches of
+ * batch_size rows restarting with every run) makes of the same rows.  A row is WRITTEN when its argmaxes are below 10 / at most 2, both
+ * scores exist and the writer's genotype search does not run off a short batch (nsnp_vcf.c); its genotype text and which score is its QUAL
+ * follow the writer.  It is in the DICTIONARY unless its genotype is 0/0 or 1/1 with QUAL >= quality_threshold, a SUPPORT when its
+ * genotype is 0/1 with QUAL >= support_quality, a CANDIDATE when QUAL < quality_threshold.  A GROUP is a candidate with adjacent_size
+ * supports strictly left and strictly right of it in its own run: 2 adjacent_size + 1 rows in row order.
+ *   run_off  device int64 [n_runs + 1], ascending from 0 to N: the rows of every contig, one run each.  Inside a run column 0 must
+ *            ascend strictly.
+ *   cuts     device float32 [8], merge.group_cuts: the smallest probability whose QUAL reaches quality_threshold, the same for
+ *            support_quality (+inf: none does), the first and the last probability that has a score, 1.0 when -0.0 scores as 0.0 does,
+ *            three zeros.  The kernels compare bit patterns and evaluate no logarithm.
+ *   group_rows int32 / group_keys int64 [cap_groups, 2 adjacent_size + 1] (device): the row index and column 0 of every member, groups in
+ *            candidate order.
+ *   meta     int64 [4] in device or pinned host memory = { groups found, status, first offending row, supports }.  groups found may
+ *            exceed cap_groups: then only the first cap_groups were written.  status NSNP_GROUPS_KEY_ORDER: column 0 of the named row
+ *            is not above the row in front of it in the same run (the groups mean nothing then); otherwise the row is -1.
+ *   scratch  nsnp_pileup_groups_scratch_bytes(N) bytes of device memory, 16-byte aligned, the caller's (0 = N out of range).  Behind the
+ *            call its first N bytes hold the flag byte of every row: NSNP_GROUPS_WRITTEN | _DICT | _CANDIDATE | _SUPPORT | _GROUP (the
+ *            candidate of a group) - which contigs have a dictionary entry at all is read from them.
+ * The coverage channels are not read: the writer skips a row whose depth is not finite, which counts of reads never are.
+ * Asynchronous on `stream`, no host visit.  N == 0 is a no-op that writes meta = 0.  NSNP_EINVAL with nothing launched: N < 0,
+ * adjacent_size outside 1..32, batch_size < 1, n_runs < 0 (or 0 with N > 0), cap_groups < 0, a null pointer with N > 0 (group_rows /
+ * group_keys may be null with cap_groups 0).  NSNP_ESHAPE for N above 2^31 - 16. */
+#define NSNP_GROUPS_OK 0
+#define NSNP_GROUPS_KEY_ORDER 1
+#define NSNP_GROUPS_WRITTEN   1
+#define NSNP_GROUPS_DICT      2
+#define NSNP_GROUPS_CANDIDATE 4
+#define NSNP_GROUPS_SUPPORT   8
+#define NSNP_GROUPS_GROUP     16
+size_t nsnp_pileup_groups_scratch_bytes(int64_t N);
+int nsnp_pileup_select_groups(nsnp_ctx* ctx, const double* rows, const uint8_t* ref_base, int64_t N, const int64_t* run_off, int n_runs,
+                              int64_t batch_size, int adjacent_size, const float* cuts, int32_t* group_rows, int64_t* group_keys,
+                              int64_t cap_groups, int64_t* meta, void* scratch, void* stream);
+
 /* host_tensors: the 58 fp32 tensors of model_dev.LSTMNetwork.state_dict() in order
  * (pileup_encoder 26, haplotype_encoder 26, forward_layer 6), HOST pointers.
  * hidden must be a multiple of 64; F = 105 input features; 3 layers as ont_haplotype.yaml. */

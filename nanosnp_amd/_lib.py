@@ -105,6 +105,9 @@ _SIGNATURES = {
     "nsnp_hap_read_depths": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
     "nsnp_hap_read_matrices": (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4 +
                                [C.c_int64] + [C.c_void_p] * 4),
+    "nsnp_pileup_groups_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "nsnp_pileup_select_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int] +
+                                  [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3),
     "nsnp_hap_load_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int] + [C.c_int] * 5),
     "nsnp_hap_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
@@ -1509,6 +1512,42 @@ class Context:
               self.handle, "nsnp_hap_read_matrices")
         scratch.record_stream(stream if stream is not None else torch.cuda.current_stream())
         return outs[0], outs[1], outs[2], outs[3], row_record, meta
+
+    # ---- stage-4 site groups from the call rows (pileup_groups.hip) ----
+    GROUPS_WRITTEN, GROUPS_DICT, GROUPS_CANDIDATE, GROUPS_SUPPORT, GROUPS_GROUP = 1, 2, 4, 8, 16
+    GROUPS_KEY_ORDER = 1
+
+    def pileup_select_groups(self, rows, ref_base, run_off, cuts, adjacent_size=5, batch_size=1000, cap_groups=None, meta=None, stream=None):
+        """rows: float64 cuda [N,13] (pileup_call_rows); ref_base: uint8 cuda [N]; run_off: int64 cuda [n_runs + 1], the rows of every
+        contig; cuts: float32 cuda [8] (merge.group_cuts).  -> group_rows int32 [cap, 2A+1], group_keys int64 [cap, 2A+1], meta int64 [4] =
+        {groups found, status, first offending row, supports} (include/nanosnp.h; `meta` may be a pinned tensor), flags uint8 [N] (the
+        flag byte of every row: GROUPS_WRITTEN | _DICT | _CANDIDATE | _SUPPORT | _GROUP).  cap_groups None: one group per row, the most
+        there can be.  Nothing comes back through the host: slice the outputs with meta[0] once the stream has passed the call."""
+        import torch
+        if (rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] != 13 or not rows.is_cuda or not rows.is_contiguous()):
+            raise NanoSNPError("pileup_select_groups: rows must be a contiguous float64 cuda tensor [N,13]")
+        n, dev = int(rows.shape[0]), rows.device
+        for name, t, dt, ok in (("ref_base", ref_base, torch.uint8, ref_base.numel() == n), ("run_off", run_off, torch.int64, run_off.numel() >= 1),
+                                ("cuts", cuts, torch.float32, cuts.numel() == 8)):
+            if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != dev or not ok:
+                raise NanoSNPError(f"pileup_select_groups: {name} must be a contiguous {dt} vector on the rows' device (ref_base [N], run_off "
+                                   "[n_runs + 1], cuts [8])")
+        a, cap = int(adjacent_size), n if cap_groups is None else int(cap_groups)
+        need = self.lib.nsnp_pileup_groups_scratch_bytes(n)
+        if need == 0:
+            raise NanoSNPError("pileup_select_groups: more than 2^31 - 16 rows")
+        w = 2 * a + 1 if 1 <= a <= 32 else 1
+        group_rows = torch.empty((max(cap, 0), w), dtype=torch.int32, device=dev)
+        group_keys = torch.empty((max(cap, 0), w), dtype=torch.int64, device=dev)
+        if meta is None:
+            meta = torch.empty(4, dtype=torch.int64, device=dev)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(self.lib.nsnp_pileup_select_groups(self.handle, _dptr(rows), _dptr(ref_base), n, _dptr(run_off), int(run_off.numel()) - 1, int(batch_size),
+                                                 a, _dptr(cuts), _dptr(group_rows), _dptr(group_keys), cap, _dptr(meta), _dptr(scratch),
+                                                 _stream_ptr(stream)),
+              self.handle, "nsnp_pileup_select_groups")
+        scratch.record_stream(stream if stream is not None else torch.cuda.current_stream())
+        return group_rows, group_keys, meta, scratch[:n]
 
     def hap_load_weights(self, tensors, n_features=105, hidden=256, n_layers=3, n_gt=10, n_zy=3):
         import numpy as np

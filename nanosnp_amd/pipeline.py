@@ -1708,9 +1708,41 @@ def call_mpileup_bed(model, mpileup_path_or_bytes, fasta_path, fai_text, output_
     return _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, extended_bed, confident_bed, **kw)
 
 
+def call_mpileup_groups(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, *, quality_threshold=19.0, adjacent_size=5,
+                        support_quality=14.0, reference_bug=False, nthreads=10, extended_bed=None, confident_bed=None, **kw):
+    """call_mpileup_bed that also selects the stage-4 site groups (merge.select_groups: every low-quality site with its adjacent_size nearest
+    confident heterozygous neighbours on each side) from the call rows while they are still on the device, instead of from the pileup.vcf
+    they become: -> (rows written, merge.DeviceGroups).  The file is call_mpileup_bed's, byte for byte.  The rows of every hand-over of
+    complete contigs go through nsnp_pileup_select_groups (merge.select_groups_rows) on the writer thread's stream behind their formatting;
+    the pieces are put together when the text is over, `rows` of the DeviceGroups counting the call rows of the whole run in text order.
+    groups.to_lists() equals merge.select_groups on the file with the same thresholds, nthreads and reference_bug (False here by default:
+    every contig is kept).  **kw and the refusals: as call_mpileup_bed; also NanoSNPError for positions that do not ascend strictly inside
+    a contig (select_groups would keep the last row of a repeated position)."""
+    import torch
+    from . import merge
+    from ._lib import KEY_SHIFT
+    batch_size, score_mode = kw.get("batch_size", 1000), kw.get("score_mode", host.SCORE_FLOAT64)
+    parts, offsets = [], [0]
+
+    def on_contigs(rows, table, ctx):
+        key = rows[:, 0].to(torch.int64)
+        ref_base = table.genome[table.seq_off[key >> KEY_SHIFT] + (key & ((1 << KEY_SHIFT) - 1)) - 1]
+        parts.append(merge.select_groups_rows(ctx, rows, ref_base, table.names, quality_threshold=quality_threshold, adjacent_size=adjacent_size,
+                                              support_quality=support_quality, batch_size=batch_size, score_mode=score_mode, reference_bug=False))
+        offsets.append(offsets[-1] + int(rows.shape[0]))
+
+    n_rows = _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, extended_bed, confident_bed, on_contigs=on_contigs, **kw)
+    if not parts:
+        dev = torch.device("cuda", model.ctx.device)
+        return n_rows, merge.DeviceGroups.empty(kw.get("contigs") or fai_names(fai_text), adjacent_size, dev, score_mode)
+    return n_rows, merge.DeviceGroups.concat(parts, offsets[:-1], nthreads, reference_bug)
+
+
 def _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_file, extended_bed, confident_bed, contigs=None, batch_size=1000,
-                  score_mode=host.SCORE_FLOAT64, chunk_bytes=64 << 20, min_af=0.12, min_coverage=6, stats=None):
-    """the one body of call_mpileup and call_mpileup_bed"""
+                  score_mode=host.SCORE_FLOAT64, chunk_bytes=64 << 20, min_af=0.12, min_coverage=6, stats=None, on_contigs=None):
+    """the one body of call_mpileup, call_mpileup_bed and call_mpileup_groups.  on_contigs(rows, table, ctx) (None: nothing below changes):
+    called on the writer thread, under its stream and with its context, with the call rows of every hand-over of complete contigs - in
+    text order, behind their formatting and before they are released"""
     import time
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
@@ -1757,6 +1789,8 @@ def _call_mpileup(model, mpileup_path_or_bytes, fasta_path, fai_text, output_fil
                         carry.append(rows[keep:])
                     rows = rows[:keep]
                 parts = _format_key_rows(rows, table, batch_size, score_mode, wctx, nthreads=0 if last else few) if rows.shape[0] else []
+                if on_contigs is not None and rows.shape[0]:
+                    on_contigs(rows, table, wctx)
             nr = 0
             for t_, r_ in parts:
                 f.write(t_); nr += r_
